@@ -8,7 +8,14 @@
 A step = forward + masked relative-L2 loss + backward (+ RCCL gradient all-reduce) + global-norm clip + fused Adam,
 T_ar = 1, on BASELINE.json configs[1]: DPOT-Tiny (embed 512, depth 4, 4 blocks, modes 32, patch 8), per-GPU batch 32,
 fp32, synthetic N(0,1) fields already resident in HBM.  Weak scaling: every rank processes its own batch of 32.
-Rank 0 prints ONE JSON line (metric/value/unit + `roofline` for the AFNO mixer kernel + `cpu_baseline`).
+Rank 0 prints ONE JSON line (metric / value / unit / ms_per_step / dtype + the run's configuration).
+
+A plain run only sets up, warms up, times the `--steps` steps and prints that line.  `--full` adds everything else this
+script measures, each in runs of its own: the sustained rate, the `roofline` of the dominant kernels, the other GEMM
+precisions, inference, the input-pipeline-inclusive rate, `cpu_baseline` and BASELINE configs[2..4] as `other_configs`.
+`--dump-outputs DIR` writes what the last timed step computed (loss, prediction, gradient norm, updated parameters) as
+DIR/<name>.npy, fp32; the inputs and the initial weights are seeded, so two builds run with the same arguments can be
+compared output for output.
 
 `--gpus N` without a launcher (WORLD_SIZE unset) re-executes itself under torch.distributed.run on 127.0.0.1.
 `--config {T,S,M,L,L20}` selects the other BASELINE.json configs (default T = configs[1], the headline):
@@ -54,6 +61,9 @@ FP32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32
 BF16_MFMA_PEAK_TFLOPS = 2500.0     # MI355X_MICROARCH.md: dense bf16 MFMA
 SUSTAINED_FP32_MFMA_TFLOPS = 132.8   # register-only MFMA loop, random operands (profiles/r02_mfma_f32_peak.txt)
 HBM_PEAK_GBS = 8000.0              # MI355X_MICROARCH.md: HBM3E spec
+# --dump-outputs: at most this many fp32 elements of the prediction / of the parameters (24 + 32 MB, < 64 MB in all; the
+# DPOT-Tiny parameters, 7.5 M, are written whole)
+DUMP_MAX_PRED, DUMP_MAX_PARAMS = 6 << 20, 8 << 20
 
 
 def log(*a):
@@ -78,23 +88,30 @@ def parse():
     ap.add_argument("--no-overlap", action="store_true",
                     help="N>1: one graph of fwd+bwd, then all buckets, then Adam (round-1 behaviour, for comparison)")
     ap.add_argument("--sustain-seconds", type=float, default=2.0,
-                    help="N=1: also time a sustained run of about this many seconds of replays (DVFS-honest figure)")
+                    help="--full, N=1: also time a sustained run of about this many seconds of replays (DVFS-honest)")
     ap.add_argument("--noise-scale", type=float, default=0.0005,
                     help="train_temporal.py:205 noise injection (configs/pretrain_tiny.yaml:71 uses 0.0005)")
     ap.add_argument("--skip-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pipeline", action="store_true", help="skip the input-pipeline-inclusive timing")
+    ap.add_argument("--no-pipeline", action="store_true", help="--full: skip the input-pipeline-inclusive timing")
     ap.add_argument("--gemm-precision", default=os.environ.get("DPOT_GEMM_PRECISION"),
                     choices=("f32", "bf16x6", "auto"),
                     help="how the fp32 GEMMs form their products (default: f32 = native fp32 MFMA for the headline config T, "
                          "auto for S / M / L / L20 - see CONFIG_GEMM)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra timing with --gemm-precision auto")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the extra timings at the other GEMM precisions")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run (config T, N=1): do NOT append BASELINE configs[2..4] (S, M, L at batch 16, L20) as "
+                    help="--full run (config T, N=1): do NOT append BASELINE configs[2..4] (S, M, L at batch 16, L20) as "
                          "`other_configs` (each is one short child run of this script)")
     ap.add_argument("--full-json", default=None, help="also write the VERBOSE record (every note / description) to this file")
     ap.add_argument("--brief", action="store_true",
-                    help="only the step timing and the dominant-kernel roofline (what the `other_configs` children run)")
+                    help="with --full: only the step timing and the dominant-kernel roofline (what the `other_configs` "
+                         "children run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline step timing (sustained rate, rooflines, other "
+                         "precisions, inference, input pipeline, CPU baseline, other configs); off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (fp32; a larger prediction or "
+                         "parameter vector than DUMP_MAX_PRED / DUMP_MAX_PARAMS elements as a fixed, seeded sample)")
     return ap.parse_args()
 
 
@@ -578,8 +595,8 @@ L20_FASTEST = {"batch": 9, "keep_last": 20}
 
 def _child(args, key, steps, warm, extra=(), env=None, timeout=300):
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", key, "--brief", "--steps", str(steps),
-           "--warmup", str(warm), "--noise-scale", str(args.noise_scale)] + list(extra)
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", key, "--full", "--brief", "--steps",
+           str(steps), "--warmup", str(warm), "--noise-scale", str(args.noise_scale)] + list(extra)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=dict(os.environ, **(env or {})))
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     if r.returncode != 0 or not line:
@@ -590,7 +607,7 @@ def _child(args, key, steps, warm, extra=(), env=None, timeout=300):
 def other_configs(args):
     """BASELINE configs[2..4] (DPOT-S / -M / -L at batch 16 / the 20-step DPOT-L rollout), each as ONE short child run of
     this script (`--config X --brief`): fresh process = fresh kernel-selection state, the same timing code as the headline.
-    Kept short (the default run must finish within minutes): steps / warm-up scaled to the step time.  Entries are COMPACT
+    Kept short (the --full run must finish within minutes): steps / warm-up scaled to the step time.  Entries are COMPACT
     (numbers; a few hundred bytes each) so that the driver's 8 KB stdout tail holds all of them."""
     res = []
     for key, steps, warm in (("S", 20, 5), ("M", 20, 5), ("L", 8, 3), ("L20", 2, 1)):
@@ -696,7 +713,8 @@ def compact_line(out: dict) -> dict:
               "baseline_md_ceiling", "x_of_baseline_md_ceiling"):
         if k in out:
             c[k] = out[k]
-    c["roofline"] = _compact_roofline(out.get("roofline"))
+    if "roofline" in out:
+        c["roofline"] = _compact_roofline(out["roofline"])
     for k in ("gemm_auto", "gemm_f32", "all_f32", "inference", "pipeline_inclusive"):
         if k in out:
             c[k] = {kk: vv for kk, vv in out[k].items() if kk not in ("what", "note", "gemm_precision")}
@@ -728,6 +746,28 @@ def _self_launch(n: int) -> int:
            "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     log("[bench] no launcher detected (WORLD_SIZE unset): " + " ".join(cmd))
     return subprocess.call(cmd, env=env)
+
+
+def dump_outputs(path: str, loss, pred, opt, grad_scale: float) -> None:
+    """--dump-outputs: what a caller of the timed step holds after its last replay - the loss, the prediction, the global
+    gradient norm the clip used and the updated flat parameters - as fp32 .npy files.  An array larger than its cap is
+    replaced by its flattened elements at a fixed sample of indices (seed 0, ascending; the same for every build)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+
+    def put(name, t, cap=None):
+        t = t.detach().float()
+        if cap is not None and t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+    put("loss", loss)
+    if pred is not None:
+        put("pred", pred, DUMP_MAX_PRED)
+    put("grad_norm", opt.grad_norm(grad_scale))
+    put("params", opt.fp.flat, DUMP_MAX_PARAMS)
+    log(f"[bench] outputs of the last timed step written to {path}")
 
 
 def _flush_c_stdio():
@@ -854,13 +894,15 @@ def main():
             graphed = None
 
     step_idx = [0]
+    eager_pred = [None]                                        # the eager step's prediction (a graph keeps its own)
 
     def one_step():
         lr = lr_at(step_idx[0])
         step_idx[0] += 1
         if graphed is None:
-            return train_step(model, opt, xx, yy, msk, noise_scale=args.noise_scale, lr=lr, reducer=reducer,
-                              grad_scale=grad_scale)[0]
+            loss, eager_pred[0] = train_step(model, opt, xx, yy, msk, noise_scale=args.noise_scale, lr=lr, reducer=reducer,
+                                             grad_scale=grad_scale)
+            return loss
         if dp_on and args.no_overlap:
             graphed.replay()
             reducer.begin_step()
@@ -897,6 +939,9 @@ def main():
         rank_host_us = [float(a[1]) / args.steps * 1e6 for a in allt]
         elapsed = max(float(a[0]) for a in allt)
     final_loss = float(loss.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, eager_pred[0] if graphed is None else getattr(graphed, "pred", None), opt,
+                     grad_scale)
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
@@ -949,7 +994,7 @@ def main():
                                    f"forked inside the capture)" if isinstance(graphed, GraphedTrainStep) else
                                    f"segmented hipGraph chain ({len(graphed.graphs)} segments), bucket all-reduce on a "
                                    f"side stream overlapped with the remaining backward; {reducer.n_buckets} buckets")
-        if not dp_on and graphed is not None and args.sustain_seconds > 0 and not args.brief:
+        if args.full and not dp_on and graphed is not None and args.sustain_seconds > 0 and not args.brief:
             # the K-step figure above covers < 0.1 s of GPU time; a sustained run shows what the clocks settle at
             n_sus = max(args.steps, int(args.sustain_seconds / (elapsed / args.steps)))
             torch.cuda.synchronize()
@@ -988,19 +1033,21 @@ def main():
             t_ceiling = alg_mlp / (BF16_MFMA_PEAK_TFLOPS * 1e12) + (alg - alg_mlp) / (FP32_MFMA_PEAK_TFLOPS * 1e12)
             out["baseline_md_ceiling"] = round(1.0 / t_ceiling, 1)
             out["x_of_baseline_md_ceiling"] = round(per_gpu * t_ceiling, 4)
-        try:
-            mix = mixer_roofline(model, B)
-            if mlp_prec == "bf16" and not headline:
-                # the dominant kernel of these configs is the bf16 panel GEMM; the mixer goes to other_kernels
-                out["roofline"] = bf16_mlp_roofline(model, B)
-                others = mix.pop("other_kernels", [])
-                out["roofline"]["other_kernels"] = [mix] + others
-            else:
-                out["roofline"] = mix
-        except Exception as e:                                 # pragma: no cover
-            log(f"[bench] roofline probe failed: {e}")
-            out["roofline"] = None
-        if not headline and not dp_on and graphed is not None and args.gemm_precision == "auto" and not args.no_alt:
+        if args.full:
+            try:
+                mix = mixer_roofline(model, B)
+                if mlp_prec == "bf16" and not headline:
+                    # the dominant kernel of these configs is the bf16 panel GEMM; the mixer goes to other_kernels
+                    out["roofline"] = bf16_mlp_roofline(model, B)
+                    others = mix.pop("other_kernels", [])
+                    out["roofline"]["other_kernels"] = [mix] + others
+                else:
+                    out["roofline"] = mix
+            except Exception as e:                             # pragma: no cover
+                log(f"[bench] roofline probe failed: {e}")
+                out["roofline"] = None
+        if args.full and not headline and not dp_on and graphed is not None and args.gemm_precision == "auto" \
+                and not args.no_alt:
             # the bf16-channel-MLP configs run `auto`; the same step with every fp32 GEMM on native fp32 MFMA, beside it
             try:
                 model.gemm_precision = "f32"
@@ -1020,7 +1067,8 @@ def main():
                 log(f"[bench] gemm_f32 timing failed: {e}")
             finally:
                 model.gemm_precision = args.gemm_precision
-        if args.config in ("M", "L") and not dp_on and graphed is not None and mlp_prec == "bf16" and not args.no_alt:
+        if args.full and args.config in ("M", "L") and not dp_on and graphed is not None and mlp_prec == "bf16" \
+                and not args.no_alt:
             # BASELINE configs[3] / [4] do not say bf16 (only configs[2] does): the SAME step with every GEMM on native fp32
             # MFMA - channel MLP included - i.e. the figure inside north_star's rtol 1e-4 (the parity gate of this mode:
             # tests/test_gpu_sizes.py::test_vs_reference_golden, fp32 leg).  Fresh model / optimiser / graph: weight packs and
@@ -1057,8 +1105,8 @@ def main():
                 del g32, m32, o32
             except Exception as e:                             # pragma: no cover
                 log(f"[bench] all_f32 timing failed: {type(e).__name__}: {e}")
-        if headline and not dp_on and graphed is not None and args.gemm_precision == "f32" and not args.no_alt \
-                and not args.brief:
+        if args.full and headline and not dp_on and graphed is not None and args.gemm_precision == "f32" \
+                and not args.no_alt and not args.brief:
             # not the headline: the same step with the large GEMMs on the bf16x6 kernel (fp32 emulated by operand
             # splitting on the bf16 matrix cores, same accuracy class - DESIGN.md "bf16x6"); a fresh graph is captured
             # because the kernel choice is baked in at capture time
@@ -1081,7 +1129,7 @@ def main():
                 log(f"[bench] gemm_auto timing failed: {e}")
             finally:
                 model.gemm_precision = args.gemm_precision
-        if not dp_on and T_ar == 1 and not args.brief:
+        if args.full and not dp_on and T_ar == 1 and not args.brief:
             # forward-only (inference) rate of the same batch, SURVEY 8(d): no_grad forward, hipGraph replay
             try:
                 with torch.no_grad():
@@ -1104,7 +1152,7 @@ def main():
                                     "what": "DPOTNet forward only (no_grad), batch %d, hipGraph replay" % B}
             except Exception as e:                             # pragma: no cover
                 log(f"[bench] inference timing failed: {e}")
-        if headline and not dp_on and graphed is not None and not args.no_pipeline and not args.brief:
+        if args.full and headline and not dp_on and graphed is not None and not args.no_pipeline and not args.brief:
             # input-pipeline-inclusive rate (never `value`): raw 64x64 single-channel trajectories in host memory (the
             # ns2d_fno_1e-5 shape) -> pinned staging -> ONE H2D copy per batch on a copy stream -> device-side bilinear
             # resize to 128^2 + channel pad with ones + temporal window (csrc/data.hip) -> double-buffered batch slots;
@@ -1141,10 +1189,10 @@ def main():
                             "batching inclusive, single host thread"}
             except Exception as e:                             # pragma: no cover
                 log(f"[bench] pipeline-inclusive timing failed: {type(e).__name__}: {e}")
-        if headline and not dp_on and not args.skip_cpu_baseline and not args.brief:
+        if args.full and headline and not dp_on and not args.skip_cpu_baseline and not args.brief:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
             out["speedup_vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
-        if headline and not dp_on and not args.brief and not args.no_other_configs and args.batch is None:
+        if args.full and headline and not dp_on and not args.brief and not args.no_other_configs and args.batch is None:
             # BASELINE configs[2..4] through this same script, so that the driver's record carries them:
             # the model of this process is released first - DPOT-L at batch 16 wants the HBM to itself
             del graphed, model, opt, fp
