@@ -78,9 +78,9 @@ class _Sink:
 def _epoch_of(sinks):
     """(FlatParams, its weights epoch) of the first flat-bound parameter, or None.  DPOTNet keeps its derived weights
     (AFNO packs, panel packs, the de-embed matrix) in PERSISTENT buffers that every forward outside a weights_scope
-    rewrites in place, and the stage backwards read them again without autograd version tracking; train.FusedAdam bumps
-    the epoch when it changes the parameters.  (Parameters changed by other means are the caller's responsibility:
-    run backward before modifying them.)"""
+    rewrites in place, and the stage backwards read them again without autograd version tracking; FlatParams.touch()
+    advances the epoch whenever the parameters change.  (Parameters changed by other means are the caller's
+    responsibility: run backward before modifying them.)"""
     for sk in sinks:
         if sk.fp is not None:
             return sk.fp, sk.fp.epoch

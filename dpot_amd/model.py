@@ -15,7 +15,6 @@ The model only runs on a CUDA (ROCm) device; calling it with CPU tensors raises 
 from __future__ import annotations
 
 import numpy as np
-import os
 
 import torch
 import torch.nn as nn
@@ -23,9 +22,8 @@ import torch.nn as nn
 from . import _lib, ops
 import contextlib
 
-from .functional import (AdaINFn, BlockFn, EmbedFn, HeadFn, embed_derived, embed_grid_matrix, embed_layout_jobs,
-                         head_derived, head_layout_jobs,
-                         mlp_pack_kind)
+from .functional import AdaINFn, BlockFn, EmbedFn, HeadFn
+from .packs import ModelPacks
 
 ACTIVATIONS = ("gelu", "tanh", "sigmoid", "relu", "leaky_relu", "softplus", "ELU", "silu")
 
@@ -133,8 +131,8 @@ class DPOTNet(nn.Module):
         # precision of every OTHER fp32 GEMM of this model: None = the process default (ops.set_gemm_precision /
         # DPOT_GEMM_PRECISION), or 'f32' (native fp32 MFMA) | 'bf16x6' | 'auto' (the fp32-accurate operand split where faster)
         self.gemm_precision = None
-        self._scope_depth = 0
-        self._scope_cache = None
+        # every weight-derived copy the kernels read (packed / padded / transposed weights) and when it is fresh
+        self.packs = ModelPacks()
         # optional callable(b, lat) -> lat, called with the latent ENTERING stage b (1..depth = block b-1,
         # depth+1 = the head); train.SegmentedTrainStep cuts the autograd graph there
         self._boundary_hook = None
@@ -146,117 +144,9 @@ class DPOTNet(nn.Module):
         GEMM matrices, padded / transposed conv weights, the folded embed matrices) are computed by the FIRST forward
         call and re-used by the following ones: an auto-regressive rollout calls the model T_ar times per optimiser
         step on unchanged weights (train_temporal.py:201-219, evaluate.py:193-213).  The caller promises not to
-        modify parameters inside the scope; outside a scope every forward derives them afresh."""
-        self._scope_depth += 1
-        dev = self.pos_embed.device
-        if self._scope_depth == 1:
-            self._scope_cache = None
-            if dev.type == "cuda":
-                with ops.precision_scope(self.gemm_precision, self.mlp_precision):
-                    self._derived_weights()
-        try:
+        modify parameters inside the scope; outside a scope every forward derives them afresh (packs.ModelPacks)."""
+        with self.packs.scope(self):
             yield self
-        finally:
-            self._scope_depth -= 1
-            if self._scope_depth == 0:
-                self._scope_cache = None
-
-    def _derived_weights(self):
-        if self._scope_depth > 0 and self._scope_cache is not None:
-            return self._scope_cache
-        pe, ta, ol = self.patch_embed.proj, self.time_agg_layer, self.out_layer
-        grid = None
-        if ops.embed_supported(self.in_channels, self.patch_size, self.in_timesteps, pe[0].weight.shape[0],
-                               self.img_size // self.patch_size):
-            grid = getattr(self, "_embed_grid", None)
-            if grid is None or grid.device != self._gx.device:
-                grid = self._embed_grid = embed_grid_matrix(self._gx, self._gy, self._gt, self.img_size, self.img_size,
-                                                            self.in_timesteps, self.in_channels, self.patch_size)
-        # every small layout piece of the model (padded conv weights, pos_embed^T + bias, de-embed bias per pixel, padded
-        # tail weights) in ONE launch from a device-resident job table with persistent outputs (ops.LayoutJobs)
-        lay_e = lay_h = None
-        if ops.tune("fused_small") != 0:
-            je = embed_layout_jobs(self.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias)
-            jh = head_layout_jobs(ol[0].bias, ol[4].weight, ol[4].bias, self.patch_size, ol[0].weight.shape[1])
-            lj = getattr(self, "_layout_jobs", None)
-            if lj is None or lj.key != ops.LayoutJobs.key_of(je + jh):
-                lj = self._layout_jobs = ops.LayoutJobs(je + jh)
-            lay = lj.refresh()
-            lay_e, lay_h = lay[:len(je)], lay[len(je):]
-        emb = embed_derived(self.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, ta.w,
-                            ta.gamma if self.time_agg == "exp_mlp" else None, self._tt, self.in_timesteps, grid=grid,
-                            layouts=lay_e)
-        # Wbig = [[Wr, Wi], [-Wi, Wr]] of every AFNO layer + its fragment-block-major forms, ONE launch for all layers
-        pk = []
-        if len(self.blocks):
-            pairs = [p for blk in self.blocks for p in ((blk.filter.w1, blk.filter.b1), (blk.filter.w2, blk.filter.b2))]
-            ap = getattr(self, "_afno_packs", None)
-            if ap is None or ap.key != tuple(t.data_ptr() for p in pairs for t in p):
-                ap = self._afno_packs = ops.AfnoPacks(pairs)
-            pk = ap.refresh()
-        PP_old = self.patch_size ** 2 * ol[0].weight.shape[1]
-        wt_buf = getattr(self, "_wt_buf", None)
-        if wt_buf is None or wt_buf.device != ol[0].weight.device or wt_buf.numel() != self.embed_dim * PP_old:
-            wt_buf = self._wt_buf = torch.empty(self.embed_dim, PP_old, dtype=torch.float32, device=ol[0].weight.device)
-        head = head_derived(ol[0].weight, ol[0].bias, ol[4].weight, ol[4].bias, self.patch_size, wt_out=wt_buf,
-                            layouts=lay_h)
-        mlp_pk, head_pk = self._panel_packs_refresh(wt_buf)
-        d = (emb, pk, head + (head_pk,), mlp_pk)
-        if self._scope_depth > 0:
-            self._scope_cache = d
-        return d
-
-    def _panel_packs_refresh(self, wt):
-        """fragment-block-major copies of the static weights of the panel GEMMs, refreshed by ONE launch each per
-        optimiser step: per block W1, W1^T, W2, W2^T (channel-MLP forward x W^T and data gradient dy W) - fp32 for
-        csrc/gemm_panel.hip, or bf16 for csrc/gemm_bf16p.hip when the channel-MLP precision is 'bf16' - and the de-embed
-        matrix wt [E, P*P*old] both ways (fp32).  Returns (per-block tuples | None, (wt fwd, wt bwd) | None)."""
-        E = self.embed_dim
-        n_out = wt.shape[1]
-        mlp_pk = head_pk = None
-        nb = len(self.blocks)
-
-        def mlp_jobs():
-            jobs = []
-            for b in self.blocks:
-                w1, w2 = b.mlp[0].weight, b.mlp[2].weight                   # [mh, E, 1, 1], [E, mh, 1, 1]
-                jobs += [(w1, mh, E, E, False), (w1, E, mh, E, True), (w2, E, mh, mh, False), (w2, mh, E, mh, True)]
-            return jobs
-
-        def cached(attr, key, make_jobs, bf16, planes=1):
-            pp = getattr(self, attr, None)
-            if pp is None or pp.key_all != key:
-                pp = ops.PanelPacks(make_jobs(), bf16=bf16, planes=planes)
-                pp.key_all = key
-                setattr(self, attr, pp)
-            pp.refresh()
-            return pp
-
-        wkey = tuple(b.mlp[i].weight.data_ptr() for b in self.blocks for i in (0, 2))
-        kind = None
-        if nb:
-            mh = self.blocks[0].mlp[0].weight.shape[0]
-            kind = mlp_pack_kind(E, mh)
-            if kind in ("bf16", "bf16x6"):
-                planes = 3 if kind == "bf16x6" else 1
-                pp = cached("_panel_packs_" + kind, wkey, mlp_jobs, True, planes)
-                mlp_pk = [ops.MlpPacks(pp.bufs[4 * i:4 * i + 4], kind) for i in range(nb)]
-        f32_mlp = kind == "f32"
-        use_head = (ops.panel_enabled() and ops.gemm_panel_supported(1, n_out, E)
-                    and ops.gemm_panel_supported(1, E, n_out))
-        if f32_mlp or use_head:
-            def jobs32():
-                jobs = mlp_jobs() if f32_mlp else []
-                if use_head:
-                    jobs += [(wt, n_out, E, n_out, True), (wt, E, n_out, n_out, False)]
-                return jobs
-            pp = cached("_panel_packs", wkey + (wt.data_ptr(), f32_mlp, use_head), jobs32, False)
-            n0 = 4 * nb if f32_mlp else 0
-            if f32_mlp:
-                mlp_pk = [ops.MlpPacks(pp.bufs[4 * i:4 * i + 4], "f32") for i in range(nb)]
-            if use_head:
-                head_pk = tuple(pp.bufs[n0:n0 + 2])
-        return mlp_pk, head_pk
 
     def forward(self, x):
         with ops.precision_scope(self.gemm_precision, self.mlp_precision):
@@ -283,7 +173,7 @@ class DPOTNet(nn.Module):
         pe, ta = self.patch_embed.proj, self.time_agg_layer
         P = self.patch_size
         h = self.latent_size[0]
-        d_emb, pk, d_head, mlp_pk = self._derived_weights()
+        d_emb, pk, d_head, mlp_pk = self.packs.derive(self)
         lat = EmbedFn.apply(x, self.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, ta.w,
                             ta.gamma if self.time_agg == "exp_mlp" else None, self._gx, self._gy, self._gt, self._tt,
                             P, self._act, d_emb)

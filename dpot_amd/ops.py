@@ -279,13 +279,21 @@ def gemm_panel_supported(M: int, N: int, K: int) -> bool:
     return bool(_lib.load().dpot_gemm_panel_supported(M, N, K))
 
 
+def _device_table(struct, entries, dev) -> Tensor:
+    """job table of a one-launch kernel: one ctypes `struct` per entry (a tuple of its fields in _lib's order), as raw bytes
+    in device memory"""
+    import numpy as np
+    arr = (struct * len(entries))(*(struct(*e) for e in entries))
+    return torch.from_numpy(np.frombuffer(bytearray(arr), dtype=np.uint8)).to(dev)
+
+
 class PanelPacks:
     """Fragment-block-major copies of a set of static weights, refreshed by ONE launch (dpot_panel_pack_weights) from a
     job table that lives in device memory.  jobs = [(src tensor, rows, K, ld, trans)]; the destination buffers are
-    allocated once, so the table stays valid while the sources do not move."""
+    allocated once, so the table stays valid while the sources do not move.  refresh() always launches: whether a set
+    is still fresh is decided by its owner (packs.ModelPacks)."""
 
     def __init__(self, jobs, bf16: bool = False, planes: int = 1):
-        import numpy as np
         dev = jobs[0][0].device
         self.bf16 = bf16
         self.planes = planes if bf16 else 0       # 1: plain bf16, 3: bf16x6 split (fp32-accurate)
@@ -295,33 +303,13 @@ class PanelPacks:
                          for _, rows, K, _, _ in jobs]
         else:
             self.bufs = [torch.empty(rows * K, dtype=torch.float32, device=dev) for _, rows, K, _, _ in jobs]
-        self.key = tuple(j[0].data_ptr() for j in jobs)
-        host = np.zeros(len(jobs) * C.sizeof(_lib.PackJob), dtype=np.uint8)
-        tab = (_lib.PackJob * len(jobs)).from_buffer(host)
-        for i, ((src, rows, K, ld, trans), dst) in enumerate(zip(jobs, self.bufs)):
-            tab[i].src, tab[i].dst, tab[i].rows, tab[i].K, tab[i].ld, tab[i].trans = src.data_ptr(), dst.data_ptr(), rows, K, ld, int(trans)
-        self.table = torch.from_numpy(host).to(dev)
+        self.table = _device_table(_lib.PackJob, [(src.data_ptr(), dst.data_ptr(), rows, K, ld, int(trans))
+                                                  for (src, rows, K, ld, trans), dst in zip(jobs, self.bufs)], dev)
         self.n = len(jobs)
         self.max_elems = max(rows * K for _, rows, K, _, _ in jobs)
         self.jobs = list(jobs)                    # (the table holds raw pointers: this also keeps the sources alive)
-        # round 6: an optimiser that writes these packs itself (train.FusedAdam -> dpot_adam_step_packs) records here what the
-        # packs are fresh FOR - (its FlatParams, that buffer's epoch, the sources' tensor versions); refresh() is then a no-op
-        # until anything else moves the parameters (FlatParams.epoch bumps, load_state_dict / in-place writes bump _version)
-        self.fresh_for = None
 
-    def _fresh_key(self, fp):
-        return (id(fp), fp.epoch, tuple(j[0]._version for j in self.jobs[::2]))
-
-    def is_fresh(self) -> bool:
-        ff = self.fresh_for
-        return ff is not None and ff[1] == self._fresh_key(ff[0])
-
-    def mark_fresh(self, fp) -> None:
-        self.fresh_for = (fp, self._fresh_key(fp))
-
-    def refresh(self, force: bool = False) -> None:
-        if not force and self.is_fresh():
-            return
+    def refresh(self) -> None:
         lib = _lib.load()
         if self.bf16:
             check(lib.dpot_bf16_pack_jobs(self.table.data_ptr(), self.n, self.max_elems, self.planes, _stream()),
@@ -334,30 +322,16 @@ class LayoutJobs:
     """Small weight-only layout products (zero-padded copies, small transposes, bias broadcasts, "+ bias") refreshed by ONE
     launch (dpot_layout_jobs) from a device-resident table.  jobs = [(src, add | None, (d0, d1, d2), (v0, v1, v2),
     (s0, s1, s2))]: out[i0, i1, i2] = (inside v ? src.flat[i0 s0 + i1 s1 + i2 s2] : 0) + (add[i2] if add is not None).
-    self.out[i]: persistent [d0, d1, d2] tensors (the table stays valid while the sources do not move: self.key)."""
+    self.out[i]: persistent [d0, d1, d2] tensors (the table stays valid while the sources do not move)."""
 
     def __init__(self, jobs):
-        import numpy as np
         dev = jobs[0][0].device
         self.out = [torch.empty(d, dtype=torch.float32, device=dev) for _, _, d, _, _ in jobs]
-        self.key = LayoutJobs.key_of(jobs)
         self.sources = [(j[0], j[1]) for j in jobs]        # the table holds raw pointers: keep the tensors alive
-        host = np.zeros(len(jobs) * C.sizeof(_lib.LayoutJob), dtype=np.uint8)
-        tab = (_lib.LayoutJob * len(jobs)).from_buffer(host)
-        for i, ((src, add, d, v, st), dst) in enumerate(zip(jobs, self.out)):
-            t = tab[i]
-            t.src, t.add, t.dst = src.data_ptr(), (add.data_ptr() if add is not None else None), dst.data_ptr()
-            t.d0, t.d1, t.d2 = d
-            t.v0, t.v1, t.v2 = v
-            t.s0, t.s1, t.s2 = st
-        self.table = torch.from_numpy(host).to(dev)
+        self.table = _device_table(_lib.LayoutJob, [(src.data_ptr(), _p(add), dst.data_ptr(), *d, *v, *st)
+                                                    for (src, add, d, v, st), dst in zip(jobs, self.out)], dev)
         self.n = len(jobs)
         self.max_elems = max(d[0] * d[1] * d[2] for _, _, d, _, _ in jobs)
-
-    @staticmethod
-    def key_of(jobs):
-        """every raw pointer the device table would hold (src AND add of each job): the cache key of a LayoutJobs"""
-        return tuple(j[0].data_ptr() for j in jobs) + tuple(j[1].data_ptr() for j in jobs if j[1] is not None)
 
     def refresh(self):
         check(_lib.load().dpot_layout_jobs(self.table.data_ptr(), self.n, self.max_elems, _stream()), "layout_jobs")
@@ -682,27 +656,20 @@ class AfnoPacks:
     pairs = [(w [2,nb,bs,bs], b [2,nb,bs]), ...];  self.items[i] = (wbig, bbig, fwd | None, bwd | None)"""
 
     def __init__(self, pairs):
-        import numpy as np
         n = len(pairs)
         _, nb, bs, _ = pairs[0][0].shape
         dev = pairs[0][0].device
         N = 2 * bs
         self.nb, self.bs, self.n = nb, bs, n
-        self.key = tuple(t.data_ptr() for p in pairs for t in p)
         fused = afno_mlp2_supported(nb, bs)
         self.layout = 1 if fused and afno_mlp3_supported(nb, bs) else 0      # three-product (Wr, Wi) fragment packs
         wbig = torch.empty(n, nb, N, N, dtype=torch.float32, device=dev)
         bbig = torch.empty(n, nb, N, dtype=torch.float32, device=dev)
         fwd = torch.empty_like(wbig) if fused else None
         bwd = torch.empty_like(wbig) if fused else None
-        host = np.zeros(n * C.sizeof(_lib.AfnoPackJob), dtype=np.uint8)
-        tab = (_lib.AfnoPackJob * n).from_buffer(host)
-        for i, (w, b) in enumerate(pairs):
-            tab[i].w, tab[i].b = _req(w, "w").data_ptr(), _req(b, "b").data_ptr()
-            tab[i].wbig, tab[i].bbig = wbig[i].data_ptr(), bbig[i].data_ptr()
-            tab[i].fwd = fwd[i].data_ptr() if fused else None
-            tab[i].bwd = bwd[i].data_ptr() if fused else None
-        self.table = torch.from_numpy(host).to(dev)
+        self.table = _device_table(_lib.AfnoPackJob, [
+            (_req(w, "w").data_ptr(), _req(b, "b").data_ptr(), wbig[i].data_ptr(), bbig[i].data_ptr(),
+             fwd[i].data_ptr() if fused else None, bwd[i].data_ptr() if fused else None) for i, (w, b) in enumerate(pairs)], dev)
         # bf16x6 packs (csrc/afno_mlp6.hip): items alternate (first-layer weight, second-layer weight) - pairs of a filter
         self.wbig = wbig
         self.fwd6 = self.bwd6 = None               # allocated by the first refresh that wants them (3 bytes per weight element
@@ -1330,7 +1297,6 @@ class AdamPackPlan:
 
     @staticmethod
     def build(flat: Tensor, n_active: int, pp: "PanelPacks"):
-        import numpy as np
         lib = _lib.load()
         if not pp.bf16 or pp.planes != 1 or pp.n % 2:
             return None
@@ -1347,15 +1313,12 @@ class AdamPackPlan:
         self = AdamPackPlan()
         self.pp = pp
         dev = flat.device
-        ntiles, tile_job = 0, []
-        host = np.zeros(len(jobs) * C.sizeof(_lib.AdamPackJob), dtype=np.uint8)
-        tab = (_lib.AdamPackJob * len(jobs)).from_buffer(host)
+        ntiles, tile_job, tab = 0, [], []
         ranges, pos = [], 0
         for i, (off, R, K, drow, dtr) in enumerate(jobs):
             if off < pos:
                 return None                                   # overlapping weights: not a layout this plan understands
-            t = tab[i]
-            t.off, t.dst_rows, t.dst_trans, t.R, t.K, t.tile0 = off, drow.data_ptr(), dtr.data_ptr(), R, K, ntiles
+            tab.append((off, drow.data_ptr(), dtr.data_ptr(), R, K, ntiles))
             nt = (R // 64) * (K // 256)
             tile_job += [i] * nt
             ntiles += nt
@@ -1370,11 +1333,9 @@ class AdamPackPlan:
                 st, ln = st + c, ln - c
         self.ntiles, self.nranges = ntiles, len(split)
         self.max_range = max((c for _, c in split), default=0)
-        self.jobs_dev = torch.from_numpy(host).to(dev)
+        self.jobs_dev = _device_table(_lib.AdamPackJob, tab, dev)
         self.tile_job_dev = torch.tensor(tile_job, dtype=torch.int32, device=dev)
-        rh = np.array(split, dtype=np.int64).reshape(-1, 2) if split else np.zeros((0, 2), dtype=np.int64)
-        self.ranges_dev = torch.from_numpy(rh).to(dev)
-        self.key = (base, n_active, id(pp))
+        self.ranges_dev = torch.tensor(split, dtype=torch.int64).view(-1, 2).to(dev)
         return self
 
 

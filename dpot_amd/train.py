@@ -67,7 +67,7 @@ class FlatParams:
         self.filled: List[bool] = [False] * n_p      # slot already holds a gradient contribution this step
         self.pending: List[int] = [0] * n_p          # forward uses whose backward has not delivered yet
         self.callbacks: List[Callable[[int], None]] = []   # fired with the parameter index when its grad is final
-        self.epoch = 0                               # bumped by the optimiser whenever it changes the parameters
+        self.epoch = 0                               # advanced by touch() whenever the parameters change
         with torch.no_grad():
             for i, (p, o) in enumerate(zip(self.params, self.offsets)):
                 n = p.numel()
@@ -93,6 +93,13 @@ class FlatParams:
     def fire(self, i: int) -> None:
         for cb in self.callbacks:
             cb(i)
+
+    def touch(self) -> None:
+        """Declare the parameters changed.  The optimiser, a graph replay and the reducer's broadcast call it; call it yourself
+        after writing parameters in a way their tensor versions do not see (through ``p.data`` or ``fp.flat``).  Every
+        weight-derived copy of the model is then re-derived by the next forward (packs.ModelPacks), and the backward of a
+        forward that ran before raises instead of reading overwritten copies (functional._check_epoch)."""
+        self.epoch += 1
 
 
 class FusedAdam:
@@ -122,6 +129,8 @@ class FusedAdam:
         self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
         self.step_count = 0                       # host mirror of step_dev (number of steps ENQUEUED)
         self.param_groups = [{"lr": lr}]          # minimal torch.optim surface for LR schedulers / logging
+        self.packs = getattr(flat.model, "packs", None)       # the model's packs.ModelPacks (None: a model without one)
+        self.wrote = None                         # the pack set the last launch() wrote along with the parameters, or None
 
     @property
     def n_active(self) -> int:
@@ -146,41 +155,19 @@ class FusedAdam:
         use_clip = self.max_norm is not None
         if use_clip:
             ops.sumsq(g, self.sumsq, self._part)
-        plan = self._pack_plan()
+        plan = self.packs.adam_plan(self.fp.flat, n) if self.packs is not None else None
         if plan is not None:
             # round 6: the channel-MLP weights leave the optimiser ALSO as their two bf16 packs - the next forward's pack
-            # launch (a second read of every weight written here) disappears (PanelPacks.refresh sees them fresh)
+            # launch (a second read of every weight written here) disappears (the owner sees them fresh)
             ops.adam_step_packs(plan, self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, self.hyper,
                                 self.sumsq if use_clip else None, grad_scale)
         else:
             ops.adam_step(self.fp.flat[:n], g, self.exp_avg[:n], self.exp_avg_sq[:n], self.hyper,
                           self.sumsq if use_clip else None, grad_scale)
-        self.fp.epoch += 1            # parameters changed: a backward of an EARLIER forward must not run any more
+        self.fp.touch()               # parameters changed: a backward of an EARLIER forward must not run any more
+        self.wrote = plan.pp if plan is not None else None
         if plan is not None:
-            plan.pp.mark_fresh(self.fp)
-
-    def mark_packs_fresh(self) -> None:
-        """after a graph replay whose captured Adam launch wrote the weight packs (the host-side record cannot see it)"""
-        plan = self._pack_plan()
-        if plan is not None:
-            plan.pp.mark_fresh(self.fp)
-
-    def _pack_plan(self):
-        """the dpot_adam_step_packs tables for the model's plain-bf16 channel-MLP weight packs (DPOTNet._panel_packs_bf16, made
-        by its first forward in that mode), or None: no such packs / a weight that does not tile / DPOT_TUNE packs=0"""
-        if ops.tune("packs") == 0:
-            return None
-        pp = getattr(self.fp.model, "_panel_packs_bf16", None)
-        if pp is None:
-            self._plan = None
-            return None
-        key = (self.fp.flat.data_ptr(), self.n_active, id(pp))
-        plan = getattr(self, "_plan", None)
-        if plan is None or plan.key != key:
-            plan = self._plan = ops.AdamPackPlan.build(self.fp.flat, self.n_active, pp) or False
-            if plan:
-                plan.key = key
-        return plan or None
+            self.packs.mark_fresh(plan.pp, self.fp)
 
     def step(self, lr: Optional[float] = None, grad_scale: float = 1.0) -> None:
         self.stage_hyper(lr)
@@ -206,11 +193,11 @@ class FusedAdam:
         self.step_dev.copy_(sd)
         self.step_count, self.lr = sc, lr
         self.param_groups[0]["lr"] = lr
-        self.fp.epoch += 1                       # parameters changed behind the packs' back ...
-        plan = self._pack_plan()
+        self.fp.touch()                          # parameters changed behind the packs' back ...
+        plan = self.packs.adam_plan(self.fp.flat, self.n_active) if self.packs is not None else None
         if plan is not None:                     # ... so bring the optimiser-owned weight packs back in line right away: a graph
-            plan.pp.refresh(force=True)          # captured after this (GraphedTrainStep warm-up) relies on them being fresh
-            plan.pp.mark_fresh(self.fp)
+            plan.pp.refresh()                    # captured after this (graph-step warm-up) must not capture their pack launch
+            self.packs.mark_fresh(plan.pp, self.fp)
 
     # -- checkpoint format of the reference: torch.optim state_dict (train_temporal.py:244,281) ------------
     def state_dict(self, model: nn.Module) -> dict:
@@ -395,7 +382,52 @@ def _retire_collective_watchdog_work(seconds: float = 0.4) -> None:
     time.sleep(seconds)
 
 
-class GraphedTrainStep:
+class _GraphStep:
+    """What the captured train steps share: static batch buffers, the eager warm-up before the capture, and the replay protocol
+    of the weight packs their captured Adam launch writes (``owned``: FusedAdam.wrote at the capture, or None)."""
+    owned = None
+
+    def _static_batch(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor]) -> None:
+        self.xx, self.yy = xx.clone(), yy.clone()
+        self.msk = msk.clone() if msk is not None else None
+
+    def stage(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor] = None) -> None:
+        self.xx.copy_(xx, non_blocking=True)
+        self.yy.copy_(yy, non_blocking=True)
+        if msk is not None and self.msk is not None:
+            self.msk.copy_(msk, non_blocking=True)
+
+    def _warm_up(self, n: int, body: Callable[[], None], settle: bool = False) -> None:
+        """eager warm-up on a side stream (allocator + lazy inits).  The warm-up iterations are NOT training steps: parameters,
+        Adam moments and the step counter are restored afterwards (a fine-tune of a pretrained checkpoint must not receive
+        unscheduled full-lr updates before its first replay)"""
+        snap = self.opt.snapshot()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(n):
+                body()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        if settle:
+            _retire_collective_watchdog_work()
+        self.opt.restore(snap)
+
+    def _replay(self, lr: Optional[float], run: Callable[[], None]) -> Tensor:
+        """the graphs hold no pack launch for the set their Adam writes (it was fresh at the capture): refresh it first if
+        anything moved the parameters since (load_state_dict, touch()); after the replay its Adam has written it"""
+        opt = self.opt
+        opt.stage_hyper(lr)
+        if self.owned is not None:
+            opt.packs.ensure_fresh(self.owned)
+        run()
+        opt.fp.touch()
+        if self.owned is not None:
+            opt.packs.mark_fresh(self.owned, opt.fp)
+        return self.loss
+
+
+class GraphedTrainStep(_GraphStep):
     """Captures forward + loss + backward + clip + Adam of a fixed-shape batch into one hipGraph.
 
     ``stage(xx, yy, msk)`` copies a batch into the static input buffers, ``replay(lr)`` runs the step.  The
@@ -406,8 +438,7 @@ class GraphedTrainStep:
                  T_bundle: int = 1, noise_scale: float = 0.0, warmup: int = 2, reducer=None,
                  grad_scale: float = 1.0, capture_collectives: bool = False):
         self.model, self.opt = model, opt
-        self.xx, self.yy = xx.clone(), yy.clone()
-        self.msk = msk.clone() if msk is not None else None
+        self._static_batch(xx, yy, msk)
         if reducer is not None and getattr(reducer, "world", 1) > 1 and not capture_collectives:
             raise ValueError("GraphedTrainStep captures the WHOLE step into one graph; pass capture_collectives=True to "
                              "capture the bucket all-reduces with it, or use SegmentedTrainStep (collectives between graphs)")
@@ -425,24 +456,12 @@ class GraphedTrainStep:
             self.reducer.skip_zero_tail = False
         self.grad_scale = grad_scale
         self.T_bundle, self.noise_scale = T_bundle, noise_scale
-        # eager warm-up on a side stream (allocator + lazy inits).  The warm-up iterations are NOT training steps:
-        # parameters, Adam moments and the step counter are restored afterwards (a fine-tune of a pretrained
-        # checkpoint must not receive unscheduled full-lr updates before its first replay)
-        snap = opt.snapshot()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._body(stage=True)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        if self.reducer is not None:
-            _retire_collective_watchdog_work()
-        opt.restore(snap)
+        self._warm_up(warmup, lambda: self._body(stage=True), settle=self.reducer is not None)
         self.graph = torch.cuda.CUDAGraph()
         opt.zero_grad()
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             self.loss, self.pred = self._body(stage=False)
+        self.owned = opt.wrote
         self.warmup_steps = warmup
 
     def _body(self, stage: bool):
@@ -460,21 +479,11 @@ class GraphedTrainStep:
         opt.launch(self.grad_scale)
         return loss.detach(), pred.detach()
 
-    def stage(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor] = None) -> None:
-        self.xx.copy_(xx, non_blocking=True)
-        self.yy.copy_(yy, non_blocking=True)
-        if msk is not None and self.msk is not None:
-            self.msk.copy_(msk, non_blocking=True)
-
     def replay(self, lr: Optional[float] = None) -> Tensor:
-        self.opt.stage_hyper(lr)
-        self.graph.replay()
-        self.opt.fp.epoch += 1        # the captured Adam + pack launches rewrote the parameters and their packed copies
-        self.opt.mark_packs_fresh()   # (the captured Adam wrote the weight packs too, if it owned them at capture time)
-        return self.loss
+        return self._replay(lr, self.graph.replay)
 
 
-class SegmentedTrainStep:
+class SegmentedTrainStep(_GraphStep):
     """The data-parallel train step (any T_ar, as train_temporal_parallel.py:214-244 runs it under DDP) as a CHAIN of
     hipGraphs, cut where a gradient bucket becomes final, so that the RCCL all-reduce of bucket k runs on the reducer's side stream while the compute stream
     replays the backward of the earlier stages - the overlap torch-DDP gets from autograd hooks
@@ -497,8 +506,7 @@ class SegmentedTrainStep:
                  noise_scale: float = 0.0, warmup: int = 2, T_bundle: int = 1):
         self.T_bundle = T_bundle
         self.model, self.opt, self.reducer = model, opt, reducer
-        self.xx, self.yy = xx.clone(), yy.clone()
-        self.msk = msk.clone() if msk is not None else None
+        self._static_batch(xx, yy, msk)
         self.noise_scale = noise_scale
         self.grad_scale = reducer.grad_scale
         depth = len(model.blocks)
@@ -506,20 +514,16 @@ class SegmentedTrainStep:
         # buckets in backward order (tail excluded); a bucket whose first stage is b > 0 needs a cut at boundary b
         self.bwd_buckets = [k for k in range(reducer.n_buckets - 1, -1, -1) if k != reducer.tail_bucket]
         self.cut_at = sorted({norm(reducer.first_stage_of_bucket(k)) for k in self.bwd_buckets} - {0})
-        snap = opt.snapshot()
+
+        def eager_step():
+            opt.stage_hyper(opt.lr)
+            for fn in self._segment_fns():
+                fn()
+            opt.launch(self.grad_scale)
+
         reducer.detach()
         try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(warmup):
-                    opt.stage_hyper(opt.lr)
-                    for fn in self._segment_fns():
-                        fn()
-                    opt.launch(self.grad_scale)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            opt.restore(snap)
+            self._warm_up(warmup, eager_step)
             self.graphs: List[torch.cuda.CUDAGraph] = []
             pool = torch.cuda.graph_pool_handle()
             for fn in self._segment_fns():
@@ -530,6 +534,7 @@ class SegmentedTrainStep:
             self.opt_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.opt_graph, pool=pool, capture_error_mode="thread_local"):
                 opt.launch(self.grad_scale)
+            self.owned = opt.wrote
         finally:
             reducer.attach()
             model._boundary_hook = None
@@ -576,15 +581,11 @@ class SegmentedTrainStep:
                 leaf.grad = None
             yield seg
 
-    def stage(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor] = None) -> None:
-        self.xx.copy_(xx, non_blocking=True)
-        self.yy.copy_(yy, non_blocking=True)
-        if msk is not None and self.msk is not None:
-            self.msk.copy_(msk, non_blocking=True)
-
     def replay(self, lr: Optional[float] = None) -> Tensor:
+        return self._replay(lr, self._run)
+
+    def _run(self) -> None:
         red = self.reducer
-        self.opt.stage_hyper(lr)
         red.begin_step()
         for g, k in zip(self.graphs, self.bwd_buckets):
             g.replay()
@@ -595,9 +596,6 @@ class SegmentedTrainStep:
             red._launched[red.tail_bucket] = True
         red.finish()                          # compute stream joins the side stream
         self.opt_graph.replay()
-        self.opt.fp.epoch += 1                # as FusedAdam.launch: an eager backward of an earlier forward must fail
-        self.opt.mark_packs_fresh()
-        return self.loss
 
 
 # ------------------------------------------------------------------------------------------------------

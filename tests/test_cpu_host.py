@@ -297,3 +297,34 @@ def test_adam_pack_plan_tables(built_lib):
     pp2.jobs = [(bad, 64, 200, 200, False), (bad, 200, 64, 200, True)]
     pp2.n, pp2.bufs = 2, [torch.zeros(64 * 200, dtype=torch.bfloat16)] * 2
     assert ops.AdamPackPlan.build(bad.view(-1), bad.numel(), pp2) is None
+
+
+def test_model_packs_freshness_rule():
+    """packs.ModelPacks: only the set the optimiser marked is fresh, and only until the parameters move - FlatParams.touch()
+    (optimiser step, graph replay, a write through fp.flat) or a tensor version of one of its sources (load_state_dict)"""
+    from dpot_amd.packs import ModelPacks
+    from dpot_amd.train import FlatParams
+
+    class FakeSet:
+        def __init__(self, w):
+            self.jobs, self.launches = [(w,), (w,)], 0
+
+        def refresh(self):
+            self.launches += 1
+
+    lin = torch.nn.Linear(4, 4)
+    fp = FlatParams(lin, tail_prefixes=())
+    mine, other, mp = FakeSet(lin.weight), FakeSet(lin.weight), ModelPacks()
+    mp.mark_fresh(mine, fp)
+    mp.ensure_fresh(mine)
+    mp.ensure_fresh(other)
+    assert (mine.launches, other.launches) == (0, 1)
+    fp.touch()
+    mp.ensure_fresh(mine)
+    assert mine.launches == 1
+    mp.mark_fresh(mine, fp)
+    with torch.no_grad():
+        lin.weight.add_(1.0)                                 # an in-place write through autograd: a new tensor version
+    assert not mp.is_fresh(mine)
+    mp.mark_fresh(mine, fp)
+    assert mp.is_fresh(mine) and not mp.is_fresh(other)

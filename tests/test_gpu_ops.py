@@ -660,7 +660,7 @@ def test_bf16_panel_model_step_within_bf16_bound_of_fp32(ops, monkeypatch):
         try:
             y, _ = m(x)
             (y ** 2).sum().backward()
-            used = getattr(m, "_panel_packs_bf16", None) is not None
+            used = m.packs.get("bf16") is not None
         finally:
             ops.set_mlp_precision(None)
         return y.detach(), {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}, used

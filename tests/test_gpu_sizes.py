@@ -592,7 +592,7 @@ def test_vs_reference_golden(name, B):
             ((y * up_y).sum() + (c * up_c).sum()).backward()
             torch.cuda.synchronize()
             if info is not None:
-                info["p6"] = getattr(m._afno_packs, "fwd6", None) is not None
+                info["p6"] = getattr(m.packs.get("afno"), "fwd6", None) is not None
         finally:
             ops.set_mlp_precision(None)
         return y.detach(), c.detach(), xg.grad, OrderedDict((k, p.grad) for k, p in m.named_parameters())

@@ -556,31 +556,103 @@ def test_adam_writes_the_weight_packs(monkeypatch):
         xx, yy, msk = _batch(cfg, 4)
         opt = _opt(m)
         losses = [train_step(m, opt, xx, yy, msk, lr=lr)[0].item() for lr in (1e-3, 2e-3, 5e-4)]
-        pp = m._panel_packs_bf16
+        pp = m.packs.get("bf16")
+        plan = m.packs.adam_plan(opt.fp.flat, opt.n_active)
         if packs == "1":
-            assert opt._pack_plan() is not None and opt._pack_plan().ntiles == 2 * 2 * (512 // 64) * (256 // 256)
-            assert pp.is_fresh()
+            assert plan is not None and plan.ntiles == 2 * 2 * (512 // 64) * (256 // 256) and opt.wrote is pp
+            assert m.packs.is_fresh(pp)
             mine = [b.clone() for b in pp.bufs]
-            pp.refresh(force=True)
+            pp.refresh()
             assert all(torch.equal(a, b) for a, b in zip(mine, pp.bufs)), "packs written by Adam != packs of the parameters"
             # (c) load_state_dict bumps the tensor versions: the packs are no longer trusted
             m.load_state_dict(m.state_dict())
-            assert not pp.is_fresh()
+            assert not m.packs.is_fresh(pp)
             snap = opt.snapshot()
             opt.restore(snap)                      # re-packs eagerly and trusts them again (graph warm-up relies on it)
-            assert pp.is_fresh()
+            assert m.packs.is_fresh(pp)
         else:
-            assert opt._pack_plan() is None and not pp.is_fresh()
+            assert plan is None and opt.wrote is None and not m.packs.is_fresh(pp)
         g = GraphedTrainStep(m, opt, xx, yy, msk, warmup=1)
+        assert g.owned is (pp if packs == "1" else None)
         losses += [g.replay(lr).item() for lr in (1e-3, 3e-3, 1e-3)]
         if packs == "1":
             mine = [b.clone() for b in pp.bufs]
-            pp.refresh(force=True)
+            pp.refresh()
             assert all(torch.equal(a, b) for a, b in zip(mine, pp.bufs)), "packs after graph replays"
         runs[packs] = (losses, opt.fp.flat.clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone())
     assert runs["0"][0] == runs["1"][0], (runs["0"][0], runs["1"][0])
     for a, b in zip(runs["0"][1:], runs["1"][1:]):
         assert torch.equal(a, b)
+
+
+_BF16_KW = dict(R.MINI, embed_dim=256, n_blocks=2, depth=2, mlp_ratio=2)     # (channel MLP on the bf16 packs Adam writes)
+
+
+def _bf16_model(salt=7, mlp="bf16"):
+    m, cfg = build(_BF16_KW, salt=salt)
+    m.mlp_precision = mlp
+    return m, cfg
+
+
+@pytest.mark.parametrize("kind", ["graphed", "segmented"])
+def test_replay_after_load_state_dict_equals_eager_step(kind):
+    """a captured step whose Adam writes the bf16 packs holds no pack launch; after load_state_dict (the documented resume
+    path) its next replay must run on packs of the NEW parameters - as the eager step from the same state does"""
+    from dpot_amd.dp import BucketedGradReducer
+    from dpot_amd.train import GraphedTrainStep, SegmentedTrainStep, train_step
+    m, cfg = _bf16_model()
+    xx, yy, msk = _batch(cfg, 4)
+    opt = _opt(m)
+    if kind == "graphed":
+        step = GraphedTrainStep(m, opt, xx, yy, msk, warmup=1)
+    else:
+        step = SegmentedTrainStep(m, opt, BucketedGradReducer(opt.fp, n_buckets=4, overlap=True), xx, yy, msk, warmup=1)
+    step.replay(1e-3)
+    m.load_state_dict(R.recipe_state_dict(cfg, salt=11))
+    snap = opt.snapshot()
+    loss = step.replay(2e-3).item()
+    m2, _ = _bf16_model()
+    opt2 = _opt(m2)
+    opt2.restore(snap)                                         # same parameters, moments and step counter
+    assert loss == train_step(m2, opt2, xx, yy, msk, lr=2e-3)[0].item()
+    if kind == "graphed":
+        assert torch.equal(opt.fp.flat, opt2.fp.flat)
+    else:                                                      # (tolerance of the segmented-vs-eager test above)
+        d = (opt.fp.flat - opt2.fp.flat).double().norm() / opt2.fp.flat.double().norm()
+        assert d.item() <= 1e-5, d.item()
+
+
+def test_replay_marks_fresh_only_the_packs_its_adam_wrote():
+    """captured with the f32 channel MLP, the graph's Adam writes no bf16 packs: a bf16 forward after a replay must re-pack,
+    not trust packs the replay never wrote"""
+    from dpot_amd.train import GraphedTrainStep
+    m, cfg = _bf16_model(mlp="f32")
+    xx, yy, msk = _batch(cfg, 4)
+    g = GraphedTrainStep(m, _opt(m), xx, yy, msk, warmup=1)
+    assert g.owned is None
+    m.mlp_precision = "bf16"
+    with torch.no_grad():
+        m(xx)                                                  # makes the bf16 packs
+        g.replay(1e-3)
+        after_replay = m(xx)[0]
+        m.packs.get("bf16").refresh()
+        after_refresh = m(xx)[0]
+    assert torch.equal(after_replay, after_refresh)
+
+
+def test_touch_after_a_flat_write_repacks():
+    """writes through fp.flat change no tensor version: FlatParams.touch() declares them, and the next forward re-packs"""
+    from dpot_amd.train import train_step
+    m, cfg = _bf16_model()
+    xx, yy, msk = _batch(cfg, 4)
+    opt = _opt(m)
+    train_step(m, opt, xx, yy, msk, lr=1e-3)                  # Adam wrote the packs: they are fresh
+    m2, _ = _bf16_model(salt=11)
+    fp2 = _opt(m2).fp                                          # (the same flat layout as the model under test)
+    with torch.no_grad():
+        opt.fp.flat[:] = fp2.flat
+        opt.fp.touch()
+        assert torch.equal(m(xx)[0], m2(xx)[0])
 
 
 @pytest.mark.parametrize("E,mh,depth", [(1024, 4096, 3), (1536, 6144, 2)])
