@@ -59,6 +59,16 @@ class AdamRange(C.Structure):
     _fields_ = [("start", C.c_int64), ("len", C.c_int64)]
 
 
+class LambChunk(C.Structure):
+    """mirror of struct dpot_lamb_chunk"""
+    _fields_ = [("off", C.c_int64), ("len", C.c_int32), ("tensor", C.c_int32)]
+
+
+class LambTensor(C.Structure):
+    """mirror of struct dpot_lamb_tensor"""
+    _fields_ = [("first_chunk", C.c_int32), ("n_chunks", C.c_int32)]
+
+
 class LayoutJob(C.Structure):
     """mirror of struct dpot_layout_job"""
     _fields_ = [("src", c_fp), ("add", c_fp), ("dst", c_fp), ("d0", C.c_int32), ("d1", C.c_int32), ("d2", C.c_int32),
@@ -146,6 +156,9 @@ SIGNATURES = {
     "dpot_sumsq": (c_i, [c_fp, c_i64, c_fp, c_fp, c_i, c_fp]),
     "dpot_adam_step": (c_i, [c_fp] * 4 + [c_i64, c_fp, c_fp, c_f, c_fp]),
     "dpot_adam_stage": (c_i, [c_fp, c_fp, c_f, c_d, c_d, c_f, c_f, c_f, c_i, c_fp]),
+    "dpot_lamb_chunk_elems": (c_i, []),
+    "dpot_lamb_step": (c_i, [c_fp] * 5 + [c_fp, c_f, c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_i, c_fp]),
+    "dpot_lamb_stage": (c_i, [c_fp, c_fp, c_d, c_d, c_d, c_f, c_f, c_f, c_f, c_i, c_i, c_fp]),
     "dpot_noise_chunks": (c_i, [c_i, c_i]),
     "dpot_noise_inject": (c_i, [c_fp] * 4 + [c_f] + [c_i] * 3 + [c_fp]),
     "dpot_noise_inject_rng": (c_i, [c_fp] * 4 + [c_f] + [c_i] * 3 + [c_fp]),

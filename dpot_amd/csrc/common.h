@@ -186,10 +186,8 @@ __device__ __forceinline__ void block_sum2_d(double& a, double& b, double* sh) {
 struct AdamCoef {
   float b1, b2, omb1, omb2, eps, wd, step, sb2, gs;
 };
-__device__ __forceinline__ AdamCoef adam_coef(const float* __restrict__ hyper, const float* __restrict__ sumsq,
-                                              float grad_scale) {
-  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
-  const float bc1 = hyper[5], bc2 = hyper[6], max_norm = hyper[7];
+// grad_scale times the clip coefficient of clip_grad_norm_ (sumsq == NULL: no clipping); shared with the LAMB kernels
+__device__ __forceinline__ float clip_grad_scale(float max_norm, const float* __restrict__ sumsq, float grad_scale) {
   float gs = grad_scale;
   if (sumsq) {
     const float total_norm = sqrtf(sumsq[0]) * grad_scale;
@@ -197,6 +195,13 @@ __device__ __forceinline__ AdamCoef adam_coef(const float* __restrict__ hyper, c
     if (coef > 1.f) coef = 1.f;
     gs *= coef;
   }
+  return gs;
+}
+__device__ __forceinline__ AdamCoef adam_coef(const float* __restrict__ hyper, const float* __restrict__ sumsq,
+                                              float grad_scale) {
+  const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
+  const float bc1 = hyper[5], bc2 = hyper[6], max_norm = hyper[7];
+  const float gs = clip_grad_scale(max_norm, sumsq, grad_scale);
   return AdamCoef{b1, b2, 1.f - b1, 1.f - b2, eps, wd, lr / bc1, sqrtf(bc2), gs};
 }
 __device__ __forceinline__ void adam_update(const AdamCoef& c, float& pv, float gv, float& mv, float& vv) {

@@ -1,5 +1,5 @@
 // loss_opt.hip - masked relative-L2 loss (utils/criterion.py:38-59), global gradient norm + clip
-// (train_temporal.py:228), fused flat-buffer Adam (utils/optimizer.py:26-52), noise injection
+// (train_temporal.py:228), fused flat-buffer Adam (utils/optimizer.py:26-52) and LAMB (:359-499), noise injection
 // (train_temporal.py:205).  All HBM-bound streaming kernels; no host synchronisation anywhere: the loss,
 // the gradient norm and the learning-rate schedule live in device memory so the whole step can be captured
 // in one hipGraph.
@@ -244,6 +244,149 @@ __global__ void adam_stage_kernel(float* __restrict__ hyper, long long* __restri
   hyper[5] = (float)(1.0 - pow(b1, (double)t));
   hyper[6] = (float)(1.0 - pow(b2, (double)t));
   hyper[7] = max_norm;
+}
+
+// ---- fused LAMB over a flat buffer (utils/optimizer.py:359-499) ---------------------------------------------------
+// Per-tensor norms need a segmented reduction: the buffer is cut into chunks of <= LAMB_CHUNK elements that each lie in
+// ONE tensor (host-built table), one 256-thread workgroup per chunk writes its partial {sum p^2, sum r^2} in double, and
+// one wave per tensor sums that tensor's partials in chunk order.  No atomics: every step reduces in the same order, so
+// data-parallel replicas that start equal stay equal without talking to each other.
+constexpr int LAMB_CHUNK = 8192;   // 8 float4 per lane: a 110 M-parameter model is ~13.5 K workgroups
+
+struct LambCoef {
+  float b1, b2, omb1, omb2, eps, wd, step, gs;
+};
+__device__ __forceinline__ LambCoef lamb_coef(const float* __restrict__ hyper, const float* __restrict__ sumsq,
+                                              float grad_scale) {
+  return LambCoef{hyper[0], hyper[1], hyper[2], hyper[3], hyper[4], hyper[5], hyper[7],
+                  clip_grad_scale(hyper[6], sumsq, grad_scale)};
+}
+// the Adam direction r of one element (m, v already updated; p the value BEFORE this step's update).  The moments pass
+// and the update pass both form r with this one expression (no product a contraction could fuse differently), so the
+// trust-ratio update uses bit for bit the r whose norm it was scaled by.
+__device__ __forceinline__ float lamb_r(const LambCoef& c, float pv, float mv, float vv) {
+  float r = mv / (sqrtf(vv) + c.eps);
+  if (c.wd != 0.f) r = fmaf(c.wd, pv, r);
+  return r;
+}
+__device__ __forceinline__ float lamb_moments(const LambCoef& c, float pv, float gv, float& mv, float& vv) {
+  gv *= c.gs;
+  mv = fmaf(c.b1, mv, c.omb1 * gv);
+  vv = fmaf(c.b2, vv, (c.omb2 * gv) * gv);
+  return lamb_r(c, pv, mv, vv);
+}
+
+// one workgroup per chunk: moments, r, the chunk's partial norms; ADAM (trust ratio not applied): also p -= lr*bc*r
+template <bool ADAM>
+__global__ __launch_bounds__(256) void lamb_moments_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v,
+                                                           const float* __restrict__ hyper,
+                                                           const float* __restrict__ sumsq, float grad_scale,
+                                                           const dpot_lamb_chunk* __restrict__ chunks,
+                                                           double* __restrict__ part) {
+  __shared__ double sh[32];
+  const LambCoef c = lamb_coef(hyper, sumsq, grad_scale);
+  const dpot_lamb_chunk ch = chunks[blockIdx.x];
+  float* __restrict__ pc = p + ch.off;
+  const float* __restrict__ gc = g + ch.off;
+  float* __restrict__ mc = m + ch.off;
+  float* __restrict__ vc = v + ch.off;
+  double sp = 0.0, sr = 0.0;
+  auto one = [&](float& pv, float gv, float& mv, float& vv) __attribute__((always_inline)) {
+    const float r = lamb_moments(c, pv, gv, mv, vv);
+    sp += (double)pv * (double)pv;
+    sr += (double)r * (double)r;
+    if (ADAM) pv = fmaf(-c.step, r, pv);
+  };
+  const int n4 = ch.len >> 2;
+  for (int i = threadIdx.x; i < n4; i += 256) {   // chunk offsets are multiples of 4 floats: 16-byte aligned
+    float4 pv = reinterpret_cast<const float4*>(pc)[i];
+    const float4 gv = reinterpret_cast<const float4*>(gc)[i];
+    float4 mv = reinterpret_cast<const float4*>(mc)[i];
+    float4 vv = reinterpret_cast<const float4*>(vc)[i];
+    one(pv.x, gv.x, mv.x, vv.x);
+    one(pv.y, gv.y, mv.y, vv.y);
+    one(pv.z, gv.z, mv.z, vv.z);
+    one(pv.w, gv.w, mv.w, vv.w);
+    reinterpret_cast<float4*>(mc)[i] = mv;
+    reinterpret_cast<float4*>(vc)[i] = vv;
+    if (ADAM) reinterpret_cast<float4*>(pc)[i] = pv;
+  }
+  const int i = (n4 << 2) + threadIdx.x;          // the last 1-3 elements of a tensor whose size is not a multiple of 4
+  if (i < ch.len) {
+    float pv = pc[i], mv = mc[i], vv = vc[i];
+    one(pv, gc[i], mv, vv);
+    mc[i] = mv;
+    vc[i] = vv;
+    if (ADAM) pc[i] = pv;
+  }
+  block_sum2_d(sp, sr, sh);
+  if (threadIdx.x == 0) {
+    part[2 * blockIdx.x] = sp;
+    part[2 * blockIdx.x + 1] = sr;
+  }
+}
+
+// one wave per tensor: its chunk partials in fixed order -> weight_norm (clamped), adam_norm, trust_ratio
+__global__ __launch_bounds__(64) void lamb_norms_kernel(const double* __restrict__ part,
+                                                        const dpot_lamb_tensor* __restrict__ tensors,
+                                                        const float* __restrict__ hyper, float* __restrict__ norms,
+                                                        int ntensors) {
+  const dpot_lamb_tensor t = tensors[blockIdx.x];
+  double sp = 0.0, sr = 0.0;
+  for (int k = threadIdx.x; k < t.n_chunks; k += 64) {
+    sp += part[2 * (t.first_chunk + k)];
+    sr += part[2 * (t.first_chunk + k) + 1];
+  }
+  sp = wave_sum_d(sp);
+  sr = wave_sum_d(sr);
+  if (threadIdx.x == 0) {
+    const float clamp = hyper[8];
+    float wn = (float)sqrt(sp);
+    if (wn > clamp) wn = clamp;                     // torch.clamp(0, clamp_value); a NaN norm stays NaN
+    const float an = (float)sqrt(sr);
+    norms[blockIdx.x] = wn;
+    norms[ntensors + blockIdx.x] = an;
+    norms[2 * ntensors + blockIdx.x] = (wn == 0.f || an == 0.f) ? 1.f : wn / an;
+  }
+}
+
+// LAMB proper (adam=False): p -= (lr*bc * trust_ratio[tensor]) * r, r re-formed from the updated moments and the old p
+__global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ p, const float* __restrict__ m,
+                                                         const float* __restrict__ v, const float* __restrict__ hyper,
+                                                         const dpot_lamb_chunk* __restrict__ chunks,
+                                                         const float* __restrict__ trust) {
+  const LambCoef c = lamb_coef(hyper, nullptr, 1.f);
+  const dpot_lamb_chunk ch = chunks[blockIdx.x];
+  const float a = c.step * trust[ch.tensor];         // the reference's 0-d fp32 product step_size * trust_ratio
+  float* __restrict__ pc = p + ch.off;
+  const float* __restrict__ mc = m + ch.off;
+  const float* __restrict__ vc = v + ch.off;
+  const int n4 = ch.len >> 2;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    float4 pv = reinterpret_cast<const float4*>(pc)[i];
+    const float4 mv = reinterpret_cast<const float4*>(mc)[i];
+    const float4 vv = reinterpret_cast<const float4*>(vc)[i];
+    pv.x = fmaf(-a, lamb_r(c, pv.x, mv.x, vv.x), pv.x);
+    pv.y = fmaf(-a, lamb_r(c, pv.y, mv.y, vv.y), pv.y);
+    pv.z = fmaf(-a, lamb_r(c, pv.z, mv.z, vv.z), pv.z);
+    pv.w = fmaf(-a, lamb_r(c, pv.w, mv.w, vv.w), pv.w);
+    reinterpret_cast<float4*>(pc)[i] = pv;
+  }
+  const int i = (n4 << 2) + threadIdx.x;
+  if (i < ch.len) pc[i] = fmaf(-a, lamb_r(c, pc[i], mc[i], vc[i]), pc[i]);
+}
+
+// host side of a LAMB step (as adam_stage_kernel: everything by value, the step counter on the device).  1 - beta is
+// formed in double as Python does (exp_avg.mul_(beta1).add_(grad, alpha=1 - beta1)); bc and lr*bc in double.
+__global__ void lamb_stage_kernel(float* __restrict__ hyper, long long* __restrict__ step, double lr, double b1,
+                                  double b2, float eps, float wd, float max_norm, float clamp, int debias, int advance) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const long long t = step[0] + advance;
+  step[0] = t;
+  const double bc = debias ? sqrt(1.0 - pow(b2, (double)t)) / (1.0 - pow(b1, (double)t)) : 1.0;
+  hyper[0] = (float)b1; hyper[1] = (float)b2; hyper[2] = (float)(1.0 - b1); hyper[3] = (float)(1.0 - b2);
+  hyper[4] = eps; hyper[5] = wd; hyper[6] = max_norm; hyper[7] = (float)(lr * bc); hyper[8] = clamp;
 }
 
 // ---- noise injection ----------------------------------------------------------------------------------------
@@ -566,6 +709,44 @@ extern "C" int dpot_adam_stage(float* hyper, int64_t* step, float lr, double bet
   hipLaunchKernelGGL(adam_stage_kernel, dim3(1), dim3(64), 0, as_stream(stream), hyper,
                      reinterpret_cast<long long*>(step), lr, beta1, beta2, eps, weight_decay, max_norm, advance);
   return check_launch("adam_stage_kernel");
+}
+
+extern "C" int dpot_lamb_chunk_elems(void) { return LAMB_CHUNK; }
+
+extern "C" int dpot_lamb_step(float* p, const float* g, float* m, float* v, const float* hyper, const float* sumsq,
+                              float grad_scale, const dpot_lamb_chunk* chunks_dev, int nchunks,
+                              const dpot_lamb_tensor* tensors_dev, int ntensors, double* part, float* norms, int adam,
+                              dpot_stream_t stream) {
+  DPOT_REQUIRE(p && g && m && v && hyper && chunks_dev && tensors_dev && part && norms, "lamb_step: null pointer");
+  DPOT_REQUIRE(nchunks > 0 && ntensors > 0 && ntensors <= nchunks, "lamb_step: bad table sizes");
+  DPOT_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), "lamb_step: buffers must be 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  if (adam)
+    hipLaunchKernelGGL(lamb_moments_kernel<true>, dim3(nchunks), dim3(256), 0, st, p, g, m, v, hyper, sumsq, grad_scale,
+                       chunks_dev, part);
+  else
+    hipLaunchKernelGGL(lamb_moments_kernel<false>, dim3(nchunks), dim3(256), 0, st, p, g, m, v, hyper, sumsq,
+                       grad_scale, chunks_dev, part);
+  int rc = check_launch("lamb_moments_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(lamb_norms_kernel, dim3(ntensors), dim3(64), 0, st, (const double*)part, tensors_dev, hyper, norms,
+                     ntensors);
+  rc = check_launch("lamb_norms_kernel");
+  if (rc || adam) return rc;
+  hipLaunchKernelGGL(lamb_apply_kernel, dim3(nchunks), dim3(256), 0, st, p, (const float*)m, (const float*)v, hyper,
+                     chunks_dev, (const float*)(norms + 2 * (size_t)ntensors));
+  return check_launch("lamb_apply_kernel");
+}
+
+extern "C" int dpot_lamb_stage(float* hyper, int64_t* step, double lr, double beta1, double beta2, float eps,
+                               float weight_decay, float max_norm, float clamp_value, int debias, int advance,
+                               dpot_stream_t stream) {
+  DPOT_REQUIRE(hyper && step, "lamb_stage: null pointer");
+  DPOT_REQUIRE(advance >= 0, "lamb_stage: advance must be >= 0");
+  hipLaunchKernelGGL(lamb_stage_kernel, dim3(1), dim3(64), 0, as_stream(stream), hyper,
+                     reinterpret_cast<long long*>(step), lr, beta1, beta2, eps, weight_decay, max_norm, clamp_value,
+                     debias ? 1 : 0, advance);
+  return check_launch("lamb_stage_kernel");
 }
 
 extern "C" int dpot_noise_chunks(int S, int C) {

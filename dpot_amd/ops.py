@@ -1356,6 +1356,58 @@ def adam_stage(hyper: Tensor, step: Tensor, lr: float, beta1: float, beta2: floa
                                       max_norm, advance, _stream()), "adam_stage")
 
 
+class LambPlan:
+    """Device tables of dpot_lamb_step for one flat buffer: tensor k = the `numels[k]` elements at element offset
+    `offsets[k]` (a multiple of 4; padding between tensors belongs to no chunk and is never read or written), cut into
+    chunks of <= dpot_lamb_chunk_elems() elements that each lie in one tensor.  `part` is the per-chunk scratch of the
+    norm reduction.  Built once on the host; the tables stay valid while the buffer does not move."""
+
+    def __init__(self, offsets, numels, size: int, device):
+        lib = _lib.load()
+        ce = lib.dpot_lamb_chunk_elems()
+        if not offsets or len(offsets) != len(numels):
+            raise ValueError("LambPlan: need one offset per tensor and at least one tensor")
+        chunks, tensors, end = [], [], 0
+        for k, (off, n) in enumerate(zip(offsets, numels)):
+            off, n = int(off), int(n)
+            if off % 4 or n <= 0 or off < end or off + n > size:
+                raise ValueError(f"LambPlan: tensor {k} at [{off}, {off + n}) is not a 4-aligned, ordered range of the "
+                                 f"{size}-element buffer")
+            tensors.append((len(chunks), (n + ce - 1) // ce))
+            chunks += [(off + s, min(ce, n - s), k) for s in range(0, n, ce)]
+            end = off + n
+        self.size, self.nchunks, self.ntensors, self.chunk_elems = size, len(chunks), len(tensors), ce
+        self.chunks_dev = _device_table(_lib.LambChunk, chunks, device)
+        self.tensors_dev = _device_table(_lib.LambTensor, tensors, device)
+        self.part = torch.zeros(2 * len(chunks), dtype=torch.float64, device=device)
+
+
+def lamb_step(plan: LambPlan, p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, sumsq_: Optional[Tensor],
+              norms: Tensor, grad_scale: float = 1.0, adam: bool = False) -> None:
+    """one LAMB step over the tensors of `plan` (include/dpot_hip.h dpot_lamb_step); norms (3 * plan.ntensors floats)
+    receives weight_norm, adam_norm and trust_ratio per tensor"""
+    for t, name in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+        _req(t, name)
+        if t.numel() < plan.size:
+            raise _lib.DpotHipError(f"lamb_step: {name} has {t.numel()} elements, the plan addresses {plan.size}")
+    if norms.dtype != torch.float32 or norms.numel() < 3 * plan.ntensors or not norms.is_contiguous():
+        raise _lib.DpotHipError(f"lamb_step: norms must be >= {3 * plan.ntensors} contiguous float32")
+    check(_lib.load().dpot_lamb_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), hyper.data_ptr(), _p(sumsq_),
+                                     grad_scale, plan.chunks_dev.data_ptr(), plan.nchunks, plan.tensors_dev.data_ptr(),
+                                     plan.ntensors, plan.part.data_ptr(), norms.data_ptr(), int(bool(adam)), _stream()),
+          "lamb_step")
+
+
+def lamb_stage(hyper: Tensor, step: Tensor, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+               max_norm: float, clamp_value: float, debias: bool, advance: int = 1) -> None:
+    """step[0] += advance; hyper <- {betas, 1 - betas, eps, wd, max_norm, lr * bias correction(step), clamp_value} (>= 9
+    floats), by value in the launch packet as adam_stage"""
+    if hyper.numel() < 9:
+        raise _lib.DpotHipError("lamb_stage: hyper needs >= 9 floats")
+    check(_lib.load().dpot_lamb_stage(hyper.data_ptr(), step.data_ptr(), lr, beta1, beta2, eps, weight_decay, max_norm,
+                                      clamp_value, int(bool(debias)), advance, _stream()), "lamb_stage")
+
+
 _rng_states = {}
 
 

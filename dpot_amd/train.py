@@ -102,7 +102,32 @@ class FlatParams:
         self.epoch += 1
 
 
-class FusedAdam:
+class FlatOptimizer:
+    """What the fused optimisers over a FlatParams buffer share, and what the train steps duck-type on: ``fp``, ``lr``,
+    ``param_groups``, ``n_active``, ``packs``, ``wrote``; ``zero_grad``, ``stage_hyper(lr)`` (host side of a step, not
+    capturable), ``launch(grad_scale)`` (device side, capturable), ``step``, ``grad_norm``, ``snapshot`` / ``restore``,
+    ``state_dict(model)`` / ``load_state_dict(sd, model)``."""
+
+    @property
+    def n_active(self) -> int:
+        return self.fp.total if self.update_tail else self.fp.n_head
+
+    def zero_grad(self) -> None:
+        self.fp.zero_grad()
+
+    def step(self, lr: Optional[float] = None, grad_scale: float = 1.0) -> None:
+        self.stage_hyper(lr)
+        self.launch(grad_scale)
+
+    def grad_norm(self, grad_scale: float = 1.0) -> Tensor:
+        """global norm of the gradients currently in the flat buffer (device tensor; reading it synchronises):
+        after a step, the value its clip used (train_temporal.py:228 returns it from clip_grad_norm_)"""
+        out = torch.empty_like(self.sumsq)
+        ops.sumsq(self.fp.grad[:self.n_active], out, self._part)
+        return out.sqrt() * grad_scale
+
+
+class FusedAdam(FlatOptimizer):
     """Adam with L2 weight decay folded into the gradient (utils/optimizer.py:9-52 semantics) + global-norm clip
     (train_temporal.py:228), as ONE kernel over the flat buffer.  ``update_tail=False`` reproduces the single-GPU
     reference where cls_head has no gradient and is therefore skipped by the optimiser.
@@ -131,13 +156,6 @@ class FusedAdam:
         self.param_groups = [{"lr": lr}]          # minimal torch.optim surface for LR schedulers / logging
         self.packs = getattr(flat.model, "packs", None)       # the model's packs.ModelPacks (None: a model without one)
         self.wrote = None                         # the pack set the last launch() wrote along with the parameters, or None
-
-    @property
-    def n_active(self) -> int:
-        return self.fp.total if self.update_tail else self.fp.n_head
-
-    def zero_grad(self) -> None:
-        self.fp.zero_grad()
 
     def stage_hyper(self, lr: Optional[float] = None, advance: int = 1) -> None:
         """host side of a step (NOT capturable by design: call it right before a graph replay)"""
@@ -168,17 +186,6 @@ class FusedAdam:
         self.wrote = plan.pp if plan is not None else None
         if plan is not None:
             self.packs.mark_fresh(plan.pp, self.fp)
-
-    def step(self, lr: Optional[float] = None, grad_scale: float = 1.0) -> None:
-        self.stage_hyper(lr)
-        self.launch(grad_scale)
-
-    def grad_norm(self, grad_scale: float = 1.0) -> Tensor:
-        """global norm of the gradients currently in the flat buffer (device tensor; reading it synchronises):
-        after a step, the value its clip used (train_temporal.py:228 returns it from clip_grad_norm_)"""
-        out = torch.empty_like(self.sumsq)
-        ops.sumsq(self.fp.grad[:self.n_active], out, self._part)
-        return out.sqrt() * grad_scale
 
     # -- snapshot / restore (graph warm-up, tests) --------------------------------------------------------
     def snapshot(self):
@@ -234,6 +241,147 @@ class FusedAdam:
                 self.exp_avg[off:off + n].copy_(st["exp_avg"].reshape(-1))
                 self.exp_avg_sq[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
                 steps.add(int(st["step"]))
+        if len(steps) > 1:
+            raise ValueError(f"per-parameter step counts differ ({sorted(steps)}): the fused optimiser keeps one")
+        step = steps.pop() if steps else 0
+        self.step_dev.fill_(step)
+        self.step_count = step
+        g = sd.get("param_groups", [{}])[0]
+        self.lr = g.get("lr", self.lr)
+        self.betas = tuple(g.get("betas", self.betas))
+        self.eps = g.get("eps", self.eps)
+        self.weight_decay = g.get("weight_decay", self.weight_decay)
+        self.param_groups[0]["lr"] = self.lr
+
+
+class FusedLamb(FlatOptimizer):
+    """LAMB (utils/optimizer.py:359-499, the reference's ``--opt lamb``) + global-norm clip (train_temporal.py:228) over the
+    flat buffer, per parameter tensor: the trust ratio min(||p||, clamp_value) / ||r|| of every tensor is reduced on the
+    device (csrc/loss_opt.hip lamb_*: fixed-order chunked reduction, no atomics), so a step is capturable and bit-for-bit
+    reproducible.  Weight decay is added to the step r, not to the gradient (unlike Adam).  ``adam=True`` (what the
+    reference's scripts pass) does not apply the trust ratio but still records weight_norm / adam_norm / trust_ratio, as
+    the reference's state does.  Host/device protocol as FusedAdam (``stage_hyper`` then ``launch``).
+
+    LAMB writes no derived weight packs: ``wrote`` stays None, so a model with the bf16 channel MLP re-derives its packs
+    in the next forward (inside a captured graph too)."""
+
+    def __init__(self, flat: FlatParams, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
+                 eps: float = 1e-6, weight_decay: float = 0.0, clamp_value: float = 10.0, adam: bool = False,
+                 debias: bool = False, max_norm: Optional[float] = None, update_tail: bool = False):
+        if lr <= 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if eps < 0.0:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if weight_decay < 0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if clamp_value < 0.0:
+            raise ValueError(f"Invalid clamp value: {clamp_value}")
+        self.fp = flat
+        self.lr, self.betas, self.eps, self.weight_decay = lr, tuple(betas), eps, weight_decay
+        self.clamp_value, self.adam, self.debias = clamp_value, adam, debias
+        self.max_norm = max_norm
+        self.update_tail = update_tail
+        dev = flat.flat.device
+        self.exp_avg = torch.zeros_like(flat.flat)
+        self.exp_avg_sq = torch.zeros_like(flat.flat)
+        self.hyper = torch.zeros(16, dtype=torch.float32, device=dev)
+        self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
+        n_act = self.n_active
+        # the tensors the optimiser updates (FlatParams.offsets are ordered; the tail starts at n_head)
+        self.members = [k for k, off in enumerate(flat.offsets) if off < n_act]
+        self.plan = ops.LambPlan([flat.offsets[k] for k in self.members],
+                                 [flat.params[k].numel() for k in self.members], n_act, dev)
+        nt = len(self.members)
+        self.norms = torch.zeros(3 * nt, dtype=torch.float32, device=dev)
+        self.weight_norm, self.adam_norm, self.trust_ratio = self.norms[:nt], self.norms[nt:2 * nt], self.norms[2 * nt:]
+        self.step_count = 0
+        self.param_groups = [{"lr": lr}]
+        self.packs = getattr(flat.model, "packs", None)
+        self.wrote = None                         # LAMB never writes the weight packs
+
+    def stage_hyper(self, lr: Optional[float] = None, advance: int = 1) -> None:
+        """host side of a step (NOT capturable by design: call it right before a graph replay)"""
+        if lr is not None:
+            self.lr = lr
+            self.param_groups[0]["lr"] = lr
+        self.step_count += advance
+        ops.lamb_stage(self.hyper, self.step_dev, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                       self.max_norm if self.max_norm is not None else 0.0, self.clamp_value, self.debias, advance)
+
+    def launch(self, grad_scale: float = 1.0) -> None:
+        """device side of a step (capturable): ||g||^2 (with clipping), then the LAMB launches"""
+        use_clip = self.max_norm is not None
+        if use_clip:
+            ops.sumsq(self.fp.grad[:self.n_active], self.sumsq, self._part)
+        ops.lamb_step(self.plan, self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, self.hyper,
+                      self.sumsq if use_clip else None, self.norms, grad_scale, self.adam)
+        self.fp.touch()
+        self.wrote = None
+
+    # -- snapshot / restore (graph warm-up, tests) --------------------------------------------------------
+    def snapshot(self):
+        return (self.fp.flat.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.step_dev.clone(),
+                self.norms.clone(), self.step_count, self.lr)
+
+    def restore(self, snap) -> None:
+        flat, m, v, sd, norms, sc, lr = snap
+        self.fp.flat.copy_(flat)
+        self.exp_avg.copy_(m)
+        self.exp_avg_sq.copy_(v)
+        self.step_dev.copy_(sd)
+        self.norms.copy_(norms)
+        self.step_count, self.lr = sc, lr
+        self.param_groups[0]["lr"] = lr
+        self.fp.touch()                          # no pack is marked fresh: the next forward re-derives what it needs
+
+    # -- checkpoint format of the reference's Lamb (a torch.optim.Optimizer state_dict) ---------------------
+    def state_dict(self, model: nn.Module) -> dict:
+        """{'state': {i: {'step', 'exp_avg', 'exp_avg_sq', 'weight_norm', 'adam_norm', 'trust_ratio'}}, 'param_groups':
+        [{'lr', 'betas', 'eps', 'weight_decay', 'params'}]}, i = index in ``model.parameters()`` order; the norms are 0-d
+        tensors.  Tensors the optimiser does not update have no entry."""
+        order = {id(p): i for i, p in enumerate(model.parameters())}
+        state = {}
+        step = int(self.step_dev.item())
+        if step > 0:
+            for j, k in enumerate(self.members):
+                p, off = self.fp.params[k], self.fp.offsets[k]
+                n = p.numel()
+                state[order[id(p)]] = {"step": step,
+                                       "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
+                                       "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone(),
+                                       "weight_norm": self.weight_norm[j].clone(),
+                                       "adam_norm": self.adam_norm[j].clone(),
+                                       "trust_ratio": self.trust_ratio[j].clone()}
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+                 "params": list(range(len(order)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd: dict, model: nn.Module) -> None:
+        """also reads a checkpoint of the reference's Lamb, whose trust_ratio is the plain number 1 where a norm was 0"""
+        order = {id(p): i for i, p in enumerate(model.parameters())}
+        steps = set()
+        nt = len(self.members)
+        norms = torch.zeros(3 * nt, dtype=torch.float32)
+        with torch.no_grad():
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+            for j, k in enumerate(self.members):
+                p, off = self.fp.params[k], self.fp.offsets[k]
+                st = sd["state"].get(order[id(p)])
+                if st is None:
+                    continue
+                n = p.numel()
+                self.exp_avg[off:off + n].copy_(st["exp_avg"].reshape(-1))
+                self.exp_avg_sq[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
+                for q, key in enumerate(("weight_norm", "adam_norm", "trust_ratio")):
+                    if key in st:
+                        norms[q * nt + j] = float(st[key])
+                steps.add(int(st["step"]))
+            self.norms.copy_(norms)
         if len(steps) > 1:
             raise ValueError(f"per-parameter step counts differ ({sorted(steps)}): the fused optimiser keeps one")
         step = steps.pop() if steps else 0
@@ -349,7 +497,7 @@ class _SlideFn(torch.autograd.Function):
         return dxx, dim
 
 
-def train_step(model: nn.Module, opt: FusedAdam, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
+def train_step(model: nn.Module, opt: FlatOptimizer, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
                noise_scale: float = 0.0, lr: Optional[float] = None, reducer=None,
                grad_scale: float = 1.0) -> Tuple[Tensor, Tensor]:
     """one optimisation step; returns (loss, pred) as device tensors - no host sync."""
@@ -434,7 +582,7 @@ class GraphedTrainStep(_GraphStep):
     ~500 kernel launches of a DPOT-Tiny step then cost one graph launch instead of ~3 ms of Python/HIP launch
     overhead (the GPU work itself is ~4 ms at B=32)."""
 
-    def __init__(self, model: nn.Module, opt: FusedAdam, xx: Tensor, yy: Tensor, msk: Optional[Tensor],
+    def __init__(self, model: nn.Module, opt: FlatOptimizer, xx: Tensor, yy: Tensor, msk: Optional[Tensor],
                  T_bundle: int = 1, noise_scale: float = 0.0, warmup: int = 2, reducer=None,
                  grad_scale: float = 1.0, capture_collectives: bool = False):
         self.model, self.opt = model, opt
@@ -502,7 +650,7 @@ class SegmentedTrainStep(_GraphStep):
     are therefore made in the first forward call only; segment 0 holds the whole rollout forward, the loss, the complete
     backward of AR steps T-1 .. 1 and the backward of AR step 0 down to its last cut."""
 
-    def __init__(self, model: nn.Module, opt: FusedAdam, reducer, xx: Tensor, yy: Tensor, msk: Optional[Tensor],
+    def __init__(self, model: nn.Module, opt: FlatOptimizer, reducer, xx: Tensor, yy: Tensor, msk: Optional[Tensor],
                  noise_scale: float = 0.0, warmup: int = 2, T_bundle: int = 1):
         self.T_bundle = T_bundle
         self.model, self.opt, self.reducer = model, opt, reducer
@@ -629,7 +777,7 @@ def _end_stray_captures(streams) -> None:
         pass
 
 
-def make_dp_step(model: nn.Module, opt: FusedAdam, reducer, xx: Tensor, yy: Tensor, msk: Optional[Tensor],
+def make_dp_step(model: nn.Module, opt: FlatOptimizer, reducer, xx: Tensor, yy: Tensor, msk: Optional[Tensor],
                  noise_scale: float = 0.0, warmup: int = 2, T_bundle: int = 1, try_one_graph: bool = True):
     """The N > 1 train step with the FAST mode chosen by verification (round 6): returns (step, info).
 

@@ -13,6 +13,7 @@
  *   models/dpot.py:315-321  out_layer           -> dpot_gemm_f32 + dpot_pixel_shuffle
  *   utils/criterion.py:38-59 SimpleLpLoss       -> dpot_rel_l2_fwd / _bwd
  *   utils/optimizer.py:9-52 adam()              -> dpot_sumsq + dpot_adam_step
+ *   utils/optimizer.py:359-499 Lamb.step()      -> dpot_sumsq + dpot_lamb_step
  *
  * Conventions
  *   - plain pointers and sizes only; every pointer is a DEVICE pointer unless stated otherwise
@@ -435,6 +436,35 @@ int dpot_adam_step(float* p, const float* g, float* m, float* v, int64_t n, cons
  * so the host may enqueue any number of steps ahead (hipGraph replays included). */
 int dpot_adam_stage(float* hyper, int64_t* step, float lr, double beta1, double beta2, float eps,
                     float weight_decay, float max_norm, int advance, dpot_stream_t stream);
+
+/* LAMB over a flat fp32 buffer (utils/optimizer.py:359-499), per parameter tensor, with the clip of train_temporal.py:228:
+ *   g' = g * grad_scale * clip;  m = b1*m + (1-b1)*g';  v = b2*v + (1-b2)*g'^2;  r = m / (sqrt(v) + eps) + wd*p;
+ *   weight_norm = min(||p||, clamp_value) (p before the update);  adam_norm = ||r||;
+ *   trust_ratio = (weight_norm == 0 || adam_norm == 0) ? 1 : weight_norm / adam_norm;
+ *   p -= lr*bc * (adam ? 1 : trust_ratio) * r,  bc = debias ? sqrt(1-b2^t) / (1-b1^t) : 1.
+ * The buffer is cut into chunks of at most dpot_lamb_chunk_elems() elements, each inside ONE tensor (DEVICE table
+ * chunks_dev[nchunks]; off a multiple of 4, the padding between tensors in no chunk); tensors_dev[ntensors] lists each
+ * tensor's chunks (consecutive entries).  part: 2*nchunks doubles of scratch (per-chunk sum p^2, sum r^2); norms: 3*ntensors
+ * floats = weight_norm[ntensors], adam_norm[ntensors], trust_ratio[ntensors] (written every step, adam or not).  Fixed
+ * reduction order, no atomics: the result does not depend on the launch.  adam != 0: 2 launches (moments + update, norms);
+ * adam == 0: 3 (moments, norms, update with the trust ratio).  hyper (DEVICE, >= 9 floats) is what dpot_lamb_stage writes;
+ * sumsq may be NULL (no clipping). */
+typedef struct dpot_lamb_chunk {
+  int64_t off;
+  int32_t len, tensor;
+} dpot_lamb_chunk;
+typedef struct dpot_lamb_tensor {
+  int32_t first_chunk, n_chunks;
+} dpot_lamb_tensor;
+int dpot_lamb_chunk_elems(void);
+int dpot_lamb_step(float* p, const float* g, float* m, float* v, const float* hyper, const float* sumsq, float grad_scale,
+                   const dpot_lamb_chunk* chunks_dev, int nchunks, const dpot_lamb_tensor* tensors_dev, int ntensors,
+                   double* part, float* norms, int adam, dpot_stream_t stream);
+/* host side of a LAMB step, one one-thread launch with every value by value: step[0] += advance (DEVICE int64);
+ * hyper = {b1, b2, 1-b1, 1-b2, eps, weight_decay, max_norm (0 = no clip), lr*bc, clamp_value}, the bias correction bc
+ * formed in double from the double betas and the device step counter */
+int dpot_lamb_stage(float* hyper, int64_t* step, double lr, double beta1, double beta2, float eps, float weight_decay,
+                    float max_norm, float clamp_value, int debias, int advance, dpot_stream_t stream);
 
 /* xx_out = xx + noise_scale * ||xx||_2(over X,Y,T per (b,c)) * eps   (train_temporal.py:205)
  * xx, eps: [B, S, C]; norms: B*C*(1 + dpot_noise_chunks(S, C)) floats - [B, C] norms followed by the chunk partials */
