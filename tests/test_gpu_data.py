@@ -4,18 +4,20 @@ import numpy as np
 import pytest
 import torch
 
+import guard
+from guard import guarded  # noqa: F401  (fixture)
 from helpers import assert_close, load
 from oracle import data_ref as D
 
 pytestmark = pytest.mark.gpu
 
 
-def test_resize_pad_window_golden_and_batched():
+def test_resize_pad_window_golden_and_batched(guarded):
     from dpot_amd.data import resize_pad_window
     fx = load("g12_data")
     for k in range(4):
         H, W, T, Cc, res, nc, t_in, t_ar, t0 = (int(v) for v in fx[f"c{k}.meta"])
-        raw = D.recipe_sample((H, W, T, Cc), salt=100 + k).contiguous().cuda()
+        raw = guard.wrap(D.recipe_sample((H, W, T, Cc), salt=100 + k), "cuda")
         xx, yy = resize_pad_window([raw], [t0], res, t_in, t_ar, nc)
         assert_close(xx[0], fx[f"c{k}.x"], f"case {k} x", rtol=1e-6, atol_scale=1e-6)
         assert_close(yy[0], fx[f"c{k}.y"], f"case {k} y", rtol=1e-6, atol_scale=1e-6)
@@ -23,13 +25,13 @@ def test_resize_pad_window_golden_and_batched():
     shapes = [(64, 64, 20, 1), (128, 128, 14, 3), (256, 256, 12, 4), (100, 60, 16, 2)] * 20      # 80 samples: 2 launches
     starts = [min(i % 3, s[2] - 11) for i, s in enumerate(shapes)]
     raws = [D.recipe_sample(s, salt=7 + i) for i, s in enumerate(shapes)]
-    xx, yy = resize_pad_window([r.cuda() for r in raws], starts, 128, 10, 1, 4)
+    xx, yy = resize_pad_window([guard.wrap(r, "cuda") for r in raws], starts, 128, 10, 1, 4)
     for i in (0, 1, 2, 3, 64, 79):
         xr, yr = D.window(D.pad_data(raws[i], 128, 4), starts[i], 10, 1)
         assert_close(xx[i], xr, f"sample {i} x", rtol=1e-6, atol_scale=1e-6)
         assert_close(yy[i], yr, f"sample {i} y", rtol=1e-6, atol_scale=1e-6)
     with pytest.raises(Exception):
-        resize_pad_window([raws[0].cuda()], [15], 128, 10, 1, 4)          # window runs past the trajectory
+        resize_pad_window([guard.wrap(raws[0], "cuda")], [15], 128, 10, 1, 4)         # window runs past the trajectory
 
 
 def test_device_batcher_double_buffer_overlaps_and_is_exact():
@@ -87,12 +89,12 @@ def test_test_mode_windows_downsample_and_idx_cls_golden():
         assert_close(gy[0], fx[f"t{k}.y"], f"batcher test case {k} y", rtol=1e-6, atol_scale=1e-6)
 
 
-def test_resize_pad_window_rejects_wrongly_shaped_output_buffers():
+def test_resize_pad_window_rejects_wrongly_shaped_output_buffers(guarded):
     """caller-supplied out_xx / out_yy must have the down-sampled shape the kernel writes"""
     from dpot_amd import _lib
     from dpot_amd.data import resize_pad_window
-    raw = [torch.rand(16, 16, 8, 1, device="cuda")]
-    ok_x = torch.empty(1, 16, 16, 4, 4, device="cuda")
+    raw = [guard.wrap(torch.rand(16, 16, 8, 1, device="cuda"))]
+    ok_x = guard.full_nan((1, 16, 16, 4, 4))
     with pytest.raises(_lib.DpotHipError, match="out_xx"):
         resize_pad_window(raw, [0], 32, 4, 2, 4, out_xx=torch.empty(1, 32, 32, 4, 4, device="cuda"), downsample=(2, 2))
     with pytest.raises(_lib.DpotHipError, match="out_yy"):
@@ -103,3 +105,4 @@ def test_resize_pad_window_rejects_wrongly_shaped_output_buffers():
                           downsample=(2, 2))
     xx, yy = resize_pad_window(raw, [0], 32, 4, 2, 4, out_xx=ok_x, downsample=(2, 2))
     assert xx is ok_x and tuple(yy.shape) == (1, 16, 16, 2, 4)
+    assert torch.isfinite(xx).all() and torch.isfinite(yy).all()          # both were NaN before the launch: fully written

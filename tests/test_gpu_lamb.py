@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import guard
+from guard import guarded  # noqa: F401  (fixture)
 from helpers import load
 from lamb_ref import LambState, config, lamb_step
 from oracle import dpot_ref as R
@@ -40,9 +42,10 @@ def _layout(numels, pad_to=4):
 
 # ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("c", ["a", "b", "c"])
-def test_op_level_lamb_vs_reference_and_restatement(c):
+def test_op_level_lamb_vs_reference_and_restatement(c, guarded):
     """ops.lamb_stage + ops.lamb_step on a flat buffer holding the g14 tensors (and an untouched tail), grad_scale 0.5: the
-    per-step updates, the per-tensor norms and the final moments equal the reference's Lamb and the restatement"""
+    per-step updates, the per-tensor norms and the final moments equal the reference's Lamb and the restatement.  Every
+    buffer the kernels see sits between guards (tests/guard.py): the chunk tables of the plan, the flat buffers, the slots"""
     from dpot_amd import ops
     fx = load("g14_lamb")
     kw = config(fx, c)
@@ -55,14 +58,15 @@ def test_op_level_lamb_vs_reference_and_restatement(c):
     p = torch.randn(total, device=dev)
     for n, o, k in zip(names, offs, numels):
         p[o:o + k] = torch.from_numpy(fx[f"p0.{n}"].reshape(-1)).to(dev)
-    g = torch.zeros(total, device=dev)
-    m, v = torch.zeros(total, device=dev), torch.zeros(total, device=dev)
-    hyper = torch.zeros(16, device=dev)
-    step = torch.zeros(1, dtype=torch.int64, device=dev)
-    sumsq, part = torch.zeros(1, device=dev), torch.zeros(1024, device=dev)
+    p = guard.wrap(p)
+    g = guard.wrap(torch.zeros(total, device=dev))
+    m, v = guard.wrap(torch.zeros(total, device=dev)), guard.wrap(torch.zeros(total, device=dev))
+    hyper = guard.wrap(torch.zeros(16, device=dev))
+    step = guard.wrap(torch.zeros(1, dtype=torch.int64, device=dev))
+    sumsq, part = guard.wrap(torch.zeros(1, device=dev)), guard.wrap(torch.zeros(1024, device=dev))
     plan = ops.LambPlan(offs, numels, n_act, dev)
     nt = len(names)
-    norms = torch.zeros(3 * nt, device=dev)
+    norms = guard.wrap(torch.zeros(3 * nt, device=dev))
     s = 0.5
     tail0 = p[n_act:].clone()
     params = [fx[f"p0.{n}"].astype(np.float64) for n in names]
@@ -114,10 +118,10 @@ def _dpot_m_like_sizes():
     return head, tail
 
 
-def test_chunk_table_edge_cases_on_dpot_m_layout():
+def test_chunk_table_edge_cases_on_dpot_m_layout(guarded):
     """per-tensor norms over the chunk table of a DPOT-M-sized buffer (a 10.5 M-element tensor, tiny neighbours, sizes that
     are not multiples of 4, a tail outside n_active) equal float64 norms of the true ranges; the padding slots and the tail
-    stay untouched bit for bit; a second run reproduces every bit"""
+    stay untouched bit for bit; a second run reproduces every bit; nothing is written outside the buffers (tests/guard.py)"""
     from dpot_amd import ops
     head, tail = _dpot_m_like_sizes()
     assert max(head) > 1 << 20
@@ -127,7 +131,7 @@ def test_chunk_table_edge_cases_on_dpot_m_layout():
     dev = "cuda"
     gen = torch.Generator(device=dev).manual_seed(14)
     p0 = torch.randn(total, device=dev, generator=gen) * 0.05
-    g = torch.randn(total, device=dev, generator=gen)
+    g = guard.wrap(torch.randn(total, device=dev, generator=gen))
     m0 = torch.randn(total, device=dev, generator=gen) * 0.01
     v0 = torch.rand(total, device=dev, generator=gen) * 1e-3
     p0[offs[1]:offs[1] + sizes[1]] = 0.0                         # one all-zero tensor
@@ -139,9 +143,10 @@ def test_chunk_table_edge_cases_on_dpot_m_layout():
     wd, eps, clamp = 1e-4, 1e-6, 10.0
     runs = []
     for _ in range(2):
-        p, m, v = p0.clone(), m0.clone(), v0.clone()
-        hyper, step = torch.zeros(16, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
-        norms = torch.zeros(3 * len(head), device=dev)
+        p, m, v = guard.wrap(p0), guard.wrap(m0), guard.wrap(v0)
+        hyper = guard.wrap(torch.zeros(16, device=dev))
+        step = guard.wrap(torch.zeros(1, dtype=torch.int64, device=dev))
+        norms = guard.wrap(torch.zeros(3 * len(head), device=dev))
         ops.lamb_stage(hyper, step, 1e-3, 0.9, 0.999, eps, wd, 0.0, clamp, True)
         ops.lamb_step(plan, p, g, m, v, hyper, None, norms, adam=False)
         torch.cuda.synchronize()

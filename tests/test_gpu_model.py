@@ -9,6 +9,8 @@ import os
 import pytest
 import torch
 
+import guard
+from guard import guarded  # noqa: F401  (fixture)
 from helpers import assert_close, assert_sub, load, set_tune, tune_value
 from oracle import dpot_ref as R
 
@@ -37,7 +39,7 @@ def _block_fn(m, x, h):
                          m.n_blocks, m.modes, m._act)
 
 
-def test_afno_mixer_golden_one_launch_layer(monkeypatch):
+def test_afno_mixer_golden_one_launch_layer(monkeypatch, guarded):
     """the same reference golden (g1_afno_tiny: the DPOT-Tiny layer, E = 512, 4 blocks of 128) through the ONE-launch form
     of the mixer's forward (csrc/afno_fused.hip, SURVEY 8 f4: rfft2 -> both MLP layers -> irfft2 + x in one kernel), which
     `auto` only selects from 205 (sample, block) workgroups on; the backward consumes the S / pre-activation it saves"""
@@ -48,11 +50,11 @@ def test_afno_mixer_golden_one_launch_layer(monkeypatch):
     calls = []
     real = ops.afno_fused_fwd
     monkeypatch.setattr(ops, "afno_fused_fwd", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
-    test_afno_mixer_golden("g1_afno_tiny")
+    test_afno_mixer_golden("g1_afno_tiny", guarded)
     assert calls, "the one-launch kernel did not run"
 
 
-def test_afno_mixer_golden_bf16x6_kernel(monkeypatch):
+def test_afno_mixer_golden_bf16x6_kernel(monkeypatch, guarded):
     """round 6: the same reference golden (g1_afno_tiny, 128 channels per block) through the bf16x6 mixer kernel
     (csrc/afno_mlp6.hip) that gemm_precision 'auto' selects at 96 channels per block and DPOT_TUNE mixer6=2 everywhere:
     forward through the three-launch form, backward through its data-gradient form - same tolerance (fp32-accurate)"""
@@ -64,12 +66,12 @@ def test_afno_mixer_golden_bf16x6_kernel(monkeypatch):
     real = ops.afno_mlp2
     monkeypatch.setattr(ops, "afno_mlp2", lambda *a, **k: (calls.append(k.get("layout")), real(*a, **k))[1])
     with ops.precision_scope("auto", None):
-        test_afno_mixer_golden("g1_afno_tiny")
+        test_afno_mixer_golden("g1_afno_tiny", guarded)
     assert calls and all(l == 2 for l in calls), calls
 
 
 @pytest.mark.parametrize("name", ["g1_afno_trunc", "g1_afno_tiny"])
-def test_afno_mixer_golden(name):
+def test_afno_mixer_golden(name, guarded):
     """AFNO2D alone (golden g1, written by the imported reference's AFNO2D module): the PRODUCT mixer -
     functional.AFNO2DFn = the helpers BlockFn runs: rfft2 -> afno_mlp3_kernel (both layers, three-product form; the two
     generic GEMMs at block sizes the fused kernel does not cover) -> irfft2 + residual, and backward through
@@ -80,7 +82,7 @@ def test_afno_mixer_golden(name):
     B, h, E, nb, modes = (int(fx[k]) for k in ("B", "h", "E", "nb", "modes"))
     cfg = R.DPOTConfig(img_size=h * 8, patch_size=8, embed_dim=E, n_blocks=nb, modes=modes, depth=1)
     pre = "blocks.0.filter."
-    sd = {k[len(pre):]: v.cuda().requires_grad_(True) for k, v in R.recipe_state_dict(cfg, salt=3).items()
+    sd = {k[len(pre):]: guard.wrap(v, "cuda").requires_grad_(True) for k, v in R.recipe_state_dict(cfg, salt=3).items()
           if k.startswith(pre)}
     x = R.recipe_input((B, h, h, E), salt=11)
     up = (R.recipe_input((B, h, h, E), salt=12) * 0.3)
@@ -89,9 +91,9 @@ def test_afno_mixer_golden(name):
     if name == "g1_afno_tiny" and not opted_out:      # the DPOT-Tiny layer must run on the fused three-product kernel
         assert ops.afno_mlp2_supported(nb, bs) and ops.afno_mlp3_supported(nb, bs)
         assert ops.afno_wgrad2_splitk(B * min(modes, h) * min(modes, h // 2 + 1), nb, bs) > 0
-    xg = x.cuda().view(B, h * h, E).requires_grad_(True)
+    xg = guard.wrap(x, "cuda").view(B, h * h, E).requires_grad_(True)
     y = AFNO2DFn.apply(xg, sd["w1"], sd["b1"], sd["w2"], sd["b2"], h, h, nb, modes, 1)
-    (y * up.cuda().view(B, h * h, E)).sum().backward()
+    (y * guard.wrap(up, "cuda").view(B, h * h, E)).sum().backward()
     full = name == "g1_afno_trunc"
     cmp = (lambda t, k: assert_close(t.reshape(fx[k].shape), fx[k], k)) if full else \
         (lambda t, k: assert_sub(t, fx, k, k))
@@ -101,14 +103,14 @@ def test_afno_mixer_golden(name):
         cmp(sd[k].grad, "d" + k)
 
 
-def test_block_golden():
+def test_block_golden(guarded):
     fx = load("g2_block")
     B, h, E, nb = (int(fx[k]) for k in ("B", "h", "E", "nb"))
     kw = dict(img_size=h * 8, patch_size=8, embed_dim=E, n_blocks=nb, modes=32, depth=1, mlp_ratio=2)
     m, cfg = build(kw, salt=5)
     from dpot_amd import ops
-    x = R.recipe_input((B, h, h, E), salt=21).cuda().view(B, h * h, E).requires_grad_(True)
-    up = (R.recipe_input((B, h, h, E), salt=22) * 0.3).cuda().view(B, h * h, E)
+    x = guard.wrap(R.recipe_input((B, h, h, E), salt=21), "cuda").view(B, h * h, E).requires_grad_(True)
+    up = guard.wrap(R.recipe_input((B, h, h, E), salt=22) * 0.3, "cuda").view(B, h * h, E)
     gn, _, _ = ops.groupnorm_fwd(x.detach(), m.blocks[0].norm1.weight.detach(), m.blocks[0].norm1.bias.detach())
     assert_close(gn.view(B, h, h, E), fx["gn"], "groupnorm")
     y = _block_fn(m, x, h)
@@ -121,19 +123,19 @@ def test_block_golden():
             assert_close(g["blocks.0." + k[2:]], fx[k], k)
 
 
-def test_embed_and_head_golden():
+def test_embed_and_head_golden(guarded):
     from dpot_amd.functional import EmbedFn, HeadFn
     kw = dict(R.MINI, depth=1)
     m, cfg = build(kw, salt=7)
     B = 2
     fx = load("g3_embed")
-    x = R.recipe_input((B, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=31).cuda()
+    x = guard.wrap(R.recipe_input((B, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=31), "cuda")
     x.requires_grad_(True)
     pe, ta = m.patch_embed.proj, m.time_agg_layer
     lat = EmbedFn.apply(x, m.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, ta.w, ta.gamma, m._gx,
                         m._gy, m._gt, m._tt, m.patch_size, m._act)
     h = cfg.latent
-    up = (R.recipe_input((B, h, h, cfg.embed_dim), salt=32) * 0.3).cuda().view(B, h * h, -1)
+    up = guard.wrap(R.recipe_input((B, h, h, cfg.embed_dim), salt=32) * 0.3, "cuda").view(B, h * h, -1)
     (lat * up).sum().backward()
     assert_close(lat.view(B, h, h, -1), fx["agg"], "embed.agg")
     assert_close(x.grad, fx["dx"], "embed.dx")
@@ -144,14 +146,14 @@ def test_embed_and_head_golden():
     # out layer + cls head
     fx = load("g3_out")
     m.zero_grad()
-    latin = R.recipe_input((B, h, h, cfg.embed_dim), salt=33).cuda().view(B, h * h, -1).requires_grad_(True)
+    latin = guard.wrap(R.recipe_input((B, h, h, cfg.embed_dim), salt=33), "cuda").view(B, h * h, -1).requires_grad_(True)
     ol, ch = m.out_layer, m.cls_head
     pred, cls = HeadFn.apply(latin, ol[0].weight, ol[0].bias, ol[2].weight, ol[2].bias, ol[4].weight, ol[4].bias,
                              ch[0].weight, ch[0].bias, ch[2].weight, ch[2].bias, ch[4].weight, ch[4].bias, h, h,
                              m.patch_size, m._act)
     pred = pred.view(B, cfg.img_size, cfg.img_size, cfg.out_timesteps, cfg.out_channels)
-    up_o = (R.recipe_input(tuple(pred.shape), salt=34) * 0.3).cuda()
-    up_c = (R.recipe_input(tuple(cls.shape), salt=35) * 0.3).cuda()
+    up_o = guard.wrap(R.recipe_input(tuple(pred.shape), salt=34) * 0.3, "cuda")
+    up_c = guard.wrap(R.recipe_input(tuple(cls.shape), salt=35) * 0.3, "cuda")
     ((pred * up_o).sum() + (cls * up_c).sum()).backward()
     assert_close(pred, fx["y"], "out.y")
     assert_close(cls, fx["cls"], "out.cls")
@@ -163,17 +165,17 @@ def test_embed_and_head_golden():
 
 
 @pytest.mark.parametrize("name,normalize", [("g4_mini", False), ("g4_mini_norm", True)])
-def test_full_mini_model_golden(name, normalize):
+def test_full_mini_model_golden(name, normalize, guarded):
     fx = load(name)
     m, cfg = build(dict(R.MINI, normalize=normalize), salt=9)
     x = R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=41)
     if normalize:
         x = x * 2.0 + 0.7
-    x = x.cuda().requires_grad_(True)
+    x = guard.wrap(x, "cuda").requires_grad_(True)
     y, c = m(x)
     assert y.is_contiguous() and tuple(y.shape) == (2, cfg.img_size, cfg.img_size, 1, cfg.out_channels)
-    up_y = (R.recipe_input(tuple(y.shape), salt=42) * 0.3).cuda()
-    up_c = (R.recipe_input(tuple(c.shape), salt=43) * 0.3).cuda()
+    up_y = guard.wrap(R.recipe_input(tuple(y.shape), salt=42) * 0.3, "cuda")
+    up_c = guard.wrap(R.recipe_input(tuple(c.shape), salt=43) * 0.3, "cuda")
     ((y * up_y).sum() + (c * up_c).sum()).backward()
     assert_close(y, fx["pred"], "pred")
     assert_close(c, fx["cls"], "cls")
@@ -285,7 +287,7 @@ def test_train_step_vs_oracle_two_steps_and_graph():
 
 
 @pytest.mark.parametrize("out_channels,act", [(4, "gelu"), (3, "gelu"), (4, "silu"), (9, "tanh")])
-def test_head_fused_tail_vs_oracle(out_channels, act):
+def test_head_fused_tail_vs_oracle(out_channels, act, guarded):
     """out_layer_dim == 32 takes the fused per-pixel tail kernels (csrc/tail.hip): forward + every gradient vs oracle"""
     from dpot_amd.functional import HeadFn
     kw = dict(R.MINI, depth=1, out_layer_dim=32, out_channels=out_channels, act=act)
@@ -298,13 +300,13 @@ def test_head_fused_tail_vs_oracle(out_channels, act):
     up_o = R.recipe_input(tuple(o_ref.shape), salt=34) * 0.3
     up_c = R.recipe_input(tuple(c_ref.shape), salt=35) * 0.3
     ((o_ref * up_o).sum() + (c_ref * up_c).sum()).backward()
-    latin = lat.cuda().view(B, h * h, -1).requires_grad_(True)
+    latin = guard.wrap(lat, "cuda").view(B, h * h, -1).requires_grad_(True)
     ol, ch = m.out_layer, m.cls_head
     pred, cls = HeadFn.apply(latin, ol[0].weight, ol[0].bias, ol[2].weight, ol[2].bias, ol[4].weight, ol[4].bias,
                              ch[0].weight, ch[0].bias, ch[2].weight, ch[2].bias, ch[4].weight, ch[4].bias, h, h,
                              m.patch_size, m._act)
     pred = pred.view(B, cfg.img_size, cfg.img_size, cfg.out_timesteps, cfg.out_channels)
-    ((pred * up_o.cuda()).sum() + (cls * up_c.cuda()).sum()).backward()
+    ((pred * guard.wrap(up_o, "cuda")).sum() + (cls * guard.wrap(up_c, "cuda")).sum()).backward()
     assert_close(pred, o_ref, "fused tail fwd")
     assert_close(latin.grad.view(B, h, h, -1), lo.grad, "fused tail dlat")
     for k, p in m.named_parameters():

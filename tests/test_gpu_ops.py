@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import guard
+from guard import guarded  # noqa: F401  (fixture)
 from helpers import assert_close, set_tune
 from oracle import dpot_ref as R
 
@@ -20,6 +22,17 @@ def ops():
     _lib.load()
     assert torch.cuda.is_available()
     return _ops
+
+
+@pytest.fixture(autouse=True)
+def _guard(guarded):
+    """every test of this module runs on guarded, poisoned allocations (tests/guard.py) and checks the guards when it ends"""
+    yield guarded
+
+
+def dev(t):
+    """a test input on the GPU, inside a guarded buffer"""
+    return guard.wrap(t, "cuda")
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -40,8 +53,8 @@ def test_gemm_layouts(ops, transA, transB, M, N, K, tile):
     A = rnd(K, M, seed=1) if transA else rnd(M, K, seed=1)
     B = rnd(N, K, seed=2) if transB else rnd(K, N, seed=2)
     ref = (A.t() if transA else A).double() @ (B.t() if transB else B).double()
-    Ad, Bd = A.cuda(), B.cuda()
-    C = torch.full((M, N), float("nan"), device="cuda")
+    Ad, Bd = dev(A), dev(B)
+    C = guard.full_nan((M, N))
     ops.gemm(Ad, Bd, C, M, N, K, transA=transA, transB=transB, lda=A.shape[1], ldb=B.shape[1], ldc=N, tile=tile)
     assert_close(C, ref, f"gemm {M}x{N}x{K} tA={transA} tB={transB}")
 
@@ -52,7 +65,7 @@ def test_gemm_epilogue_activations(ops, act):
     A, W, b = rnd(M, K, seed=3), rnd(N, K, seed=4, scale=0.3), rnd(N, seed=5)
     res = rnd(M, N, seed=6)
     a_id = ops.ACT_IDS[act]
-    y, pre = ops.linear_fwd(A.cuda(), W.cuda(), b.cuda(), act=a_id, save_pre=True, res=res.cuda())
+    y, pre = ops.linear_fwd(dev(A), dev(W), dev(b), act=a_id, save_pre=True, res=dev(res))
     pre_ref = A.double() @ W.double().t() + b.double()
     assert_close(pre, pre_ref, "preact")
     assert_close(y, ACTS[act](pre_ref) + res.double(), f"act {act}")
@@ -60,7 +73,7 @@ def test_gemm_epilogue_activations(ops, act):
     dy = rnd(M, N, seed=7)
     W2 = rnd(N, K, seed=8, scale=0.3)
     aux = rnd(M, K, seed=9)
-    dx = ops.linear_bwd_data(dy.cuda(), W2.cuda(), act=a_id, aux=aux.cuda())
+    dx = ops.linear_bwd_data(dev(dy), dev(W2), act=a_id, aux=dev(aux))
     a = aux.double().requires_grad_(True)
     ACTS[act](a).sum().backward()
     assert_close(dx, (dy.double() @ W2.double()) * a.grad, f"dact {act}")
@@ -70,12 +83,12 @@ def test_gemm_residual_row_map_and_accumulate(ops):
     M, N, K, T, tok = 240, 64, 36, 4, 12                    # rows are (b, tok, t): res row = (m / T) % tok
     A, W, b = rnd(M, K, seed=1), rnd(N, K, seed=2), rnd(N, seed=3)
     pos = rnd(tok, N, seed=4)
-    y, _ = ops.linear_fwd(A.cuda(), W.cuda(), b.cuda(), res=pos.cuda(), res_div=T, res_mod=tok)
+    y, _ = ops.linear_fwd(dev(A), dev(W), dev(b), res=dev(pos), res_div=T, res_mod=tok)
     idx = (torch.arange(M) // T) % tok
     assert_close(y, A.double() @ W.double().t() + b.double() + pos.double()[idx], "row-mapped residual")
-    C = rnd(M, N, seed=5).cuda()
+    C = dev(rnd(M, N, seed=5))
     C0 = C.clone()
-    ops.gemm(A.cuda(), W.cuda(), C, M, N, K, transB=True, lda=K, ldb=K, ldc=N, accumulate=True)
+    ops.gemm(dev(A), dev(W), C, M, N, K, transB=True, lda=K, ldb=K, ldc=N, accumulate=True)
     assert_close(C, C0.cpu().double() + A.double() @ W.double().t(), "accumulate")
 
 
@@ -83,10 +96,10 @@ def test_gemm_batched_strided_and_splitk(ops):
     nb, bs, Mm = 4, 24, 300                                  # the AFNO mixer call pattern, bs not a multiple of 32
     E2 = 2 * bs * nb
     S, Wb, bb = rnd(Mm, E2, seed=1), rnd(nb, 2 * bs, 2 * bs, seed=2, scale=0.2), rnd(nb, 2 * bs, seed=3)
-    O = torch.full((Mm, E2), float("nan"), device="cuda")
-    Opre = torch.empty_like(O)
+    O = guard.full_nan((Mm, E2))
+    Opre = guard.full_nan(O.shape)
     kw = dict(lda=E2, ldb=2 * bs, ldc=E2, batch=nb, strideA=2 * bs, strideB=4 * bs * bs, strideC=2 * bs)
-    ops.gemm(S.cuda(), Wb.cuda(), O, Mm, 2 * bs, 2 * bs, bias=bb.cuda(), strideBias=2 * bs, act=1, mode=ops.EPI_ACT,
+    ops.gemm(dev(S), dev(Wb), O, Mm, 2 * bs, 2 * bs, bias=dev(bb), strideBias=2 * bs, act=1, mode=ops.EPI_ACT,
              preact=Opre, ldpre=E2, stridePre=2 * bs, **kw)
     ref = torch.einsum("mki,kio->mko", S.double().view(Mm, nb, 2 * bs), Wb.double()) + bb.double()
     assert_close(Opre, ref.reshape(Mm, E2), "batched preact")
@@ -95,8 +108,8 @@ def test_gemm_batched_strided_and_splitk(ops):
     dO = rnd(Mm, E2, seed=4)
     outs = []
     for _ in range(2):
-        dW = torch.empty(nb, 2 * bs, 2 * bs, device="cuda")
-        ops.gemm(S.cuda(), dO.cuda(), dW, 2 * bs, 2 * bs, Mm, transA=True, lda=E2, ldb=E2, ldc=2 * bs, batch=nb,
+        dW = guard.full_nan((nb, 2 * bs, 2 * bs,))
+        ops.gemm(dev(S), dev(dO), dW, 2 * bs, 2 * bs, Mm, transA=True, lda=E2, ldb=E2, ldc=2 * bs, batch=nb,
                  strideA=2 * bs, strideB=2 * bs, strideC=4 * bs * bs, splitk=5)
         outs.append(dW)
     refw = torch.einsum("mki,mko->kio", S.double().view(Mm, nb, 2 * bs), dO.double().view(Mm, nb, 2 * bs))
@@ -110,9 +123,9 @@ def test_gemm_fused_column_sums(ops, splitk):
     nb, bs, Mm = 4, 24, 333                                  # batched mixer wgrad: db = colsum(dO) per block
     E2 = 2 * bs * nb
     S, dO = rnd(Mm, E2, seed=1), rnd(Mm, E2, seed=4)
-    dW = torch.empty(nb, 2 * bs, 2 * bs, device="cuda")
-    db = torch.full((E2,), float("nan"), device="cuda")
-    ops.gemm(S.cuda(), dO.cuda(), dW, 2 * bs, 2 * bs, Mm, transA=True, lda=E2, ldb=E2, ldc=2 * bs, batch=nb,
+    dW = guard.full_nan((nb, 2 * bs, 2 * bs,))
+    db = guard.full_nan((E2,))
+    ops.gemm(dev(S), dev(dO), dW, 2 * bs, 2 * bs, Mm, transA=True, lda=E2, ldb=E2, ldc=2 * bs, batch=nb,
              strideA=2 * bs, strideB=2 * bs, strideC=4 * bs * bs, splitk=splitk, colsum_out=db, colsum_of=2,
              strideColsum=2 * bs)
     assert_close(dW, torch.einsum("mki,mko->kio", S.double().view(Mm, nb, 2 * bs), dO.double().view(Mm, nb, 2 * bs)),
@@ -120,17 +133,17 @@ def test_gemm_fused_column_sums(ops, splitk):
     assert_close(db, dO.double().sum(0), "colsum of B")
     for M, N, K in [(70000, 200, 130), (1000, 512, 512), (32, 12, 512)]:   # nn.Linear wgrad + bias grad, several tiles
         dy, x = rnd(M, N, seed=1), rnd(M, K, seed=2)
-        dWl, dbl = ops.linear_bwd_wb(dy.cuda(), x.cuda())
+        dWl, dbl = ops.linear_bwd_wb(dev(dy), dev(x))
         assert_close(dWl, dy.double().t() @ x.double(), f"wgrad {M}x{N}x{K}")
         assert_close(dbl, dy.double().sum(0), f"bias grad {M}x{N}x{K}")
-        dWl2, dbl2 = ops.linear_bwd_wb(dy.cuda(), x.cuda())
+        dWl2, dbl2 = ops.linear_bwd_wb(dev(dy), dev(x))
         assert torch.equal(dbl, dbl2) and torch.equal(dWl, dWl2)
 
 
 def test_linear_bwd_weight_auto_splitk_large_k(ops):
     M, N, K = 65536, 32, 32                                  # out-layer tail wgrad: tiny output, huge contraction
     dy, x = rnd(M, N, seed=1), rnd(M, K, seed=2)
-    dW = ops.linear_bwd_weight(dy.cuda(), x.cuda())
+    dW = ops.linear_bwd_weight(dev(dy), dev(x))
     assert_close(dW, dy.double().t() @ x.double(), "wgrad")
 
 
@@ -156,7 +169,7 @@ def test_rfft2_irfft2_vs_torch(ops, B, h, w, E, nb, modes):
     bs = E // nb
     mx, my = min(modes, h), min(modes, w // 2 + 1)
     x = rnd(B, h, w, E, seed=1)
-    spec = ops.rfft2(x.cuda().view(B, h * w, E), h, w, nb, mx, my, 0)            # [B*mx*my, 2E]
+    spec = ops.rfft2(dev(x).view(B, h * w, E), h, w, nb, mx, my, 0)            # [B*mx*my, 2E]
     ref = torch.fft.rfft2(x.double(), dim=(1, 2), norm="ortho")[:, :mx, :my]     # [B,mx,my,E]
     got = spec.cpu().view(B, mx, my, nb, 2, bs)
     assert_close(got[..., 0, :].reshape(B, mx, my, E), ref.real, "rfft2.re")
@@ -168,7 +181,7 @@ def test_rfft2_irfft2_vs_torch(ops, B, h, w, E, nb, modes):
     full[:, :mx, :my] = torch.complex(sre.double(), sim.double())
     yref = torch.fft.irfft2(full, s=(h, w), dim=(1, 2), norm="ortho") + res.double()
     planar = torch.stack([sre.view(B, mx, my, nb, bs), sim.view(B, mx, my, nb, bs)], dim=-2).reshape(B * mx * my, 2 * E)
-    y = ops.irfft2(planar.cuda(), B, h, w, E, nb, mx, my, 1, res=res.cuda().view(B, h * w, E))
+    y = ops.irfft2(dev(planar), B, h, w, E, nb, mx, my, 1, res=dev(res).view(B, h * w, E))
     assert_close(y.view(B, h, w, E), yref, "irfft2")
 
 
@@ -183,7 +196,7 @@ def test_dft_adjoints_match_autograd(ops, h, mx, my):
     s = torch.fft.rfft2(x, dim=(1, 2), norm="ortho")[:, :mx, :my]
     (s.real * G.real + s.imag * G.imag).sum().backward()
     planar = torch.stack([G.real.view(B, mx, my, nb, bs), G.imag.view(B, mx, my, nb, bs)], dim=-2)
-    gx = ops.irfft2(planar.reshape(B * mx * my, 2 * E).float().cuda(), B, h, w, E, nb, mx, my, 0)
+    gx = ops.irfft2(dev(planar.reshape(B * mx * my, 2 * E).float()), B, h, w, E, nb, mx, my, 0)
     assert_close(gx.view(B, h, w, E), x.grad, "adjoint of rfft2")
     Sr = rnd(B, mx, my, E, seed=4).double().requires_grad_(True)
     Si = rnd(B, mx, my, E, seed=5).double().requires_grad_(True)
@@ -191,7 +204,7 @@ def test_dft_adjoints_match_autograd(ops, h, mx, my):
     full[:, :mx, :my] = torch.complex(Sr, Si)
     g = rnd(B, h, w, E, seed=6)
     (torch.fft.irfft2(full, s=(h, w), dim=(1, 2), norm="ortho") * g.double()).sum().backward()
-    gs = ops.rfft2(g.cuda().view(B, h * w, E), h, w, nb, mx, my, 1).cpu().view(B, mx, my, nb, 2, bs)
+    gs = ops.rfft2(dev(g).view(B, h * w, E), h, w, nb, mx, my, 1).cpu().view(B, mx, my, nb, 2, bs)
     assert_close(gs[..., 0, :].reshape(B, mx, my, E), Sr.grad, "adjoint of irfft2 (re)")
     assert_close(gs[..., 1, :].reshape(B, mx, my, E), Si.grad, "adjoint of irfft2 (im)")
 
@@ -199,12 +212,12 @@ def test_dft_adjoints_match_autograd(ops, h, mx, my):
 def test_afno_pack_unpack(ops):
     nb, bs = 3, 8
     w, b = rnd(2, nb, bs, bs, seed=1), rnd(2, nb, bs, seed=2)
-    wb, bb = ops.afno_pack(w.cuda(), b.cuda())
+    wb, bb = ops.afno_pack(dev(w), dev(b))
     ref = torch.cat([torch.cat([w[0], w[1]], dim=2), torch.cat([-w[1], w[0]], dim=2)], dim=1)
     assert torch.equal(wb.cpu(), ref)
     assert torch.equal(bb.cpu(), b.permute(1, 0, 2).reshape(nb, 2 * bs))
     dwb, dbb = rnd(nb, 2 * bs, 2 * bs, seed=3), rnd(nb, 2 * bs, seed=4)
-    dw, db = ops.afno_unpack_grad(dwb.cuda(), dbb.cuda(), nb, bs)
+    dw, db = ops.afno_unpack_grad(dev(dwb), dev(dbb), nb, bs)
     assert_close(dw[0], dwb[:, :bs, :bs] + dwb[:, bs:, bs:], "dWr")
     assert_close(dw[1], dwb[:, :bs, bs:] - dwb[:, bs:, :bs], "dWi")
     assert torch.equal(db.cpu(), dbb.view(nb, 2, bs).permute(1, 0, 2).contiguous())
@@ -220,9 +233,9 @@ def test_groupnorm(ops, B, T, E):
     gd, bd = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
     yref = torch.nn.functional.group_norm(xd.permute(0, 2, 1), 8, gd, bd, 1e-5).permute(0, 2, 1)
     (yref * dy.double()).sum().backward()
-    y, mean, rstd = ops.groupnorm_fwd(x.cuda(), gamma.cuda(), beta.cuda())
+    y, mean, rstd = ops.groupnorm_fwd(dev(x), dev(gamma), dev(beta))
     assert_close(y, yref, "gn fwd")
-    dx, dg, db = ops.groupnorm_bwd(dy.cuda(), x.cuda(), mean, rstd, gamma.cuda(), add=add.cuda())
+    dx, dg, db = ops.groupnorm_bwd(dev(dy), dev(x), mean, rstd, dev(gamma), add=dev(add))
     assert_close(dx, xd.grad + add.double(), "gn dx")
     assert_close(dg, gd.grad, "gn dgamma")
     assert_close(db, bd.grad, "gn dbeta")
@@ -233,11 +246,11 @@ def test_patchify_unpatchify(ops):
     B, X, T, Cc, P = 2, 24, 3, 2, 4
     x = rnd(B, X, X, T, Cc, seed=1)
     gx, gt = R.unit_grid(X), R.unit_grid(T)
-    A = ops.patchify(x.cuda(), gx.cuda(), gx.cuda(), gt.cuda(), P)
+    A = ops.patchify(dev(x), dev(gx), dev(gx), dev(gt), P)
     ref = R.patchify(R.append_grid(x), P).reshape(-1, (Cc + 3) * P * P)
     assert torch.equal(A.cpu(), ref)
     dA = rnd(*A.shape, seed=2)
-    dx = ops.unpatchify(dA.cuda(), B, X, X, T, Cc, P)
+    dx = ops.unpatchify(dev(dA), B, X, X, T, Cc, P)
     xr = x.clone().requires_grad_(True)
     (R.patchify(R.append_grid(xr), P).reshape(-1, (Cc + 3) * P * P) * dA).sum().backward()
     assert torch.equal(dx.cpu(), xr.grad)
@@ -246,31 +259,31 @@ def test_patchify_unpatchify(ops):
 def test_small_data_movement_ops(ops):
     B, h, w, P, Cc = 2, 3, 5, 4, 3
     z = rnd(B * h * w * P * P, Cc, seed=1)
-    out = ops.pixel_shuffle(z.cuda(), B, h, w, P, Cc)
+    out = ops.pixel_shuffle(dev(z), B, h, w, P, Cc)
     ref = z.view(B, h, w, P, P, Cc).permute(0, 1, 3, 2, 4, 5).reshape(B, h * P, w * P, Cc)
     assert torch.equal(out.cpu(), ref)
     back = ops.pixel_shuffle(out, B, h, w, P, Cc, inverse=True)
     assert torch.equal(back.cpu(), z)
     src = rnd(35, 448, seed=2)
-    assert torch.equal(ops.copy2d_pad(src.cuda(), 35, 448, 36, 448).cpu(), torch.cat([src, torch.zeros(1, 448)]))
-    assert torch.equal(ops.copy2d_pad(src.cuda(), 35, 448, 30, 440).cpu(), src[:30, :440])
+    assert torch.equal(ops.copy2d_pad(dev(src), 35, 448, 36, 448).cpu(), torch.cat([src, torch.zeros(1, 448)]))
+    assert torch.equal(ops.copy2d_pad(dev(src), 35, 448, 30, 440).cpu(), src[:30, :440])
     t = rnd(5, 70, 33, seed=3)
-    assert torch.equal(ops.transpose2d(t.cuda(), 5, 70, 33).cpu(), t.transpose(1, 2).contiguous())
+    assert torch.equal(ops.transpose2d(dev(t), 5, 70, 33).cpu(), t.transpose(1, 2).contiguous())
     Xm = rnd(5000, 77, seed=4)
-    assert_close(ops.colsum(Xm.cuda(), 5000, 77), Xm.double().sum(0), "colsum")
-    assert_close(ops.colsum(Xm.cuda(), 5000, 40, ld=77), Xm[:, :40].double().sum(0), "colsum ld")
+    assert_close(ops.colsum(dev(Xm), 5000, 77), Xm.double().sum(0), "colsum")
+    assert_close(ops.colsum(dev(Xm), 5000, 40, ld=77), Xm[:, :40].double().sum(0), "colsum ld")
     Bq, Rr, T, N = 3, 6, 4, 40
     Xg = rnd(Bq * Rr * T, N, seed=5)
-    assert_close(ops.group_rowsum(Xg.cuda(), Bq, Rr, T, N), Xg.double().view(Bq, Rr, T, N).sum((0, 2)), "group_rowsum")
+    assert_close(ops.group_rowsum(dev(Xg), Bq, Rr, T, N), Xg.double().view(Bq, Rr, T, N).sum((0, 2)), "group_rowsum")
     xt = rnd(3, 50, 64, seed=6)
-    assert_close(ops.token_mean(xt.cuda()), xt.double().mean(1), "token_mean")
+    assert_close(ops.token_mean(dev(xt)), xt.double().mean(1), "token_mean")
     dy, addt = rnd(3, 64, seed=7), rnd(3, 50, 64, seed=8)
-    assert_close(ops.token_mean_bwd(dy.cuda(), 50, add=addt.cuda()), dy.double()[:, None, :] / 50 + addt.double(),
+    assert_close(ops.token_mean_bwd(dev(dy), 50, add=dev(addt)), dy.double()[:, None, :] / 50 + addt.double(),
                  "token_mean_bwd")
     sc, sh = rnd(3, 64, seed=9), rnd(3, 64, seed=10)
-    assert_close(ops.scale_shift(xt.cuda(), sc.cuda(), sh.cuda()), xt.double() * sc.double()[:, None] + sh.double()[:, None],
+    assert_close(ops.scale_shift(dev(xt), dev(sc), dev(sh)), xt.double() * sc.double()[:, None] + sh.double()[:, None],
                  "scale_shift")
-    dxs, dsc, dsh = ops.scale_shift_bwd(addt.cuda(), xt.cuda(), sc.cuda())
+    dxs, dsc, dsh = ops.scale_shift_bwd(dev(addt), dev(xt), dev(sc))
     assert_close(dxs, addt.double() * sc.double()[:, None], "scale_shift_bwd dx")
     assert_close(dsc, (addt.double() * xt.double()).sum(1), "scale_shift_bwd dscale")
     assert_close(dsh, addt.double().sum(1), "scale_shift_bwd dshift")
@@ -281,13 +294,13 @@ def test_timeagg_scale(ops):
     w = rnd(T, E, E, seed=1)
     gamma = (2 ** torch.linspace(-10, 10, E)).unsqueeze(0) * (0.9 + 0.2 * torch.rand(1, E, generator=torch.Generator().manual_seed(2)))
     tt = torch.linspace(0, 1, T)
-    ws = ops.timeagg_scale_w(w.cuda(), gamma.cuda(), tt.cuda())
+    ws = ops.timeagg_scale_w(dev(w), dev(gamma), dev(tt))
     temb = torch.cos(tt.unsqueeze(-1) @ gamma)                                   # fp32 arguments, as the reference
     assert_close(ws, w.double() * temb.double()[:, :, None], "timeagg scale")
     dws = rnd(T, E, E, seed=3)
     wd, gd = w.double().requires_grad_(True), gamma.double().requires_grad_(True)
     ((wd * torch.cos(tt.double().unsqueeze(-1) @ gd)[:, :, None]) * dws.double()).sum().backward()
-    dw, dg = ops.timeagg_scale_w_bwd(dws.cuda(), w.cuda(), gamma.cuda(), tt.cuda())
+    dw, dg = ops.timeagg_scale_w_bwd(dev(dws), dev(w), dev(gamma), dev(tt))
     assert_close(dw, wd.grad, "timeagg dw", rtol=2e-4, atol_scale=2e-4)       # cos of fp32-rounded t*gamma (~1e3 rad)
     assert_close(dg, gd.grad, "timeagg dgamma", rtol=2e-4, atol_scale=2e-4)
 
@@ -304,8 +317,8 @@ def test_rel_l2_loss_and_grad(ops):
         xr = x.clone().requires_grad_(True)
         lref = R.rel_l2_loss(xr, y, m)
         lref.backward()
-        xg = x.cuda().requires_grad_(True)
-        l = rel_l2_loss(xg, y.cuda(), m.cuda() if m is not None else None)
+        xg = dev(x).requires_grad_(True)
+        l = rel_l2_loss(xg, dev(y), dev(m) if m is not None else None)
         (l * 1.7).backward()
         assert abs(l.item() - lref.item()) <= 1e-5 * abs(lref.item())
         assert_close(xg.grad, 1.7 * xr.grad, "loss grad")
@@ -314,22 +327,22 @@ def test_rel_l2_loss_and_grad(ops):
 def test_sumsq_adam_noise(ops):
     n = 1_000_003
     g = rnd(n + 1, seed=1)[:n].contiguous()
-    gd = torch.zeros(n + 5, device="cuda")[:n]
+    gd = dev(torch.zeros(n + 5))[:n]
     gd.copy_(g)
-    out, part = torch.zeros(1, device="cuda"), torch.zeros(1024, device="cuda")
+    out, part = dev(torch.zeros(1)), dev(torch.zeros(1024))
     ops.sumsq(gd, out, part)
     assert abs(out.item() - (g.double() ** 2).sum().item()) <= 1e-6 * (g.double() ** 2).sum().item()
     # Adam vs the oracle's update rule, 3 steps, with clipping active (max_norm below the gradient norm)
     p0, m0, v0 = rnd(n, seed=2), torch.zeros(n), torch.zeros(n)
-    p, m, v = p0.clone().cuda(), m0.clone().cuda(), v0.clone().cuda()
+    p, m, v = dev(p0), dev(m0), dev(v0)
     pr, mr, vr = p0.clone(), m0.clone(), v0.clone()
     lr, b1, b2, eps, wd, max_norm, gscale = 1e-3, 0.9, 0.9, 1e-8, 1e-6, 50.0, 0.5
-    hyper = torch.zeros(8, device="cuda")
+    hyper = dev(torch.zeros(8))
     for step in range(1, 4):
         gk = rnd(n, seed=10 + step)
-        ops.sumsq(gk.cuda(), out, part)
+        ops.sumsq(dev(gk), out, part)
         hyper.copy_(torch.tensor([lr, b1, b2, eps, wd, 1 - b1 ** step, 1 - b2 ** step, max_norm]))
-        ops.adam_step(p, gk.cuda(), m, v, hyper, out, gscale)
+        ops.adam_step(p, dev(gk), m, v, hyper, out, gscale)
         gs = gk * gscale
         coef = R.clip_coef(R.grad_global_norm([gs]), max_norm)
         assert coef.item() < 1.0
@@ -338,7 +351,7 @@ def test_sumsq_adam_noise(ops):
     assert_close(m, mr, "exp_avg")
     assert_close(v, vr, "exp_avg_sq")
     xx, epsn = rnd(2, 8, 8, 3, 4, seed=5), rnd(2, 8, 8, 3, 4, seed=6)
-    got = ops.noise_inject(xx.cuda(), epsn.cuda(), 0.05)
+    got = ops.noise_inject(dev(xx), dev(epsn), 0.05)
     ref = xx + 0.05 * torch.sum(xx ** 2, dim=(1, 2, 3), keepdim=True) ** 0.5 * epsn
     assert_close(got, ref, "noise inject")
 
@@ -351,8 +364,8 @@ def test_sumsq_adam_noise(ops):
                                         (257, 129, 64, 64)])
 def test_gemm_bf16x6_layouts(ops, transA, transB, M, N, K, tile):
     A, B = rnd(K, M, seed=1) if transA else rnd(M, K, seed=1), rnd(N, K, seed=2) if transB else rnd(K, N, seed=2)
-    C = torch.full((M, N), float("nan"), device="cuda")
-    ops.gemm(A.cuda(), B.cuda(), C, M, N, K, transA=transA, transB=transB, lda=A.shape[1], ldb=B.shape[1], ldc=N,
+    C = guard.full_nan((M, N))
+    ops.gemm(dev(A), dev(B), C, M, N, K, transA=transA, transB=transB, lda=A.shape[1], ldb=B.shape[1], ldc=N,
              tile=tile, precision=ops.GEMM_BF16X6)
     ref = (A.double().t() if transA else A.double()) @ (B.double().t() if transB else B.double())
     assert_close(C, ref, f"bf16x6 {M}x{N}x{K} tA={transA} tB={transB}")
@@ -368,8 +381,8 @@ def test_gemm_bf16x6_is_fp32_accurate(ops):
         ref = A.double() @ B.double().t()
         errs = {}
         for name, prec in (("f32", ops.GEMM_F32), ("bf16x6", ops.GEMM_BF16X6)):
-            C = torch.empty(M, N, device="cuda")
-            ops.gemm(A.cuda(), B.cuda(), C, M, N, K, transB=True, lda=K, ldb=K, ldc=N, precision=prec)
+            C = guard.full_nan((M, N,))
+            ops.gemm(dev(A), dev(B), C, M, N, K, transB=True, lda=K, ldb=K, ldc=N, precision=prec)
             errs[name] = ((C.cpu().double() - ref).abs().max() / ref.abs().max()).item()
         assert errs["bf16x6"] <= 1.5 * errs["f32"] + 1e-7, errs
         assert errs["bf16x6"] < 5e-6, errs
@@ -379,9 +392,9 @@ def test_gemm_bf16x6_epilogue_splitk_colsum(ops):
     M, N, K = 300, 200, 4100                                  # wgrad pattern with a partial last K-slab
     dy, x = rnd(K, M, seed=1), rnd(K, N, seed=2)
     for splitk in (1, 7):
-        dW = torch.full((M, N), float("nan"), device="cuda")
-        db = torch.full((M,), float("nan"), device="cuda")
-        ops.gemm(dy.cuda(), x.cuda(), dW, M, N, K, transA=True, lda=M, ldb=N, ldc=N, splitk=splitk, colsum_out=db,
+        dW = guard.full_nan((M, N))
+        db = guard.full_nan((M,))
+        ops.gemm(dev(dy), dev(x), dW, M, N, K, transA=True, lda=M, ldb=N, ldc=N, splitk=splitk, colsum_out=db,
                  colsum_of=1, precision=ops.GEMM_BF16X6, tile=128)
         assert_close(dW, dy.double().t() @ x.double(), f"bf16x6 wgrad sk{splitk}")
         assert_close(db, dy.double().sum(0), f"bf16x6 fused bias grad sk{splitk}")
@@ -389,9 +402,9 @@ def test_gemm_bf16x6_epilogue_splitk_colsum(ops):
     nb, bs, Mm = 4, 24, 300
     E2 = 2 * bs * nb
     S, Wb, bb = rnd(Mm, E2, seed=1), rnd(nb, 2 * bs, 2 * bs, seed=2, scale=0.2), rnd(nb, 2 * bs, seed=3)
-    O = torch.full((Mm, E2), float("nan"), device="cuda")
-    Opre = torch.empty_like(O)
-    ops.gemm(S.cuda(), Wb.cuda(), O, Mm, 2 * bs, 2 * bs, bias=bb.cuda(), strideBias=2 * bs, act=1, mode=ops.EPI_ACT,
+    O = guard.full_nan((Mm, E2))
+    Opre = guard.full_nan(O.shape)
+    ops.gemm(dev(S), dev(Wb), O, Mm, 2 * bs, 2 * bs, bias=dev(bb), strideBias=2 * bs, act=1, mode=ops.EPI_ACT,
              preact=Opre, ldpre=E2, stridePre=2 * bs, lda=E2, ldb=2 * bs, ldc=E2, batch=nb, strideA=2 * bs,
              strideB=4 * bs * bs, strideC=2 * bs, precision=ops.GEMM_BF16X6)
     ref = torch.einsum("mki,kio->mko", S.double().view(Mm, nb, 2 * bs), Wb.double()) + bb.double()
@@ -405,7 +418,7 @@ def test_model_step_gemm_auto_matches_f32(ops):
     from oracle import dpot_ref as R
     cfg = R.DPOTConfig(**R.TINY)
     sd = R.recipe_state_dict(cfg)
-    x = R.recipe_input((4, 128, 128, 10, 4)).cuda()
+    x = dev(R.recipe_input((4, 128, 128, 10, 4)))
     outs = {}
     try:
         for prec in ("f32", "auto"):
@@ -429,7 +442,7 @@ def test_block_mlp_precision_override(ops):
     cfg = R.DPOTConfig(**R.MINI)
     m = DPOTNet(**R.MINI).cuda()
     m.load_state_dict(R.recipe_state_dict(cfg, salt=4))
-    x = R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=9).cuda()
+    x = dev(R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=9))
     try:
         with torch.no_grad():
             y32, _ = m(x)
@@ -454,9 +467,9 @@ def test_gemm_afno_wgrad_epilogue(ops, precision):
     nb, bs, Mm = 3, 40, 700
     E2 = 2 * bs * nb
     S, dO = rnd(Mm, E2, seed=1), rnd(Mm, E2, seed=4)
-    dw = torch.full((2, nb, bs, bs), float("nan"), device="cuda")
-    db = torch.full((2, nb, bs), float("nan"), device="cuda")
-    ops.gemm(S.cuda(), dO.cuda(), dw, 2 * bs, 2 * bs, Mm, transA=True, lda=E2, ldb=E2, ldc=2 * bs, batch=nb,
+    dw = guard.full_nan((2, nb, bs, bs))
+    db = guard.full_nan((2, nb, bs))
+    ops.gemm(dev(S), dev(dO), dw, 2 * bs, 2 * bs, Mm, transA=True, lda=E2, ldb=E2, ldc=2 * bs, batch=nb,
              strideA=2 * bs, strideB=2 * bs, strideC=4 * bs * bs, splitk=5, colsum_out=db, colsum_of=2,
              mode=ops.EPI_AFNO_WGRAD, precision=precision)
     dWbig = torch.einsum("mki,mko->kio", S.double().view(Mm, nb, 2 * bs), dO.double().view(Mm, nb, 2 * bs))
@@ -470,7 +483,7 @@ def test_noise_inject_in_kernel_generator(ops):
     """eps drawn inside the kernel (Philox4x32-10 + Box-Muller): right scale per (b,c), N(0,1) statistics, a fresh
     draw per call (the device-side offset advances), reproducible from the same {seed, offset}"""
     B, X, T, C = 3, 32, 10, 4
-    xx = (rnd(B, X, X, T, C, seed=3) * torch.tensor([1.0, 5.0, 0.2, 2.0])).cuda()
+    xx = dev(rnd(B, X, X, T, C, seed=3) * torch.tensor([1.0, 5.0, 0.2, 2.0]))
     st = ops.rng_state(xx.device)
     st.copy_(torch.tensor([1234, 0], device=st.device))
     s = 0.05
@@ -509,14 +522,14 @@ def test_afno_mlp2_fused_two_layers(ops, nb, bs, M, act):
     pre_ref = torch.einsum("mkn,kno->mko", Xd, W1.double()) + b1.double()
     mid_ref = f(pre_ref)
     Y_ref = torch.einsum("mkn,kno->mko", mid_ref, W2.double()) + b2.double()
-    W1T, W1B = ops.afno_block_weights(W1.cuda())                 # blocked W (forward), blocked W^T (backward)
-    W2T, W2B = ops.afno_block_weights(W2.cuda())
-    Y, pre, mid = ops.afno_mlp2(X.cuda(), W1T, b1.cuda(), W2T, b2.cuda(), nb, bs, ops.ACT_IDS[act], mode=0,
+    W1T, W1B = ops.afno_block_weights(dev(W1))                 # blocked W (forward), blocked W^T (backward)
+    W2T, W2B = ops.afno_block_weights(dev(W2))
+    Y, pre, mid = ops.afno_mlp2(dev(X), W1T, dev(b1), W2T, dev(b2), nb, bs, ops.ACT_IDS[act], mode=0,
                                 want_pre=True, want_mid=True)
     assert_close(pre, pre_ref.reshape(M, -1), "pre")
     assert_close(mid, mid_ref.reshape(M, -1), "mid")
     assert_close(Y, Y_ref.reshape(M, -1), "Y")
-    Yi, p_none, m_none = ops.afno_mlp2(X.cuda(), W1T, b1.cuda(), W2T, b2.cuda(), nb, bs, ops.ACT_IDS[act], mode=0)
+    Yi, p_none, m_none = ops.afno_mlp2(dev(X), W1T, dev(b1), W2T, dev(b2), nb, bs, ops.ACT_IDS[act], mode=0)
     assert p_none is None and m_none is None and torch.equal(Yi, Y)          # inference form: same numbers, no stores
     # backward data path: dO1pre = (dO2 W2^T) * act'(pre), dS = dO1pre W1^T
     dO2 = rnd(M, nb * N, seed=6)
@@ -525,13 +538,13 @@ def test_afno_mlp2_fused_two_layers(ops, nb, bs, M, act):
     dact = pr.grad
     dmid_ref = torch.einsum("mko,kno->mkn", dO2.double().view(M, nb, N), W2.double()) * dact
     dS_ref = torch.einsum("mko,kno->mkn", dmid_ref, W1.double())
-    dS, _, dmid = ops.afno_mlp2(dO2.cuda(), W2B, None, W1B, None, nb, bs, ops.ACT_IDS[act], mode=1,
-                                aux=pre_ref.float().reshape(M, -1).contiguous().cuda(), want_mid=True)
+    dS, _, dmid = ops.afno_mlp2(dev(dO2), W2B, None, W1B, None, nb, bs, ops.ACT_IDS[act], mode=1,
+                                aux=dev(pre_ref.float().reshape(M, -1)), want_mid=True)
     assert_close(dmid, dmid_ref.reshape(M, -1), "dO1pre")
     assert_close(dS, dS_ref.reshape(M, -1), "dS")
     # round 3: the backward launch can also re-derive the forward's activated layer-1 output act(aux)
-    dS2, o1, dmid2 = ops.afno_mlp2(dO2.cuda(), W2B, None, W1B, None, nb, bs, ops.ACT_IDS[act], mode=1,
-                                   aux=pre_ref.float().reshape(M, -1).contiguous().cuda(), want_mid=True, want_pre=True)
+    dS2, o1, dmid2 = ops.afno_mlp2(dev(dO2), W2B, None, W1B, None, nb, bs, ops.ACT_IDS[act], mode=1,
+                                   aux=dev(pre_ref.float().reshape(M, -1)), want_mid=True, want_pre=True)
     assert_close(o1, f(pre_ref.float().double()).reshape(M, -1), "act(aux) re-derived by the backward launch")
     assert_close(dS2, dS_ref.reshape(M, -1), "dS (with act(aux) output)")
     assert_close(dmid2, dmid_ref.reshape(M, -1), "dO1pre (with act(aux) output)")
@@ -544,19 +557,19 @@ def test_plain_bf16_mlp_mode_is_reduced_precision_but_sane(ops):
     M, K, N = 4096, 1024, 1024
     A, W = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=1.0 / math.sqrt(K))
     ref = A.double() @ W.double().t()
-    y32, _ = ops.linear_fwd(A.cuda(), W.cuda(), None)
-    y16, _ = ops.linear_fwd(A.cuda(), W.cuda(), None, precision=ops.GEMM_BF16)
+    y32, _ = ops.linear_fwd(dev(A), dev(W), None)
+    y16, _ = ops.linear_fwd(dev(A), dev(W), None, precision=ops.GEMM_BF16)
     e32 = (y32.cpu().double() - ref).norm() / ref.norm()
     e16 = (y16.cpu().double() - ref).norm() / ref.norm()
     assert e32 < 1e-6 and 1e-4 < e16 < 8e-3, (e32.item(), e16.item())
-    dW = ops.linear_bwd_weight(y16, A.cuda(), precision=ops.GEMM_BF16)                # TN, split-K
+    dW = ops.linear_bwd_weight(y16, dev(A), precision=ops.GEMM_BF16)                # TN, split-K
     dref = y16.cpu().double().t() @ A.double()
     assert (dW.cpu().double() - dref).norm() / dref.norm() < 8e-3
     from dpot_amd import DPOTNet
     cfg = R.DPOTConfig(**R.MINI)
     m = DPOTNet(**R.MINI).cuda()
     m.load_state_dict(R.recipe_state_dict(cfg, salt=4))
-    x = R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=9).cuda()
+    x = dev(R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=9))
     try:
         y_ref, _ = m(x)
         ops.set_mlp_precision("bf16")
@@ -570,33 +583,38 @@ def test_plain_bf16_mlp_mode_is_reduced_precision_but_sane(ops):
 
 
 @pytest.mark.parametrize("M,N,K", [(8192, 512, 512), (333, 256, 96), (100, 64, 32), (4096, 1024, 4096), (1000, 192, 64),
-                                   (77, 1536, 6144 // 4)])
+                                   (77, 1536, 6144 // 4),
+                                   # edges of dpot_gemm_panel_supported (M > 0, K % 32, N a multiple of 64): one row, one row
+                                   # less / more than the 64-row panel and than a 16-row tile, the smallest N and K
+                                   (1, 64, 32), (63, 64, 32), (65, 64, 64), (17, 192, 32), (15, 128, 96)])
 def test_gemm_panel_static_weight(ops, M, N, K):
     """panel GEMM (csrc/gemm_panel.hip) with a pre-packed weight: forward form x W^T (+bias, GELU, pre-activation),
     data-gradient form dy W (* act'(aux)) through the transposed pack, residual epilogue, ragged panels"""
     assert ops.gemm_panel_supported(M, N, K)
     A, W = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=1.0 / math.sqrt(K))            # W [N, K] = nn.Linear layout
     b, R_ = rnd(N, seed=3, scale=0.3), rnd(M, N, seed=4)
-    Wd = W.cuda()
+    Wd = dev(W)
     pk = ops.PanelPacks([(Wd, N, K, K, False), (Wd, K, N, K, True)])                 # W (forward), W^T (dgrad)
     pk.refresh()
     pre_ref = A.double() @ W.double().t() + b.double()
-    y, pre = ops.gemm_panel(A.cuda(), pk.bufs[0], N, bias=b.cuda(), act=1, mode=ops.EPI_ACT, save_pre=True)
+    y, pre = ops.gemm_panel(dev(A), pk.bufs[0], N, bias=dev(b), act=1, mode=ops.EPI_ACT, save_pre=True)
     assert_close(pre, pre_ref, "pre")
     assert_close(y, torch.nn.functional.gelu(pre_ref), "gelu(pre)")
-    y2, _ = ops.gemm_panel(A.cuda(), pk.bufs[0], N, bias=b.cuda(), res=R_.cuda())
+    y2, _ = ops.gemm_panel(dev(A), pk.bufs[0], N, bias=dev(b), res=dev(R_))
     assert_close(y2, pre_ref + R_.double(), "linear + residual")
     if dpot_ok := ops.gemm_panel_supported(M, K, N):
         dY, aux = rnd(M, N, seed=5), rnd(M, K, seed=6)
         pr = aux.double().clone().requires_grad_(True)
         torch.nn.functional.gelu(pr).backward(torch.ones_like(pr))
         dx_ref = (dY.double() @ W.double()) * pr.grad
-        dx, _ = ops.gemm_panel(dY.cuda(), pk.bufs[1], K, act=1, mode=ops.EPI_DACT, aux=aux.cuda())
+        dx, _ = ops.gemm_panel(dev(dY), pk.bufs[1], K, act=1, mode=ops.EPI_DACT, aux=dev(aux))
         assert_close(dx, dx_ref, "dgrad * gelu'")
 
 
 @pytest.mark.parametrize("M,N,K", [(8192, 1024, 1024), (300, 256, 64), (4096, 512, 2048), (129, 768, 96), (1, 256, 32),
-                                   (65500, 256, 64), (16400, 1024, 96)])   # >= 512 tiles: the two-workgroup kernel, ragged M
+                                   (65500, 256, 64), (16400, 1024, 96),
+                                   # one row less / more than the 32-row rounding of the packs (dpot_bf16_packed_elems)
+                                   (31, 256, 32), (33, 256, 256), (63, 512, 256)])   # >= 512 tiles: the two-workgroup kernel, ragged M
 def test_gemm_bf16_panel(ops, M, N, K):
     """bf16 panel GEMM (csrc/gemm_bf16p.hip): packed bf16 operands, fp32 accumulation.  Checked against an fp64 product of
     the bf16-ROUNDED operands (exactly what the kernel multiplies: error there is fp32 accumulation only) and, loosely,
@@ -604,25 +622,25 @@ def test_gemm_bf16_panel(ops, M, N, K):
     assert ops.gemm_bf16p_supported(M, N, K)
     A, W = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=1.0 / math.sqrt(K))
     b, R_ = rnd(N, seed=3, scale=0.3), rnd(M, N, seed=4)
-    Wd = W.cuda()
+    Wd = dev(W)
     pk = ops.PanelPacks([(Wd, N, K, K, False), (Wd, K, N, K, True)] if K % 256 == 0 else [(Wd, N, K, K, False)], bf16=True)
     pk.refresh()
     Ab, Wb = A.bfloat16().double(), W.bfloat16().double()
     pre_ref = Ab @ Wb.t() + b.double()
-    Ap = ops.bf16_pack_rows(A.cuda())
-    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT, save_pre=True)
+    Ap = ops.bf16_pack_rows(dev(A))
+    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT, save_pre=True)
     assert_close(pre, pre_ref, "pre (vs product of the rounded operands)", rtol=2e-5, atol_scale=2e-5)
     assert_close(y, torch.nn.functional.gelu(pre_ref), "gelu", rtol=2e-5, atol_scale=2e-5)
     full = A.double() @ W.double().t() + b.double()
     assert ((pre.cpu().double() - full).norm() / full.norm()).item() < 8e-3
-    y2, _ = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), res=R_.cuda())
+    y2, _ = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=dev(b), res=dev(R_))
     assert_close(y2, pre_ref + R_.double(), "linear + residual", rtol=2e-5, atol_scale=2e-5)
     if K % 256 == 0:                                                 # data-gradient form through the transposed pack
         dY, aux = rnd(M, N, seed=5), rnd(M, K, seed=6)
         pr = aux.double().clone().requires_grad_(True)
         torch.nn.functional.gelu(pr).backward(torch.ones_like(pr))
         dx_ref = (dY.bfloat16().double() @ Wb) * pr.grad
-        dx, _ = ops.gemm_bf16p(ops.bf16_pack_rows(dY.cuda()), pk.bufs[1], M, K, N, act=1, mode=ops.EPI_DACT, aux=aux.cuda())
+        dx, _ = ops.gemm_bf16p(ops.bf16_pack_rows(dev(dY)), pk.bufs[1], M, K, N, act=1, mode=ops.EPI_DACT, aux=dev(aux))
         assert_close(dx, dx_ref, "dgrad * gelu'", rtol=2e-5, atol_scale=2e-5)
 
 
@@ -633,10 +651,10 @@ def test_gemm_bf16_panel_wgrad_splitk(ops, M, N, K, splitk):
     k-dimension = tokens) and split-K over it (fixed-order reduction: deterministic); ragged last split"""
     dy, x = rnd(K, M, seed=1), rnd(K, N, seed=2)                           # [tokens, features]
     ref = dy.bfloat16().double().t() @ x.bfloat16().double()
-    dyp, xp = ops.bf16_pack_rows(dy.cuda(), trans=True), ops.bf16_pack_rows(x.cuda(), trans=True)
+    dyp, xp = ops.bf16_pack_rows(dev(dy), trans=True), ops.bf16_pack_rows(dev(x), trans=True)
     # the transposed pack is the row pack of the transposed matrix
-    assert torch.equal(dyp, ops.bf16_pack_rows(dy.t().contiguous().cuda()))
-    out = torch.full((M, N), float("nan"), device="cuda")
+    assert torch.equal(dyp, ops.bf16_pack_rows(dev(dy.t())))
+    out = guard.full_nan((M, N))
     dw, _ = ops.gemm_bf16p(dyp, xp, M, N, K, out=out, splitk=splitk)
     assert dw.data_ptr() == out.data_ptr()
     assert_close(dw, ref, "dW", rtol=3e-5, atol_scale=3e-5)
@@ -651,7 +669,7 @@ def test_bf16_panel_model_step_within_bf16_bound_of_fp32(ops, monkeypatch):
     from dpot_amd import DPOTNet
     kw = dict(R.MINI, embed_dim=256, out_layer_dim=32, depth=2, mlp_ratio=1, n_blocks=4)
     cfg = R.DPOTConfig(**kw)
-    x = R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=9).cuda()
+    x = dev(R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=9))
 
     def run(prec):
         m = DPOTNet(**kw).cuda()
@@ -686,12 +704,12 @@ def test_implicit_patch_embed_matches_patch_matrix_path(ops, B, X, Y, T, hid, ac
     assert ops.embed_supported(Cc, P, T, hid, Y // P)
     K0 = (Cc + 3) * P * P
     hidp = (hid + 3) // 4 * 4
-    x = rnd(B, X, Y, T, Cc, seed=1).cuda()
-    w0 = rnd(hid, Cc + 3, P, P, seed=2, scale=1.0 / math.sqrt(K0)).cuda()
-    b0 = rnd(hid, seed=3, scale=0.2).cuda()
-    gx = torch.linspace(0, 1, X).cuda()
-    gy = torch.linspace(0, 1, Y).cuda()
-    gt = torch.linspace(0, 1, T).cuda()
+    x = dev(rnd(B, X, Y, T, Cc, seed=1))
+    w0 = dev(rnd(hid, Cc + 3, P, P, seed=2, scale=1.0 / math.sqrt(K0)))
+    b0 = dev(rnd(hid, seed=3, scale=0.2))
+    gx = dev(torch.linspace(0, 1, X))
+    gy = dev(torch.linspace(0, 1, Y))
+    gt = dev(torch.linspace(0, 1, T))
     A0 = ops.patchify(x, gx, gy, gt, P)
     w0p = ops.copy2d_pad(w0, hid, K0, hidp, K0)
     b0p = ops.copy2d_pad(b0, 1, hid, 1, hidp).view(hidp)
@@ -699,7 +717,7 @@ def test_implicit_patch_embed_matches_patch_matrix_path(ops, B, X, Y, T, hid, ac
     grid = F.embed_grid_matrix(gx, gy, gt, X, Y, T, Cc, P)
     assert torch.equal(grid, A0[:grid.shape[0], Cc * P * P:])
     wfrag = ops.embed_pack_w0(w0)
-    bt = torch.empty(grid.shape[0], hidp, device="cuda")
+    bt = guard.full_nan((grid.shape[0], hidp,))
     ops.gemm(grid, w0p[:, Cc * P * P:], bt, grid.shape[0], hidp, grid.shape[1], transB=True, lda=grid.shape[1], ldb=K0,
              ldc=hidp, bias=b0p)
     Hh, Hpre = ops.embed_fwd(x, wfrag, bt, hidp, act)
@@ -708,16 +726,16 @@ def test_implicit_patch_embed_matches_patch_matrix_path(ops, B, X, Y, T, hid, ac
     assert_close(Hpre, Hpre_ref, "Hpre vs patch-matrix path", rtol=2e-5, atol_scale=2e-6)
     assert_close(Hh[:, :hid], Hh_ref[:, :hid], "Hh", rtol=2e-5, atol_scale=2e-6)
     # weight gradient
-    dH = rnd(A0.shape[0], hidp, seed=5).cuda()
+    dH = dev(rnd(A0.shape[0], hidp, seed=5))
     dw_ref = dH.double().t() @ A0.double()                              # [hidp, K0]
-    dw0 = torch.full((hid, K0), float("nan"), device="cuda")
+    dw0 = guard.full_nan((hid, K0))
     ops.embed_wgrad(x, dH, dw0, hid)
     tokT = grid.shape[0]
     dHs = ops.group_rowsum(dH, B, tokT, 1, hidp)
     kg = grid.shape[1]
     ops.gemm(dHs, grid, dw0[:, K0 - kg:], hid, kg, tokT, transA=True, lda=hidp, ldb=kg, ldc=K0)
     assert_close(dw0, dw_ref[:hid], "dW0 (data + grid columns)", rtol=3e-5, atol_scale=3e-6)
-    dw0b = torch.empty_like(dw0)
+    dw0b = guard.full_nan(dw0.shape)
     ops.embed_wgrad(x, dH, dw0b, hid)
     assert torch.equal(dw0b[:, :Cc * P * P], dw0[:, :Cc * P * P]), "implicit wgrad must be deterministic"
 
@@ -730,33 +748,33 @@ def test_gemm_bf16x6_panel_is_fp32_accurate(ops, M, N, K):
     assert ops.gemm_bf16p_supported(M, N, K)
     A, W = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=1.0 / math.sqrt(K))
     b, R_ = rnd(N, seed=3, scale=0.3), rnd(M, N, seed=4)
-    Wd = W.cuda()
+    Wd = dev(W)
     pk = ops.PanelPacks([(Wd, N, K, K, False)], bf16=True, planes=3)
     pk.refresh()
-    Ap = ops.bf16_pack_rows(A.cuda(), planes=3)
+    Ap = ops.bf16_pack_rows(dev(A), planes=3)
     ref = A.double() @ W.double().t() + b.double()
-    y32, _ = ops.linear_fwd(A.cuda(), Wd, b.cuda())                    # native fp32 MFMA for comparison
-    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT, save_pre=True, planes=3)
+    y32, _ = ops.linear_fwd(dev(A), Wd, dev(b))                    # native fp32 MFMA for comparison
+    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT, save_pre=True, planes=3)
     e6 = ((pre.cpu().double() - ref).norm() / ref.norm()).item()
     e32 = ((y32.cpu().double() - ref).norm() / ref.norm()).item()
     assert e6 < 2.0 * e32 + 1e-7, (e6, e32)
     assert_close(pre, ref, "pre", rtol=2e-5, atol_scale=2e-6)
     assert_close(y, torch.nn.functional.gelu(ref), "gelu", rtol=2e-5, atol_scale=2e-6)
-    y2, _ = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), res=R_.cuda(), planes=3)
+    y2, _ = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=dev(b), res=dev(R_), planes=3)
     assert_close(y2, ref + R_.double(), "linear + residual", rtol=2e-5, atol_scale=2e-6)
     if K % 256 == 0:
         pkT = ops.PanelPacks([(Wd, K, N, K, True)], bf16=True, planes=3)
         pkT.refresh()
         dY = rnd(M, N, seed=5)
-        dx, _ = ops.gemm_bf16p(ops.bf16_pack_rows(dY.cuda(), planes=3), pkT.bufs[0], M, K, N, planes=3)
+        dx, _ = ops.gemm_bf16p(ops.bf16_pack_rows(dev(dY), planes=3), pkT.bufs[0], M, K, N, planes=3)
         assert_close(dx, dY.double() @ W.double(), "dgrad", rtol=2e-5, atol_scale=2e-6)
     if M % 32 == 0 or True:
         # weight-gradient form: rows = features (N resp. K), GEMM k-dim = tokens (M, padded to 32 by the pack)
         Mt = (M // 32) * 32
         if Mt >= 32 and K % 256 == 0:
             dY = rnd(Mt, N, seed=6)
-            dw, _ = ops.gemm_bf16p(ops.bf16_pack_rows(dY.cuda(), trans=True, planes=3),
-                                   ops.bf16_pack_rows(A[:Mt].contiguous().cuda(), trans=True, planes=3), N, K, Mt,
+            dw, _ = ops.gemm_bf16p(ops.bf16_pack_rows(dev(dY), trans=True, planes=3),
+                                   ops.bf16_pack_rows(dev(A[:Mt]), trans=True, planes=3), N, K, Mt,
                                    planes=3, splitk=3 if Mt >= 96 else 1)
             assert_close(dw, dY.double().t() @ A[:Mt].double(), "wgrad (split-K)", rtol=2e-5, atol_scale=2e-6)
 
@@ -769,11 +787,11 @@ def test_weight_gradient_kernel_vs_fp64(ops, M, N, K, batch, cs):
     odd slab counts per split"""
     lda, ldb = M * batch, N * batch
     A, B = rnd(K, lda, seed=1), rnd(K, ldb, seed=2)
-    Ad, Bd = A.cuda(), B.cuda()
+    Ad, Bd = dev(A), dev(B)
 
     def run():
-        C = torch.full((batch, M, N), float("nan"), device="cuda")
-        csum = torch.full((batch, M if cs == 1 else N), float("nan"), device="cuda") if cs else None
+        C = guard.full_nan((batch, M, N))
+        csum = guard.full_nan((batch, M if cs == 1 else N)) if cs else None
         sk = ops.auto_splitk(M, N, K, batch, tn=True)
         ops.gemm(Ad, Bd, C, M, N, K, transA=True, lda=lda, ldb=ldb, ldc=N, batch=batch, strideA=M, strideB=N,
                  strideC=M * N, splitk=sk, colsum_out=csum, colsum_of=cs, strideColsum=(M if cs == 1 else N))
@@ -790,10 +808,10 @@ def test_weight_gradient_kernel_vs_fp64(ops, M, N, K, batch, cs):
     assert torch.equal(C, C2), "deterministic"
 
 
-@pytest.mark.parametrize("M,K", [(128, 256), (4096, 1024), (192, 768)])
+@pytest.mark.parametrize("M,K", [(128, 256), (4096, 1024), (192, 768), (64, 256)])      # (64, 256): the smallest admitted
 def test_bf16_pack_both_equals_the_two_single_packs(ops, M, K):
     """the fused pass produces bit-identical row-form and transposed packs to dpot_bf16_pack_rows, and the column sums"""
-    x = rnd(M, K, seed=3).cuda()
+    x = dev(rnd(M, K, seed=3))
     pr, pt, cs = ops.bf16_pack_both(x, want_colsum=True)
     assert torch.equal(pr, ops.bf16_pack_rows(x))
     assert torch.equal(pt, ops.bf16_pack_rows(x, trans=True))
@@ -812,7 +830,7 @@ def test_bf16_mlp_pack_both_path_matches_separate_packs(ops, monkeypatch):
     from dpot_amd import DPOTNet
     kw = dict(R.MINI, img_size=64, embed_dim=256, out_layer_dim=32, depth=2, mlp_ratio=1, n_blocks=4)
     cfg = R.DPOTConfig(**kw)
-    x = R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=9).cuda()
+    x = dev(R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=9))
 
     def run(both, recompute=False):
         set_tune(monkeypatch, pack_both=1 if both else 0)
@@ -848,7 +866,7 @@ def test_bf16x6_mixer_in_the_model_with_recomputation(ops, monkeypatch, bs):
     set_tune(monkeypatch, mixer6=2)
     kw = dict(R.MINI, img_size=256, patch_size=8, embed_dim=2 * bs, out_layer_dim=32, depth=2, mlp_ratio=1, n_blocks=2, modes=32)
     cfg = R.DPOTConfig(**kw)
-    x = R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=9).cuda()
+    x = dev(R.recipe_input((2, cfg.img_size, cfg.img_size, cfg.in_timesteps, cfg.in_channels), salt=9))
     calls = []
     real = ops.afno_mlp2
     monkeypatch.setattr(ops, "afno_mlp2", lambda *a, **k: (calls.append(k.get("layout")), real(*a, **k))[1])
@@ -891,6 +909,24 @@ def _unpack_frag(pk, M, N):
     return t.permute(0, 2, 5, 3, 6, 1, 4).reshape(M, N)                   # row bits [s][j >> 2][kh][j & 3]
 
 
+@pytest.mark.parametrize("rows,K", [(50, 64), (1, 16), (31, 48), (33, 256), (95, 32)])
+@pytest.mark.parametrize("trans", [False, True])
+def test_bf16_pack_rows_pads_ragged_rows_with_zeros(ops, rows, K, trans):
+    """dpot_bf16_pack_rows at rows % 32 != 0 (row form, and the transposed form = the row pack of x^T): the pack holds
+    dpot_bf16_packed_elems = ceil(rows / 32) * 32 rows; the real rows are the bf16 rounding of x, and the padded rows are
+    exact zeros whatever the buffer held before (the wrapper's buffer is poisoned with NaN by tests/guard.py) - the GEMM
+    multiplies them like any other row"""
+    x = rnd(K, rows, seed=7) if trans else rnd(rows, K, seed=7)
+    pk = ops.bf16_pack_rows(dev(x), trans=trans)
+    Rp = (rows + 31) // 32 * 32
+    assert pk.dtype == torch.bfloat16 and pk.numel() == Rp * K == ops._lib.load().dpot_bf16_packed_elems(rows, K, 1)
+    got = _unpack_rows(pk, Rp, K).cpu()
+    want = (x.t() if trans else x).bfloat16().float()
+    assert torch.equal(got[:rows], want)
+    assert torch.equal(got[rows:], torch.zeros(Rp - rows, K))
+    assert torch.equal(pk, ops.bf16_pack_rows(dev(x), trans=trans))          # a second poisoned buffer: the same bits
+
+
 def test_gemm_bf16_panel_saved_activation_derivative(ops):
     """round 3: the EPI_ACT launch of the bf16 channel MLP saves act'(pre-activation) as a bf16 pack instead of the fp32
     pre-activation, and the EPI_DACT launch multiplies by that pack: (a) the pack holds bf16(act'(pre)) - checked against
@@ -898,11 +934,11 @@ def test_gemm_bf16_panel_saved_activation_derivative(ops):
     launch fed with the pack == the same launch fed with the fp32 pre-activation, to the rounding of the pack"""
     M, N, K = 256, 512, 256
     A, W, b = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=1.0 / math.sqrt(K)), rnd(N, seed=3, scale=0.3)
-    pk = ops.PanelPacks([(W.cuda(), N, K, K, False)], bf16=True)
+    pk = ops.PanelPacks([(dev(W), N, K, K, False)], bf16=True)
     pk.refresh()
-    Ap = ops.bf16_pack_rows(A.cuda())
-    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT, save_pre=True)
-    y2, D, pr, _, _ = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT,
+    Ap = ops.bf16_pack_rows(dev(A))
+    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT, save_pre=True)
+    y2, D, pr, _, _ = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT,
                                             save_dact=True, pack_rows=True)
     assert D.dtype == torch.bfloat16 and torch.equal(y, y2)
     p64 = pre.double().cpu().requires_grad_(True)
@@ -912,7 +948,7 @@ def test_gemm_bf16_panel_saved_activation_derivative(ops):
     assert ((got - want).abs() <= 2.0 ** -8 * want.abs() + 1e-6).all()      # one bf16 ulp (8-bit significand)
     # (b) an act'-product epilogue on the same shapes: out = (dY W^T) * act'(pre)
     dY = rnd(M, K, seed=5)
-    dYp = ops.bf16_pack_rows(dY.cuda())
+    dYp = ops.bf16_pack_rows(dev(dY))
     ref, _ = ops.gemm_bf16p(dYp, pk.bufs[0], M, N, K, act=1, mode=ops.EPI_DACT, aux=pre)
     out, _, _, _, _ = ops.gemm_bf16p_packed(dYp, pk.bufs[0], M, N, K, act=1, mode=ops.EPI_DACT, dact=D)
     lin, _ = ops.gemm_bf16p(dYp, pk.bufs[0], M, N, K)                      # dY W^T without the derivative
@@ -926,17 +962,17 @@ def test_gemm_bf16_panel_packed_epilogue_outputs(ops):
     bit-identical to packing the fp32 output afterwards; the fp32 store can be skipped"""
     M, N, K = 256, 512, 256
     A, W, b = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=1.0 / math.sqrt(K)), rnd(N, seed=3, scale=0.3)
-    Wd = W.cuda()
+    Wd = dev(W)
     pk = ops.PanelPacks([(Wd, N, K, K, False)], bf16=True)
     pk.refresh()
-    Ap = ops.bf16_pack_rows(A.cuda())
-    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT, save_pre=True)
-    y2, pre2, pr, pt, cs = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT,
+    Ap = ops.bf16_pack_rows(dev(A))
+    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT, save_pre=True)
+    y2, pre2, pr, pt, cs = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT,
                                                  save_pre=True, pack_rows=True, pack_trans=True, colsum=True)
     assert torch.equal(y, y2) and torch.equal(pre, pre2)
     assert torch.equal(pr, ops.bf16_pack_rows(y)) and torch.equal(pt, ops.bf16_pack_rows(y, trans=True))
     assert_close(cs, y.double().sum(0), "colsum", rtol=2e-5, atol_scale=2e-6)
-    y3, _, pr3, pt3, cs3 = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT,
+    y3, _, pr3, pt3, cs3 = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT,
                                                  pack_trans=True, store=False)
     assert y3 is None and pr3 is None and cs3 is None and torch.equal(pt3, pt)
 
@@ -953,7 +989,7 @@ def test_afno_mlp3_three_product_form(ops, nb, bs, M, act):
     w1, w2 = rnd(2, nb, bs, bs, seed=2, scale=1.0 / math.sqrt(N)), rnd(2, nb, bs, bs, seed=3, scale=1.0 / math.sqrt(N))
     b1, b2 = rnd(2, nb, bs, seed=4, scale=0.3), rnd(2, nb, bs, seed=5, scale=0.3)
     X = rnd(M, nb * N, seed=1)
-    packs = ops.AfnoPacks([(w1.cuda(), b1.cuda()), (w2.cuda(), b2.cuda())])
+    packs = ops.AfnoPacks([(dev(w1), dev(b1)), (dev(w2), dev(b2))])
     assert packs.layout == 1
     (wb1, bb1, f1, bw1), (wb2, bb2, f2, bw2) = packs.refresh()
     f = ACTS[act]
@@ -966,7 +1002,7 @@ def test_afno_mlp3_three_product_form(ops, nb, bs, M, act):
     mid_ref = f(pre_ref)
     midc = torch.complex(mid_ref.view(M, nb, 2, bs)[:, :, 0], mid_ref.view(M, nb, 2, bs)[:, :, 1])
     Y_ref = planar(torch.einsum("mki,kio->mko", midc, W2c) + B2c)
-    Y, pre, mid = ops.afno_mlp2(X.cuda(), f1, bb1, f2, bb2, nb, bs, ops.ACT_IDS[act], mode=0, want_pre=True,
+    Y, pre, mid = ops.afno_mlp2(dev(X), f1, bb1, f2, bb2, nb, bs, ops.ACT_IDS[act], mode=0, want_pre=True,
                                 want_mid=True, layout=1)
     assert_close(pre, pre_ref, "pre")
     assert_close(mid, mid_ref, "mid")
@@ -974,7 +1010,7 @@ def test_afno_mlp3_three_product_form(ops, nb, bs, M, act):
     # against the four-product kernel on the same weights (Wbig packs)
     W1T, W1B = ops.afno_block_weights(wb1)
     W2T, W2B = ops.afno_block_weights(wb2)
-    Y4, pre4, mid4 = ops.afno_mlp2(X.cuda(), W1T, bb1, W2T, bb2, nb, bs, ops.ACT_IDS[act], mode=0, want_pre=True,
+    Y4, pre4, mid4 = ops.afno_mlp2(dev(X), W1T, bb1, W2T, bb2, nb, bs, ops.ACT_IDS[act], mode=0, want_pre=True,
                                    want_mid=True)
     assert_close(Y, Y4.double(), "Y vs four-product kernel", rtol=2e-5, atol_scale=2e-5)
     # backward data path
@@ -985,8 +1021,8 @@ def test_afno_mlp3_three_product_form(ops, nb, bs, M, act):
     Wbig1, Wbig2 = wb1.cpu().double(), wb2.cpu().double()                       # [nb, N, N], W[k][n]
     dmid_ref = torch.einsum("mko,kno->mkn", dO2.double().view(M, nb, N), Wbig2) * dact.view(M, nb, N)
     dS_ref = torch.einsum("mko,kno->mkn", dmid_ref, Wbig1)
-    dS, o1, dmid = ops.afno_mlp2(dO2.cuda(), bw2, None, bw1, None, nb, bs, ops.ACT_IDS[act], mode=1,
-                                 aux=pre_ref.float().contiguous().cuda(), want_mid=True, want_pre=True, layout=1)
+    dS, o1, dmid = ops.afno_mlp2(dev(dO2), bw2, None, bw1, None, nb, bs, ops.ACT_IDS[act], mode=1,
+                                 aux=dev(pre_ref.float()), want_mid=True, want_pre=True, layout=1)
     assert_close(dmid, dmid_ref.reshape(M, -1), "dO1pre")
     assert_close(dS, dS_ref.reshape(M, -1), "dS")
     assert_close(o1, f(pre_ref.float().double()), "act(aux) re-derived by the backward launch")     # == the forward's mid
@@ -1007,7 +1043,7 @@ def test_afno_mlp6_bf16x6_form(ops, monkeypatch, nb, bs, M, act):
     b1, b2 = rnd(2, nb, bs, seed=4, scale=0.3), rnd(2, nb, bs, seed=5, scale=0.3)
     X = rnd(M, nb * N, seed=1)
     with ops.precision_scope("auto", None):
-        packs = ops.AfnoPacks([(w1.cuda(), b1.cuda()), (w2.cuda(), b2.cuda())])
+        packs = ops.AfnoPacks([(dev(w1), dev(b1)), (dev(w2), dev(b2))])
         it1, it2 = packs.refresh()
     assert it1.p6 is not None and it2.p6 is not None
     (wb1, bb1, f1, bw1), (wb2, bb2, f2, bw2) = it1, it2
@@ -1021,16 +1057,16 @@ def test_afno_mlp6_bf16x6_form(ops, monkeypatch, nb, bs, M, act):
     mid_ref = f(pre_ref)
     midc = torch.complex(mid_ref.view(M, nb, 2, bs)[:, :, 0], mid_ref.view(M, nb, 2, bs)[:, :, 1])
     Y_ref = planar(torch.einsum("mki,kio->mko", midc, W2c) + B2c)
-    Y, pre, mid = ops.afno_mlp2(X.cuda(), it1.p6[0], bb1, it2.p6[0], bb2, nb, bs, ops.ACT_IDS[act], mode=0, want_pre=True,
+    Y, pre, mid = ops.afno_mlp2(dev(X), it1.p6[0], bb1, it2.p6[0], bb2, nb, bs, ops.ACT_IDS[act], mode=0, want_pre=True,
                                 want_mid=True, layout=2)
     assert_close(pre, pre_ref, "pre")
     assert_close(mid, mid_ref, "mid")
     assert_close(Y, Y_ref, "Y")
     # inference form (nothing but Y stored) gives the same Y
-    Yi, _, _ = ops.afno_mlp2(X.cuda(), it1.p6[0], bb1, it2.p6[0], bb2, nb, bs, ops.ACT_IDS[act], mode=0, layout=2)
+    Yi, _, _ = ops.afno_mlp2(dev(X), it1.p6[0], bb1, it2.p6[0], bb2, nb, bs, ops.ACT_IDS[act], mode=0, layout=2)
     assert torch.equal(Yi, Y)
     # against the fp32 three-product kernel on the same weights
-    Y3, _, _ = ops.afno_mlp2(X.cuda(), f1, bb1, f2, bb2, nb, bs, ops.ACT_IDS[act], mode=0, layout=1)
+    Y3, _, _ = ops.afno_mlp2(dev(X), f1, bb1, f2, bb2, nb, bs, ops.ACT_IDS[act], mode=0, layout=1)
     assert_close(Y, Y3.double(), "Y vs the fp32 kernel", rtol=2e-5, atol_scale=2e-5)
     # no worse than the fp32 kernel against float64 (both ~3e-7 norm-wise)
     e6 = (Y.double().cpu() - Y_ref).norm() / Y_ref.norm()
@@ -1044,8 +1080,8 @@ def test_afno_mlp6_bf16x6_form(ops, monkeypatch, nb, bs, M, act):
     Wbig1, Wbig2 = wb1.cpu().double(), wb2.cpu().double()                       # [nb, N, N], W[k][n]
     dmid_ref = torch.einsum("mko,kno->mkn", dO2.double().view(M, nb, N), Wbig2) * dact.view(M, nb, N)
     dS_ref = torch.einsum("mko,kno->mkn", dmid_ref, Wbig1)
-    dS, o1, dmid = ops.afno_mlp2(dO2.cuda(), it2.p6[1], None, it1.p6[1], None, nb, bs, ops.ACT_IDS[act], mode=1,
-                                 aux=pre_ref.float().contiguous().cuda(), want_mid=True, want_pre=True, layout=2)
+    dS, o1, dmid = ops.afno_mlp2(dev(dO2), it2.p6[1], None, it1.p6[1], None, nb, bs, ops.ACT_IDS[act], mode=1,
+                                 aux=dev(pre_ref.float()), want_mid=True, want_pre=True, layout=2)
     assert_close(dmid, dmid_ref.reshape(M, -1), "dO1pre")
     assert_close(dS, dS_ref.reshape(M, -1), "dS")
     assert_close(o1, f(pre_ref.float().double()), "act(aux) re-derived by the backward launch")     # == the forward's mid
@@ -1053,7 +1089,9 @@ def test_afno_mlp6_bf16x6_form(ops, monkeypatch, nb, bs, M, act):
 
 @pytest.mark.parametrize("nb,bs,Mm", [(4, 128, 4608), (2, 64, 32 * 13), (8, 128, 32 * 9),
                                       # round 3: bs = 96 (DPOT-Large, N = 192) on the 192 x 192-tile kernel
-                                      (16, 96, 2176), (3, 96, 32 * 5), (16, 96, 32)])
+                                      (16, 96, 2176), (3, 96, 32 * 5), (16, 96, 32),
+                                      # slab counts that do not divide among the splits: 29 / 6, 37 / 8, 23 / 5
+                                      (4, 128, 32 * 29), (2, 64, 32 * 37), (3, 96, 32 * 23)])
 def test_afno_wgrad2_both_layers_one_launch(ops, nb, bs, Mm):
     """dpot_afno_wgrad2: the weight + bias gradients of both AFNO MLP layers from one launch of the weight-gradient kernel
     (2*nb independent N x N problems) + one un-packing reduce, against float64 complex arithmetic"""
@@ -1061,9 +1099,9 @@ def test_afno_wgrad2_both_layers_one_launch(ops, nb, bs, Mm):
     sk = ops.afno_wgrad2_splitk(Mm, nb, bs)
     assert sk >= 1
     S, dO1, O1, dO2 = (rnd(Mm, nb * N, seed=k) for k in (1, 2, 3, 4))
-    dw1, dw2 = (torch.full((2, nb, bs, bs), float("nan"), device="cuda") for _ in range(2))
-    db1, db2 = (torch.full((2, nb, bs), float("nan"), device="cuda") for _ in range(2))
-    ops.afno_wgrad2(S.cuda(), dO1.cuda(), O1.cuda(), dO2.cuda(), nb, bs, dw1, db1, dw2, db2, sk)
+    dw1, dw2 = (guard.full_nan((2, nb, bs, bs)) for _ in range(2))
+    db1, db2 = (guard.full_nan((2, nb, bs)) for _ in range(2))
+    ops.afno_wgrad2(dev(S), dev(dO1), dev(O1), dev(dO2), nb, bs, dw1, db1, dw2, db2, sk)
 
     def ref(A, Bm):
         Ac = A.double().view(Mm, nb, 2, bs)
@@ -1076,23 +1114,35 @@ def test_afno_wgrad2_both_layers_one_launch(ops, nb, bs, Mm):
         rw, rb = ref(A, Bm)
         assert_close(dw, rw, f"dw {nm}", rtol=2e-5, atol_scale=2e-6)
         assert_close(db, rb, f"db {nm}", rtol=2e-5, atol_scale=2e-6)
+    # the same call again: a fresh NaN-poisoned workspace and fresh outputs must give the same bits (no state between calls)
+    again = [guard.full_nan(t.shape) for t in (dw1, db1, dw2, db2)]
+    ops.afno_wgrad2(dev(S), dev(dO1), dev(O1), dev(dO2), nb, bs, again[0], again[1], again[2], again[3], sk)
+    for a, b in zip(again, (dw1, db1, dw2, db2)):
+        assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("T,E,mh", [(8192, 512, 512), (32 * 11, 128, 384), (1024, 256, 128)])
+@pytest.mark.parametrize("T,E,mh", [(8192, 512, 512), (32 * 11, 128, 384), (1024, 256, 128),
+                                    # slab counts that do not divide among the splits: 37 / 8, 53 / 11, 101 / 15
+                                    (32 * 37, 256, 128), (32 * 53, 128, 128), (32 * 101, 512, 256)])
 def test_mlp_wgrad2_both_layers_one_launch(ops, T, E, mh):
     """dpot_mlp_wgrad2: dW2 = do2^T Hh, db2, dW1 = dHpre^T xn2 (stored un-transposed), db1 from one launch + one reduce"""
     sk = ops.mlp_wgrad2_splitk(T, E, mh)
     assert sk >= 1
     do2, Hh, xn2, dH = rnd(T, E, seed=1), rnd(T, mh, seed=2), rnd(T, E, seed=3), rnd(T, mh, seed=4)
-    dW2 = torch.full((E, mh), float("nan"), device="cuda")
-    dW1 = torch.full((mh, E), float("nan"), device="cuda")
-    db2 = torch.full((E,), float("nan"), device="cuda")
-    db1 = torch.full((mh,), float("nan"), device="cuda")
-    ops.mlp_wgrad2(do2.cuda(), Hh.cuda(), xn2.cuda(), dH.cuda(), dW2, db2, dW1, db1, sk)
+    dW2 = guard.full_nan((E, mh))
+    dW1 = guard.full_nan((mh, E))
+    db2 = guard.full_nan((E,))
+    db1 = guard.full_nan((mh,))
+    ops.mlp_wgrad2(dev(do2), dev(Hh), dev(xn2), dev(dH), dW2, db2, dW1, db1, sk)
     assert_close(dW2, do2.double().t() @ Hh.double(), "dW2", rtol=2e-5, atol_scale=2e-6)
     assert_close(dW1, dH.double().t() @ xn2.double(), "dW1", rtol=2e-5, atol_scale=2e-6)
     assert_close(db2, do2.double().sum(0), "db2", rtol=2e-5, atol_scale=2e-6)
     assert_close(db1, dH.double().sum(0), "db1", rtol=2e-5, atol_scale=2e-6)
+    # the same call again: a fresh NaN-poisoned workspace and fresh outputs must give the same bits (no state between calls)
+    again = [guard.full_nan(t.shape) for t in (dW2, db2, dW1, db1)]
+    ops.mlp_wgrad2(dev(do2), dev(Hh), dev(xn2), dev(dH), again[0], again[1], again[2], again[3], sk)
+    for a, b in zip(again, (dW2, db2, dW1, db1)):
+        assert torch.equal(a, b)
 
 
 def test_bf16_panel_packed_epilogue_dact_with_colsum_and_strided_pack(ops):
@@ -1100,29 +1150,123 @@ def test_bf16_panel_packed_epilogue_dact_with_colsum_and_strided_pack(ops):
     column sums (no fp32 store); and dpot_bf16_pack_both on a row window of a wider matrix (ld > K)"""
     M, N, K = 128, 256, 512
     dY, W, aux = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=1.0 / math.sqrt(K)), rnd(M, N, seed=3)
-    Wd = W.cuda()
+    Wd = dev(W)
     pk = ops.PanelPacks([(Wd, N, K, K, False)], bf16=True)
     pk.refresh()
-    Ap = ops.bf16_pack_rows(dY.cuda())
-    ref, _ = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, act=1, mode=ops.EPI_DACT, aux=aux.cuda())
-    c, pre, pr, pt, cs = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, act=1, mode=ops.EPI_DACT, aux=aux.cuda(),
+    Ap = ops.bf16_pack_rows(dev(dY))
+    ref, _ = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, act=1, mode=ops.EPI_DACT, aux=dev(aux))
+    c, pre, pr, pt, cs = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, act=1, mode=ops.EPI_DACT, aux=dev(aux),
                                                pack_rows=True, pack_trans=True, colsum=True, store=False)
     assert c is None and pre is None
     assert torch.equal(pr, ops.bf16_pack_rows(ref)) and torch.equal(pt, ops.bf16_pack_rows(ref, trans=True))
     assert_close(cs, ref.double().sum(0), "colsum", rtol=2e-5, atol_scale=2e-6)
-    wide = rnd(192, 1024, seed=5).cuda()
+    wide = dev(rnd(192, 1024, seed=5))
     win = wide[64:, 256:768]                                   # [128, 512] window, ld = 1024
     r1, t1, c1 = ops.bf16_pack_both(win, want_colsum=True)
     r2, t2, c2 = ops.bf16_pack_both(win.contiguous(), want_colsum=True)
     assert torch.equal(r1, r2) and torch.equal(t1, t2) and torch.equal(c1, c2)
 
 
+@pytest.mark.parametrize("n0,k0,n1,k1,T", [(256, 256, 256, 256, 32 * 100), (128, 256, 256, 512, 32 * 70),
+                                           (256, 256, 128, 256, 32 * 37), (512, 256, 512, 256, 32 * 50)])
+def test_bf16_panel_pair_splitk_uneven_splits_twice(ops, n0, k0, n1, k1, T):
+    """the pair launch with the split factor dpot_gemm_bf16p_pair_splitk picks, at token counts whose 32-token slabs do not
+    divide among the splits (100 / 6, 70 / 4, 37 / 2, 50 / 3): both products against the float64 product of the bf16-rounded
+    operands, and a second call (a fresh NaN-poisoned workspace) gives the same bits"""
+    sk = ops._lib.load().dpot_gemm_bf16p_pair_splitk(n0, k0, n1, k1, T)
+    assert sk >= 2 and (T // 32) % sk != 0
+    dy0, x0, dy1, x1 = rnd(T, n0, seed=1), rnd(T, k0, seed=2), rnd(T, n1, seed=3), rnd(T, k1, seed=4)
+    packs = [ops.bf16_pack_rows(dev(t), trans=True) for t in (dy0, x0, dy1, x1)]
+    r = lambda t: t.bfloat16().double()
+    C0, C1 = ops.gemm_bf16p_pair(packs[0], packs[1], n0, k0, packs[2], packs[3], n1, k1, T)
+    assert_close(C0, r(dy0).t() @ r(x0), "split pair product 0")
+    assert_close(C1, r(dy1).t() @ r(x1), "split pair product 1")
+    D0, D1 = ops.gemm_bf16p_pair(packs[0], packs[1], n0, k0, packs[2], packs[3], n1, k1, T, splitk=sk)
+    assert torch.equal(C0, D0) and torch.equal(C1, D1)
+
+
+@pytest.mark.parametrize("M", [32, 96, 160])
+def test_gemm_bf16_panel_packed_epilogue_small_m_and_ragged_m_rejected(ops, M):
+    """the packed-output epilogue (row pack, transposed pack, act' pack, column sums) at the smallest M it admits and at M
+    that are multiples of 32 but not of the 64 / 128-row tiles: every pack is read back WHOLE (wrapper buffers are
+    NaN-poisoned, so a chunk the epilogue skips would show) and equals the pack of the fp32 output; that output against
+    float64.  The kernel admits packs only at M % 32 == 0, so a pack never has padded rows: a ragged M must be refused, not
+    written with rows that depend on what the buffer held"""
+    N, K = 512, 256
+    A, W, b = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=1.0 / math.sqrt(K)), rnd(N, seed=3, scale=0.3)
+    pk = ops.PanelPacks([(dev(W), N, K, K, False)], bf16=True)
+    pk.refresh()
+    Ap = ops.bf16_pack_rows(dev(A))
+    bd = dev(b)
+    y, pre, pr, pt, cs = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=bd, act=1, mode=ops.EPI_ACT, save_pre=True,
+                                               pack_rows=True, pack_trans=True, colsum=True)
+    pre_ref = A.bfloat16().double() @ W.bfloat16().double().t() + b.double()
+    assert_close(pre, pre_ref, "pre", rtol=2e-5, atol_scale=2e-5)
+    assert_close(y, torch.nn.functional.gelu(pre_ref), "gelu", rtol=2e-5, atol_scale=2e-5)
+    assert pr.numel() == M * N and pt.numel() == M * N
+    assert torch.equal(pr, ops.bf16_pack_rows(y)) and torch.equal(pt, ops.bf16_pack_rows(y, trans=True))
+    assert torch.isfinite(pr.float()).all() and torch.isfinite(pt.float()).all()
+    assert torch.equal(_unpack_rows(pr, M, N).cpu(), y.cpu().bfloat16().float())
+    assert torch.equal(_unpack_rows(pt, N, M).cpu(), y.cpu().t().bfloat16().float())
+    assert_close(cs, y.double().sum(0), "colsum", rtol=2e-5, atol_scale=2e-6)
+    y2, D, pr2, _, _ = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=bd, act=1, mode=ops.EPI_ACT, save_dact=True,
+                                             pack_rows=True)
+    assert torch.equal(y, y2) and torch.equal(pr, pr2) and D.numel() == M * N
+    p64 = pre.double().cpu().requires_grad_(True)
+    torch.nn.functional.gelu(p64).sum().backward()
+    got = _unpack_frag(D, M, N).double().cpu()
+    assert ((got - p64.grad).abs() <= 2.0 ** -8 * p64.grad.abs() + 1e-6).all()    # one bf16 ulp, as the M = 256 test
+    Ar = ops.bf16_pack_rows(dev(rnd(M - 1, K, seed=1)))
+    with pytest.raises(ops._lib.DpotHipError):
+        ops.gemm_bf16p_packed(Ar, pk.bufs[0], M - 1, N, K, bias=bd, act=1, mode=ops.EPI_ACT, pack_rows=True, pack_trans=True)
+
+
+@pytest.mark.parametrize("co", [3, 4, 9])
+@pytest.mark.parametrize("B,h,w,P", [(2, 3, 5, 4), (3, 5, 7, 8), (1, 33, 31, 8)])
+@pytest.mark.parametrize("act", ["gelu", "silu"])
+def test_out_tail_ragged_tile_counts_vs_fp64(ops, B, h, w, P, co, act):
+    """dpot_out_tail_fwd / _bwd (csrc/tail.hip) called directly at pixel counts whose 32-pixel tiles do not divide among the
+    4-wave workgroups, nor among the grid once it is capped (15, 210 and 2046 tiles: 512 workgroups for out_channels <= 4,
+    256 above - dpot_out_tail_partial_rows is sized for the larger), for co <= 4 and > 4: output, dUpre and the five
+    parameter-gradient sums against float64 autograd; the partial rows the smaller grid does not reach come from a
+    NaN-poisoned buffer; a second backward call gives the same bits"""
+    npix = B * h * w * P * P
+    ntiles = npix // 32
+    assert ops.out_tail_supported(32, co, npix) and ntiles % 4 != 0
+    assert ops._lib.load().dpot_out_tail_partial_rows(B, h, w, P) == min((ntiles + 3) // 4, 512)
+    f = ACTS[act]
+    upre, dout = rnd(npix, 32, seed=1), rnd(B, h * P, w * P, co, seed=2)
+    w2, b2 = rnd(32, 32, seed=3, scale=1.0 / math.sqrt(32)), rnd(32, seed=4, scale=0.3)
+    w4, b4 = rnd(co, 32, seed=5, scale=1.0 / math.sqrt(32)), rnd(co, seed=6, scale=0.3)
+    leaves = [t.double().requires_grad_(True) for t in (upre, w2, b2, w4, b4)]
+    U, W2, B2, W4, B4 = leaves
+    u = f(U)
+    z = f(u @ W2.t() + B2) @ W4.t() + B4
+    out_ref = z.view(B, h, w, P, P, co).permute(0, 1, 3, 2, 4, 5).reshape(B, h * P, w * P, co)
+    (out_ref * dout.double()).sum().backward()
+    w2d, b2d = dev(w2), dev(b2)
+    w4p, b4p = ops.out_tail_pad(dev(w4), dev(b4), co)
+    out = ops.out_tail_fwd(dev(upre), w2d, b2d, w4p, b4p, B, h, w, P, co, ops.ACT_IDS[act])
+    assert_close(out, out_ref, "tail fwd")
+    dupre, (g2w, g4w, g2b, g0b, g4b) = ops.out_tail_bwd(dev(upre), dev(dout), w2d, b2d, w4p, B, h, w, P, co, ops.ACT_IDS[act])
+    assert_close(dupre, U.grad, "tail dUpre")
+    assert_close(g2w, W2.grad, "tail dW2")
+    assert_close(g4w, W4.grad, "tail dW4")
+    assert_close(g2b, B2.grad, "tail db2")
+    assert_close(g0b, U.grad.sum(0), "tail colsum(dUpre)")
+    assert_close(g4b, B4.grad, "tail db4")
+    dupre2, res2 = ops.out_tail_bwd(dev(upre), dev(dout), w2d, b2d, w4p, B, h, w, P, co, ops.ACT_IDS[act])
+    assert torch.equal(dupre, dupre2) and all(torch.equal(a, b) for a, b in zip(res2, (g2w, g4w, g2b, g0b, g4b)))
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("M,N,K,act", [(32, 512, 512, 1), (5, 12, 512, 0), (33, 1024, 1024, 1), (64, 100, 1536, 0), (1, 7, 2048, 1)])
+@pytest.mark.parametrize("M,N,K,act", [(32, 512, 512, 1), (5, 12, 512, 0), (33, 1024, 1024, 1), (64, 100, 1536, 0), (1, 7, 2048, 1),
+                                       # the row cap, one output column, one K chunk (dpot_small_linear_supported)
+                                       (128, 1, 512, 1), (128, 3, 512, 0), (31, 5, 512, 1)])
 def test_small_linear_vs_fp64(ops, M, N, K, act):
     """few-row Linear (cls_head on the token mean): one wave per output column, against float64"""
     torch.manual_seed(M + N)
-    x = torch.randn(M, K, device="cuda"); W = torch.randn(N, K, device="cuda") * 0.05; b = torch.randn(N, device="cuda")
+    x = dev(torch.randn(M, K, device="cuda")); W = dev(torch.randn(N, K, device="cuda") * 0.05); b = dev(torch.randn(N, device="cuda"))
     assert ops.small_linear_supported(M, N, K)
     y, pre = ops.linear_fwd(x, W, b, act=act, save_pre=True)
     ref = x.double() @ W.double().t() + b.double()
@@ -1147,14 +1291,14 @@ def test_groupnorm_deferred_param_grads_match(ops):
     torch.manual_seed(3)
     B, T, E, G = 6, 64, 256, 8
     outs = []
-    for add in (None, torch.randn(B, T, E, device="cuda")):
-        x = torch.randn(B, T, E, device="cuda"); dy = torch.randn(B, T, E, device="cuda"); gw = torch.randn(E, device="cuda")
-        _, mean, rstd = ops.groupnorm_fwd(x, gw, torch.zeros(E, device="cuda"), G)
+    for add in (None, dev(torch.randn(B, T, E, device="cuda"))):
+        x = dev(torch.randn(B, T, E, device="cuda")); dy = dev(torch.randn(B, T, E, device="cuda")); gw = dev(torch.randn(E, device="cuda"))
+        _, mean, rstd = ops.groupnorm_fwd(x, gw, dev(torch.zeros(E)), G)
         dx0, dg0, db0 = ops.groupnorm_bwd(dy, x, mean, rstd, gw, G, add=add)
         dx1, part = ops.groupnorm_bwd(dy, x, mean, rstd, gw, G, add=add, defer=True)
         assert torch.equal(dx0, dx1)
         outs.append((part, dg0, db0))
-    slot = torch.zeros(E, device="cuda")
+    slot = dev(torch.zeros(E))
     res = ops.groupnorm_param_grads([(outs[0][0], slot, None), (outs[1][0], None, None)])
     assert res[0][0].data_ptr() == slot.data_ptr()
     for (dg, db), (_, dg0, db0) in zip(res, outs):
@@ -1167,8 +1311,8 @@ def test_bf16_panel_pair_launch_matches_single(ops):
     up to the split-K summation order of the singles (compared against the products of the bf16-rounded operands)"""
     torch.manual_seed(11)
     T, n0, k0, n1, k1 = 1024, 256, 512, 512, 256
-    dy0 = torch.randn(T, n0, device="cuda"); x0 = torch.randn(T, k0, device="cuda")
-    dy1 = torch.randn(T, n1, device="cuda"); x1 = torch.randn(T, k1, device="cuda")
+    dy0 = dev(torch.randn(T, n0, device="cuda")); x0 = dev(torch.randn(T, k0, device="cuda"))
+    dy1 = dev(torch.randn(T, n1, device="cuda")); x1 = dev(torch.randn(T, k1, device="cuda"))
     packs = [ops.bf16_pack_rows(t, trans=True) for t in (dy0, x0, dy1, x1)]
     C0, C1 = ops.gemm_bf16p_pair(packs[0], packs[1], n0, k0, packs[2], packs[3], n1, k1, T, splitk=1)
     r = lambda t: t.bfloat16().double()
@@ -1186,8 +1330,8 @@ def test_bf16_panel_pair_launch_matches_single(ops):
     # the pair launch runs them as 768 tiles of 128 x 192 (2 x 3 compute waves) - same products, same k order: bit-equal to
     # the single launches on 256-wide tiles
     T, n0, k0, n1, k1 = 512, 1536, 6144, 6144, 1536
-    dy0 = torch.randn(T, n0, device="cuda"); x0 = torch.randn(T, k0, device="cuda")
-    dy1 = torch.randn(T, n1, device="cuda"); x1 = torch.randn(T, k1, device="cuda")
+    dy0 = dev(torch.randn(T, n0, device="cuda")); x0 = dev(torch.randn(T, k0, device="cuda"))
+    dy1 = dev(torch.randn(T, n1, device="cuda")); x1 = dev(torch.randn(T, k1, device="cuda"))
     packs = [ops.bf16_pack_rows(t, trans=True) for t in (dy0, x0, dy1, x1)]
     assert ops.gemm_bf16p_pair_wanted(n0, k0, n1, k1, T)
     C0, C1 = ops.gemm_bf16p_pair(packs[0], packs[1], n0, k0, packs[2], packs[3], n1, k1, T, splitk=1)
@@ -1199,14 +1343,15 @@ def test_bf16_panel_pair_launch_matches_single(ops):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,T,E,G", [(4, 1024, 1536, 8), (2, 200, 96, 8), (1, 4096, 768, 8)])
+@pytest.mark.parametrize("B,T,E,G", [(4, 1024, 1536, 8), (2, 200, 96, 8), (1, 4096, 768, 8),
+                                     (1, 1000, 1536, 8)])      # 59 chunks of 17 rows, the last one holds 14
 def test_groupnorm_chunked_vs_fp64(ops, monkeypatch, B, T, E, G):
     """few, large (sample, group) slabs: the chunked kernels (statistics merged through a workspace) against float64
     and against the one-workgroup-per-slab kernels (compared via NULL workspace)"""
     torch.manual_seed(B + T)
-    x = torch.randn(B, T, E, device="cuda") * 1.7 + 0.8
-    gw = torch.randn(E, device="cuda"); gb = torch.randn(E, device="cuda")
-    dy = torch.randn(B, T, E, device="cuda"); add = torch.randn(B, T, E, device="cuda")
+    x = dev(torch.randn(B, T, E, device="cuda") * 1.7 + 0.8)
+    gw = dev(torch.randn(E, device="cuda")); gb = dev(torch.randn(E, device="cuda"))
+    dy = dev(torch.randn(B, T, E, device="cuda")); add = dev(torch.randn(B, T, E, device="cuda"))
     assert ops.groupnorm_ws_elems(B, T, E, G) > 0
     y, mean, rstd = ops.groupnorm_fwd(x, gw, gb, G)
     xd = x.double().view(B, T, G, E // G)
@@ -1235,7 +1380,7 @@ def test_groupnorm_chunked_statistics_hard_cases(ops, case):
     sampled with a stride over the whole chunk, so such a region enters it only in proportion to its size"""
     B, T, E, G = 2, 2048, 768, 8
     torch.manual_seed(5)
-    x = torch.randn(B, T, E, device="cuda")
+    x = dev(torch.randn(B, T, E, device="cuda"))
     if case == "large_mean":
         x = x * 0.05 + 300.0
     elif case == "outlier_first":
@@ -1246,7 +1391,7 @@ def test_groupnorm_chunked_statistics_hard_cases(ops, case):
         x[:, :32, :] += 1.0                      # the first 32 tokens of every sample: +100 sigma (a masked / constant border)
     else:
         x = x * 1e-4 + 2.0
-    gw = torch.ones(E, device="cuda"); gb = torch.zeros(E, device="cuda")
+    gw = dev(torch.ones(E)); gb = dev(torch.zeros(E))
     assert ops.groupnorm_ws_elems(B, T, E, G) > 0
     y, mean, rstd = ops.groupnorm_fwd(x, gw, gb, G)
     xd = x.double().view(B, T, G, E // G)
@@ -1266,15 +1411,15 @@ def test_gemm_bf16_panel_large_shape(ops, M):
     act' pack the derivative of the activation at the kernel's own pre-activation"""
     N, K = 2048, 256                               # 64 x 8 tiles = 512
     A, W, b = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=1.0 / math.sqrt(K)), rnd(N, seed=3, scale=0.3)
-    pk = ops.PanelPacks([(W.cuda(), N, K, K, False)], bf16=True)
+    pk = ops.PanelPacks([(dev(W), N, K, K, False)], bf16=True)
     pk.refresh()
-    Ap = ops.bf16_pack_rows(A.cuda())
+    Ap = ops.bf16_pack_rows(dev(A))
     Ab, Wb = A.bfloat16().double(), W.bfloat16().double()
     ref = Ab @ Wb.t() + b.double()
-    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT, save_pre=True)
+    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT, save_pre=True)
     assert_close(pre, ref, "pre-activation", rtol=2e-6, atol_scale=2e-6)
     assert_close(y, torch.nn.functional.gelu(ref), "output", rtol=4e-6, atol_scale=4e-6)
-    y2, D, pr, pt, cs = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT,
+    y2, D, pr, pt, cs = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT,
                                               save_dact=True, pack_rows=True, pack_trans=True, colsum=True)
     assert torch.equal(y, y2)
     assert torch.equal(_unpack_rows(pr, M, N), y.bfloat16().float())
@@ -1285,7 +1430,7 @@ def test_gemm_bf16_panel_large_shape(ops, M):
     assert ((_unpack_frag(D, M, N).double().cpu() - p64.grad).abs() <= 2.0 ** -8 * p64.grad.abs() + 1e-6).all()
     # the act'-product launch (fc2 data gradient form) on the same many-tile grid, without an fp32 output
     dY = rnd(M, K, seed=5)
-    dYp = ops.bf16_pack_rows(dY.cuda())
+    dYp = ops.bf16_pack_rows(dev(dY))
     lin, _ = ops.gemm_bf16p(dYp, pk.bufs[0], M, N, K)
     want = lin * _unpack_frag(D, M, N)
     _, _, pr2, pt2, cs2 = ops.gemm_bf16p_packed(dYp, pk.bufs[0], M, N, K, act=1, mode=ops.EPI_DACT, dact=D, pack_rows=True,
@@ -1293,8 +1438,8 @@ def test_gemm_bf16_panel_large_shape(ops, M):
     assert torch.equal(_unpack_rows(pr2, M, N), want.bfloat16().float())
     assert torch.equal(_unpack_rows(pt2, N, M), want.t().contiguous().bfloat16().float())
     assert_close(cs2, want.double().sum(0), "column sums of the act' product", rtol=1e-5, atol_scale=1e-5)
-    res = rnd(M, N, seed=7).cuda()
-    z, _ = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), res=res)
+    res = dev(rnd(M, N, seed=7))
+    z, _ = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=dev(b), res=res)
     assert_close(z, ref + res.double().cpu(), "residual epilogue", rtol=2e-6, atol_scale=2e-6)
 
 
@@ -1306,8 +1451,8 @@ def test_groupnorm_applied_on_the_load_of_its_consumer(ops, B, h, E, nb):
     to the two-launch forms; statistics-only GroupNorm == the statistics of the full kernel"""
     tok = h * h
     mx, my = h, h // 2 + 1
-    x = (rnd(B, tok, E, seed=1) * 1.3 + 0.2).cuda()
-    g, b = (1 + 0.3 * rnd(E, seed=2)).cuda(), (0.2 * rnd(E, seed=3)).cuda()
+    x = dev(rnd(B, tok, E, seed=1) * 1.3 + 0.2)
+    g, b = dev(1 + 0.3 * rnd(E, seed=2)), dev(0.2 * rnd(E, seed=3))
     xn, mean, rstd = ops.groupnorm_fwd(x, g, b)
     if ops.groupnorm_stats_supported(B, tok, E):
         m2, r2 = ops.groupnorm_stats(x, g, b)
@@ -1325,7 +1470,7 @@ def test_groupnorm_applied_on_the_load_of_its_consumer(ops, B, h, E, nb):
         pr1, pt1, _ = ops.bf16_pack_both(x.view(M, E), norm=(mean, rstd, g, b, tok))
         assert torch.equal(pr0, pr1) and torch.equal(pt0, pt1)
     if ops.gn_dft_supported(h, h, E):
-        g2, b2 = (1 + 0.3 * rnd(E, seed=4)).cuda(), (0.2 * rnd(E, seed=5)).cuda()
+        g2, b2 = dev(1 + 0.3 * rnd(E, seed=4)), dev(0.2 * rnd(E, seed=5))
         y1, xn2, mm, rr = ops.irfft2_gn(S_ref, x, mean, rstd, g, b, g2, b2, h, h, nb, mx, my)
         y1b, none, mmb, rrb = ops.irfft2_gn(S_ref, x, mean, rstd, g, b, g2, b2, h, h, nb, mx, my, want_xn2=False)
         assert none is None and torch.equal(y1, y1b) and torch.equal(mm, mmb) and torch.equal(rr, rrb)
@@ -1340,16 +1485,16 @@ def test_gemm_bf16_panel_192_wide_tiles(ops):
     256-wide kernel: fp64 product of the bf16-rounded operands, residual epilogue, packed outputs, act' pack"""
     M, N, K = 4096, 1536, 512
     A, W, b = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=1.0 / math.sqrt(K)), rnd(N, seed=3, scale=0.3)
-    pk = ops.PanelPacks([(W.cuda(), N, K, K, False)], bf16=True)
+    pk = ops.PanelPacks([(dev(W), N, K, K, False)], bf16=True)
     pk.refresh()
-    Ap = ops.bf16_pack_rows(A.cuda())
+    Ap = ops.bf16_pack_rows(dev(A))
     ref = A.bfloat16().double() @ W.bfloat16().double().t() + b.double()
-    res = rnd(M, N, seed=7).cuda()
-    z, _ = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), res=res)
+    res = dev(rnd(M, N, seed=7))
+    z, _ = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=dev(b), res=res)
     assert_close(z, ref + res.double().cpu(), "residual epilogue", rtol=2e-6, atol_scale=2e-6)
-    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT, save_pre=True)
+    y, pre = ops.gemm_bf16p(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT, save_pre=True)
     assert_close(pre, ref, "pre-activation", rtol=2e-6, atol_scale=2e-6)
-    y2, D, pr, pt, cs = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=b.cuda(), act=1, mode=ops.EPI_ACT,
+    y2, D, pr, pt, cs = ops.gemm_bf16p_packed(Ap, pk.bufs[0], M, N, K, bias=dev(b), act=1, mode=ops.EPI_ACT,
                                               save_dact=True, pack_rows=True, pack_trans=True, colsum=True)
     assert torch.equal(y, y2)
     assert torch.equal(_unpack_rows(pr, M, N), y.bfloat16().float())
@@ -1360,7 +1505,7 @@ def test_gemm_bf16_panel_192_wide_tiles(ops):
     assert ((_unpack_frag(D, M, N).double().cpu() - p64.grad).abs() <= 2.0 ** -8 * p64.grad.abs() + 1e-6).all()
     # weight-gradient form with split-K on the same column count (K = tokens)
     dy, x = rnd(M, 256, seed=8), rnd(M, N, seed=9)
-    dyT, xT = ops.bf16_pack_rows(dy.cuda(), trans=True), ops.bf16_pack_rows(x.cuda(), trans=True)
+    dyT, xT = ops.bf16_pack_rows(dev(dy), trans=True), ops.bf16_pack_rows(dev(x), trans=True)
     g, _ = ops.gemm_bf16p(dyT, xT, 256, N, M)
     assert_close(g, dy.bfloat16().double().t() @ x.bfloat16().double(), "weight-gradient form", rtol=4e-6, atol_scale=4e-6)
 
@@ -1375,9 +1520,9 @@ def test_groupnorm_dft_fused_kernels_vs_separate(ops, E, nb, modes):
     if not ops.gn_dft_supported(h, h, E):
         pytest.skip("fused GroupNorm-DFT kernels switched off (DPOT_TUNE gn_fuse=0): the separate kernels run")
     mx, my = min(modes, h), min(modes, h // 2 + 1)
-    x = (rnd(B, h * h, E, seed=1) * 1.7 + 0.4).cuda()
-    g1, b1 = (1 + 0.3 * rnd(E, seed=2)).cuda(), (0.2 * rnd(E, seed=3)).cuda()
-    g2, b2 = (1 + 0.3 * rnd(E, seed=4)).cuda(), (0.2 * rnd(E, seed=5)).cuda()
+    x = dev(rnd(B, h * h, E, seed=1) * 1.7 + 0.4)
+    g1, b1 = dev(1 + 0.3 * rnd(E, seed=2)), dev(0.2 * rnd(E, seed=3))
+    g2, b2 = dev(1 + 0.3 * rnd(E, seed=4)), dev(0.2 * rnd(E, seed=5))
     tol = dict(rtol=2e-5, atol_scale=2e-5)
     # K1: norm1 + rfft2
     xn1, m1, r1 = ops.groupnorm_fwd(x, g1, b1)
@@ -1387,7 +1532,7 @@ def test_groupnorm_dft_fused_kernels_vs_separate(ops, E, nb, modes):
     assert_close(r1f, r1, "rstd1", **tol)
     assert_close(S, S_ref, "gn_rfft2 spectrum", **tol)
     # K2: irfft2 + x_orig + norm2
-    O2 = (rnd(B * mx * my, 2 * E, seed=6) * 0.8).cuda()
+    O2 = dev(rnd(B * mx * my, 2 * E, seed=6) * 0.8)
     y1_ref = ops.irfft2(O2, B, h, h, E, nb, mx, my, 1, res=xn1)
     xn2_ref, m2, r2 = ops.groupnorm_fwd(y1_ref, g2, b2)
     y1, xn2, m2f, r2f = ops.irfft2_gn(O2, x, m1, r1, g1, b1, g2, b2, h, h, nb, mx, my)
@@ -1396,7 +1541,7 @@ def test_groupnorm_dft_fused_kernels_vs_separate(ops, E, nb, modes):
     assert_close(m2f, m2, "mean2", **tol)
     assert_close(r2f, r2, "rstd2", **tol)
     # K3: norm2 backward + rfft2 with the adjoint column weights
-    dxn2 = rnd(B, h * h, E, seed=7).cuda()
+    dxn2 = dev(rnd(B, h * h, E, seed=7))
     dy1_ref, part2_ref = ops.groupnorm_bwd(dxn2, y1_ref, m2, r2, g2, defer=True)
     dO2_ref = ops.rfft2(dy1_ref, h, h, nb, mx, my, 1)
     dy1, part2, dO2 = ops.gn_bwd_rfft2(dxn2, y1_ref, m2, r2, g2, h, h, nb, mx, my, col_weights=1)
@@ -1404,8 +1549,8 @@ def test_groupnorm_dft_fused_kernels_vs_separate(ops, E, nb, modes):
     assert_close(part2, part2_ref, "gn_bwd_rfft2 partials", **tol)
     assert_close(dO2, dO2_ref, "gn_bwd_rfft2 spectrum", **tol)
     # K4: adjoint irfft2 + skip + norm1 backward + outer skip
-    dS = (rnd(B * mx * my, 2 * E, seed=8) * 0.8).cuda()
-    dout = rnd(B, h * h, E, seed=9).cuda()
+    dS = dev(rnd(B * mx * my, 2 * E, seed=8) * 0.8)
+    dout = dev(rnd(B, h * h, E, seed=9))
     dxn1_ref = ops.irfft2(dS, B, h, h, E, nb, mx, my, 0, res=dy1_ref)
     dx_ref, part1_ref = ops.groupnorm_bwd(dxn1_ref, x, m1, r1, g1, add=dout, defer=True)
     dx, part1 = ops.irfft2_gn_bwd(dS, dy1_ref, x, m1, r1, g1, h, h, nb, mx, my, add=dout, col_weights=0)
@@ -1423,9 +1568,9 @@ def test_groupnorm_rfft2_fused_with_a_large_group_mean(ops):
     B, h, E, nb = 2, 16, 512, 4
     if not ops.gn_dft_supported(h, h, E):
         pytest.skip("fused GroupNorm-DFT kernels switched off")
-    g1, b1 = (1 + 0.3 * rnd(E, seed=2)).cuda(), (0.2 * rnd(E, seed=3)).cuda()
+    g1, b1 = dev(1 + 0.3 * rnd(E, seed=2)), dev(0.2 * rnd(E, seed=3))
     for ratio in (1e2, 1e3):
-        x = (rnd(B, h * h, E, seed=1) + ratio).cuda()
+        x = dev(rnd(B, h * h, E, seed=1) + ratio)
         xd = x.double().view(B, h * h, 8, E // 8)
         mu = xd.mean(dim=(1, 3), keepdim=True)
         var = xd.var(dim=(1, 3), unbiased=False, keepdim=True)
@@ -1458,11 +1603,11 @@ def test_afno_layer_one_launch_vs_three_launches(ops, monkeypatch, E, nb, B, nor
     if not ops.afno_fused_supported(h, h, E, nb, mx, my, G=G if norm else 0):
         pytest.skip("one-launch AFNO layer not available")
     a = ops.ACT_IDS[act]
-    x = (rnd(B, h * h, E, seed=1) * 1.3 + 0.25).cuda()
-    g1, b1 = (1 + 0.3 * rnd(E, seed=2)).cuda(), (0.2 * rnd(E, seed=3)).cuda()
-    g2, b2 = (1 + 0.3 * rnd(E, seed=4)).cuda(), (0.2 * rnd(E, seed=5)).cuda()
-    w1, w2 = (rnd(2, nb, bs, bs, seed=6) * 0.09).cuda(), (rnd(2, nb, bs, bs, seed=7) * 0.09).cuda()
-    bb1, bb2 = (rnd(2, nb, bs, seed=8) * 0.1).cuda(), (rnd(2, nb, bs, seed=9) * 0.1).cuda()
+    x = dev(rnd(B, h * h, E, seed=1) * 1.3 + 0.25)
+    g1, b1 = dev(1 + 0.3 * rnd(E, seed=2)), dev(0.2 * rnd(E, seed=3))
+    g2, b2 = dev(1 + 0.3 * rnd(E, seed=4)), dev(0.2 * rnd(E, seed=5))
+    w1, w2 = dev(rnd(2, nb, bs, bs, seed=6) * 0.09), dev(rnd(2, nb, bs, bs, seed=7) * 0.09)
+    bb1, bb2 = dev(rnd(2, nb, bs, seed=8) * 0.1), dev(rnd(2, nb, bs, seed=9) * 0.1)
     packed = ops.AfnoPacks([(w1, bb1), (w2, bb2)]).refresh()
     assert getattr(packed[0], "layout", 0) == 1
     n = (g1, b1, g2, b2) if norm else (None, None, None, None)
@@ -1538,10 +1683,10 @@ def test_groupnorm_bwd_writes_the_gradient_packs(ops, B, T, E, add):
     if rows == 0:
         pytest.skip("pack-emitting GroupNorm backward not available for this shape")
     torch.manual_seed(B + T + E)
-    x = torch.randn(B, T, E, device="cuda") * 1.5 + 0.3
-    dy = torch.randn(B, T, E, device="cuda")
-    gw, gb = torch.randn(E, device="cuda"), torch.randn(E, device="cuda")
-    res = torch.randn(B, T, E, device="cuda") if add else None
+    x = dev(torch.randn(B, T, E, device="cuda") * 1.5 + 0.3)
+    dy = dev(torch.randn(B, T, E, device="cuda"))
+    gw, gb = dev(torch.randn(E, device="cuda")), dev(torch.randn(E, device="cuda"))
+    res = dev(torch.randn(B, T, E, device="cuda")) if add else None
     _, mean, rstd = ops.groupnorm_fwd(x, gw, gb, G)
     dx0, part0 = ops.groupnorm_bwd(dy, x, mean, rstd, gw, G, add=res, defer=True)
     dx, part, pr, pt, cs = ops.groupnorm_bwd_packs(dy, x, mean, rstd, gw, G, add=res)

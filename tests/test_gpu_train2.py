@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import guard
+from guard import guarded  # noqa: F401  (fixture)
 from helpers import RTOL, assert_close, load, set_tune
 from oracle import dpot_ref as R
 
@@ -117,16 +119,16 @@ def test_grad_norm_without_clipping():
 
 # ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", [(2, 8, 8, 4, 3), (3, 16, 16, 10, 4)])
-def test_noise_backward_and_window_slide_vs_autograd(shape):
+def test_noise_backward_and_window_slide_vs_autograd(shape, guarded):
     from dpot_amd import ops
     from dpot_amd.train import _NoiseFn, _SlideFn
     g = torch.Generator().manual_seed(3)
-    xx = torch.randn(*shape, generator=g).cuda()
-    eps = torch.randn(*shape, generator=g).cuda()
-    up = torch.randn(*shape, generator=g).cuda()
+    xx = guard.wrap(torch.randn(*shape, generator=g), "cuda")
+    eps = guard.wrap(torch.randn(*shape, generator=g), "cuda")
+    up = guard.wrap(torch.randn(*shape, generator=g), "cuda")
     s = 0.3
     # explicit eps: against torch autograd of the reference expression (train_temporal.py:205)
-    a = xx.clone().requires_grad_(True)
+    a = guard.wrap(xx).requires_grad_(True)
     (_NoiseFn.apply(a, eps, s) * up).sum().backward()
     b = xx.clone().requires_grad_(True)
     ref = b + s * torch.sum(b ** 2, dim=(1, 2, 3), keepdim=True) ** 0.5 * eps
@@ -134,7 +136,7 @@ def test_noise_backward_and_window_slide_vs_autograd(shape):
     assert_close(a.grad, b.grad, "noise bwd (eps given)")
     # in-kernel generator: the backward re-draws the forward's noise from the saved generator state
     if xx.numel() % 4 == 0:
-        c = xx.clone().requires_grad_(True)
+        c = guard.wrap(xx).requires_grad_(True)
         out = _NoiseFn.apply(c, None, s)
         (out * up).sum().backward()
         n = torch.sum(xx ** 2, dim=(1, 2, 3), keepdim=True) ** 0.5
@@ -143,8 +145,8 @@ def test_noise_backward_and_window_slide_vs_autograd(shape):
         assert_close(c.grad, want, "noise bwd (in-kernel generator)", rtol=1e-3, atol_scale=1e-3)
     # window slide
     Tb = 2 if shape[3] > 2 else 1
-    im = torch.randn(*shape[:3], Tb, shape[4], generator=g).cuda()
-    a, ai = xx.clone().requires_grad_(True), im.clone().requires_grad_(True)
+    im = guard.wrap(torch.randn(*shape[:3], Tb, shape[4], generator=g), "cuda")
+    a, ai = guard.wrap(xx).requires_grad_(True), guard.wrap(im).requires_grad_(True)
     o = _SlideFn.apply(a, ai)
     (o * up).sum().backward()
     b, bi = xx.clone().requires_grad_(True), im.clone().requires_grad_(True)
@@ -531,9 +533,9 @@ def test_backward_after_graph_replay_raises():
     assert torch.isfinite(opt.grad_norm()).item()
 
 
-def test_window_slide_rejects_mismatched_prediction():
+def test_window_slide_rejects_mismatched_prediction(guarded):
     from dpot_amd import _lib, ops
-    xx = torch.zeros(2, 8, 8, 4, 3, device="cuda")
+    xx = guard.wrap(torch.zeros(2, 8, 8, 4, 3, device="cuda"))
     with pytest.raises(_lib.DpotHipError):
         ops.window_slide(xx, torch.zeros(2, 8, 8, 1, 4, device="cuda"))      # out_channels != in_channels
     with pytest.raises(_lib.DpotHipError):
@@ -712,3 +714,50 @@ def test_adam_step_packs_at_model_sizes(E, mh, depth):
         assert torch.equal(pb[n_active:], p0[n_active:])                      # the tail is not touched
         for a, b in zip(ref.bufs, pk.bufs):
             assert torch.equal(a.view(torch.int16), b.view(torch.int16))
+
+
+def test_adam_step_packs_at_the_smallest_weight(guarded):
+    """dpot_adam_step_packs at the smallest weight dpot_adam_pack_supported admits (rows = 64, K = 256: ONE 64 x 256 tile)
+    between small tensors, on guarded buffers (tests/guard.py): parameters and moments bit-identical to dpot_adam_step and
+    within the neighbouring test's bound of the float64 update rule; both packs, NaN before the launch, bit-identical to the
+    packs of the updated weight; the tail beyond n_active and every guard untouched"""
+    from dpot_amd import ops
+    rows, K = 64, 256
+    assert ops._lib.load().dpot_adam_pack_supported(rows, K) and not ops._lib.load().dpot_adam_pack_supported(rows - 32, K)
+    sizes = [100, rows * K, 36, 64]
+    offs, off = [], 0
+    for n in sizes:
+        offs.append(off)
+        off += (n + 3) // 4 * 4
+    n_active = offs[-1]
+    gen = torch.Generator().manual_seed(64)
+    p0, g = torch.randn(off, generator=gen) * 0.05, torch.randn(off, generator=gen) * 0.01
+    m0, v0 = torch.randn(off, generator=gen) * 0.01, torch.rand(off, generator=gen) * 1e-4
+    lr, b1, b2, eps, wd, gscale = 1e-3, 0.9, 0.9, 1e-8, 1e-6, 0.5
+    hyper = guard.wrap(torch.zeros(8), "cuda")
+    step = guard.wrap(torch.zeros(1, dtype=torch.int64), "cuda")
+    ops.adam_stage(hyper, step, lr, b1, b2, eps, wd, 1e9, 1)
+    gd = guard.wrap(g, "cuda")
+    weight = lambda p: p[offs[1]:offs[1] + rows * K].view(rows, K)
+    jobs = lambda p: [(weight(p), rows, K, K, False), (weight(p), K, rows, K, True)]
+    pa, ma, va = (guard.wrap(t, "cuda") for t in (p0, m0, v0))
+    ops.adam_step(pa[:n_active], gd[:n_active], ma[:n_active], va[:n_active], hyper, None, gscale)
+    ref = ops.PanelPacks(jobs(pa), bf16=True)
+    ref.refresh()
+    pb, mb, vb = (guard.wrap(t, "cuda") for t in (p0, m0, v0))
+    pk = ops.PanelPacks(jobs(pb), bf16=True)
+    for b in pk.bufs:
+        b.fill_(float("nan"))
+    plan = ops.AdamPackPlan.build(pb, n_active, pk)
+    assert plan is not None and plan.ntiles == 1
+    ops.adam_step_packs(plan, pb, gd, mb, vb, hyper, None, gscale)
+    torch.cuda.synchronize()
+    assert torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb)
+    assert torch.equal(pb[n_active:].cpu(), p0[n_active:]) and torch.equal(mb[n_active:].cpu(), m0[n_active:])
+    for a, b in zip(ref.bufs, pk.bufs):
+        assert torch.isfinite(b.float()).all() and torch.equal(a.view(torch.int16), b.view(torch.int16))
+    pr, mr, vr = p0[:n_active].clone().double(), m0[:n_active].clone().double(), v0[:n_active].clone().double()
+    R.adam_update(pr, g[:n_active].double() * gscale, mr, vr, 1, lr, b1, b2, eps, wd)
+    assert (pb[:n_active].cpu().double() - pr).abs().max().item() <= 2e-3 * lr
+    assert_close(mb[:n_active], mr, "exp_avg")
+    assert_close(vb[:n_active], vr, "exp_avg_sq")
