@@ -3,11 +3,14 @@
     from dpot_amd import DPOTNet            # drop-in for models/dpot.py::DPOTNet of HaoZhongkai/DPOT
     from dpot_amd.train import FlatParams, FusedAdam, FusedLamb, train_step, GraphedTrainStep
     from dpot_amd.dp import BucketedGradReducer
+    from dpot_amd import StepMetrics, cls_ce_loss     # device-side training metrics, the dataset-classification loss
 
 The compute path is libdpot_hip.so (hand-written HIP kernels behind the C ABI in include/dpot_hip.h).
 """
 from .model import DPOTNet  # noqa: F401
 from . import _lib  # noqa: F401
+from .functional import ClsCEFn, cls_ce_loss  # noqa: F401
+from .train import StepMetrics  # noqa: F401
 
-__version__ = "0.2.7"
-__all__ = ["DPOTNet"]
+__version__ = "0.2.8"
+__all__ = ["DPOTNet", "StepMetrics", "ClsCEFn", "cls_ce_loss"]

@@ -159,6 +159,10 @@ SIGNATURES = {
     "dpot_lamb_chunk_elems": (c_i, []),
     "dpot_lamb_step": (c_i, [c_fp] * 5 + [c_fp, c_f, c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_i, c_fp]),
     "dpot_lamb_stage": (c_i, [c_fp, c_fp, c_d, c_d, c_d, c_f, c_f, c_f, c_f, c_i, c_i, c_fp]),
+    "dpot_cls_ce_fwd": (c_i, [c_fp] * 4 + [c_i, c_i, c_fp]),
+    "dpot_cls_ce_bwd": (c_i, [c_fp] * 5 + [c_i, c_i, c_fp]),
+    "dpot_rel_l2_combine": (c_i, [c_fp, c_fp, c_i64, c_i, c_i, c_i, c_fp, c_fp]),
+    "dpot_metrics_accum": (c_i, [c_fp] * 4 + [c_i, c_fp, c_f, c_i64, c_i64, c_i64, c_fp]),
     "dpot_noise_chunks": (c_i, [c_i, c_i]),
     "dpot_noise_inject": (c_i, [c_fp] * 4 + [c_f] + [c_i] * 3 + [c_fp]),
     "dpot_noise_inject_rng": (c_i, [c_fp] * 4 + [c_f] + [c_i] * 3 + [c_fp]),

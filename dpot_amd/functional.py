@@ -956,7 +956,7 @@ class RelL2Fn(torch.autograd.Function):
     """sum_b sum_c ||(x-y) m||_2 / (||y m||_2 + 1e-8) / n_channels_b   (SimpleLpLoss(size_average=False))"""
 
     @staticmethod
-    def forward(ctx, x, y, mask: Optional[Tensor]):
+    def forward(ctx, x, y, mask: Optional[Tensor], stats_out: Optional[Tensor] = None):
         x, y = ops._req(x.contiguous(), "pred"), ops._req(y.contiguous(), "target")
         B, Cc = x.shape[0], x.shape[-1]
         Tt = x.shape[-2] if x.dim() >= 3 else 1
@@ -971,7 +971,9 @@ class RelL2Fn(torch.autograd.Function):
                 raise ValueError(f"mask shape {tuple(mask.shape)} does not broadcast over {tuple(x.shape)}")
         else:
             Tt_m = 1
-        loss, stats = ops.rel_l2_fwd(x, y, mask, B, S, Cc, Tt_m)
+        # stats_out: a caller-owned slot the statistics are left in (and the backward reads them from): the per-step slots of
+        # train.StepMetrics, from which ops.rel_l2_combine forms the full-rollout loss.  Same kernels, same result.
+        loss, stats = ops.rel_l2_fwd(x, y, mask, B, S, Cc, Tt_m, stats=stats_out)
         ctx.save_for_backward(x, y, mask if mask is not None else x.new_empty(0), stats)
         ctx.meta = (B, S, Cc, Tt_m, mask is not None)
         return loss.view(())
@@ -981,7 +983,29 @@ class RelL2Fn(torch.autograd.Function):
         x, y, mask, stats = ctx.saved_tensors
         B, S, Cc, Tt_m, has_mask = ctx.meta
         dx = ops.rel_l2_bwd(x, y, mask if has_mask else None, stats, g.contiguous().view(1), B, S, Cc, Tt_m)
-        return dx, None, None
+        return dx, None, None, None
+
+
+class ClsCEFn(torch.autograd.Function):
+    """CrossEntropyLoss(reduction='sum')(logits, labels) and the number of rows whose argmax equals the label
+    (train_temporal.py:209-213), both from one launch; backward: gloss * (softmax - onehot), one launch.
+    Returns (loss 0-d float32, correct 0-d int64), both views of the 4-word dpot_cls_ce_out slot (ops.cls_ce_fwd);
+    `slot` = None, or a 1-element list holding a caller-owned slot (a list, so that autograd does not see it as an input)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, slot=None):
+        logits = ops._req(logits.contiguous(), "logits")
+        labels = labels.contiguous().view(-1)
+        out, row_stats = ops.cls_ce_fwd(logits, labels, slot[0] if slot else None)
+        ctx.save_for_backward(logits, labels, row_stats)
+        correct = out[1]
+        ctx.mark_non_differentiable(correct)
+        return ops.cls_out_loss(out), correct
+
+    @staticmethod
+    def backward(ctx, g, _gc):
+        logits, labels, row_stats = ctx.saved_tensors
+        return ops.cls_ce_bwd(logits, labels, row_stats, g.contiguous().view(1)), None, None
 
 
 class AdaINFn(torch.autograd.Function):
@@ -999,5 +1023,12 @@ class AdaINFn(torch.autograd.Function):
         return ops.scale_shift_bwd(g.contiguous(), lat, scale)
 
 
-def rel_l2_loss(x: Tensor, y: Tensor, mask: Optional[Tensor] = None) -> Tensor:
-    return RelL2Fn.apply(x, y, mask)
+def rel_l2_loss(x: Tensor, y: Tensor, mask: Optional[Tensor] = None, stats_out: Optional[Tensor] = None) -> Tensor:
+    return RelL2Fn.apply(x, y, mask, stats_out)
+
+
+def cls_ce_loss(logits: Tensor, labels: Tensor, out: Optional[Tensor] = None):
+    """-> (loss, correct): the summed cross-entropy of logits [B, n_cls] against int64 labels [B] / [B, 1] (differentiable in
+    the logits) and the count of rows whose first maximal logit is the label.  Rows with a label outside [0, n_cls) add
+    nothing to either and get a zero gradient; `out` (optional 4-word int64 slot) then holds their count in word 3."""
+    return ClsCEFn.apply(logits, labels, [out] if out is not None else None)

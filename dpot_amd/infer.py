@@ -87,9 +87,14 @@ def load_components_from_pretrained(model: nn.Module, state_dict: Union[str, Map
 # ------------------------------------------------------------------------------------------------------
 @torch.no_grad()
 def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
-                 step=None) -> Tuple[Tensor, Tensor, Tensor]:
+                 step=None, metrics=None) -> Tuple[Tensor, Tensor, Tensor]:
     """evaluate.py:193-213.  Returns (pred [B,X,Y,T_ar,C], sum of the per-step losses, loss of the whole rollout).
-    `step(xx) -> im` defaults to the model's forward (a GraphedRollout passes its graph replay)."""
+    `step(xx) -> im` defaults to the model's forward (a GraphedRollout passes its graph replay).
+    metrics: a train.StepMetrics - the test loop's test_l2_step / test_l2_full (train_temporal.py:252-281) are accumulated
+    on the device (one launch per rollout, no synchronisation; `metrics.read()` at the end of the loop), and the loss of the
+    whole rollout is formed from the statistics the per-step losses left (ops.rel_l2_combine) instead of a second pass over
+    the concatenated fields - equal to the two-pass value at the parity tolerance (tests/test_gpu_metrics.py), not bit for
+    bit: without `metrics` the returned value stays on the two-pass path."""
     # weight-only products (packed AFNO weights, folded embed matrices, ...) once per rollout, not once per AR step
     scope = model.weights_scope() if (step is None and hasattr(model, "weights_scope")) else contextlib.nullcontext()
     step = step or (lambda x: model(x)[0])
@@ -97,16 +102,27 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
     loss_steps = None
     preds = []
     xx = xx.contiguous()
+    n_steps = len(range(0, T_ar, T_bundle))
+    if metrics is not None:
+        metrics._check_steps(n_steps)
     with scope:
-        for t in range(0, T_ar, T_bundle):
+        for k, t in enumerate(range(0, T_ar, T_bundle)):
             y = yy[..., t:t + T_bundle, :]
             im = step(xx)
-            l = rel_l2_loss(im, y.contiguous(), msk)
+            slot = None
+            if metrics is not None:
+                B, Cc = im.shape[0], im.shape[-1]
+                slot = metrics.stats_slot(k, B, im.numel() // (B * Cc), Cc)
+            l = rel_l2_loss(im, y.contiguous(), msk, slot)
             loss_steps = l if loss_steps is None else loss_steps + l
             preds.append(im)
             if t + T_bundle < T_ar:
                 xx = ops.window_slide(xx, im.contiguous())               # xx[..., T_bundle:, :] ++ im, one kernel
     pred = preds[0] if len(preds) == 1 else torch.cat(preds, dim=-2)
+    if metrics is not None:
+        metrics.end_rollout(loss_steps, n_steps, pred.shape[0], pred.shape[-1], 0)
+        metrics.accumulate()
+        return pred, loss_steps, metrics.l2_full.clone().view(())
     loss_full = rel_l2_loss(pred.contiguous(), yy.contiguous(), msk)
     return pred, loss_steps, loss_full
 
@@ -137,7 +153,7 @@ class GraphedRollout:
         self.graph.replay()
         return self.im.clone()          # the graph's output buffer is overwritten by the next replay
 
-    def __call__(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1):
+    def __call__(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1, metrics=None):
         if tuple(xx.shape) != tuple(self.x.shape):
             raise ValueError(f"GraphedRollout captured for input {tuple(self.x.shape)}, got {tuple(xx.shape)}")
-        return rollout_eval(self.model, xx, yy, msk, T_bundle, step=self.step)
+        return rollout_eval(self.model, xx, yy, msk, T_bundle, step=self.step, metrics=metrics)

@@ -1259,9 +1259,17 @@ def out_tail_bwd(upre: Tensor, dout: Tensor, w2: Tensor, b2: Tensor, w4p: Tensor
 # ------------------------------------------------------------------------------------------------------
 # loss / optimiser
 # ------------------------------------------------------------------------------------------------------
-def rel_l2_fwd(x: Tensor, y: Tensor, mask: Optional[Tensor], B: int, S: int, Cc: int, Tt: int):
+def rel_l2_fwd(x: Tensor, y: Tensor, mask: Optional[Tensor], B: int, S: int, Cc: int, Tt: int,
+               stats: Optional[Tensor] = None):
+    """stats: a caller-owned buffer of >= rel_l2_stats_elems(B, S, Cc) floats to use instead of a fresh one (the per-step
+    slot of train.StepMetrics: rel_l2_combine then reads every step's statistics from one strided buffer)"""
     nch = _lib.load().dpot_rel_l2_chunks(S, Cc)
-    stats = torch.empty(1 + nch, B, Cc, 4, dtype=torch.float32, device=x.device)
+    if stats is None:
+        stats = torch.empty(1 + nch, B, Cc, 4, dtype=torch.float32, device=x.device)
+    else:
+        _req(stats, "stats")
+        if stats.numel() < (1 + nch) * B * Cc * 4 or stats.data_ptr() % 16:
+            raise _lib.DpotHipError(f"rel_l2_fwd: the stats slot needs {(1 + nch) * B * Cc * 4} floats, 16-byte aligned")
     loss = torch.empty(1, dtype=torch.float32, device=x.device)
     check(_lib.load().dpot_rel_l2_fwd(x.data_ptr(), y.data_ptr(), _p(mask), stats.data_ptr(), loss.data_ptr(), B, S,
                                       Cc, Tt, _stream()), "rel_l2_fwd")
@@ -1274,6 +1282,116 @@ def rel_l2_bwd(x: Tensor, y: Tensor, mask: Optional[Tensor], stats: Tensor, glos
     check(_lib.load().dpot_rel_l2_bwd(x.data_ptr(), y.data_ptr(), _p(mask), stats.data_ptr(), gloss.data_ptr(),
                                       dx.data_ptr(), B, S, Cc, Tt, _stream()), "rel_l2_bwd")
     return dx
+
+
+# ---- training metrics (csrc/metrics.hip) ------------------------------------------------------------------------------
+CLS_OUT_WORDS = 4        # struct dpot_cls_ce_out as int64 words: {float loss + pad, correct, valid, invalid}
+METRICS_WORDS = 12       # struct dpot_metrics as 8-byte words: 4 doubles, then 8 int64
+METRICS_FLOATS = ("l2_step", "l2_full", "cls_loss", "grad_norm")
+METRICS_INTS = ("cls_correct", "cls_total", "cls_invalid", "samples", "ar_steps", "opt_steps", "nonfinite_steps")
+
+
+def _req_labels(labels: Tensor, B: int) -> Tensor:
+    if not labels.is_cuda:
+        raise _lib.DpotHipError(f"labels must live on the MI355X (got a {labels.device} tensor): dpot_amd has no CPU path")
+    if labels.dtype != torch.int64 or not labels.is_contiguous() or labels.numel() != B:
+        raise _lib.DpotHipError(f"labels must be {B} contiguous int64 values, got {tuple(labels.shape)} {labels.dtype}")
+    return labels
+
+
+def cls_ce_fwd(logits: Tensor, labels: Tensor, out: Optional[Tensor] = None):
+    """CrossEntropyLoss(reduction='sum') + argmax accuracy of logits [B, n_cls] against int64 labels [B] (or [B, 1]), one
+    launch.  Returns (out, row_stats): `out` = 4 int64 words holding struct dpot_cls_ce_out - word 0 is the float32 loss
+    (`cls_out_loss(out)`), then correct, valid, invalid; row_stats [B, 2] = {row max, log-sum-exp} for `cls_ce_bwd`.
+    A label outside [0, n_cls) reads no memory: its row adds nothing to the loss or the counts and is counted in `invalid`
+    (nothing aborts - check `invalid` where the labels are not trusted).  `out`: a caller-owned slot (StepMetrics)."""
+    _req(logits, "logits")
+    if logits.dim() != 2:
+        raise _lib.DpotHipError(f"logits must be [B, n_cls], got {tuple(logits.shape)}")
+    B, n_cls = logits.shape
+    _req_labels(labels, B)
+    if out is None:
+        out = torch.empty(CLS_OUT_WORDS, dtype=torch.int64, device=logits.device)
+    elif out.dtype != torch.int64 or out.numel() != CLS_OUT_WORDS or not out.is_contiguous() or out.device != logits.device:
+        raise _lib.DpotHipError(f"cls_ce_fwd: out must be {CLS_OUT_WORDS} contiguous int64 words on {logits.device}")
+    row_stats = torch.empty(B, 2, dtype=torch.float32, device=logits.device)
+    check(_lib.load().dpot_cls_ce_fwd(logits.data_ptr(), labels.data_ptr(), row_stats.data_ptr(), out.data_ptr(), B, n_cls,
+                                      _stream()), "cls_ce_fwd")
+    return out, row_stats
+
+
+def cls_out_loss(out: Tensor) -> Tensor:
+    """the float32 loss of a dpot_cls_ce_out slot, as a 0-d view (no launch)"""
+    return out.view(torch.float32)[0]
+
+
+def cls_ce_bwd(logits: Tensor, labels: Tensor, row_stats: Tensor, gloss: Tensor) -> Tensor:
+    """gloss[0] * (softmax(logits) - onehot(labels)); zeros for the rows whose label is outside [0, n_cls)"""
+    _req(logits, "logits")
+    _req(row_stats, "row_stats")
+    _req(gloss, "gloss")
+    B, n_cls = logits.shape
+    _req_labels(labels, B)
+    dl = torch.empty_like(logits)
+    check(_lib.load().dpot_cls_ce_bwd(logits.data_ptr(), labels.data_ptr(), row_stats.data_ptr(), gloss.data_ptr(),
+                                      dl.data_ptr(), B, n_cls, _stream()), "cls_ce_bwd")
+    return dl
+
+
+def rel_l2_stats_elems(B: int, S: int, Cc: int) -> int:
+    """floats of the `stats` buffer of one rel_l2_fwd call (its first B*Cc*4 are what rel_l2_combine reads)"""
+    return (1 + _lib.load().dpot_rel_l2_chunks(S, Cc)) * B * Cc * 4
+
+
+class StatsTable:
+    """DEVICE table of the per-step `stats` pointers for `rel_l2_combine` when the steps' buffers are separate tensors.
+    Built once (one host-to-device copy); valid while the tensors it names live - it keeps them alive."""
+
+    def __init__(self, stats):
+        self.stats = [_req(s, "stats") for s in stats]
+        if not self.stats:
+            raise ValueError("StatsTable: need at least one step")
+        if any(s.data_ptr() % 16 for s in self.stats):
+            raise _lib.DpotHipError("StatsTable: every stats buffer must be 16-byte aligned")
+        self.n_steps = len(self.stats)
+        self.table = torch.tensor([s.data_ptr() for s in self.stats], dtype=torch.int64).to(self.stats[0].device)
+
+
+def rel_l2_combine(stats, B: int, Cc: int, n_steps: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+    """relative L2 of the WHOLE rollout (SimpleLpLoss of the predictions concatenated along time) from the statistics the
+    per-step rel_l2_fwd calls left - no second pass over the fields.  stats: a StatsTable, or ONE contiguous tensor
+    [n_steps, >= B*Cc*4] whose row t is step t's stats buffer.  Returns a 1-element float32 tensor."""
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=(stats.table if isinstance(stats, StatsTable) else stats).device)
+    if isinstance(stats, StatsTable):
+        n = stats.n_steps if n_steps is None else n_steps
+        if not 0 < n <= stats.n_steps or any(s.numel() < B * Cc * 4 for s in stats.stats[:n]):
+            raise _lib.DpotHipError("rel_l2_combine: the table does not hold n_steps buffers of >= B*C*4 floats")
+        args = (stats.table.data_ptr(), None, 0)
+    else:
+        _req(stats, "stats")
+        if stats.dim() != 2 or stats.shape[1] < B * Cc * 4:
+            raise _lib.DpotHipError(f"rel_l2_combine: stats must be [n_steps, >= {B * Cc * 4}], got {tuple(stats.shape)}")
+        n = stats.shape[0] if n_steps is None else n_steps
+        if not 0 < n <= stats.shape[0]:
+            raise _lib.DpotHipError(f"rel_l2_combine: n_steps {n} outside (0, {stats.shape[0]}]")
+        args = (None, stats.data_ptr(), stats.stride(0))
+    check(_lib.load().dpot_rel_l2_combine(*args, n, B, Cc, out.data_ptr(), _stream()), "rel_l2_combine")
+    return out
+
+
+def metrics_accum(acc: Tensor, l2_step: Optional[Tensor], l2_full: Optional[Tensor], cls_out: Optional[Tensor], n_cls_out: int,
+                  sumsq_: Optional[Tensor], grad_scale: float, samples: int, ar_steps: int, opt_steps: int) -> None:
+    """acc (int64 [2, METRICS_WORDS] = two struct dpot_metrics): acc[0] += this step's values, acc[1] = them; one launch"""
+    if not acc.is_cuda:
+        raise _lib.DpotHipError(f"the metrics accumulator must live on the MI355X (got a {acc.device} tensor): no CPU path")
+    if acc.dtype != torch.int64 or acc.numel() != 2 * METRICS_WORDS or not acc.is_contiguous():
+        raise _lib.DpotHipError(f"metrics_accum: acc must be {2 * METRICS_WORDS} contiguous int64 words")
+    if n_cls_out and (cls_out is None or cls_out.numel() < n_cls_out * CLS_OUT_WORDS):
+        raise _lib.DpotHipError("metrics_accum: cls_out holds fewer than n_cls_out results")
+    check(_lib.load().dpot_metrics_accum(acc.data_ptr(), _p(l2_step), _p(l2_full), _p(cls_out) if n_cls_out else None,
+                                         n_cls_out, _p(sumsq_), grad_scale, samples, ar_steps, opt_steps, _stream()),
+          "metrics_accum")
 
 
 def sumsq(g: Tensor, out: Tensor, part: Tensor, accumulate: bool = False) -> Tensor:

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .functional import clear_grad_packs, rel_l2_loss
+from .functional import clear_grad_packs, cls_ce_loss, rel_l2_loss
 
 Tensor = torch.Tensor
 
@@ -414,21 +414,161 @@ def one_cycle_lr(step: int, total_steps: int, max_lr: float, pct_start: float = 
 
 
 # ------------------------------------------------------------------------------------------------------
+class StepMetrics:
+    """What the reference's loop logs (train_temporal.py:221-223, 232-237; the test loop :252-281), kept on the DEVICE: a
+    persistent accumulator that ONE small launch per step folds the step's scalars into - inside the captured graph, after
+    the optimiser - and a copy of the last step's values.  Nothing here synchronises except ``read()``.
+
+    Pass it as ``metrics=`` to rollout / train_step / GraphedTrainStep / SegmentedTrainStep / make_dp_step /
+    infer.rollout_eval.  It owns the per-AR-step slots the step's kernels write: the relative-L2 statistics of every AR step
+    (``ops.rel_l2_combine`` forms the full-rollout loss from them: no second pass over the fields) and the cross-entropy
+    results.  ``T_ar_steps_max``: the largest number of AR steps (T_ar / T_bundle) of a rollout it will see.
+
+    Accumulated (``read()``; sums over the steps since ``reset()``): l2_step, l2_full, cls_loss, grad_norm (the norm the
+    optimiser's clip used; 0 for an optimiser without max_norm), cls_correct, cls_total (rows with a label inside
+    [0, n_cls)), cls_invalid (rows outside: they contribute to nothing else), samples, ar_steps, opt_steps and
+    nonfinite_steps (steps whose loss was NaN / inf: counted, never acted on)."""
+
+    def __init__(self, device, T_ar_steps_max: int = 1):
+        if T_ar_steps_max < 1:
+            raise ValueError(f"StepMetrics: T_ar_steps_max must be >= 1, got {T_ar_steps_max}")
+        self.device = torch.device(device)
+        self.T_max = int(T_ar_steps_max)
+        self.acc = torch.zeros(2, ops.METRICS_WORDS, dtype=torch.int64, device=self.device)     # [running, last step]
+        self.cls_out = torch.zeros(self.T_max, ops.CLS_OUT_WORDS, dtype=torch.int64, device=self.device)
+        self.l2_full = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.l2_stats: Optional[Tensor] = None          # [T_max, stats floats of one AR step], sized by the first rollout
+        self._pending = None
+
+    # -- slots the rollout hands to its kernels ------------------------------------------------------------
+    def _check_steps(self, n_steps: int) -> None:
+        if n_steps > self.T_max:
+            raise ValueError(f"StepMetrics was built for <= {self.T_max} AR steps per rollout, this one has {n_steps}")
+
+    def stats_slot(self, k: int, B: int, S: int, Cc: int) -> Tensor:
+        n = ops.rel_l2_stats_elems(B, S, Cc)
+        if self.l2_stats is None or self.l2_stats.shape[1] != n:
+            self.l2_stats = torch.zeros(self.T_max, n, dtype=torch.float32, device=self.device)
+        return self.l2_stats[k]
+
+    def cls_slot(self, k: int) -> Tensor:
+        return self.cls_out[k]
+
+    def end_rollout(self, l2_step: Tensor, n_steps: int, B: int, Cc: int, n_cls_out: int) -> None:
+        """after the last AR step: one launch forms the full-rollout loss from the step statistics; the values wait for
+        ``accumulate``"""
+        ops.rel_l2_combine(self.l2_stats, B, Cc, n_steps, out=self.l2_full)
+        self._pending = (l2_step.detach().view(1), n_steps, B, n_cls_out)
+
+    def accumulate(self, opt=None, grad_scale: float = 1.0) -> None:
+        """fold the rollout that just ended into the accumulator (ONE launch, capturable).  The step classes call it after
+        the optimiser launch; call it yourself after a bare ``rollout(..., metrics=m)``."""
+        if self._pending is None:
+            raise RuntimeError("StepMetrics.accumulate: no rollout has run with this object since the last accumulate")
+        l2_step, n_steps, B, n_cls_out = self._pending
+        self._pending = None
+        sumsq = opt.sumsq if (opt is not None and getattr(opt, "max_norm", None) is not None) else None
+        ops.metrics_accum(self.acc, l2_step, self.l2_full, self.cls_out, n_cls_out, sumsq, grad_scale, B, n_steps, 1)
+
+    # -- reading -------------------------------------------------------------------------------------------
+    def reset(self) -> None:
+        """zero the accumulator by a launch (capturable; the epoch boundary).  No synchronisation."""
+        self.acc.zero_()
+
+    def snapshot(self) -> Tensor:
+        return self.acc.clone()
+
+    def restore(self, snap: Tensor) -> None:
+        self.acc.copy_(snap)
+
+    def last(self) -> Dict[str, Tensor]:
+        """the LAST step's values as 0-d device tensors (views: no launch, no synchronisation) - what the reference hands
+        to its writer per iteration (train_temporal.py:236-237)"""
+        row = self.acc[1]
+        d = {k: row[i:i + 1].view(torch.float64)[0] for i, k in enumerate(ops.METRICS_FLOATS)}
+        d.update({k: row[len(ops.METRICS_FLOATS) + i] for i, k in enumerate(ops.METRICS_INTS)})
+        return d
+
+    def read(self, group=None) -> Dict[str, float]:
+        """the ONLY call that synchronises: the accumulator as a plain dict, plus the reference's normalisations
+        train_l2_step_avg = l2_step / samples / ar_steps_per_sample, train_l2_full_avg = l2_full / samples,
+        cls_acc = cls_correct / cls_total (and the same two averages under the test loop's names).  ``group``: a
+        dp.BucketedGradReducer or a process group - the accumulator is then summed over the ranks with ONE all-reduce,
+        here at read time and never per step."""
+        nf = len(ops.METRICS_FLOATS)
+        row = self.acc[0]
+        vals = torch.cat([row[:nf].view(torch.float64), row[nf:nf + len(ops.METRICS_INTS)].to(torch.float64)])
+        if group is not None:
+            import torch.distributed as dist
+            pg = getattr(group, "pg", group) if not isinstance(group, bool) else None
+            if dist.is_available() and dist.is_initialized():
+                dist.all_reduce(vals, op=dist.ReduceOp.SUM, group=pg)
+        return self.normalise(vals.cpu().tolist())
+
+    @staticmethod
+    def normalise(vals: Sequence[float]) -> Dict[str, float]:
+        """the dict of ``read()`` from the 11 accumulated numbers (METRICS_FLOATS then METRICS_INTS order)"""
+        nf = len(ops.METRICS_FLOATS)
+        d: Dict[str, float] = {k: float(v) for k, v in zip(ops.METRICS_FLOATS, vals[:nf])}
+        d.update({k: int(round(v)) for k, v in zip(ops.METRICS_INTS, vals[nf:])})
+        nan = float("nan")
+        per = d["ar_steps"] / d["opt_steps"] if d["opt_steps"] else nan
+        d["ar_steps_per_sample"] = per
+        d["train_l2_step_avg"] = d["l2_step"] / d["samples"] / per if d["samples"] and d["opt_steps"] else nan
+        d["train_l2_full_avg"] = d["l2_full"] / d["samples"] if d["samples"] else nan
+        d["test_l2_step_avg"], d["test_l2_full_avg"] = d["train_l2_step_avg"], d["train_l2_full_avg"]
+        d["cls_acc"] = d["cls_correct"] / d["cls_total"] if d["cls_total"] else nan
+        d["cls_loss_avg"] = d["cls_loss"] / d["cls_total"] if d["cls_total"] else nan
+        d["grad_norm_avg"] = d["grad_norm"] / d["opt_steps"] if d["opt_steps"] else nan
+        return d
+
+
+def check_cls_args(opt, cls: Optional[Tensor], cls_weight: float) -> None:
+    """a weighted classification loss needs labels, and an optimiser that updates cls_head: with ``update_tail=False`` the
+    head would receive gradients and silently never move"""
+    if cls_weight != 0.0:
+        if cls is None:
+            raise ValueError(f"cls_weight = {cls_weight} needs the dataset labels (cls=...)")
+        if opt is not None and not getattr(opt, "update_tail", False):
+            raise ValueError(f"cls_weight = {cls_weight} trains cls_head, but the optimiser was built with update_tail=False "
+                             "and would leave it frozen; build it with update_tail=True")
+
+
 def rollout(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
-            noise_scale: float = 0.0, noise: Optional[List[Tensor]] = None) -> Tuple[Tensor, Tensor]:
-    """auto-regressive rollout with summed per-step loss (train_temporal.py:201-219)"""
+            noise_scale: float = 0.0, noise: Optional[List[Tensor]] = None, cls: Optional[Tensor] = None,
+            cls_weight: float = 0.0, metrics: Optional[StepMetrics] = None) -> Tuple[Tensor, Tensor]:
+    """auto-regressive rollout with summed per-step loss (train_temporal.py:201-219).  Returns (loss, pred); ``loss`` is
+    the relative-L2 rollout loss whatever ``cls_weight`` is - ``rollout_total`` also returns the loss to differentiate."""
+    return rollout_total(model, xx, yy, msk, T_bundle, noise_scale, noise, cls, cls_weight, metrics)[:2]
+
+
+def rollout_total(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
+                  noise_scale: float = 0.0, noise: Optional[List[Tensor]] = None, cls: Optional[Tensor] = None,
+                  cls_weight: float = 0.0, metrics: Optional[StepMetrics] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """``rollout`` with the dataset-classification branch of train_temporal.py:209-213: cls = the int64 dataset index per
+    sample ([B] or [B, 1], as data.DeviceBatcher delivers idx_cls).  Returns (loss, pred, total) with
+    total = loss + cls_weight * sum over the AR steps of CrossEntropyLoss(reduction='sum')(cls_pred, cls) when
+    cls_weight != 0, else total IS loss: the cross-entropy then runs forward-only for ``metrics`` and cls_head receives no
+    gradient.  metrics: a StepMetrics that collects the rollout's scalars (call its ``accumulate`` afterwards)."""
+    check_cls_args(None, cls, cls_weight)
     scope = model.weights_scope() if hasattr(model, "weights_scope") else contextlib.nullcontext()
     with scope:
-        return _rollout(model, xx, yy, msk, T_bundle, noise_scale, noise)
+        return _rollout(model, xx, yy, msk, T_bundle, noise_scale, noise, cls, cls_weight, metrics)
 
 
-def _rollout(model, xx, yy, msk, T_bundle, noise_scale, noise):
+def _rollout(model, xx, yy, msk, T_bundle, noise_scale, noise, cls=None, cls_weight=0.0, metrics=None):
     loss = None
+    cls_loss = None
     preds = []
     T_ar = yy.shape[-2]
     xx = ops._req(xx.contiguous(), "xx")
     n_steps = len(range(0, T_ar, T_bundle))
     tell = hasattr(model, "_ar_pos")
+    want_cls = cls is not None and (cls_weight != 0.0 or metrics is not None)
+    if metrics is not None:
+        metrics._check_steps(n_steps)
+    if want_cls:
+        cls = cls.contiguous().view(-1)
     for k, t in enumerate(range(0, T_ar, T_bundle)):
         if tell:
             model._ar_pos = (k, n_steps)            # DPOTNet.recompute_keep_last: which AR steps keep their activations
@@ -440,17 +580,32 @@ def _rollout(model, xx, yy, msk, T_bundle, noise_scale, noise):
             else:
                 xx = _NoiseFn.apply(xx, noise[k] if noise is not None else None, noise_scale)
         try:
-            im, _ = model(xx)
+            im, cls_pred = model(xx)
         finally:
             if tell:
                 model._ar_pos = None                # (never left behind: a later plain forward must not see a stale position)
-        l = rel_l2_loss(im, y, msk)
+        if metrics is not None:
+            B, Cc = im.shape[0], im.shape[-1]
+            l = rel_l2_loss(im, y, msk, metrics.stats_slot(k, B, im.numel() // (B * Cc), Cc))
+        else:
+            l = rel_l2_loss(im, y, msk)
         loss = l if loss is None else loss + l
+        if want_cls:
+            slot = metrics.cls_slot(k) if metrics is not None else None
+            if cls_weight != 0.0:
+                cl, _ = cls_ce_loss(cls_pred, cls, slot)
+                cls_loss = cl if cls_loss is None else cls_loss + cl
+            else:                                   # an observer: no graph, so HeadFn.backward sees no dcls
+                with torch.no_grad():
+                    cls_ce_loss(cls_pred.detach(), cls, slot)
         preds.append(im)
         if t + T_bundle < T_ar:
             xx = _SlideFn.apply(xx, im)
     pred = preds[0] if len(preds) == 1 else torch.cat(preds, dim=-2)
-    return loss, pred
+    total = loss if cls_loss is None else loss + cls_weight * cls_loss
+    if metrics is not None:
+        metrics.end_rollout(loss, n_steps, pred.shape[0], pred.shape[-1], n_steps if want_cls else 0)
+    return loss, pred, total
 
 
 class _NoiseFn(torch.autograd.Function):
@@ -499,17 +654,22 @@ class _SlideFn(torch.autograd.Function):
 
 def train_step(model: nn.Module, opt: FlatOptimizer, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
                noise_scale: float = 0.0, lr: Optional[float] = None, reducer=None,
-               grad_scale: float = 1.0) -> Tuple[Tensor, Tensor]:
-    """one optimisation step; returns (loss, pred) as device tensors - no host sync."""
+               grad_scale: float = 1.0, cls: Optional[Tensor] = None, cls_weight: float = 0.0,
+               metrics: Optional[StepMetrics] = None) -> Tuple[Tensor, Tensor]:
+    """one optimisation step; returns (loss, pred) as device tensors - no host sync.  cls / cls_weight / metrics: see
+    ``rollout_total`` and ``StepMetrics``; the returned loss stays the relative-L2 rollout loss."""
+    check_cls_args(opt, cls, cls_weight)
     opt.zero_grad()
     if reducer is not None:
         reducer.begin_step()
-    loss, pred = rollout(model, xx, yy, msk, T_bundle, noise_scale)
-    loss.backward()
+    loss, pred, total = rollout_total(model, xx, yy, msk, T_bundle, noise_scale, None, cls, cls_weight, metrics)
+    total.backward()
     clear_grad_packs()
     if reducer is not None:
         reducer.finish()
     opt.step(lr, grad_scale)
+    if metrics is not None:
+        metrics.accumulate(opt, grad_scale)
     return loss.detach(), pred.detach()
 
 
@@ -534,22 +694,38 @@ class _GraphStep:
     """What the captured train steps share: static batch buffers, the eager warm-up before the capture, and the replay protocol
     of the weight packs their captured Adam launch writes (``owned``: FusedAdam.wrote at the capture, or None)."""
     owned = None
+    cls = None                    # static label buffer (int64, next to xx / yy / msk), or None
+    cls_weight = 0.0
+    metrics = None
 
-    def _static_batch(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor]) -> None:
+    def _static_batch(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor], cls: Optional[Tensor] = None,
+                      cls_weight: float = 0.0, metrics: Optional[StepMetrics] = None) -> None:
+        check_cls_args(self.opt, cls, cls_weight)
         self.xx, self.yy = xx.clone(), yy.clone()
         self.msk = msk.clone() if msk is not None else None
+        self.cls = cls.clone() if cls is not None else None
+        self.cls_weight, self.metrics = cls_weight, metrics
 
-    def stage(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor] = None) -> None:
+    def stage(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor] = None, cls: Optional[Tensor] = None) -> None:
         self.xx.copy_(xx, non_blocking=True)
         self.yy.copy_(yy, non_blocking=True)
         if msk is not None and self.msk is not None:
             self.msk.copy_(msk, non_blocking=True)
+        if cls is not None:
+            if self.cls is None:
+                raise ValueError("stage(cls=...): this step was built without labels (pass cls= to its constructor)")
+            self.cls.copy_(cls.view(self.cls.shape), non_blocking=True)
+
+    def _rollout(self):
+        return rollout_total(self.model, self.xx, self.yy, self.msk, self.T_bundle, self.noise_scale, None, self.cls,
+                             self.cls_weight, self.metrics)
 
     def _warm_up(self, n: int, body: Callable[[], None], settle: bool = False) -> None:
         """eager warm-up on a side stream (allocator + lazy inits).  The warm-up iterations are NOT training steps: parameters,
         Adam moments and the step counter are restored afterwards (a fine-tune of a pretrained checkpoint must not receive
         unscheduled full-lr updates before its first replay)"""
         snap = self.opt.snapshot()
+        msnap = self.metrics.snapshot() if self.metrics is not None else None        # ... and they are not logged either
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -560,6 +736,8 @@ class _GraphStep:
         if settle:
             _retire_collective_watchdog_work()
         self.opt.restore(snap)
+        if msnap is not None:
+            self.metrics.restore(msnap)
 
     def _replay(self, lr: Optional[float], run: Callable[[], None]) -> Tensor:
         """the graphs hold no pack launch for the set their Adam writes (it was fresh at the capture): refresh it first if
@@ -584,9 +762,10 @@ class GraphedTrainStep(_GraphStep):
 
     def __init__(self, model: nn.Module, opt: FlatOptimizer, xx: Tensor, yy: Tensor, msk: Optional[Tensor],
                  T_bundle: int = 1, noise_scale: float = 0.0, warmup: int = 2, reducer=None,
-                 grad_scale: float = 1.0, capture_collectives: bool = False):
+                 grad_scale: float = 1.0, capture_collectives: bool = False, cls: Optional[Tensor] = None,
+                 cls_weight: float = 0.0, metrics: Optional[StepMetrics] = None):
         self.model, self.opt = model, opt
-        self._static_batch(xx, yy, msk)
+        self._static_batch(xx, yy, msk, cls, cls_weight, metrics)
         if reducer is not None and getattr(reducer, "world", 1) > 1 and not capture_collectives:
             raise ValueError("GraphedTrainStep captures the WHOLE step into one graph; pass capture_collectives=True to "
                              "capture the bucket all-reduces with it, or use SegmentedTrainStep (collectives between graphs)")
@@ -619,12 +798,14 @@ class GraphedTrainStep(_GraphStep):
         opt.zero_grad()
         if self.reducer is not None:
             self.reducer.begin_step()
-        loss, pred = rollout(self.model, self.xx, self.yy, self.msk, self.T_bundle, self.noise_scale)
-        loss.backward()
+        loss, pred, total = self._rollout()
+        total.backward()
         clear_grad_packs()
         if self.reducer is not None:
             self.reducer.finish()
         opt.launch(self.grad_scale)
+        if self.metrics is not None:             # last node of the graph: the step's scalars join the device accumulator
+            self.metrics.accumulate(opt, self.grad_scale)
         return loss.detach(), pred.detach()
 
     def replay(self, lr: Optional[float] = None) -> Tensor:
@@ -651,10 +832,11 @@ class SegmentedTrainStep(_GraphStep):
     backward of AR steps T-1 .. 1 and the backward of AR step 0 down to its last cut."""
 
     def __init__(self, model: nn.Module, opt: FlatOptimizer, reducer, xx: Tensor, yy: Tensor, msk: Optional[Tensor],
-                 noise_scale: float = 0.0, warmup: int = 2, T_bundle: int = 1):
+                 noise_scale: float = 0.0, warmup: int = 2, T_bundle: int = 1, cls: Optional[Tensor] = None,
+                 cls_weight: float = 0.0, metrics: Optional[StepMetrics] = None):
         self.T_bundle = T_bundle
         self.model, self.opt, self.reducer = model, opt, reducer
-        self._static_batch(xx, yy, msk)
+        self._static_batch(xx, yy, msk, cls, cls_weight, metrics)
         self.noise_scale = noise_scale
         self.grad_scale = reducer.grad_scale
         depth = len(model.blocks)
@@ -668,6 +850,8 @@ class SegmentedTrainStep(_GraphStep):
             for fn in self._segment_fns():
                 fn()
             opt.launch(self.grad_scale)
+            if metrics is not None:
+                metrics.accumulate(opt, self.grad_scale)
 
         reducer.detach()
         try:
@@ -682,6 +866,8 @@ class SegmentedTrainStep(_GraphStep):
             self.opt_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.opt_graph, pool=pool, capture_error_mode="thread_local"):
                 opt.launch(self.grad_scale)
+                if metrics is not None:          # the last segment: after the optimiser
+                    metrics.accumulate(opt, self.grad_scale)
             self.owned = opt.wrote
         finally:
             reducer.attach()
@@ -710,11 +896,11 @@ class SegmentedTrainStep(_GraphStep):
             self.model._boundary_hook = hook
             calls[0] = 0
             try:
-                loss, pred = rollout(self.model, self.xx, self.yy, self.msk, self.T_bundle, self.noise_scale)
+                loss, pred, total = self._rollout()
             finally:
                 self.model._boundary_hook = None
             assert len(cuts) == len(self.cut_at), f"expected {len(self.cut_at)} graph cuts, the forward made {len(cuts)}"
-            loss.backward()
+            total.backward()
             clear_grad_packs()
             self.loss, self.pred = loss.detach(), pred.detach()
 
@@ -778,7 +964,8 @@ def _end_stray_captures(streams) -> None:
 
 
 def make_dp_step(model: nn.Module, opt: FlatOptimizer, reducer, xx: Tensor, yy: Tensor, msk: Optional[Tensor],
-                 noise_scale: float = 0.0, warmup: int = 2, T_bundle: int = 1, try_one_graph: bool = True):
+                 noise_scale: float = 0.0, warmup: int = 2, T_bundle: int = 1, try_one_graph: bool = True,
+                 cls: Optional[Tensor] = None, cls_weight: float = 0.0, metrics: Optional[StepMetrics] = None):
     """The N > 1 train step with the FAST mode chosen by verification (round 6): returns (step, info).
 
     Fast mode = ``GraphedTrainStep(capture_collectives=True)``: the whole step, bucket all-reduces included, as ONE hipGraph
@@ -796,7 +983,8 @@ def make_dp_step(model: nn.Module, opt: FlatOptimizer, reducer, xx: Tensor, yy: 
 
     def chain(why):
         reducer.skip_zero_tail = tail_flag
-        seg = SegmentedTrainStep(model, opt, reducer, xx, yy, msk, noise_scale=noise_scale, warmup=warmup, T_bundle=T_bundle)
+        seg = SegmentedTrainStep(model, opt, reducer, xx, yy, msk, noise_scale=noise_scale, warmup=warmup, T_bundle=T_bundle,
+                                 cls=cls, cls_weight=cls_weight, metrics=metrics)
         return seg, {"mode": "segmented", "why": why}
 
     tail_flag = reducer.skip_zero_tail
@@ -811,7 +999,7 @@ def make_dp_step(model: nn.Module, opt: FlatOptimizer, reducer, xx: Tensor, yy: 
     one, err = None, None
     try:
         one = GraphedTrainStep(model, opt, xx, yy, msk, T_bundle=T_bundle, noise_scale=noise_scale, warmup=max(1, warmup),
-                               reducer=reducer, capture_collectives=True)
+                               reducer=reducer, capture_collectives=True, cls=cls, cls_weight=cls_weight, metrics=metrics)
     except Exception as e:                                    # an RCCL build / driver that cannot capture its collectives
         err = f"{type(e).__name__}: {e}"[:160]
         _end_stray_captures([torch.cuda.current_stream(), reducer.stream])
@@ -823,6 +1011,7 @@ def make_dp_step(model: nn.Module, opt: FlatOptimizer, reducer, xx: Tensor, yy: 
         del one
         return chain("one-graph capture failed" + (f" here ({err})" if err else " on another rank"))
     snap = opt.snapshot()
+    msnap = metrics.snapshot() if metrics is not None else None          # the trial steps are not training steps
     rng = ops.rng_state(xx.device).clone()
     grads = []
     for mode in ("eager", "graph"):
@@ -831,12 +1020,14 @@ def make_dp_step(model: nn.Module, opt: FlatOptimizer, reducer, xx: Tensor, yy: 
         reducer.skip_zero_tail = False                        # (as the capture: the cls_head tail is always reduced)
         if mode == "eager":
             train_step(model, opt, one.xx, one.yy, one.msk, T_bundle=T_bundle, noise_scale=noise_scale, lr=opt.lr,
-                       reducer=reducer, grad_scale=reducer.grad_scale)
+                       reducer=reducer, grad_scale=reducer.grad_scale, cls=one.cls, cls_weight=cls_weight, metrics=metrics)
         else:
             one.replay(opt.lr)
         torch.cuda.synchronize()
         grads.append(opt.fp.grad[:opt.n_active].clone())
     opt.restore(snap)
+    if msnap is not None:
+        metrics.restore(msnap)
     ops.rng_state(xx.device).copy_(rng)
     same_modes = bool(torch.equal(grads[0], grads[1]))
     cs = _grad_checksum(grads[1])

@@ -466,6 +466,45 @@ int dpot_lamb_step(float* p, const float* g, float* m, float* v, const float* hy
 int dpot_lamb_stage(float* hyper, int64_t* step, double lr, double beta1, double beta2, float eps, float weight_decay,
                     float max_norm, float clamp_value, int debias, int advance, dpot_stream_t stream);
 
+/* ---- training metrics (csrc/metrics.hip): latency-sized, one launch each, fixed reduction order, no atomics ----
+ * Dataset-classification loss of train_temporal.py:209-213: CrossEntropyLoss(reduction='sum') of logits [B, n_cls] against
+ * labels (DEVICE int64 [B]) and the argmax accuracy, in ONE launch.  Per row a max-subtracted log-sum-exp (logits of +-80 do
+ * not overflow); the argmax is the FIRST maximal index (torch's rule).  1 <= n_cls <= 1024, any B > 0.  row_stats: 2*B
+ * floats {row max, log-sum-exp}, kept for the backward.  A label outside [0, n_cls) indexes nothing: its row adds nothing to
+ * loss / correct / valid and is counted in `invalid`.  out must be 8-byte aligned. */
+typedef struct dpot_cls_ce_out {
+  float loss;             /* sum over the valid rows of lse - logit[label]                  */
+  int32_t reserved;
+  int64_t correct, valid, invalid;
+} dpot_cls_ce_out;        /* 32 bytes */
+int dpot_cls_ce_fwd(const float* logits, const int64_t* labels, float* row_stats, dpot_cls_ce_out* out, int B, int n_cls,
+                    dpot_stream_t stream);
+/* dlogits [B, n_cls] = gloss[0] * (softmax - onehot); rows with a label outside [0, n_cls) receive zeros */
+int dpot_cls_ce_bwd(const float* logits, const int64_t* labels, const float* row_stats, const float* gloss, float* dlogits,
+                    int B, int n_cls, dpot_stream_t stream);
+/* SimpleLpLoss(size_average=False) of a whole rollout (the n_steps predictions concatenated along the time axis) from the
+ * first [B, C, 4] block of the `stats` each step's dpot_rel_l2_fwd left:
+ *   out[0] = sum_b 1/nch_b sum_c sqrt(sum_t d2[t,b,c]) / (sqrt(sum_t y2[t,b,c]) + 1e-8),  sum_t in double,
+ * nch_b = number of channels of sample b whose mask sum (of step 0: the mask is the same at every step) is not zero.
+ * The blocks are given EITHER as a DEVICE table of n_steps device pointers (stats_ptrs; each 16-byte aligned; build the
+ * table once) OR as one base pointer with a stride in floats between the steps (stats_base, step_stride % 4 == 0); the
+ * other of the two is NULL.  C <= 1024. */
+int dpot_rel_l2_combine(const float* const* stats_ptrs, const float* stats_base, int64_t step_stride, int n_steps, int B,
+                        int C, float* out, dpot_stream_t stream);
+/* Running metrics of train_temporal.py:221-223,232-233 without a host read: acc[0] += this step, acc[1] = this step (the
+ * "last step" copy), ONE one-workgroup launch at the end of a step.  l2_step / l2_full: 1 float each (may be NULL: 0);
+ * cls: the n_cls_out results of this step's dpot_cls_ce_fwd calls (one per AR step; n_cls_out may be 0);
+ * grad_norm = sqrt(sumsq[0]) * grad_scale, the norm the optimiser's clip used (sumsq may be NULL: 0);
+ * nonfinite_steps counts the steps whose l2_step + l2_full + cls_loss is NaN or inf (counted, never acted on).
+ * acc: 2 structs, 8-byte aligned, zeroed by the caller before the first step. */
+typedef struct dpot_metrics {
+  double l2_step, l2_full, cls_loss, grad_norm;
+  int64_t cls_correct, cls_total, cls_invalid, samples, ar_steps, opt_steps, nonfinite_steps, reserved;
+} dpot_metrics;           /* 96 bytes */
+int dpot_metrics_accum(dpot_metrics* acc, const float* l2_step, const float* l2_full, const dpot_cls_ce_out* cls,
+                       int n_cls_out, const float* sumsq, float grad_scale, int64_t samples, int64_t ar_steps,
+                       int64_t opt_steps, dpot_stream_t stream);
+
 /* xx_out = xx + noise_scale * ||xx||_2(over X,Y,T per (b,c)) * eps   (train_temporal.py:205)
  * xx, eps: [B, S, C]; norms: B*C*(1 + dpot_noise_chunks(S, C)) floats - [B, C] norms followed by the chunk partials */
 int dpot_noise_chunks(int S, int C);
