@@ -170,6 +170,8 @@ SIGNATURES = {
     "dpot_window_slide": (c_i, [c_fp] * 3 + [c_i64] + [c_i] * 3 + [c_fp]),
     "dpot_window_slide_bwd": (c_i, [c_fp] * 3 + [c_i64] + [c_i] * 3 + [c_fp]),
     "dpot_resize_pad_window": (c_i, [c_fp, c_i, c_fp, c_fp] + [c_i] * 6 + [c_fp]),
+    "dpot_spectral_resize_pad": (c_i, [c_i, c_i]),
+    "dpot_spectral_resize": (c_i, [c_fp] * 7 + [c_i] * 6 + [c_fp]),
     "dpot_panel_pack_weights": (c_i, [c_fp, c_i, c_i, c_fp]),
     "dpot_layout_jobs": (c_i, [c_fp, c_i, c_i64, c_fp]),
     "dpot_bf16_packed_elems": (c_i64, [c_i, c_i, c_i]),

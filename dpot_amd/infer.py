@@ -8,6 +8,9 @@
   appended to the input window step after step; returns the prediction, the per-step loss sum and the loss of the
   whole trajectory (both SimpleLpLoss(size_average=False)).  With fixed shapes the single forward step is one
   hipGraph that is replayed T_ar / T_bundle times (the window slide writes into the graph's static input).
+* ``refill_mask`` and ``model_res=`` - the resolution-generalisation rollout of evaluate_varyingres.py:198-248: data on
+  a res x res grid runs through a model built for another resolution; every AR step Fourier-resizes the window up to the
+  model's resolution (ops.spectral_resize, one launch) and the prediction back down.
 """
 from __future__ import annotations
 
@@ -85,16 +88,32 @@ def load_components_from_pretrained(model: nn.Module, state_dict: Union[str, Map
 
 
 # ------------------------------------------------------------------------------------------------------
+def _size2(res) -> Tuple[int, int]:
+    return (int(res), int(res)) if isinstance(res, int) else (int(res[0]), int(res[1]))
+
+
+def refill_mask(msk: Tensor, res) -> Tensor:
+    """evaluate_varyingres.py:198-201: the mask of resized data [B, res, res, 1, C] - a channel of a sample is 1 everywhere
+    if the original mask has any non-zero entry in it, else 0.  `res` is one int or (res_x, res_y)."""
+    rx, ry = _size2(res)
+    nonzero = (msk.sum(dim=(1, 2, 3)) > 0)[:, None, None, None, :]
+    return nonzero.to(torch.float32).expand(msk.shape[0], rx, ry, 1, msk.shape[-1]).contiguous()
+
+
 @torch.no_grad()
 def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
-                 step=None, metrics=None) -> Tuple[Tensor, Tensor, Tensor]:
+                 step=None, metrics=None, model_res=None) -> Tuple[Tensor, Tensor, Tensor]:
     """evaluate.py:193-213.  Returns (pred [B,X,Y,T_ar,C], sum of the per-step losses, loss of the whole rollout).
     `step(xx) -> im` defaults to the model's forward (a GraphedRollout passes its graph replay).
     metrics: a train.StepMetrics - the test loop's test_l2_step / test_l2_full (train_temporal.py:252-281) are accumulated
     on the device (one launch per rollout, no synchronisation; `metrics.read()` at the end of the loop), and the loss of the
     whole rollout is formed from the statistics the per-step losses left (ops.rel_l2_combine) instead of a second pass over
     the concatenated fields - equal to the two-pass value at the parity tolerance (tests/test_gpu_metrics.py), not bit for
-    bit: without `metrics` the returned value stays on the two-pass path."""
+    bit: without `metrics` the returned value stays on the two-pass path.
+    model_res (an int or (res_x, res_y)): evaluate_varyingres.py:228-248 - xx, yy and msk live at the DATA resolution; every
+    step Fourier-resizes the window to model_res, runs the model there and resizes the prediction back; loss, metrics and
+    the window slide stay at the data resolution.  As in the reference the two resizes also run when model_res equals the
+    data resolution (every frequency is kept then: the identity up to rounding).  None: no resize is enqueued."""
     # weight-only products (packed AFNO weights, folded embed matrices, ...) once per rollout, not once per AR step
     scope = model.weights_scope() if (step is None and hasattr(model, "weights_scope")) else contextlib.nullcontext()
     step = step or (lambda x: model(x)[0])
@@ -105,10 +124,15 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
     n_steps = len(range(0, T_ar, T_bundle))
     if metrics is not None:
         metrics._check_steps(n_steps)
+    if model_res is not None:
+        model_res, data_res = _size2(model_res), (xx.shape[1], xx.shape[2])
     with scope:
         for k, t in enumerate(range(0, T_ar, T_bundle)):
             y = yy[..., t:t + T_bundle, :]
-            im = step(xx)
+            if model_res is None:
+                im = step(xx)
+            else:
+                im = ops.spectral_resize(step(ops.spectral_resize(xx, model_res)).contiguous(), data_res)
             slot = None
             if metrics is not None:
                 B, Cc = im.shape[0], im.shape[-1]
@@ -153,7 +177,17 @@ class GraphedRollout:
         self.graph.replay()
         return self.im.clone()          # the graph's output buffer is overwritten by the next replay
 
-    def __call__(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1, metrics=None):
-        if tuple(xx.shape) != tuple(self.x.shape):
-            raise ValueError(f"GraphedRollout captured for input {tuple(self.x.shape)}, got {tuple(xx.shape)}")
-        return rollout_eval(self.model, xx, yy, msk, T_bundle, step=self.step, metrics=metrics)
+    def __call__(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1, metrics=None, model_res=None):
+        """model_res: the graph's own resolution - xx, yy, msk may then live at any data resolution; the two resizes of an
+        AR step run outside the captured graph, on the same stream (rollout_eval)"""
+        want = tuple(self.x.shape)
+        if model_res is not None:
+            if xx.dim() != 5:
+                raise ValueError(f"GraphedRollout: input must be [B, X, Y, T, C], got {tuple(xx.shape)}")
+            if _size2(model_res) != want[1:3]:
+                raise ValueError(f"GraphedRollout captured at resolution {want[1:3]}, model_res is {_size2(model_res)}")
+            want = want[:1] + tuple(xx.shape[1:3]) + want[3:]
+        if tuple(xx.shape) != want:
+            raise ValueError(f"GraphedRollout captured for input {tuple(self.x.shape)}, got {tuple(xx.shape)}"
+                             + ("" if model_res is None else f" (model_res {_size2(model_res)})"))
+        return rollout_eval(self.model, xx, yy, msk, T_bundle, step=self.step, metrics=metrics, model_res=model_res)

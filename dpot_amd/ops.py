@@ -1596,3 +1596,151 @@ def window_slide_bwd(dout: Tensor, Tb: int, need_xx: bool, need_im: bool):
     check(_lib.load().dpot_window_slide_bwd(dout.data_ptr(), _p(dxx), _p(dim), rows, T, Tb, Cc, _stream()),
           "window_slide_bwd")
     return dxx, dim
+
+
+# ------------------------------------------------------------------------------------------------------
+# Fourier ("spectral") resize: utils/utilities.py:277-305 as dense products (csrc/resize.hip)
+# ------------------------------------------------------------------------------------------------------
+def _resize_freqs(n: int, m: int, axis: int):
+    """(frequencies k, weights c_k) the resize keeps along one axis of length n -> m.  axis 0 is the full-spectrum axis
+    (the reference's top and bottom row blocks), axis 1 the half-spectrum axis of rfft2 / irfft2"""
+    import numpy as np
+    if axis == 0:
+        t1, b1 = min((n + 1) // 2, (m + 1) // 2), min(n // 2, m // 2)
+        k = np.concatenate([np.arange(t1), np.arange(-b1, 0)])
+        return k, np.ones(len(k))
+    k = np.arange(min(n // 2 + 1, m // 2 + 1))
+    # a complex-to-real inverse of length m counts every column twice but the DC one and (m even) the Nyquist one
+    return k, np.where((k == 0) | (2 * k == m), 1.0, 2.0)
+
+
+def spectral_resize_matrices(n: int, m: int, axis: int):
+    """float64 (Re D, Im D), each [m, n], of one axis of the Fourier resize n -> m:
+    D[j', j] = sum_k c_k exp(2 pi i k (j'/m - j/n)).  A plane resizes as
+    out = (Re Dx (x) Re Dy - Im Dx (x) Im Dy) in / (n_x n_y), i.e. Re Dx @ in @ Re Dy.T - Im Dx @ in @ Im Dy.T, scaled.
+    Pure host mathematics (numpy): the CPU tests check it without a GPU."""
+    import numpy as np
+    if n < 2 or m < 2 or axis not in (0, 1):
+        raise ValueError(f"spectral_resize_matrices: sizes must be >= 2 and axis 0 or 1 (got {n} -> {m}, axis {axis})")
+    k, c = _resize_freqs(n, m, axis)
+    # the phase as an exact integer over the common denominator n m, reduced before the float64 division
+    num = np.arange(m)[:, None, None] * n - np.arange(n)[None, :, None] * m            # [m, n, 1]
+    ang = 2.0 * np.pi * ((k[None, None, :] * num) % (n * m)) / float(n * m)
+    return (np.cos(ang) * c).sum(-1), (np.sin(ang) * c).sum(-1)
+
+
+def spectral_resize_im_factors(n: int, m: int):
+    """(u [m], v [n]) with Im Dx = u v^T for the full-spectrum axis, or None where Im Dx vanishes (min(n, m) odd, or
+    m == n).  The one unpaired frequency -h, h = min(n, m) / 2, is real on the side whose length is 2h."""
+    import numpy as np
+    h2 = min(n, m)
+    if h2 % 2 or n == m:
+        return None
+    h = h2 // 2
+    if n == h2:          # exp(2 pi i h x / n) = (-1)^x
+        u = -np.sin(2.0 * np.pi * ((h * np.arange(m)) % m) / m)
+        v = 1.0 - 2.0 * (np.arange(n) % 2)
+    else:                # exp(-2 pi i h x' / m) = (-1)^x'
+        u = 1.0 - 2.0 * (np.arange(m) % 2)
+        v = np.sin(2.0 * np.pi * ((h * np.arange(n)) % n) / n)
+    return u, v
+
+
+class ResizePlan:
+    """The operator matrices of dpot_spectral_resize for one size pair, built in float64, rounded to fp32, zero-padded to
+    the kernel's tile multiples (include/dpot_hip.h) and kept in device memory.  `host_matrices` is the host part alone."""
+
+    @staticmethod
+    def pads(nx: int, ny: int, mx: int, my: int):
+        """(nxp, nyp, mxp, myp): contraction and y' extents in multiples of 16, output rows in multiples of 32 - the values
+        dpot_spectral_resize_pad returns (checked when a plan is built)"""
+        r = lambda n, q: (n + q - 1) // q * q
+        return r(nx, 16), r(ny, 16), r(mx, 32), r(my, 16)
+
+    @staticmethod
+    def host_matrices(nx: int, ny: int, mx: int, my: int):
+        """dict of fp32 numpy arrays: axT [nxp, mxp], ayT [nyp, myp] and, for the two-term size pairs, byT [nyp, myp],
+        u [mxp], v [nxp] (else None)"""
+        import numpy as np
+        nxp, nyp, mxp, myp = ResizePlan.pads(nx, ny, mx, my)
+        re_x, _ = spectral_resize_matrices(nx, mx, 0)
+        re_y, im_y = spectral_resize_matrices(ny, my, 1)
+        scale = 1.0 / (nx * ny)
+
+        def padded(a, shape):
+            outp = np.zeros(shape, dtype=np.float32)
+            outp[tuple(slice(0, s) for s in a.shape)] = a.astype(np.float32)
+            return outp
+
+        h = {"axT": padded(re_x.T, (nxp, mxp)), "ayT": padded(re_y.T * scale, (nyp, myp)), "byT": None, "u": None,
+             "v": None}
+        uv = spectral_resize_im_factors(nx, mx)
+        if uv is not None:
+            h["byT"] = padded(-im_y.T * scale, (nyp, myp))
+            h["u"], h["v"] = padded(uv[0], (mxp,)), padded(uv[1], (nxp,))
+        return h
+
+    def __init__(self, nx: int, ny: int, mx: int, my: int, device):
+        lib = _lib.load()
+        self.sizes = (nx, ny, mx, my)
+        want = (lib.dpot_spectral_resize_pad(nx, 0), lib.dpot_spectral_resize_pad(ny, 0),
+                lib.dpot_spectral_resize_pad(mx, 1), lib.dpot_spectral_resize_pad(my, 0))
+        if want != self.pads(nx, ny, mx, my):
+            raise _lib.DpotHipError(f"ResizePlan: the library pads {self.sizes} to {want}, this module to "
+                                    f"{self.pads(nx, ny, mx, my)}")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DpotHipError(f"ResizePlan {self.sizes}: the matrices are uploaded when a size pair is first used - "
+                                    "call ops.resize_plan(...) (or the resize itself) once before capturing")
+        self.dev = {}
+        for name, a in self.host_matrices(nx, ny, mx, my).items():
+            if a is None:
+                self.dev[name] = None
+                continue
+            t = torch.empty(a.shape, dtype=torch.float32, device=device)
+            t.copy_(torch.from_numpy(a))
+            self.dev[name] = t
+        self.two_terms = self.dev["byT"] is not None
+
+
+_resize_plans = {}
+
+
+def resize_plan(nx: int, ny: int, mx: int, my: int, device) -> ResizePlan:
+    """the cached ResizePlan of (n_x, n_y, m_x, m_y, device)"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(nx), int(ny), int(mx), int(my), device)
+    plan = _resize_plans.get(key)
+    if plan is None:
+        plan = _resize_plans[key] = ResizePlan(*key)
+    return plan
+
+
+def spectral_resize(x: Tensor, out_size, out: Optional[Tensor] = None) -> Tensor:
+    """Fourier resize of x [B, n_x, n_y, T, C] (or [B, n_x, n_y, TC]) to out_size = (m_x, m_y) or one int for both: the
+    reference's resize(x, out_size, temporal=True) (utils/utilities.py:277-305), one kernel launch"""
+    _req(x, "spectral_resize: x")
+    if x.dim() not in (4, 5):
+        raise _lib.DpotHipError(f"spectral_resize: x must be [B, X, Y, T, C] or [B, X, Y, TC], got {tuple(x.shape)}")
+    mx, my = (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
+    B, nx, ny = x.shape[:3]
+    TC = x.numel() // max(B * nx * ny, 1)
+    if min(B, nx, ny, mx, my, TC) < 1 or min(nx, ny, mx, my) < 2:
+        raise _lib.DpotHipError(f"spectral_resize: cannot resize {tuple(x.shape)} to {(mx, my)}: every spatial size must be "
+                                ">= 2 and no dimension empty")
+    shape = (B, mx, my) + tuple(x.shape[3:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _req(out, "spectral_resize: out")
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise _lib.DpotHipError(f"spectral_resize: out must be {shape} on {x.device}, got {tuple(out.shape)} on "
+                                    f"{out.device}")
+        if out.data_ptr() == x.data_ptr():
+            raise _lib.DpotHipError("spectral_resize: out must not alias x")
+    d = resize_plan(nx, ny, mx, my, x.device).dev
+    check(_lib.load().dpot_spectral_resize(x.data_ptr(), out.data_ptr(), d["axT"].data_ptr(), d["ayT"].data_ptr(),
+                                           _p(d["byT"]), _p(d["u"]), _p(d["v"]), B, nx, ny, mx, my, TC, _stream()),
+          "spectral_resize")
+    return out

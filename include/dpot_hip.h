@@ -706,6 +706,21 @@ typedef struct dpot_sample_desc {
 int dpot_resize_pad_window(const dpot_sample_desc* samples_dev, int nsamples, float* xx, float* yy, int res, int t_in,
                            int t_ar, int n_channels, int down_h, int down_w, dpot_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Fourier ("spectral") resize of channels-last fields (csrc/resize.hip): the operator of the reference's
+ * utils/utilities.py:277-305 as dense fp32 products, one launch.
+ *   out[B, mx, my, TC] = R(in[B, nx, ny, TC]),   TC = the (t, c) planes, independent
+ *   out[x', y'] = sum_y ayT[y][y'] sum_x axT[x][x'] in[x, y]  +  u[x'] sum_y byT[y][y'] sum_x v[x] in[x, y]
+ * axT = (Re Dx)^T [nxp][mxp], ayT = (Re Dy)^T / (nx ny) and byT = -(Im Dy)^T / (nx ny) [nyp][myp], Im Dx = u v^T with
+ * u[mxp], v[nxp]: device arrays, ZERO-padded to nxp = pad(nx, 0), nyp = pad(ny, 0), myp = pad(my, 0), mxp = pad(mx, 1)
+ * with pad = dpot_spectral_resize_pad.  byT == NULL (then u, v are ignored): the one-term operator of the size pairs whose
+ * Im Dx vanishes (min(nx, mx) odd, or nx == mx).  in != out; every spatial size >= 2; ny <= 272 (the LDS intermediate);
+ * any TC >= 1 (16-byte loads and stores when TC % 4 == 0 and both fields are 16-byte aligned).  Reads nothing outside the
+ * tensors, fixed reduction order, no atomics, no allocation, legal under stream capture. */
+int dpot_spectral_resize_pad(int n, int output_rows);
+int dpot_spectral_resize(const float* in, float* out, const float* axT, const float* ayT, const float* byT, const float* u,
+                         const float* v, int B, int nx, int ny, int mx, int my, int TC, dpot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
