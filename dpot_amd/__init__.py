@@ -5,6 +5,7 @@
     from dpot_amd.dp import BucketedGradReducer
     from dpot_amd import StepMetrics, cls_ce_loss     # device-side training metrics, the dataset-classification loss
     from dpot_amd import rollout_eval, GraphedRollout, refill_mask, spectral_resize   # evaluation at any data resolution
+    from dpot_amd import RolloutEvaluator              # the PDEBench metric set of the reference's Evaluator, on the device
 
 The compute path is libdpot_hip.so (hand-written HIP kernels behind the C ABI in include/dpot_hip.h).
 """
@@ -12,9 +13,9 @@ from .model import DPOTNet  # noqa: F401
 from . import _lib  # noqa: F401
 from .functional import ClsCEFn, cls_ce_loss  # noqa: F401
 from .train import StepMetrics  # noqa: F401
-from .infer import GraphedRollout, refill_mask, rollout_eval  # noqa: F401
+from .infer import GraphedRollout, RolloutEvaluator, refill_mask, rollout_eval  # noqa: F401
 from .ops import ResizePlan, spectral_resize, spectral_resize_matrices  # noqa: F401
 
-__version__ = "0.2.8"
+__version__ = "0.2.9"
 __all__ = ["DPOTNet", "StepMetrics", "ClsCEFn", "cls_ce_loss", "GraphedRollout", "rollout_eval", "refill_mask",
-           "spectral_resize", "spectral_resize_matrices", "ResizePlan"]
+           "spectral_resize", "spectral_resize_matrices", "ResizePlan", "RolloutEvaluator"]

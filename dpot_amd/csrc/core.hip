@@ -42,6 +42,6 @@ int tune(const char* key, int dflt) {
  * argument list (the row-form operand / transposed-output arguments of 0.2.5 are gone with the kernels they selected);
  * dpot_afno_fused_bwd removed; every fallback selector behind DPOT_TUNE
  * 264: dpot_spectral_resize, dpot_spectral_resize_pad (csrc/resize.hip) */
-extern "C" int dpot_version(void) { return 264; }
+extern "C" int dpot_version(void) { return 265; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

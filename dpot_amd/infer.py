@@ -11,6 +11,9 @@
 * ``refill_mask`` and ``model_res=`` - the resolution-generalisation rollout of evaluate_varyingres.py:198-248: data on
   a res x res grid runs through a model built for another resolution; every AR step Fourier-resizes the window up to the
   model's resolution (ops.spectral_resize, one launch) and the prediction back down.
+* ``RolloutEvaluator`` - the reference's second evaluation tool, utils/criterion.py:189-239 ``Evaluator(temporal=True,
+  griddata=True, component='all')``: per-channel and per-step normalised errors, the boundary error and the error spectrum
+  in three wavenumber bands, accumulated on the device (csrc/evalmetrics.hip); ``evaluator=`` hands every rollout to it.
 """
 from __future__ import annotations
 
@@ -22,7 +25,7 @@ from typing import Dict, Iterable, Mapping, Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _lib, ops
 from .functional import rel_l2_loss
 
 Tensor = torch.Tensor
@@ -100,9 +103,101 @@ def refill_mask(msk: Tensor, res) -> Tensor:
     return nonzero.to(torch.float32).expand(msk.shape[0], rx, ry, 1, msk.shape[-1]).contiguous()
 
 
+class RolloutEvaluator:
+    """The metric set of the reference's ``Evaluator(temporal=True, griddata=True, component='all')`` (utils/criterion.py:
+    189-239 and compute_fourier_error, :246-360), kept on the DEVICE and accumulated over batches.  ``update(pred, target)``
+    enqueues two launches and never synchronises; ``read()`` is the only call that does.  After ``update`` on the batches
+    B1, B2, ... ``read()`` equals the reference's Evaluator called once on their concatenation: every metric is a mean over
+    the samples of a per-sample value (or, for the spectrum, the root of such a mean), so the accumulator holds sums over
+    the samples and the sample count.
+
+    What is computed, with e = pred - target formed in fp32 (also BEFORE the transform: the DFT is linear, and the
+    difference of two nearly equal spectra cancels in fp32 where the spectrum of the difference does not):
+
+    * ``nmae, nmse, nmxe`` [1, C]: per sample and channel, over all of X*Y*T: sum|e| / sum|target|,
+      sqrt(sum e^2 / sum target^2), max|e| / max|target|; then the mean over the samples.
+    * ``nmae_t, nmse_t, nmxe_t`` [1, T, C]: the same per time step, over X*Y.
+    * ``bdmse`` **[C, T]**: e^2 summed over the rows x = 0, nx-1 (all y) and the columns y = 0, ny-1 (all x) - the four
+      corners counted twice - divided by 2 nx + 2 ny, root, mean over the samples.  An absolute error (no target norm), and
+      the one key the reference returns channel-major (untransposed); kept so.
+    * ``fmse_low, fmse_mid, fmse_high`` [T, C]: |DFT2(e)|^2 (unnormalised forward transform) over the positive quadrant
+      0 <= i < nx//2, 0 <= j < ny//2 only, summed over the shells floor(sqrt(i^2 + j^2)) < K = min(nx//2, ny//2) (larger
+      shells are dropped); per shell sqrt(mean over the samples) / (nx ny); then the mean over the shells [0, ilow),
+      [ilow, ihigh), [ihigh, K).  An empty band (K <= ihigh, e.g. 16 x 16 with the defaults) is NaN, as in the reference.
+    * ``samples``: the number of samples seen.
+
+    A channel whose target is identically zero divides by a zero norm: inf or NaN, as IEEE arithmetic and the reference give;
+    nothing is counted specially.  There is no mask, no normalizer and no single-component mode.  All batches between two
+    ``reset()`` share X, Y, T, C (T <= T_max, C == n_channels); the batch size may change.  X <= 1024, Y <= 304 (the LDS
+    intermediate of a workgroup).  ``update`` is capturable in a hipGraph once a shape has been seen."""
+
+    def __init__(self, device, n_channels: int, T_max: int, ilow: int = 4, ihigh: int = 12):
+        if n_channels < 1 or T_max < 1:
+            raise ValueError(f"RolloutEvaluator: n_channels and T_max must be >= 1, got {n_channels}, {T_max}")
+        if not 0 <= ilow <= ihigh:
+            raise ValueError(f"RolloutEvaluator: need 0 <= ilow <= ihigh, got {ilow}, {ihigh}")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.DpotHipError(f"RolloutEvaluator must live on the MI355X (got device {self.device}): dpot_amd has no "
+                                    "CPU path")
+        self.C, self.T_max, self.ilow, self.ihigh = int(n_channels), int(T_max), int(ilow), int(ihigh)
+        self.shape: Optional[Tuple[int, int, int, int]] = None         # (X, Y, T, C) of the batches since reset()
+        self.acc: Optional[Tensor] = None
+        self._accs: Dict[Tuple[int, int, int, int], Tensor] = {}        # one accumulator per shape ever seen: no re-allocation
+
+    def update(self, pred: Tensor, target: Tensor) -> None:
+        """fold one batch in: pred, target [B, X, Y, T, C] fp32 contiguous on the GPU.  No synchronisation."""
+        if pred.dim() != 5 or pred.shape != target.shape:
+            raise _lib.DpotHipError(f"RolloutEvaluator.update: pred and target must be [B, X, Y, T, C] of one shape, got "
+                                    f"{tuple(pred.shape)} and {tuple(target.shape)}")
+        shape = tuple(int(s) for s in pred.shape[1:])
+        if shape[3] != self.C or shape[2] > self.T_max:
+            raise _lib.DpotHipError(f"RolloutEvaluator was built for {self.C} channels and T <= {self.T_max}, got "
+                                    f"{tuple(pred.shape)}")
+        if self.shape is not None and shape != self.shape:
+            raise _lib.DpotHipError(f"RolloutEvaluator: the batches between two reset() must share X, Y, T, C: "
+                                    f"{self.shape} so far, now {shape}")
+        if not (pred.is_cuda and target.is_cuda):
+            raise _lib.DpotHipError(f"RolloutEvaluator.update: pred and target must live on the MI355X (got {pred.device}, "
+                                    f"{target.device}): dpot_amd has no CPU path")
+        if self.shape is None:
+            acc = self._accs.get(shape)
+            if acc is None:
+                if torch.cuda.is_current_stream_capturing():
+                    raise _lib.DpotHipError("RolloutEvaluator: the accumulator of a shape is allocated when it is first seen - "
+                                            "run one update (and reset) before capturing")
+                X, Y, T, Cc = shape
+                acc = self._accs[shape] = ops.eval_acc_alloc(X, Y, T, Cc, self.device)
+            self.acc = acc
+        ops.eval_metrics_update(pred, target, self.acc)
+        self.shape = shape
+
+    def reset(self) -> None:
+        """zero the accumulator by a launch (no synchronisation); the next update may bring another shape"""
+        if self.acc is not None:
+            self.acc.zero_()
+        self.shape = None
+
+    def read(self, group=None) -> Dict[str, object]:
+        """the ONLY call that synchronises: the reference's ten keys as float32 numpy arrays in the reference's shapes (see
+        the class docstring; ``bdmse`` is [C, T]) plus ``samples``.  The accumulator is left as it is.  ``group``: a
+        dp.BucketedGradReducer or a process group - the sums are added over the ranks with ONE all-reduce first."""
+        if self.shape is None:
+            raise _lib.DpotHipError("RolloutEvaluator.read: no update since the last reset")
+        vals = torch.cat([self.acc[:1].to(torch.float64), self.acc[1:].view(torch.float64)])
+        if group is not None:
+            import torch.distributed as dist
+            pg = getattr(group, "pg", group) if not isinstance(group, bool) else None
+            if dist.is_available() and dist.is_initialized():
+                dist.all_reduce(vals, op=dist.ReduceOp.SUM, group=pg)
+        vals = vals.cpu().numpy()
+        X, Y, T, Cc = self.shape
+        return ops.eval_finish(vals, int(round(vals[0])), X, Y, T, Cc, self.ilow, self.ihigh)
+
+
 @torch.no_grad()
 def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
-                 step=None, metrics=None, model_res=None) -> Tuple[Tensor, Tensor, Tensor]:
+                 step=None, metrics=None, model_res=None, evaluator=None) -> Tuple[Tensor, Tensor, Tensor]:
     """evaluate.py:193-213.  Returns (pred [B,X,Y,T_ar,C], sum of the per-step losses, loss of the whole rollout).
     `step(xx) -> im` defaults to the model's forward (a GraphedRollout passes its graph replay).
     metrics: a train.StepMetrics - the test loop's test_l2_step / test_l2_full (train_temporal.py:252-281) are accumulated
@@ -113,7 +208,9 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
     model_res (an int or (res_x, res_y)): evaluate_varyingres.py:228-248 - xx, yy and msk live at the DATA resolution; every
     step Fourier-resizes the window to model_res, runs the model there and resizes the prediction back; loss, metrics and
     the window slide stay at the data resolution.  As in the reference the two resizes also run when model_res equals the
-    data resolution (every frequency is kept then: the identity up to rounding).  None: no resize is enqueued."""
+    data resolution (every frequency is kept then: the identity up to rounding).  None: no resize is enqueued.
+    evaluator: a RolloutEvaluator - `evaluator.update(pred, yy)` runs on the assembled prediction at the DATA resolution, on
+    the same stream, without a synchronisation; the returned values are untouched by it.  None: nothing is enqueued."""
     # weight-only products (packed AFNO weights, folded embed matrices, ...) once per rollout, not once per AR step
     scope = model.weights_scope() if (step is None and hasattr(model, "weights_scope")) else contextlib.nullcontext()
     step = step or (lambda x: model(x)[0])
@@ -143,6 +240,8 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
             if t + T_bundle < T_ar:
                 xx = ops.window_slide(xx, im.contiguous())               # xx[..., T_bundle:, :] ++ im, one kernel
     pred = preds[0] if len(preds) == 1 else torch.cat(preds, dim=-2)
+    if evaluator is not None:
+        evaluator.update(pred.contiguous(), yy.contiguous())
     if metrics is not None:
         metrics.end_rollout(loss_steps, n_steps, pred.shape[0], pred.shape[-1], 0)
         metrics.accumulate()
@@ -177,9 +276,10 @@ class GraphedRollout:
         self.graph.replay()
         return self.im.clone()          # the graph's output buffer is overwritten by the next replay
 
-    def __call__(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1, metrics=None, model_res=None):
+    def __call__(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1, metrics=None, model_res=None,
+                 evaluator=None):
         """model_res: the graph's own resolution - xx, yy, msk may then live at any data resolution; the two resizes of an
-        AR step run outside the captured graph, on the same stream (rollout_eval)"""
+        AR step run outside the captured graph, on the same stream (rollout_eval).  evaluator: as in rollout_eval"""
         want = tuple(self.x.shape)
         if model_res is not None:
             if xx.dim() != 5:
@@ -190,4 +290,5 @@ class GraphedRollout:
         if tuple(xx.shape) != want:
             raise ValueError(f"GraphedRollout captured for input {tuple(self.x.shape)}, got {tuple(xx.shape)}"
                              + ("" if model_res is None else f" (model_res {_size2(model_res)})"))
-        return rollout_eval(self.model, xx, yy, msk, T_bundle, step=self.step, metrics=metrics, model_res=model_res)
+        return rollout_eval(self.model, xx, yy, msk, T_bundle, step=self.step, metrics=metrics, model_res=model_res,
+                            evaluator=evaluator)

@@ -1744,3 +1744,199 @@ def spectral_resize(x: Tensor, out_size, out: Optional[Tensor] = None) -> Tensor
                                            _p(d["byT"]), _p(d["u"]), _p(d["v"]), B, nx, ny, mx, my, TC, _stream()),
           "spectral_resize")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------
+# Rollout evaluation metrics: the reference's Evaluator (utils/criterion.py:189-239, compute_fourier_error :246-360) on the
+# device (csrc/evalmetrics.hip).  The host tables are pure numpy: the CPU tests check them without a GPU.
+# ------------------------------------------------------------------------------------------------------
+EVAL_KEYS = ("nmae", "nmse", "nmxe", "nmae_t", "nmse_t", "nmxe_t", "bdmse", "fmse_low", "fmse_mid", "fmse_high")
+
+
+def eval_dft_tables(n: int):
+    """float64 (cos, sin) [n // 2, n] of the forward DFT's positive half: row i, column x holds cos / sin(2 pi i x / n), so
+    that sum_x e[x] exp(-2 pi 1j i x / n) = cos @ e - 1j * sin @ e.  The phase i x is reduced modulo n as an exact integer
+    before the float64 division."""
+    import numpy as np
+    if n < 2:
+        raise ValueError(f"eval_dft_tables: the size must be >= 2, got {n}")
+    ang = 2.0 * np.pi * ((np.arange(n // 2)[:, None] * np.arange(n)[None, :]) % n) / float(n)
+    return np.cos(ang), np.sin(ang)
+
+
+def eval_shell_table(nx: int, ny: int):
+    """int32 [nx // 2, ny // 2]: the shell floor(sqrt(i^2 + j^2)) of wavenumber (i, j) of the positive quadrant, or -1 where
+    that shell is >= K = min(nx // 2, ny // 2) and the reference drops the wavenumber.  Integer arithmetic: the float square
+    root is only a first guess that two integer comparisons correct."""
+    import numpy as np
+    if nx < 2 or ny < 2:
+        raise ValueError(f"eval_shell_table: sizes must be >= 2, got {nx} x {ny}")
+    i = np.arange(nx // 2, dtype=np.int64)[:, None]
+    j = np.arange(ny // 2, dtype=np.int64)[None, :]
+    v = i * i + j * j
+    s = np.sqrt(v.astype(np.float64)).astype(np.int64)
+    s -= (s * s > v)
+    s += ((s + 1) * (s + 1) <= v)
+    assert ((s * s <= v) & ((s + 1) * (s + 1) > v)).all()
+    K = min(nx // 2, ny // 2)
+    return np.where(s < K, s, -1).astype(np.int32)
+
+
+def eval_shell_ranges(nx: int, ny: int):
+    """int32 [nx // 2, K + 1]: entry [i, s] = number of j in [0, ny // 2) whose shell in row i is below s.  The shell grows
+    with j, so the members of shell s in row i are the j range [i, s] .. [i, s + 1]; what lies at or beyond [i, K] is
+    dropped.  This is the form of eval_shell_table the kernel walks."""
+    import numpy as np
+    sh = eval_shell_table(nx, ny).astype(np.int64)
+    K = min(nx // 2, ny // 2)
+    sh = np.where(sh < 0, K, sh)                                   # dropped: beyond every kept shell
+    return (sh[:, :, None] < np.arange(K + 1)[None, None, :]).sum(axis=1).astype(np.int32)
+
+
+def eval_acc_layout(nx: int, ny: int, T: int, C: int):
+    """(offsets, total) of the accumulator in 8-byte words: 'count' (int64), then doubles - 'c' [3, C] = nmae | nmse | nmxe,
+    'tc' [4, T, C] = nmae_t | nmse_t | nmxe_t | boundary, 'spec' [T, C, K] - every entry a sum over the samples"""
+    K = min(nx // 2, ny // 2)
+    off = {"count": 0, "c": 2, "tc": 2 + 3 * C, "spec": 2 + 3 * C + 4 * T * C}
+    return off, 2 + 3 * C + 4 * T * C + T * C * K
+
+
+def eval_finish(acc, samples: int, nx: int, ny: int, T: int, C: int, ilow: int = 4, ihigh: int = 12):
+    """the dict of RolloutEvaluator.read() from the accumulated sums (`acc`: float64 array of eval_acc_layout's words, the
+    count word ignored; `samples`: the count): the means over the samples, the root of the mean shell sums over nx ny, and
+    the three band means (an empty band is NaN, as torch.mean of an empty slice in the reference).  float32 arrays with
+    the reference's shapes: nmae.. [1, C], nmae_t.. [1, T, C], fmse_* [T, C], bdmse [C, T] (the reference returns the
+    boundary error untransposed)."""
+    import numpy as np
+    import warnings
+    acc = np.asarray(acc, dtype=np.float64)
+    off, total = eval_acc_layout(nx, ny, T, C)
+    if acc.shape != (total,):
+        raise ValueError(f"eval_finish: the accumulator of {nx}x{ny}, T={T}, C={C} has {total} words, got {acc.shape}")
+    K = min(nx // 2, ny // 2)
+    n = float(samples) if samples else float("nan")
+    c = acc[off["c"]:off["tc"]].reshape(3, C) / n
+    tc = acc[off["tc"]:off["spec"]].reshape(4, T, C) / n
+    shells = np.sqrt(acc[off["spec"]:].reshape(T, C, K) / n) / float(nx * ny)
+    out = {"nmae": c[0:1], "nmse": c[1:2], "nmxe": c[2:3], "nmae_t": tc[0:1], "nmse_t": tc[1:2], "nmxe_t": tc[2:3],
+           "bdmse": tc[3].T}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)            # the mean of an empty band IS NaN
+        for key, band in (("fmse_low", shells[..., :ilow]), ("fmse_mid", shells[..., ilow:ihigh]),
+                          ("fmse_high", shells[..., ihigh:])):
+            out[key] = band.mean(axis=-1) if band.shape[-1] else np.full((T, C), np.nan)
+    out = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
+    out["samples"] = int(samples)
+    return out
+
+
+class EvalPlan:
+    """The tables of dpot_eval_metrics_stats for one plane size, built in float64, rounded to fp32, zero-padded to the kernel's
+    tile multiples and kept in device memory.  `host_tables` is the host part alone."""
+
+    @staticmethod
+    def pads(nx: int, ny: int):
+        """(nxp, nyp, hxp, hyp): the contraction extents and the wavenumber extents nx // 2, ny // 2, each rounded up to 16 -
+        the values dpot_eval_metrics_pad returns (checked when a plan is built)"""
+        r = lambda n: (n + 15) // 16 * 16
+        return r(nx), r(ny), r(nx // 2), r(ny // 2)
+
+    @staticmethod
+    def host_tables(nx: int, ny: int):
+        """dict of numpy arrays: cxT, sxT fp32 [nxp, hxp], cy, sy fp32 [nyp, hyp], jlo int32 [nx // 2, K + 1]"""
+        import numpy as np
+        nxp, nyp, hxp, hyp = EvalPlan.pads(nx, ny)
+
+        def padded(a, shape):
+            outp = np.zeros(shape, dtype=np.float32)
+            outp[:a.shape[0], :a.shape[1]] = a.astype(np.float32)
+            return outp
+
+        cx, sx = eval_dft_tables(nx)
+        cy, sy = eval_dft_tables(ny)
+        return {"cxT": padded(cx.T, (nxp, hxp)), "sxT": padded(sx.T, (nxp, hxp)), "cy": padded(cy.T, (nyp, hyp)),
+                "sy": padded(sy.T, (nyp, hyp)), "jlo": np.ascontiguousarray(eval_shell_ranges(nx, ny))}
+
+    def __init__(self, nx: int, ny: int, device):
+        lib = _lib.load()
+        self.sizes = (nx, ny)
+        if nx > lib.dpot_eval_metrics_max_size(0) or ny > lib.dpot_eval_metrics_max_size(1):
+            raise _lib.DpotHipError(f"eval_metrics: a {nx} x {ny} plane is beyond the supported size (nx <= "
+                                    f"{lib.dpot_eval_metrics_max_size(0)}, ny <= {lib.dpot_eval_metrics_max_size(1)}: the LDS "
+                                    "intermediate of a workgroup)")
+        want = (lib.dpot_eval_metrics_pad(nx, 0), lib.dpot_eval_metrics_pad(ny, 0), lib.dpot_eval_metrics_pad(nx, 1),
+                lib.dpot_eval_metrics_pad(ny, 1))
+        if want != self.pads(nx, ny):
+            raise _lib.DpotHipError(f"EvalPlan: the library pads {self.sizes} to {want}, this module to {self.pads(nx, ny)}")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DpotHipError(f"EvalPlan {self.sizes}: the tables are uploaded when a plane size is first used - call "
+                                    "ops.eval_plan(...) (or one update) before capturing")
+        self.n_stripes = want[2] // 16
+        self.K = min(nx // 2, ny // 2)
+        self.dev = {}
+        for name, a in self.host_tables(nx, ny).items():
+            t = torch.empty(a.shape, dtype=torch.int32 if name == "jlo" else torch.float32, device=device)
+            t.copy_(torch.from_numpy(a))
+            self.dev[name] = t
+        self.work = {}
+
+    def workspace(self, B: int, TC: int, device):
+        """(statp, specp) of a batch size: allocated when it is first seen (not under capture), then reused"""
+        w = self.work.get((B, TC))
+        if w is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.DpotHipError(f"EvalPlan {self.sizes}: the workspace of B={B}, T*C={TC} is allocated when that shape "
+                                        "is first used - run one update before capturing")
+            w = self.work[(B, TC)] = (torch.empty(B * TC * self.n_stripes * 8, dtype=torch.float64, device=device),
+                                      torch.empty(B * TC * self.n_stripes * self.K, dtype=torch.float32, device=device))
+        return w
+
+
+_eval_plans = {}
+
+
+def eval_plan(nx: int, ny: int, device) -> EvalPlan:
+    """the cached EvalPlan of (n_x, n_y, device)"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(nx), int(ny), device)
+    plan = _eval_plans.get(key)
+    if plan is None:
+        plan = _eval_plans[key] = EvalPlan(*key)
+    return plan
+
+
+def eval_acc_alloc(nx: int, ny: int, T: int, C: int, device) -> Tensor:
+    """a zeroed accumulator for eval_metrics_update (int64 words; word 0 the sample count, the rest doubles)"""
+    n = eval_acc_layout(nx, ny, T, C)[1]
+    if n != _lib.load().dpot_eval_metrics_acc_elems(nx, ny, T, C):
+        raise _lib.DpotHipError(f"eval_acc_alloc: the library lays the accumulator of {nx}x{ny}, T={T}, C={C} out differently")
+    return torch.zeros(n, dtype=torch.int64, device=device)
+
+
+def eval_metrics_update(pred: Tensor, target: Tensor, acc: Tensor) -> None:
+    """acc += the Evaluator sums of this batch: pred, target [B, X, Y, T, C] fp32 contiguous on the GPU, acc from
+    eval_acc_alloc for the same (X, Y, T, C).  Two launches on the current stream, no synchronisation; capturable once the
+    plane size and the batch size have been seen (their tables and workspace are cached)."""
+    _req(pred, "eval_metrics: pred")
+    _req(target, "eval_metrics: target")
+    if pred.dim() != 5 or pred.shape != target.shape or pred.device != target.device:
+        raise _lib.DpotHipError(f"eval_metrics: pred and target must be [B, X, Y, T, C] of one shape on one device, got "
+                                f"{tuple(pred.shape)} on {pred.device} and {tuple(target.shape)} on {target.device}")
+    B, nx, ny, T, C = pred.shape
+    if min(B, T, C) < 1 or min(nx, ny) < 2:
+        raise _lib.DpotHipError(f"eval_metrics: cannot evaluate {tuple(pred.shape)}: every spatial size must be >= 2 and no "
+                                "dimension empty")
+    if (not acc.is_cuda or acc.device != pred.device or acc.dtype != torch.int64 or not acc.is_contiguous()
+            or acc.numel() != eval_acc_layout(nx, ny, T, C)[1]):
+        raise _lib.DpotHipError(f"eval_metrics: acc must be the {eval_acc_layout(nx, ny, T, C)[1]} int64 words of "
+                                f"eval_acc_alloc({nx}, {ny}, {T}, {C}) on {pred.device}")
+    plan = eval_plan(nx, ny, pred.device)
+    statp, specp = plan.workspace(B, T * C, pred.device)
+    d, lib = plan.dev, _lib.load()
+    check(lib.dpot_eval_metrics_stats(pred.data_ptr(), target.data_ptr(), d["cxT"].data_ptr(), d["sxT"].data_ptr(),
+                                      d["cy"].data_ptr(), d["sy"].data_ptr(), d["jlo"].data_ptr(), statp.data_ptr(),
+                                      specp.data_ptr(), B, nx, ny, T * C, _stream()), "eval_metrics_stats")
+    check(lib.dpot_eval_metrics_finalize(statp.data_ptr(), specp.data_ptr(), acc.data_ptr(), B, nx, ny, T, C, _stream()),
+          "eval_metrics_finalize")

@@ -721,6 +721,37 @@ int dpot_spectral_resize_pad(int n, int output_rows);
 int dpot_spectral_resize(const float* in, float* out, const float* axT, const float* ayT, const float* byT, const float* u,
                          const float* v, int B, int nx, int ny, int mx, int my, int TC, dpot_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Rollout evaluation metrics (csrc/evalmetrics.hip): the reference's Evaluator(temporal=True, griddata=True,
+ * component='all') (utils/criterion.py:189-239, compute_fourier_error :246-360) for pred, target [B, nx, ny, T, C],
+ * accumulated over batches on the device.  Two launches per batch:
+ *   dpot_eval_metrics_stats     per plane p = (t, c) and stripe of 16 wavenumbers i: the pointwise statistics of e = pred -
+ *     target (formed in fp32 before the transform) and the shell sums of |DFT2(e)|^2 over the positive quadrant
+ *     0 <= i < nx/2, 0 <= j < ny/2, shell = floor(sqrt(i^2 + j^2)) < K = min(nx/2, ny/2), as dense fp32 MFMA products.
+ *       statp [B][TC][ns][8] doubles {sum|e|, sum|t|, sum e^2, sum t^2, max|e|, max|t|, boundary sum of e^2 (rows x = 0, nx-1
+ *             and columns y = 0, ny-1: corners twice), unused};  specp [B][TC][ns][K] floats;  ns = pad(nx, 1) / 16.
+ *       cxT, sxT [nxp][hxp]: cos / sin(2 pi i x / nx), row x;  cy, sy [nyp][hyp]: cos / sin(2 pi j y / ny), row y; all
+ *       ZERO-padded, nxp = pad(nx, 0), nyp = pad(ny, 0), hxp = pad(nx, 1), hyp = pad(ny, 1), pad = dpot_eval_metrics_pad
+ *       (half = 0: n rounded up to 16; half = 1: n / 2 rounded up to 16).
+ *       jlo [nx/2][K + 1] int32: jlo[i][s] = number of j in [0, ny/2) with floor(sqrt(i^2 + j^2)) < s (row i of shell s is
+ *       the j range jlo[i][s] .. jlo[i][s+1]).
+ *   dpot_eval_metrics_finalize  acc += this batch.  acc: dpot_eval_metrics_acc_elems(nx, ny, T, C) 8-byte words, zeroed by
+ *     the caller: [0] int64 number of samples, [1] reserved, then doubles, each a sum over the samples: nmae | nmse | nmxe
+ *     [3][C] (ratios over all of X*Y*T), nmae_t | nmse_t | nmxe_t | bd [4][T][C] (ratios over X*Y; bd = sqrt(boundary sum /
+ *     (2 nx + 2 ny))), shell sums [T][C][K].  A zero target norm divides as IEEE does (inf / NaN), as the reference.
+ * Sizes: nx, ny >= 2, any parity; nx <= dpot_eval_metrics_max_size(0), ny <= dpot_eval_metrics_max_size(1) (= 304: the LDS
+ * intermediate of a workgroup) - beyond: DPOT_EUNSUP, nothing is launched.  Any TC >= 1 (16-byte loads when TC % 4 == 0
+ * and both fields are 16-byte aligned).  Reads nothing outside the tensors; every element of statp (but the unused slot)
+ * and specp is written; fixed reduction order, no atomics, no allocation, legal under stream capture. */
+int dpot_eval_metrics_pad(int n, int half);
+int dpot_eval_metrics_max_size(int axis);
+int64_t dpot_eval_metrics_acc_elems(int nx, int ny, int T, int C);
+int dpot_eval_metrics_stats(const float* pred, const float* target, const float* cxT, const float* sxT, const float* cy,
+                            const float* sy, const int32_t* jlo, double* statp, float* specp, int B, int nx, int ny, int TC,
+                            dpot_stream_t stream);
+int dpot_eval_metrics_finalize(const double* statp, const float* specp, double* acc, int B, int nx, int ny, int T, int C,
+                               dpot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
