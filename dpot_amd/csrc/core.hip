@@ -21,13 +21,15 @@ int check_launch(const char* what) {
   return DPOT_OK;
 }
 
-// DPOT_TUNE="key=val,key=val" (integers; unknown keys are ignored here - dpot_amd/ops.py rejects them): parsed on first use
+// DPOT_TUNE="key=val,key=val" (integers; unknown keys are ignored here - dpot_amd/ops.py rejects them): parsed on first use.
+// Spaces around an entry are skipped, as ops.py strips them ("panel=0, gn_fuse=0").
 int tune(const char* key, int dflt) {
   static const char* env = getenv("DPOT_TUNE");
   if (!env || !*env) return dflt;
   const size_t kl = strlen(key);
   for (const char* p = env; *p;) {
     const char* end = strchr(p, ',');
+    while (*p == ' ' || *p == '\t') ++p;
     const size_t len = end ? (size_t)(end - p) : strlen(p);
     if (len > kl + 1 && strncmp(p, key, kl) == 0 && p[kl] == '=') return atoi(p + kl + 1);
     if (!end) break;

@@ -148,8 +148,9 @@ def mlp_precision() -> Optional[int]:
 # ---- DPOT_TUNE: the ONE switchboard of the fallback-path selectors (round 6; rounds 1-5 grew 43 separate DPOT_* variables) ------
 # DPOT_TUNE="key=val,key=val" (integers).  Every key selects a PREVIOUS-GENERATION path that stays under the GPU test gate
 # (tests/test_gpu_optout.py runs parity subsets under them); the defaults are what measured fastest.  The C side reads the same
-# variable once per process (csrc/core.hip dpot::tune); this side reads it per call.  Besides DPOT_TUNE the package reads only
-# DPOT_HIP_LIB (library path), DPOT_GEMM_PRECISION and DPOT_MLP_PRECISION (process defaults of the precision modes).
+# variable once per process (csrc/core.hip dpot::tune); this side looks at it per call and parses it when it has changed.
+# Besides DPOT_TUNE the package reads only DPOT_HIP_LIB (library path), DPOT_GEMM_PRECISION and DPOT_MLP_PRECISION (process
+# defaults of the precision modes).
 TUNE_KEYS = {
     "mixer": (3, "AFNO mixer MLP: 3 = three-product fused kernel (afno_mlp3), 4 = four-product fused kernel (afno_mlp2), "
                  "0 = two generic GEMM launches"),
@@ -171,9 +172,17 @@ TUNE_KEYS = {
 }
 
 
+# (the DPOT_TUNE string, its parse): re-parsed only when the variable's string changes.  The dict IS the cache: read it only
+_tune_parsed = ("", {})
+
+
 def _parse_tune():
+    global _tune_parsed
+    env = os.environ.get("DPOT_TUNE", "")
+    if env == _tune_parsed[0]:
+        return _tune_parsed[1]
     out = {}
-    for kv in os.environ.get("DPOT_TUNE", "").split(","):
+    for kv in env.split(","):
         kv = kv.strip()
         if not kv:
             continue
@@ -181,6 +190,7 @@ def _parse_tune():
         if k not in TUNE_KEYS:
             raise ValueError(f"DPOT_TUNE: unknown key {k!r} (known: {', '.join(TUNE_KEYS)})")
         out[k] = int(v)
+    _tune_parsed = (env, out)
     return out
 
 
@@ -782,7 +792,8 @@ def afno_mlp2_supported(nb: int, bs: int) -> bool:
 
 
 def afno_mlp3_supported(nb: int, bs: int) -> bool:
-    """the three-product (Gauss / Karatsuba) form of the fused mixer kernel: bs == 128; DPOT_AFNO_3MULT=0 disables it"""
+    """the three-product (Gauss / Karatsuba) form of the fused mixer kernel: bs == 128; DPOT_TUNE mixer=4 / mixer=0 select
+    the other forms"""
     return bool(_lib.load().dpot_afno_mlp3_supported(nb, bs)) and tune("mixer") == 3
 
 
@@ -1063,7 +1074,7 @@ def patchify(x: Tensor, gx: Tensor, gy: Tensor, gt: Tensor, P: int) -> Tensor:
 
 
 def embed_supported(Cc: int, P: int, T: int, hid: int, w: int) -> bool:
-    """shapes the implicit-GEMM patch embedding covers (csrc/embed.hip); DPOT_EMBED_IMPLICIT=0 disables it"""
+    """shapes the implicit-GEMM patch embedding covers (csrc/embed.hip); DPOT_TUNE embed_implicit=0 disables it"""
     return (tune("embed_implicit") != 0
             and bool(_lib.load().dpot_embed_supported(Cc, P, T, hid, w)))
 

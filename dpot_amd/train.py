@@ -11,8 +11,8 @@
 from __future__ import annotations
 
 import contextlib
+import functools
 import math
-import os
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
@@ -103,10 +103,38 @@ class FlatParams:
 
 
 class FlatOptimizer:
-    """What the fused optimisers over a FlatParams buffer share, and what the train steps duck-type on: ``fp``, ``lr``,
-    ``param_groups``, ``n_active``, ``packs``, ``wrote``; ``zero_grad``, ``stage_hyper(lr)`` (host side of a step, not
-    capturable), ``launch(grad_scale)`` (device side, capturable), ``step``, ``grad_norm``, ``snapshot`` / ``restore``,
-    ``state_dict(model)`` / ``load_state_dict(sd, model)``."""
+    """The fused optimisers over a FlatParams buffer: everything but the update rule.  Moments, the device-side step counter,
+    the global-norm clip, snapshot / restore and the reference's torch.optim checkpoint layout live here.  A subclass sets
+    ``HYPER`` and implements ``_stage(max_norm, advance)`` (its ``ops.*_stage`` call) and ``_update(plan, sumsq, grad_scale)``
+    (its update launch); it may set ``STATE``, ``PER_TENSOR`` and ``GROUP_EXTRA`` and override ``_pack_plan``.
+
+    Host/device protocol of a step: ``stage_hyper(lr)`` enqueues a one-thread kernel that receives lr / betas / eps /
+    weight decay / max_norm BY VALUE, advances the DEVICE-side step counter and derives the bias corrections from
+    it; ``launch()`` (capturable) enqueues ||g||^2 + the update kernels, which read those values from device
+    memory.  There is no host staging buffer, so a host that runs many (graph-replayed) steps ahead of the GPU
+    cannot disturb a step that is still queued."""
+    HYPER = 0                                 # floats of the ``hyper`` block its stage kernel fills
+    STATE: Tuple[str, ...] = ()               # attributes: further tensors of a snapshot
+    PER_TENSOR: Tuple[str, ...] = ()          # attributes: one float per updated tensor, a 0-d tensor each in the checkpoint
+    GROUP_EXTRA: Dict[str, object] = {}       # further param_groups keys of the checkpoint
+
+    def __init__(self, flat: FlatParams, lr: float, betas: Tuple[float, float], eps: float, weight_decay: float,
+                 max_norm: Optional[float], update_tail: bool):
+        self.fp = flat
+        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self.max_norm = max_norm
+        self.update_tail = update_tail
+        dev = flat.flat.device
+        self.exp_avg = torch.zeros_like(flat.flat)
+        self.exp_avg_sq = torch.zeros_like(flat.flat)
+        self.hyper = torch.zeros(self.HYPER, dtype=torch.float32, device=dev)
+        self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)     # the step counter the kernels use
+        self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
+        self.step_count = 0                       # host mirror of step_dev (number of steps ENQUEUED)
+        self.param_groups = [{"lr": lr}]          # minimal torch.optim surface for LR schedulers / logging
+        self.packs = getattr(flat.model, "packs", None)       # the model's packs.ModelPacks (None: a model without one)
+        self.wrote = None                         # the pack set the last launch() wrote along with the parameters, or None
 
     @property
     def n_active(self) -> int:
@@ -119,6 +147,30 @@ class FlatOptimizer:
         self.stage_hyper(lr)
         self.launch(grad_scale)
 
+    def stage_hyper(self, lr: Optional[float] = None, advance: int = 1) -> None:
+        """host side of a step (NOT capturable by design: call it right before a graph replay)"""
+        if lr is not None:
+            self.lr = lr
+            self.param_groups[0]["lr"] = lr
+        self.step_count += advance
+        self._stage(self.max_norm if self.max_norm is not None else 0.0, advance)
+
+    def launch(self, grad_scale: float = 1.0) -> None:
+        """device side of a step (capturable): ||g||^2 (with clipping), then the update launches"""
+        use_clip = self.max_norm is not None
+        if use_clip:
+            ops.sumsq(self.fp.grad[:self.n_active], self.sumsq, self._part)
+        plan = self._pack_plan()
+        self._update(plan, self.sumsq if use_clip else None, grad_scale)
+        self.fp.touch()               # parameters changed: a backward of an EARLIER forward must not run any more
+        self.wrote = plan.pp if plan is not None else None
+        if plan is not None:
+            self.packs.mark_fresh(plan.pp, self.fp)
+
+    def _pack_plan(self):
+        """tables of the weight packs ``_update`` writes along with the parameters (their pack set is ``.pp``), or None"""
+        return None
+
     def grad_norm(self, grad_scale: float = 1.0) -> Tensor:
         """global norm of the gradients currently in the flat buffer (device tensor; reading it synchronises):
         after a step, the value its clip used (train_temporal.py:228 returns it from clip_grad_norm_)"""
@@ -126,121 +178,71 @@ class FlatOptimizer:
         ops.sumsq(self.fp.grad[:self.n_active], out, self._part)
         return out.sqrt() * grad_scale
 
-
-class FusedAdam(FlatOptimizer):
-    """Adam with L2 weight decay folded into the gradient (utils/optimizer.py:9-52 semantics) + global-norm clip
-    (train_temporal.py:228), as ONE kernel over the flat buffer.  ``update_tail=False`` reproduces the single-GPU
-    reference where cls_head has no gradient and is therefore skipped by the optimiser.
-
-    Host/device protocol of a step: ``stage_hyper(lr)`` enqueues a one-thread kernel that receives lr / betas / eps /
-    weight decay / max_norm BY VALUE, advances the DEVICE-side step counter and derives the bias corrections from
-    it; ``launch()`` (capturable) enqueues ||g||^2 + the fused clip+Adam kernel, which read those values from device
-    memory.  There is no host staging buffer, so a host that runs many (graph-replayed) steps ahead of the GPU
-    cannot disturb a step that is still queued."""
-
-    def __init__(self, flat: FlatParams, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
-                 eps: float = 1e-8, weight_decay: float = 0.0, max_norm: Optional[float] = None,
-                 update_tail: bool = False):
-        self.fp = flat
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
-        self.max_norm = max_norm
-        self.update_tail = update_tail
-        dev = flat.flat.device
-        self.exp_avg = torch.zeros_like(flat.flat)
-        self.exp_avg_sq = torch.zeros_like(flat.flat)
-        self.hyper = torch.zeros(8, dtype=torch.float32, device=dev)
-        self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)     # the step counter the kernels use
-        self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
-        self.step_count = 0                       # host mirror of step_dev (number of steps ENQUEUED)
-        self.param_groups = [{"lr": lr}]          # minimal torch.optim surface for LR schedulers / logging
-        self.packs = getattr(flat.model, "packs", None)       # the model's packs.ModelPacks (None: a model without one)
-        self.wrote = None                         # the pack set the last launch() wrote along with the parameters, or None
-
-    def stage_hyper(self, lr: Optional[float] = None, advance: int = 1) -> None:
-        """host side of a step (NOT capturable by design: call it right before a graph replay)"""
-        if lr is not None:
-            self.lr = lr
-            self.param_groups[0]["lr"] = lr
-        self.step_count += advance
-        ops.adam_stage(self.hyper, self.step_dev, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
-                       self.max_norm if self.max_norm is not None else 0.0, advance)
-
-    def launch(self, grad_scale: float = 1.0) -> None:
-        """device side of a step (capturable): ||g||^2 then fused clip + Adam."""
-        n = self.n_active
-        g = self.fp.grad[:n]
-        use_clip = self.max_norm is not None
-        if use_clip:
-            ops.sumsq(g, self.sumsq, self._part)
-        plan = self.packs.adam_plan(self.fp.flat, n) if self.packs is not None else None
-        if plan is not None:
-            # round 6: the channel-MLP weights leave the optimiser ALSO as their two bf16 packs - the next forward's pack
-            # launch (a second read of every weight written here) disappears (the owner sees them fresh)
-            ops.adam_step_packs(plan, self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, self.hyper,
-                                self.sumsq if use_clip else None, grad_scale)
-        else:
-            ops.adam_step(self.fp.flat[:n], g, self.exp_avg[:n], self.exp_avg_sq[:n], self.hyper,
-                          self.sumsq if use_clip else None, grad_scale)
-        self.fp.touch()               # parameters changed: a backward of an EARLIER forward must not run any more
-        self.wrote = plan.pp if plan is not None else None
-        if plan is not None:
-            self.packs.mark_fresh(plan.pp, self.fp)
-
     # -- snapshot / restore (graph warm-up, tests) --------------------------------------------------------
+    def _state_tensors(self) -> List[Tensor]:
+        return [self.fp.flat, self.exp_avg, self.exp_avg_sq, self.step_dev] + [getattr(self, k) for k in self.STATE]
+
     def snapshot(self):
-        return (self.fp.flat.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.step_dev.clone(),
-                self.step_count, self.lr)
+        return [t.clone() for t in self._state_tensors()], self.step_count, self.lr
 
     def restore(self, snap) -> None:
-        flat, m, v, sd, sc, lr = snap
-        self.fp.flat.copy_(flat)
-        self.exp_avg.copy_(m)
-        self.exp_avg_sq.copy_(v)
-        self.step_dev.copy_(sd)
-        self.step_count, self.lr = sc, lr
-        self.param_groups[0]["lr"] = lr
+        saved, self.step_count, self.lr = snap
+        for t, s in zip(self._state_tensors(), saved):
+            t.copy_(s)
+        self.param_groups[0]["lr"] = self.lr
         self.fp.touch()                          # parameters changed behind the packs' back ...
-        plan = self.packs.adam_plan(self.fp.flat, self.n_active) if self.packs is not None else None
+        plan = self._pack_plan()
         if plan is not None:                     # ... so bring the optimiser-owned weight packs back in line right away: a graph
             plan.pp.refresh()                    # captured after this (graph-step warm-up) must not capture their pack launch
             self.packs.mark_fresh(plan.pp, self.fp)
 
     # -- checkpoint format of the reference: torch.optim state_dict (train_temporal.py:244,281) ------------
     def state_dict(self, model: nn.Module) -> dict:
-        """{'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]} with i = index of the parameter
+        """{'state': {i: {'step', 'exp_avg', 'exp_avg_sq', ...}}, 'param_groups': [...]} with i = index of the parameter
         in ``model.parameters()`` order - what ``torch.save({'optimizer': optimizer.state_dict()})`` of the
-        reference's Adam (utils/optimizer.py:101-164) holds.  Parameters the optimiser never updates (cls_head in
-        single-GPU training) have no state entry, as in the reference."""
+        reference's optimisers (utils/optimizer.py) holds.  Parameters the optimiser never updates (cls_head in
+        single-GPU training) have no state entry, as in the reference, and before the first step nothing has.  The updated
+        tensors are a prefix of ``fp.params``, so tensor j of FlatParams is entry j of a ``PER_TENSOR`` attribute."""
         order = {id(p): i for i, p in enumerate(model.parameters())}
         n_act = self.n_active
         state = {}
         step = int(self.step_dev.item())
-        for p, off in zip(self.fp.params, self.fp.offsets):
+        for j, (p, off) in enumerate(zip(self.fp.params, self.fp.offsets)):
             if off >= n_act or step == 0:
                 continue
             n = p.numel()
             state[order[id(p)]] = {"step": step,
                                    "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
-                                   "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
+                                   "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone(),
+                                   **{k: getattr(self, k)[j].clone() for k in self.PER_TENSOR}}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
-                 "amsgrad": False, "params": list(range(len(order)))}
+                 **self.GROUP_EXTRA, "params": list(range(len(order)))}
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd: dict, model: nn.Module) -> None:
+        """a ``PER_TENSOR`` entry may be a plain number (the reference's Lamb keeps trust_ratio = 1 that way where a norm was 0).
+        Entries of tensors beyond ``n_active`` (a checkpoint written with update_tail=True): Adam keeps their moments and
+        holds their step to the one-count rule, an optimiser with per-tensor state (LAMB) has no slot for them and reads none"""
         order = {id(p): i for i, p in enumerate(model.parameters())}
+        n_act = self.n_active
         steps = set()
+        per = {k: torch.zeros(getattr(self, k).shape) for k in self.PER_TENSOR}
         with torch.no_grad():
             self.exp_avg.zero_()
             self.exp_avg_sq.zero_()
-            for p, off in zip(self.fp.params, self.fp.offsets):
+            for j, (p, off) in enumerate(zip(self.fp.params, self.fp.offsets)):
                 st = sd["state"].get(order[id(p)])
-                if st is None:
+                if st is None or (self.PER_TENSOR and off >= n_act):
                     continue
                 n = p.numel()
                 self.exp_avg[off:off + n].copy_(st["exp_avg"].reshape(-1))
                 self.exp_avg_sq[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
+                for k, vals in per.items():
+                    if k in st:
+                        vals[j] = float(st[k])
                 steps.add(int(st["step"]))
+            for k, vals in per.items():
+                getattr(self, k).copy_(vals)
         if len(steps) > 1:
             raise ValueError(f"per-parameter step counts differ ({sorted(steps)}): the fused optimiser keeps one")
         step = steps.pop() if steps else 0
@@ -254,16 +256,51 @@ class FusedAdam(FlatOptimizer):
         self.param_groups[0]["lr"] = self.lr
 
 
+class FusedAdam(FlatOptimizer):
+    """Adam with L2 weight decay folded into the gradient (utils/optimizer.py:9-52 semantics) + global-norm clip
+    (train_temporal.py:228), as ONE kernel over the flat buffer.  ``update_tail=False`` reproduces the single-GPU
+    reference where cls_head has no gradient and is therefore skipped by the optimiser.  Checkpoint state per tensor:
+    'step', 'exp_avg', 'exp_avg_sq' (utils/optimizer.py:101-164)."""
+    HYPER = 8
+    GROUP_EXTRA = {"amsgrad": False}
+
+    def __init__(self, flat: FlatParams, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
+                 eps: float = 1e-8, weight_decay: float = 0.0, max_norm: Optional[float] = None,
+                 update_tail: bool = False):
+        super().__init__(flat, lr, betas, eps, weight_decay, max_norm, update_tail)
+
+    def _stage(self, max_norm: float, advance: int) -> None:
+        ops.adam_stage(self.hyper, self.step_dev, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                       max_norm, advance)
+
+    def _pack_plan(self):
+        return self.packs.adam_plan(self.fp.flat, self.n_active) if self.packs is not None else None
+
+    def _update(self, plan, sumsq: Optional[Tensor], grad_scale: float) -> None:
+        if plan is not None:
+            # round 6: the channel-MLP weights leave the optimiser ALSO as their two bf16 packs - the next forward's pack
+            # launch (a second read of every weight written here) disappears (the owner sees them fresh)
+            ops.adam_step_packs(plan, self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, self.hyper, sumsq,
+                                grad_scale)
+        else:
+            n = self.n_active
+            ops.adam_step(self.fp.flat[:n], self.fp.grad[:n], self.exp_avg[:n], self.exp_avg_sq[:n], self.hyper, sumsq,
+                          grad_scale)
+
+
 class FusedLamb(FlatOptimizer):
     """LAMB (utils/optimizer.py:359-499, the reference's ``--opt lamb``) + global-norm clip (train_temporal.py:228) over the
     flat buffer, per parameter tensor: the trust ratio min(||p||, clamp_value) / ||r|| of every tensor is reduced on the
     device (csrc/loss_opt.hip lamb_*: fixed-order chunked reduction, no atomics), so a step is capturable and bit-for-bit
     reproducible.  Weight decay is added to the step r, not to the gradient (unlike Adam).  ``adam=True`` (what the
     reference's scripts pass) does not apply the trust ratio but still records weight_norm / adam_norm / trust_ratio, as
-    the reference's state does.  Host/device protocol as FusedAdam (``stage_hyper`` then ``launch``).
+    the reference's state does: they join 'step', 'exp_avg', 'exp_avg_sq' in the checkpoint as 0-d tensors.
 
-    LAMB writes no derived weight packs: ``wrote`` stays None, so a model with the bf16 channel MLP re-derives its packs
-    in the next forward (inside a captured graph too)."""
+    LAMB writes no derived weight packs: ``wrote`` stays None and ``restore`` marks nothing fresh, so a model with the bf16
+    channel MLP re-derives its packs in the next forward (inside a captured graph too)."""
+    HYPER = 16
+    STATE = ("norms",)
+    PER_TENSOR = ("weight_norm", "adam_norm", "trust_ratio")
 
     def __init__(self, flat: FlatParams, lr: float = 1e-3, betas: Tuple[float, float] = (0.9, 0.999),
                  eps: float = 1e-6, weight_decay: float = 0.0, clamp_value: float = 10.0, adam: bool = False,
@@ -278,121 +315,25 @@ class FusedLamb(FlatOptimizer):
             raise ValueError(f"Invalid weight_decay value: {weight_decay}")
         if clamp_value < 0.0:
             raise ValueError(f"Invalid clamp value: {clamp_value}")
-        self.fp = flat
-        self.lr, self.betas, self.eps, self.weight_decay = lr, tuple(betas), eps, weight_decay
+        super().__init__(flat, lr, tuple(betas), eps, weight_decay, max_norm, update_tail)
         self.clamp_value, self.adam, self.debias = clamp_value, adam, debias
-        self.max_norm = max_norm
-        self.update_tail = update_tail
-        dev = flat.flat.device
-        self.exp_avg = torch.zeros_like(flat.flat)
-        self.exp_avg_sq = torch.zeros_like(flat.flat)
-        self.hyper = torch.zeros(16, dtype=torch.float32, device=dev)
-        self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
-        n_act = self.n_active
-        # the tensors the optimiser updates (FlatParams.offsets are ordered; the tail starts at n_head)
+        n_act, dev = self.n_active, flat.flat.device
+        # the tensors the optimiser updates (FlatParams.offsets are ordered; the tail starts at n_head): a prefix of flat.params
         self.members = [k for k, off in enumerate(flat.offsets) if off < n_act]
         self.plan = ops.LambPlan([flat.offsets[k] for k in self.members],
                                  [flat.params[k].numel() for k in self.members], n_act, dev)
         nt = len(self.members)
+        assert self.members == list(range(nt)), "state_dict / load_state_dict index the norms by position in flat.params"
         self.norms = torch.zeros(3 * nt, dtype=torch.float32, device=dev)
         self.weight_norm, self.adam_norm, self.trust_ratio = self.norms[:nt], self.norms[nt:2 * nt], self.norms[2 * nt:]
-        self.step_count = 0
-        self.param_groups = [{"lr": lr}]
-        self.packs = getattr(flat.model, "packs", None)
-        self.wrote = None                         # LAMB never writes the weight packs
 
-    def stage_hyper(self, lr: Optional[float] = None, advance: int = 1) -> None:
-        """host side of a step (NOT capturable by design: call it right before a graph replay)"""
-        if lr is not None:
-            self.lr = lr
-            self.param_groups[0]["lr"] = lr
-        self.step_count += advance
+    def _stage(self, max_norm: float, advance: int) -> None:
         ops.lamb_stage(self.hyper, self.step_dev, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
-                       self.max_norm if self.max_norm is not None else 0.0, self.clamp_value, self.debias, advance)
+                       max_norm, self.clamp_value, self.debias, advance)
 
-    def launch(self, grad_scale: float = 1.0) -> None:
-        """device side of a step (capturable): ||g||^2 (with clipping), then the LAMB launches"""
-        use_clip = self.max_norm is not None
-        if use_clip:
-            ops.sumsq(self.fp.grad[:self.n_active], self.sumsq, self._part)
-        ops.lamb_step(self.plan, self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, self.hyper,
-                      self.sumsq if use_clip else None, self.norms, grad_scale, self.adam)
-        self.fp.touch()
-        self.wrote = None
-
-    # -- snapshot / restore (graph warm-up, tests) --------------------------------------------------------
-    def snapshot(self):
-        return (self.fp.flat.clone(), self.exp_avg.clone(), self.exp_avg_sq.clone(), self.step_dev.clone(),
-                self.norms.clone(), self.step_count, self.lr)
-
-    def restore(self, snap) -> None:
-        flat, m, v, sd, norms, sc, lr = snap
-        self.fp.flat.copy_(flat)
-        self.exp_avg.copy_(m)
-        self.exp_avg_sq.copy_(v)
-        self.step_dev.copy_(sd)
-        self.norms.copy_(norms)
-        self.step_count, self.lr = sc, lr
-        self.param_groups[0]["lr"] = lr
-        self.fp.touch()                          # no pack is marked fresh: the next forward re-derives what it needs
-
-    # -- checkpoint format of the reference's Lamb (a torch.optim.Optimizer state_dict) ---------------------
-    def state_dict(self, model: nn.Module) -> dict:
-        """{'state': {i: {'step', 'exp_avg', 'exp_avg_sq', 'weight_norm', 'adam_norm', 'trust_ratio'}}, 'param_groups':
-        [{'lr', 'betas', 'eps', 'weight_decay', 'params'}]}, i = index in ``model.parameters()`` order; the norms are 0-d
-        tensors.  Tensors the optimiser does not update have no entry."""
-        order = {id(p): i for i, p in enumerate(model.parameters())}
-        state = {}
-        step = int(self.step_dev.item())
-        if step > 0:
-            for j, k in enumerate(self.members):
-                p, off = self.fp.params[k], self.fp.offsets[k]
-                n = p.numel()
-                state[order[id(p)]] = {"step": step,
-                                       "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
-                                       "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone(),
-                                       "weight_norm": self.weight_norm[j].clone(),
-                                       "adam_norm": self.adam_norm[j].clone(),
-                                       "trust_ratio": self.trust_ratio[j].clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
-                 "params": list(range(len(order)))}
-        return {"state": state, "param_groups": [group]}
-
-    def load_state_dict(self, sd: dict, model: nn.Module) -> None:
-        """also reads a checkpoint of the reference's Lamb, whose trust_ratio is the plain number 1 where a norm was 0"""
-        order = {id(p): i for i, p in enumerate(model.parameters())}
-        steps = set()
-        nt = len(self.members)
-        norms = torch.zeros(3 * nt, dtype=torch.float32)
-        with torch.no_grad():
-            self.exp_avg.zero_()
-            self.exp_avg_sq.zero_()
-            for j, k in enumerate(self.members):
-                p, off = self.fp.params[k], self.fp.offsets[k]
-                st = sd["state"].get(order[id(p)])
-                if st is None:
-                    continue
-                n = p.numel()
-                self.exp_avg[off:off + n].copy_(st["exp_avg"].reshape(-1))
-                self.exp_avg_sq[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
-                for q, key in enumerate(("weight_norm", "adam_norm", "trust_ratio")):
-                    if key in st:
-                        norms[q * nt + j] = float(st[key])
-                steps.add(int(st["step"]))
-            self.norms.copy_(norms)
-        if len(steps) > 1:
-            raise ValueError(f"per-parameter step counts differ ({sorted(steps)}): the fused optimiser keeps one")
-        step = steps.pop() if steps else 0
-        self.step_dev.fill_(step)
-        self.step_count = step
-        g = sd.get("param_groups", [{}])[0]
-        self.lr = g.get("lr", self.lr)
-        self.betas = tuple(g.get("betas", self.betas))
-        self.eps = g.get("eps", self.eps)
-        self.weight_decay = g.get("weight_decay", self.weight_decay)
-        self.param_groups[0]["lr"] = self.lr
+    def _update(self, plan, sumsq: Optional[Tensor], grad_scale: float) -> None:
+        ops.lamb_step(self.plan, self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, self.hyper, sumsq, self.norms,
+                      grad_scale, self.adam)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -659,18 +600,54 @@ def train_step(model: nn.Module, opt: FlatOptimizer, xx: Tensor, yy: Tensor, msk
     """one optimisation step; returns (loss, pred) as device tensors - no host sync.  cls / cls_weight / metrics: see
     ``rollout_total`` and ``StepMetrics``; the returned loss stays the relative-L2 rollout loss."""
     check_cls_args(opt, cls, cls_weight)
+
+    def run():
+        return rollout_total(model, xx, yy, msk, T_bundle, noise_scale, None, cls, cls_weight, metrics)
+
+    out = _forward_backward(opt, run, reducer)
+    _optimise(opt, functools.partial(opt.step, lr), grad_scale, metrics)
+    return out
+
+
+def _forward_backward(opt: FlatOptimizer, run: Callable[[], Tuple[Tensor, Tensor, Tensor]], reducer=None):
+    """first half of THE training step, eager or under capture: gradients of ``run()``'s (loss, pred, total) into the zeroed
+    flat buffer, reduced over the ranks by a hook-driven ``reducer``; returns (loss, pred) detached"""
     opt.zero_grad()
     if reducer is not None:
         reducer.begin_step()
-    loss, pred, total = rollout_total(model, xx, yy, msk, T_bundle, noise_scale, None, cls, cls_weight, metrics)
+    loss, pred, total = run()
     total.backward()
     clear_grad_packs()
     if reducer is not None:
         reducer.finish()
-    opt.step(lr, grad_scale)
+    return loss.detach(), pred.detach()
+
+
+def _optimise(opt: FlatOptimizer, update: Callable[[float], None], grad_scale: float,
+              metrics: Optional[StepMetrics]) -> None:
+    """second half: the optimiser, then the step's scalars join the device accumulator (the last launch of a step).
+    ``update(grad_scale)`` is the optimiser call: ``opt.step`` bound to its lr (stages, then launches) in an eager step,
+    ``opt.launch`` where ``opt.stage_hyper`` has run already because it is no part of a capture"""
+    update(grad_scale)
     if metrics is not None:
         metrics.accumulate(opt, grad_scale)
-    return loss.detach(), pred.detach()
+
+
+@contextlib.contextmanager
+def trial_state(opt: FlatOptimizer, metrics: Optional[StepMetrics] = None, rng_device=None):
+    """The steps taken inside are NOT training steps (graph warm-up, the trial steps of ``make_dp_step``): parameters,
+    optimiser state and the metrics accumulator are put back when the block ends, and with ``rng_device`` the in-kernel noise
+    generator of that device as well.  A block that raises restores nothing: what raises here is a failed stream capture, and
+    the restoring launches must not go to streams that ``_end_stray_captures`` has yet to take out of capture mode."""
+    snap = opt.snapshot()
+    msnap = metrics.snapshot() if metrics is not None else None
+    rng = ops.rng_state(rng_device).clone() if rng_device is not None else None
+    yield
+    opt.restore(snap)
+    if msnap is not None:
+        metrics.restore(msnap)
+    if rng is not None:
+        ops.rng_state(rng_device).copy_(rng)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -721,23 +698,20 @@ class _GraphStep:
                              self.cls_weight, self.metrics)
 
     def _warm_up(self, n: int, body: Callable[[], None], settle: bool = False) -> None:
-        """eager warm-up on a side stream (allocator + lazy inits).  The warm-up iterations are NOT training steps: parameters,
-        Adam moments and the step counter are restored afterwards (a fine-tune of a pretrained checkpoint must not receive
-        unscheduled full-lr updates before its first replay)"""
-        snap = self.opt.snapshot()
-        msnap = self.metrics.snapshot() if self.metrics is not None else None        # ... and they are not logged either
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(n):
-                body()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        if settle:
-            _retire_collective_watchdog_work()
-        self.opt.restore(snap)
-        if msnap is not None:
-            self.metrics.restore(msnap)
+        """eager warm-up on a side stream (allocator + lazy inits): ``n`` times what a replay does, stage_hyper then ``body``.
+        The warm-up iterations are NOT training steps (a fine-tune of a pretrained checkpoint must not receive unscheduled
+        full-lr updates before its first replay), and they are not logged either"""
+        with trial_state(self.opt, self.metrics):
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(n):
+                    self.opt.stage_hyper(self.opt.lr)
+                    body()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            if settle:
+                _retire_collective_watchdog_work()
 
     def _replay(self, lr: Optional[float], run: Callable[[], None]) -> Tensor:
         """the graphs hold no pack launch for the set their Adam writes (it was fresh at the capture): refresh it first if
@@ -783,30 +757,18 @@ class GraphedTrainStep(_GraphStep):
             self.reducer.skip_zero_tail = False
         self.grad_scale = grad_scale
         self.T_bundle, self.noise_scale = T_bundle, noise_scale
-        self._warm_up(warmup, lambda: self._body(stage=True), settle=self.reducer is not None)
+        self._warm_up(warmup, self._body, settle=self.reducer is not None)
         self.graph = torch.cuda.CUDAGraph()
         opt.zero_grad()
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            self.loss, self.pred = self._body(stage=False)
+            self.loss, self.pred = self._body()
         self.owned = opt.wrote
         self.warmup_steps = warmup
 
-    def _body(self, stage: bool):
-        opt = self.opt
-        if stage:
-            opt.stage_hyper(opt.lr)
-        opt.zero_grad()
-        if self.reducer is not None:
-            self.reducer.begin_step()
-        loss, pred, total = self._rollout()
-        total.backward()
-        clear_grad_packs()
-        if self.reducer is not None:
-            self.reducer.finish()
-        opt.launch(self.grad_scale)
-        if self.metrics is not None:             # last node of the graph: the step's scalars join the device accumulator
-            self.metrics.accumulate(opt, self.grad_scale)
-        return loss.detach(), pred.detach()
+    def _body(self):
+        out = _forward_backward(self.opt, self._rollout, self.reducer)
+        _optimise(self.opt, self.opt.launch, self.grad_scale, self.metrics)
+        return out
 
     def replay(self, lr: Optional[float] = None) -> Tensor:
         return self._replay(lr, self.graph.replay)
@@ -846,12 +808,9 @@ class SegmentedTrainStep(_GraphStep):
         self.cut_at = sorted({norm(reducer.first_stage_of_bucket(k)) for k in self.bwd_buckets} - {0})
 
         def eager_step():
-            opt.stage_hyper(opt.lr)
             for fn in self._segment_fns():
                 fn()
-            opt.launch(self.grad_scale)
-            if metrics is not None:
-                metrics.accumulate(opt, self.grad_scale)
+            _optimise(opt, opt.launch, self.grad_scale, metrics)
 
         reducer.detach()
         try:
@@ -865,9 +824,7 @@ class SegmentedTrainStep(_GraphStep):
                 self.graphs.append(g)
             self.opt_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.opt_graph, pool=pool, capture_error_mode="thread_local"):
-                opt.launch(self.grad_scale)
-                if metrics is not None:          # the last segment: after the optimiser
-                    metrics.accumulate(opt, self.grad_scale)
+                _optimise(opt, opt.launch, self.grad_scale, metrics)          # the last segment
             self.owned = opt.wrote
         finally:
             reducer.attach()
@@ -891,18 +848,18 @@ class SegmentedTrainStep(_GraphStep):
                 return leaf
             return lat
 
-        def first():
-            self.opt.zero_grad()
+        def cut_rollout():
             self.model._boundary_hook = hook
             calls[0] = 0
             try:
-                loss, pred, total = self._rollout()
+                out = self._rollout()
             finally:
                 self.model._boundary_hook = None
             assert len(cuts) == len(self.cut_at), f"expected {len(self.cut_at)} graph cuts, the forward made {len(cuts)}"
-            total.backward()
-            clear_grad_packs()
-            self.loss, self.pred = loss.detach(), pred.detach()
+            return out
+
+        def first():
+            self.loss, self.pred = _forward_backward(self.opt, cut_rollout)
 
         yield first
         # one further segment per cut, from the last cut to the first
@@ -998,8 +955,10 @@ def make_dp_step(model: nn.Module, opt: FlatOptimizer, reducer, xx: Tensor, yy: 
         return chain(f"one-graph capture failed: backend '{backend}' collectives cannot be recorded in a hipGraph (RCCL only)")
     one, err = None, None
     try:
-        one = GraphedTrainStep(model, opt, xx, yy, msk, T_bundle=T_bundle, noise_scale=noise_scale, warmup=max(1, warmup),
-                               reducer=reducer, capture_collectives=True, cls=cls, cls_weight=cls_weight, metrics=metrics)
+        with trial_state(opt, metrics, xx.device):
+            one = GraphedTrainStep(model, opt, xx, yy, msk, T_bundle=T_bundle, noise_scale=noise_scale,
+                                   warmup=max(1, warmup), reducer=reducer, capture_collectives=True, cls=cls,
+                                   cls_weight=cls_weight, metrics=metrics)
     except Exception as e:                                    # an RCCL build / driver that cannot capture its collectives
         err = f"{type(e).__name__}: {e}"[:160]
         _end_stray_captures([torch.cuda.current_stream(), reducer.stream])
@@ -1010,25 +969,17 @@ def make_dp_step(model: nn.Module, opt: FlatOptimizer, reducer, xx: Tensor, yy: 
     if int(ok.item()) == 0:
         del one
         return chain("one-graph capture failed" + (f" here ({err})" if err else " on another rank"))
-    snap = opt.snapshot()
-    msnap = metrics.snapshot() if metrics is not None else None          # the trial steps are not training steps
-    rng = ops.rng_state(xx.device).clone()
     grads = []
     for mode in ("eager", "graph"):
-        opt.restore(snap)
-        ops.rng_state(xx.device).copy_(rng)
-        reducer.skip_zero_tail = False                        # (as the capture: the cls_head tail is always reduced)
-        if mode == "eager":
-            train_step(model, opt, one.xx, one.yy, one.msk, T_bundle=T_bundle, noise_scale=noise_scale, lr=opt.lr,
-                       reducer=reducer, grad_scale=reducer.grad_scale, cls=one.cls, cls_weight=cls_weight, metrics=metrics)
-        else:
-            one.replay(opt.lr)
-        torch.cuda.synchronize()
-        grads.append(opt.fp.grad[:opt.n_active].clone())
-    opt.restore(snap)
-    if msnap is not None:
-        metrics.restore(msnap)
-    ops.rng_state(xx.device).copy_(rng)
+        with trial_state(opt, metrics, xx.device):            # both from the same state, which is left as found
+            reducer.skip_zero_tail = False                    # (as the capture: the cls_head tail is always reduced)
+            if mode == "eager":
+                train_step(model, opt, one.xx, one.yy, one.msk, T_bundle=T_bundle, noise_scale=noise_scale, lr=opt.lr,
+                           reducer=reducer, grad_scale=reducer.grad_scale, cls=one.cls, cls_weight=cls_weight, metrics=metrics)
+            else:
+                one.replay(opt.lr)
+            torch.cuda.synchronize()
+            grads.append(opt.fp.grad[:opt.n_active].clone())
     same_modes = bool(torch.equal(grads[0], grads[1]))
     cs = _grad_checksum(grads[1])
     verdict = torch.tensor([1 if same_modes else 0], device=xx.device, dtype=torch.int64)

@@ -221,9 +221,9 @@ def test_load_components_warns_for_absent_known_component():
 
 
 def test_dpot_tune_switchboard(built_lib, monkeypatch):
-    """round 6: ONE environment variable (DPOT_TUNE="key=val,...") behind every fallback selector.  The Python side parses it per
-    call and rejects unknown keys; the C side (dpot_tune) parses the same string once per process - checked in a child process
-    because this one may already have cached it"""
+    """round 6: ONE environment variable (DPOT_TUNE="key=val,...") behind every fallback selector.  The Python side looks at it
+    per call (parsing it when its string has changed) and rejects unknown keys; the C side (dpot_tune) parses the same string
+    once per process - checked in a child process because this one may already have cached it - and trims spaces as Python does"""
     import subprocess
     import sys
     from dpot_amd import ops
@@ -236,11 +236,17 @@ def test_dpot_tune_switchboard(built_lib, monkeypatch):
     with pytest.raises(ValueError):
         ops.tune("mixer")
     code = ("from dpot_amd import _lib; l = _lib.load(); "
-            "print(l.dpot_tune(b'bf16p_bd', 1), l.dpot_tune(b'panel', 1), l.dpot_tune(b'wgrad_gauss', 1), l.dpot_tune(b'pan', 7))")
-    env = dict(os.environ, DPOT_TUNE="bf16p_bd=0,wgrad_gauss=0")
-    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-400:]
-    assert out.stdout.split() == ["0", "1", "0", "7"], out.stdout
+            "print(l.dpot_tune(b'bf16p_bd', 1), l.dpot_tune(b'panel', 1), l.dpot_tune(b'wgrad_gauss', 1), l.dpot_tune(b'pan', 7), "
+            "l.dpot_tune(b'gn_fuse', 1))")
+    # the second value is spaced the way ops.tune() accepts it: both sides must read the same keys from it
+    for value, want in (("bf16p_bd=0,wgrad_gauss=0", ["0", "1", "0", "7", "1"]),
+                        ("panel=0, gn_fuse=0 ,\twgrad_gauss=0", ["1", "0", "0", "7", "0"])):
+        env = dict(os.environ, DPOT_TUNE=value)
+        out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True)
+        assert out.returncode == 0, out.stderr[-400:]
+        assert out.stdout.split() == want, (value, out.stdout)
+        monkeypatch.setenv("DPOT_TUNE", value)
+        assert [str(ops.tune(k)) for k in ("bf16p_bd", "panel", "wgrad_gauss", "gn_fuse")] == want[:3] + want[4:]
     # no other DPOT_* variable is read by the package or the library any more (bench.py has its own DPOT_BENCH_* / DPOT_DP_*)
     allowed = {"DPOT_TUNE", "DPOT_HIP_LIB", "DPOT_GEMM_PRECISION", "DPOT_MLP_PRECISION"}
     for dirpath, _, files in os.walk(os.path.join(ROOT, "dpot_amd")):

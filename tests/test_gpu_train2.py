@@ -761,3 +761,61 @@ def test_adam_step_packs_at_the_smallest_weight(guarded):
     assert (pb[:n_active].cpu().double() - pr).abs().max().item() <= 2e-3 * lr
     assert_close(mb[:n_active], mr, "exp_avg")
     assert_close(vb[:n_active], vr, "exp_avg_sq")
+
+
+# ------------------------------------------------------------------------------------------------------
+def _shared_step_run(kind):
+    """mini model, batch 2, two AR steps (every parameter gradient accumulated once), clip on, metrics attached, the weighted
+    classification loss training cls_head.  max_norm = 0.5 lies below the gradient norm of these steps
+    (3.3 and 1.6 for the relative-L2 part alone in oracle.dpot_ref.train_step): the clip rescales"""
+    from dpot_amd import StepMetrics
+    from dpot_amd.train import FlatParams, FusedAdam, FusedLamb
+    m, cfg = build(R.MINI, salt=5)
+    xx, yy, msk = _batch(cfg, 2, T_ar=2)
+    cls = (torch.arange(2, device="cuda") % cfg.n_cls).view(2, 1)
+    args = dict(lr=1e-3, betas=(0.9, 0.9), weight_decay=1e-6, max_norm=0.5, update_tail=True)
+    opt = FusedAdam(FlatParams(m), **args) if kind == "adam" else FusedLamb(FlatParams(m), debias=True, **args)
+    met = StepMetrics("cuda", 2)
+    return m, opt, met, (xx, yy, msk), dict(cls=cls, cls_weight=0.5, metrics=met)
+
+
+def _shared_step_state(opt, met):
+    torch.cuda.synchronize()
+    st = {"flat": opt.fp.flat, "exp_avg": opt.exp_avg, "exp_avg_sq": opt.exp_avg_sq, "step_dev": opt.step_dev, "acc": met.acc[0]}
+    if hasattr(opt, "norms"):
+        st["norms"] = opt.norms
+    return {k: v.clone() for k, v in st.items()}, opt.step_count, opt.lr
+
+
+@pytest.mark.parametrize("kind", ["adam", "lamb"])
+def test_eager_and_replayed_steps_share_one_body_and_warm_up_is_undone(kind):
+    """train_step, the warm-up of GraphedTrainStep and its captured graph run ONE step body (train._forward_backward +
+    train._optimise), and warm-up steps sit inside train.trial_state.  (a) two eager steps and two replays from the same seeded
+    start leave parameters, moments, the step counter, LAMB's norms and the metrics accumulator bit-identical; (b) building a
+    graph step with warmup=2 on the TRAINED state (non-zero moments, step 2, a filled accumulator) leaves all of them as they
+    were.  Cells other tests hold already: Adam's warm-up from the zero state (test_graph_warmup_does_not_train), an unlogged
+    warm-up with cls_weight = 0 (test_gpu_metrics.test_metrics_observe_without_changing_the_step_and_sum_up), LAMB replay
+    against eager at T_ar = 1 without metrics (test_gpu_lamb.test_graph_replay_bit_identical_to_eager)."""
+    from dpot_amd.train import GraphedTrainStep, train_step
+    lrs = (1e-3, 2e-3)
+    m, opt, met, batch, kw = _shared_step_run(kind)
+    for lr in lrs:
+        train_step(m, opt, *batch, lr=lr, **kw)
+    eager = _shared_step_state(opt, met)
+    assert float(opt.grad_norm()) > opt.max_norm, "the clip must be active, or sumsq reaches the update unused"
+    GraphedTrainStep(m, opt, *batch, warmup=2, **kw)                     # (b)
+    after = _shared_step_state(opt, met)
+    assert after[1:] == eager[1:] == (2, lrs[-1])
+    for k, v in eager[0].items():
+        assert torch.equal(v, after[0][k]), f"{k} changed by building a graph step"
+    assert int(eager[0]["step_dev"]) == 2 and float(eager[0]["exp_avg"].abs().max()) > 0.0
+
+    m2, opt2, met2, batch2, kw2 = _shared_step_run(kind)                 # (a)
+    g = GraphedTrainStep(m2, opt2, *batch2, warmup=2, **kw2)
+    for lr in lrs:
+        g.replay(lr)
+    replayed = _shared_step_state(opt2, met2)
+    assert replayed[1:] == eager[1:]
+    for k, v in eager[0].items():
+        assert torch.equal(v, replayed[0][k]), f"{k}: replayed steps differ from eager steps"
+    assert met2.read()["opt_steps"] == 2 and met2.read()["ar_steps"] == 4
