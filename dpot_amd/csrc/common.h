@@ -41,11 +41,16 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // 1e-4 parity tolerance.  With the tail in hand
 //     gelu(x) = x Phi(x) = max(x, 0) - |x| Phi(-|x|),      Phi(x) = x >= 0 ? 1 - Phi(-|x|) : Phi(-|x|)
 // (no cancellation in the left tail; beyond |x| = 6.5 the clamped tail, 4e-11, is below fp32 resolution of the result).
-// Cost: 11 VALU instructions + one v_exp_f32 (quarter rate) = 15 issue slots - the previous Abramowitz-Stegun 7.1.26
-// form needed a reciprocal AND an exponential plus a compare / select and was 3x less accurate.  This matters: the
+// Cost: 12 VALU instructions (one of them gelu_relu's subtraction) + one v_exp_f32 (quarter rate: 4) = 16 issue slots -
+// the previous Abramowitz-Stegun 7.1.26 form needed a reciprocal AND an exponential plus a compare / select and was 3x
+// less accurate.  This matters: the
 // per-pixel tail kernels (csrc/tail.hip) are bound by VALU ISSUE, 33.5 M GELUs per launch at DPOT-Tiny B=32.
 // The clamp and the max use gfx950's v_minimum3_f32 / v_maximum3_f32 (IEEE-754-2019 minimum / maximum): unlike
 // v_min / v_max they PROPAGATE NaN, so a diverged run still surfaces as NaN loss (and they take the |x| modifier).
+// Every branch of act_fwd below propagates NaN as well (ReLU is written x < 0 ? 0 : x for that), and gelu(-inf) is NaN
+// as in torch (gelu_relu below).
+// tests/act_ref.py restates these functions in float32 numpy; tests/test_cpu_activations.py holds the restatement to the
+// bounds above and tests/test_gpu_activations.py holds every fused call site to it, point by point against float64.
 // (Packed v_pk_fma_f32 would halve the polynomial's slots, but packed fp32 is an anti-lever beside MFMAs -
 // MI355X_MICROARCH "price of one filler" - and the compiler scalarises most of it there anyway; measured: no gain.)
 __device__ __forceinline__ float normal_tail(float ax) {   // Phi(-ax), 0 <= ax <= 6.5
@@ -60,9 +65,12 @@ __device__ __forceinline__ float normal_tail(float ax) {   // Phi(-ax), 0 <= ax 
   return __builtin_amdgcn_exp2f(-r);
 }
 __device__ __forceinline__ float gelu_clamp_abs(float x) { return __builtin_elementwise_minimum(__builtin_fabsf(x), 6.5f); }
+// max(x, 0) written x - min(x, 0): the same bits for every finite x and for NaN / +inf, and NaN (-inf + inf) at -inf,
+// where torch's x * 0.5 * (1 + erf(x / sqrt 2)) is -inf * 0 = NaN as well (one more VALU slot than the max)
+__device__ __forceinline__ float gelu_relu(float x) { return x - __builtin_elementwise_minimum(x, 0.0f); }
 __device__ __forceinline__ float gelu_fwd(float x) {
   const float ax = gelu_clamp_abs(x);
-  return fmaf(-ax, normal_tail(ax), __builtin_elementwise_maximum(x, 0.0f));
+  return fmaf(-ax, normal_tail(ax), gelu_relu(x));
 }
 // cdf = Phi(x), gauss = exp(-x^2 / 2) (the Gaussian of the derivative)
 __device__ __forceinline__ void gelu_parts(float x, float& cdf, float& gauss) {
@@ -80,7 +88,7 @@ __device__ __forceinline__ void gelu_val_der(float x, float& val, float& der) {
   const float ax = gelu_clamp_abs(x);
   const float e = normal_tail(ax);
   const float phi = __builtin_amdgcn_exp2f(fmaf(x * x, -0.72134752044448170368f, -1.32574806473615975284f));
-  val = fmaf(-ax, e, __builtin_elementwise_maximum(x, 0.0f));
+  val = fmaf(-ax, e, gelu_relu(x));
   der = fmaf(x, phi, x >= 0.f ? 1.0f - e : e);
 }
 
@@ -92,7 +100,7 @@ __device__ __forceinline__ float act_fwd(int act, float x) {
     case DPOT_ACT_GELU: return gelu_fwd(x);
     case DPOT_ACT_TANH: return tanhf(x);
     case DPOT_ACT_SIGMOID: return 1.0f / (1.0f + expf(-x));
-    case DPOT_ACT_RELU: return x > 0.f ? x : 0.f;
+    case DPOT_ACT_RELU: return x < 0.f ? 0.f : x;   // NaN -> NaN and -0 -> -0, as torch.relu (x > 0 ? x : 0 made NaN a 0)
     case DPOT_ACT_LEAKY_RELU: return x > 0.f ? x : 0.1f * x;
     case DPOT_ACT_SOFTPLUS: return x > 20.f ? x : log1pf(expf(x));
     case DPOT_ACT_ELU: return x > 0.f ? x : expm1f(x);
