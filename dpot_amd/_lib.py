@@ -81,6 +81,13 @@ class AfnoPackJob(C.Structure):
     _fields_ = [("w", c_fp), ("b", c_fp), ("wbig", c_fp), ("bbig", c_fp), ("fwd", c_fp), ("bwd", c_fp)]
 
 
+class WgradBlock(C.Structure):
+    """mirror of struct dpot_wgrad_block"""
+    _fields_ = [("afno_ws", c_fp), ("dw1", c_fp), ("db1", c_fp), ("dw2", c_fp), ("db2", c_fp),
+                ("mlp_ws", c_fp), ("dW2", c_fp), ("dfb2", c_fp), ("dW1", c_fp), ("dfb1", c_fp),
+                ("gn_part", c_fp * 2), ("gn_dgamma", c_fp * 2), ("gn_dbeta", c_fp * 2)]
+
+
 class SampleDesc(C.Structure):
     """mirror of struct dpot_sample_desc"""
     _fields_ = [("data", c_fp), ("H", C.c_int32), ("W", C.c_int32), ("T", C.c_int32), ("C", C.c_int32),
@@ -197,9 +204,19 @@ SIGNATURES = {
     "dpot_mlp_wgrad2": (c_i, [c_fp] * 4 + [c_i] * 3 + [c_fp] * 5 + [c_i, c_fp]),
     "dpot_afno_wgrad2_splitk": (c_i, [c_i] * 3),
     "dpot_afno_wgrad2_ws_elems": (c_i64, [c_i] * 3),
+    "dpot_afno_wgrad2_splits12": (c_i, [c_i] * 2),
     "dpot_afno_wgrad2": (c_i, [c_fp] * 4 + [c_i] * 4 + [c_fp] * 5 + [c_i, c_fp]),
     "dpot_block_finalize": (c_i, [c_fp, c_i, c_i, c_i] + [c_fp] * 4 + [c_fp, c_i, c_i, c_i] + [c_fp] * 4 + [c_fp] * 3
                             + [c_i, c_i, c_i] + [c_fp] * 4 + [c_i, c_fp]),
+    "dpot_wgrad_batch_max_blocks": (c_i, []),
+    "dpot_tn_split_range": (c_i, [c_i] * 3 + [C.POINTER(c_i)] * 2),
+    "dpot_mlp_wgrad_batch_splitk": (c_i, [c_i] * 4),
+    "dpot_mlp_wgrad_batch_ws_elems": (c_i64, [c_i] * 4),
+    "dpot_mlp_wgrad_batch": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i] * 4 + [c_fp, c_i, c_fp]),
+    "dpot_afno_wgrad_batch_plan": (c_i, [c_i] * 4 + [C.POINTER(c_i)] * 2),
+    "dpot_afno_wgrad_batch_ws_elems": (c_i64, [c_i] * 4),
+    "dpot_afno_wgrad_batch": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i] * 5 + [c_fp] + [c_i] * 3 + [c_fp]),
+    "dpot_wgrad_batch_finalize": (c_i, [C.POINTER(WgradBlock)] + [c_i] * 11 + [c_fp]),
     "dpot_bf16_pack_both_supported": (c_i, [c_i, c_i]),
     "dpot_bf16_pack_both": (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),
     "dpot_bf16_pack_both_norm": (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_fp]),

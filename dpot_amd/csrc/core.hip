@@ -43,7 +43,9 @@ int tune(const char* key, int dflt) {
 /* 0.2.6: round 6 ABI - dpot_adam_step_packs (Adam that writes the bf16 weight packs); dpot_gemm_bf16p_pair back to its 0.2.0
  * argument list (the row-form operand / transposed-output arguments of 0.2.5 are gone with the kernels they selected);
  * dpot_afno_fused_bwd removed; every fallback selector behind DPOT_TUNE
- * 264: dpot_spectral_resize, dpot_spectral_resize_pad (csrc/resize.hip) */
-extern "C" int dpot_version(void) { return 265; }
+ * 264: dpot_spectral_resize, dpot_spectral_resize_pad (csrc/resize.hip)
+ * 266: dpot_mlp_wgrad_batch, dpot_afno_wgrad_batch, dpot_wgrad_batch_finalize and their queries (csrc/gemm_tn.hip): the weight
+ * gradients of several DPOT blocks per launch */
+extern "C" int dpot_version(void) { return 266; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

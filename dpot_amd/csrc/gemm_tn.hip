@@ -28,24 +28,31 @@ namespace dpot {
 
 typedef float tn_f32x4 __attribute__((ext_vector_type(4)));
 
-struct TnArgs {
+// one operand set of a launch: `nper` problems that differ by the batch strides (sA, sB) only
+struct TnSet {
   const float* A;        // [T, lda]  (columns = output rows n1)
   const float* B;        // [T, ldb]  (columns = output columns n2)
-  const float* A2;       // problems zb >= batch1 take their operands from (A2, B2) (same strides): the two weight
-  const float* B2;       //   gradients of an AFNO block in one launch (dpot_afno_wgrad2)
-  int batch1;
-  int cs_of2;            // column-sum operand of the second problem set (cs_of serves the first)
-  int csL;               // length of a column-sum partial slot (0: N1 or N2 by cs_of)
+  int cs_of;             // 0: no column sums, 1: of A (length N1), 2: of B (length N2)
+  int pad_;
+};
+// problem table of a launch.  A GROUP is what one reduction finishes (a DPOT block's channel MLP: two sets of one problem;
+// its AFNO layer pair: two sets of nb strided problems) - `batch` problems with a workspace of their own, ws_group floats
+// apart.  The per-block entry points launch one group; dpot_mlp_wgrad_batch / dpot_afno_wgrad_batch up to TN_MAXSETS / 2.
+// 32 sets (DPOT-M: 12 blocks = 24 sets) keep the kernel arguments at 0.9 KB
+constexpr int TN_MAXSETS = 32;
+struct TnArgs {
   int lda, ldb;
-  long long sA, sB;      // batch strides (elements)
-  int N1, N2, T, batch;
+  long long sA, sB;      // batch strides inside a set (elements)
+  int nper;              // problems per set
+  int csL;               // length of a column-sum partial slot (0: N1 or N2 by cs_of)
+  int N1, N2, T, batch;  // batch: problems per group
   int tiles1, tiles2, splits, slabs_per_split;
-  float* ws;             // [split][batch][N1][N2] (+ [split][batch][L] column-sum partials behind)
-  int cs_of;             // 0: none, 1: column sums of A (length N1), 2: of B (length N2)
-  // round 5: the AFNO weight gradient dW = S^H dO as THREE real 128 x 128 products instead of the four blocks of the
+  float* ws;             // per group [split][batch][N1][N2] (+ [split][batch][L] column-sum partials behind)
+  long long ws_group;    // floats between the workspaces of consecutive groups
+  // the AFNO weight gradient dW = S^H dO as THREE real 128 x 128 products instead of the four blocks of the
   // 256 x 256 real product (bs == 128): with A = [Ar | Ai], B = [Br | Bi] (columns)
   //   P1 = Ar^T Br, P2 = Ai^T Bi, P3 = (Ar + Ai)^T (Bi - Br);   dWr = P1 + P2,  dWi = Ar^T Bi - Ai^T Br = P3 + P1 - P2
-  // (the reduce does the recombination).  grid.x = 3: tile 0 / 1 are the ordinary tiles (0,0) / (1,1), tile 2 streams all
+  // (the reduce does the recombination).  Tile 0 / 1 are the ordinary tiles (0,0) / (1,1), tile 2 streams all
   // 256 columns of both operands in 16-token slabs (the same 32 KiB per slab) and forms the two sums on the fragments;
   // partials [split][batch][3][128][128]
   int gauss;
@@ -54,6 +61,12 @@ struct TnArgs {
   // tiles P1 / P2 into splits12 <= splits (the partial slots zs >= splits12 of those tiles are neither written nor read).
   // splits12 = splits elsewhere
   int splits12, slabs_per_split12;
+  // batched launches: a ONE-dimensional grid of nwg workgroups.  The hardware deals consecutive workgroup ids to the 8 XCDs in
+  // turn; id -> work item is the inverse of that deal, so an XCD owns a CONTIGUOUS range of work items, ordered (problem,
+  // token range, tile): one operand set per XCD at DPOT-Tiny (its operands cross into that L2 once), workgroups that share a
+  // token range next to each other
+  int raster, nwg;
+  TnSet sets[TN_MAXSETS];
 };
 
 constexpr int TN_TOK = 32;                 // tokens per slab
@@ -79,24 +92,44 @@ __global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
   const int ntiles = p.tiles1 * p.tiles2;
-  int tile, zb, zs;
-  if (p.gauss) {
+  int tile, zbg, zs;                                    // zbg: problem index over the whole launch
+  if (p.raster) {
+    const int bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3;
+    const int q = p.nwg >> 3, r = p.nwg & 7;
+    const int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    if (p.gauss) {
+      const int W = 2 * p.splits12 + p.splits;
+      zbg = w / W;
+      const int rr = w - zbg * W;
+      tile = rr < p.splits12 ? 0 : rr < 2 * p.splits12 ? 1 : 2;
+      zs = rr - (tile == 2 ? 2 * p.splits12 : tile * p.splits12);
+    } else {
+      const int per = ntiles * p.splits;
+      zbg = w / per;
+      const int rr = w - zbg * per;
+      zs = rr / ntiles;
+      tile = rr - zs * ntiles;
+    }
+  } else if (p.gauss) {
     // three-product form: a ONE-dimensional grid of exactly the workgroups that have work - per problem splits12 token ranges of
     // P1, splits12 of P2, `splits` of the sum-product tile (the hardware deals consecutive workgroups to the 8 XCDs in turn: a grid
     // with idle members leaves some XCD with more than its 32 workgroups and the launch with a second round)
     const int W = 2 * p.splits12 + p.splits;
     const int lin = blockIdx.x;
-    zb = lin / W;
-    const int r = lin - zb * W;
+    zbg = lin / W;
+    const int r = lin - zbg * W;
     tile = r < p.splits12 ? 0 : r < 2 * p.splits12 ? 1 : 2;
     zs = r - (tile == 2 ? 2 * p.splits12 : tile * p.splits12);
   } else {
     const int bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3;
     const int q = ntiles >> 3, r = ntiles & 7;
     tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    zb = blockIdx.z / p.splits;
-    zs = blockIdx.z - zb * p.splits;
+    zbg = blockIdx.z / p.splits;
+    zs = blockIdx.z - zbg * p.splits;
   }
+  const int set = zbg / p.nper, zq = zbg - set * p.nper;
+  const int grp = zbg / p.batch, zb = zbg - grp * p.batch;
+  float* const wsg = p.ws + grp * p.ws_group;
   int t1 = tile / p.tiles2, t2 = tile - t1 * p.tiles2;
   const bool g3 = p.gauss && tile == 2;                 // the sum-product tile of the three-product form
   if (p.gauss) t1 = t2 = (tile == 1 ? 1 : 0);
@@ -122,15 +155,15 @@ __global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
     // wave L issues the tokens 16L .. 16L+15 of both operands (instruction j = tokens 16L + 2j, + 2j + 1 of one operand);
     // lane -> (token parity lane >> 5, 16 B piece lane & 31)
     const int L = wave - 4;
-    const bool second = zb >= p.batch1;
-    const int zq = second ? zb - p.batch1 : zb;
+    const float* const A = p.sets[set].A;
+    const float* const B = p.sets[set].B;
     // ordinary tile: an instruction moves two token rows of 128 columns; sum-product tile: ONE token row of all 256 columns
     // (wave L: tokens 8L .. 8L+7 of a 16-token slab) - 8 + 8 instructions per slab and wave either way
-    const float* a0 = g3 ? (second ? p.A2 : p.A) + zq * p.sA + (long long)(slab0 * 16 + 8 * L) * p.lda + lane * 4
-                         : (second ? p.A2 : p.A) + zq * p.sA + (long long)(slab0 * TN_TOK + 16 * L + (lane >> 5)) * p.lda +
+    const float* a0 = g3 ? A + zq * p.sA + (long long)(slab0 * 16 + 8 * L) * p.lda + lane * 4
+                         : A + zq * p.sA + (long long)(slab0 * TN_TOK + 16 * L + (lane >> 5)) * p.lda +
                                t1 * TN_W + (lane & 31) * 4;
-    const float* b0 = g3 ? (second ? p.B2 : p.B) + zq * p.sB + (long long)(slab0 * 16 + 8 * L) * p.ldb + lane * 4
-                         : (second ? p.B2 : p.B) + zq * p.sB + (long long)(slab0 * TN_TOK + 16 * L + (lane >> 5)) * p.ldb +
+    const float* b0 = g3 ? B + zq * p.sB + (long long)(slab0 * 16 + 8 * L) * p.ldb + lane * 4
+                         : B + zq * p.sB + (long long)(slab0 * TN_TOK + 16 * L + (lane >> 5)) * p.ldb +
                                t2 * TN_W + (lane & 31) * 4;
     const long long sa2 = (g3 ? 1ll : 2ll) * p.lda, sb2 = (g3 ? 1ll : 2ll) * p.ldb;
     const long long saS = (long long)(g3 ? 16 : TN_TOK) * p.lda, sbS = (long long)(g3 ? 16 : TN_TOK) * p.ldb;
@@ -169,7 +202,7 @@ __global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
 #pragma unroll
     for (int eb = 0; eb < 4; ++eb) acc[ea][eb] = tn_f32x4{0.f, 0.f, 0.f, 0.f};
   tn_f32x4 cs = {0.f, 0.f, 0.f, 0.f};
-  const int cs_sel = zb >= p.batch1 ? p.cs_of2 : p.cs_of;
+  const int cs_sel = p.sets[set].cs_of;
   const bool cs_a = cs_sel == 1 && (p.gauss ? !g3 : t2 == 0) && wn == 0;
   const bool cs_b = cs_sel == 2 && (p.gauss ? !g3 : t1 == 0) && wm == 0;
 
@@ -248,8 +281,8 @@ __global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
 
   // partial tile: element (n1 = 4*(4*kq + r) + ea, n2 = 4*i16 + eb) of the wave's 64 x 64 block
   // (three-product form: [split][batch][3 tiles][128][128])
-  float* ws = p.gauss ? p.ws + (((long long)zs * p.batch + zb) * 3 + tile) * (TN_W * TN_W)
-                      : p.ws + ((long long)zs * p.batch + zb) * p.N1 * p.N2;
+  float* ws = p.gauss ? wsg + (((long long)zs * p.batch + zb) * 3 + tile) * (TN_W * TN_W)
+                      : wsg + ((long long)zs * p.batch + zb) * p.N1 * p.N2;
   const int ldw = p.gauss ? TN_W : p.N2;
   const int n1b = (p.gauss ? 0 : t1 * TN_W) + wm * 64, n2b = (p.gauss ? 0 : t2 * TN_W) + wn * 64 + 4 * i16;
 #pragma unroll
@@ -273,7 +306,7 @@ __global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
       const int L = p.csL ? p.csL : (cs_a ? p.N1 : p.N2);
       const int g0 = cs_a ? t1 * TN_W + wm * 64 : t2 * TN_W + wn * 64;
       const long long prod = p.gauss ? 3ll * TN_W * TN_W : (long long)p.N1 * p.N2;
-      float* wc = p.ws + (long long)p.splits * p.batch * prod + ((long long)zs * p.batch + zb) * L + g0 + 4 * i16;
+      float* wc = wsg + (long long)p.splits * p.batch * prod + ((long long)zs * p.batch + zb) * L + g0 + 4 * i16;
       *reinterpret_cast<float4*>(wc) = make_float4(cs[0], cs[1], cs[2], cs[3]);
     }
   }
@@ -315,10 +348,9 @@ __global__ __launch_bounds__(704) void gemm_tn192_kernel(const TnArgs p) {
   if (wave >= 9) {
     // ---------------------------------- loader waves ----------------------------------
     const int L = wave - 9;
-    const bool second = zb >= p.batch1;
-    const int zq = second ? zb - p.batch1 : zb;
-    const float* abase = (second ? p.A2 : p.A) + zq * p.sA + (long long)slab0 * TN_TOK * p.lda;
-    const float* bbase = (second ? p.B2 : p.B) + zq * p.sB + (long long)slab0 * TN_TOK * p.ldb;
+    const int set = zb / p.nper, zq = zb - set * p.nper;
+    const float* abase = p.sets[set].A + zq * p.sA + (long long)slab0 * TN_TOK * p.lda;
+    const float* bbase = p.sets[set].B + zq * p.sB + (long long)slab0 * TN_TOK * p.ldb;
     auto issue = [&](int t, int ring) __attribute__((always_inline)) {
       float* dst = lds + ring * TW_SLABF;
       const float* a = abase + (long long)t * TN_TOK * p.lda;
@@ -360,7 +392,7 @@ __global__ __launch_bounds__(704) void gemm_tn192_kernel(const TnArgs p) {
 #pragma unroll
     for (int eb = 0; eb < 4; ++eb) acc[ea][eb] = tn_f32x4{0.f, 0.f, 0.f, 0.f};
   tn_f32x4 cs = {0.f, 0.f, 0.f, 0.f};
-  const int cs_sel = zb >= p.batch1 ? p.cs_of2 : p.cs_of;
+  const int cs_sel = p.sets[zb / p.nper].cs_of;
   const bool cs_a = cs_sel == 1 && wn == 0;
   const bool cs_b = cs_sel == 2 && wm == 0;
   const int offA = kq * TW + wm * 64 + 4 * i16;
@@ -463,10 +495,9 @@ __global__ __launch_bounds__(896) void gemm_tn96g_kernel(const TnArgs p) {
   if (wave >= 12) {
     // ---------------------------------- loader waves (as in gemm_tn192_kernel) ----------------------------------
     const int L = wave - 12;
-    const bool second = zb >= p.batch1;
-    const int zq = second ? zb - p.batch1 : zb;
-    const float* abase = (second ? p.A2 : p.A) + zq * p.sA + (long long)slab0 * TN_TOK * p.lda;
-    const float* bbase = (second ? p.B2 : p.B) + zq * p.sB + (long long)slab0 * TN_TOK * p.ldb;
+    const int set = zb / p.nper, zq = zb - set * p.nper;
+    const float* abase = p.sets[set].A + zq * p.sA + (long long)slab0 * TN_TOK * p.lda;
+    const float* bbase = p.sets[set].B + zq * p.sB + (long long)slab0 * TN_TOK * p.ldb;
     auto issue = [&](int t, int ring) __attribute__((always_inline)) {
       float* dst = lds + ring * TG_SLABF;
       const float* a = abase + (long long)t * TN_TOK * p.lda + 4 * lane;
@@ -503,7 +534,7 @@ __global__ __launch_bounds__(896) void gemm_tn96g_kernel(const TnArgs p) {
 #pragma unroll
     for (int eb = 0; eb < 3; ++eb) acc[ea][eb] = tn_f32x4{0.f, 0.f, 0.f, 0.f};
   float cs[3] = {0.f, 0.f, 0.f};
-  const int cs_sel = zb >= p.batch1 ? p.cs_of2 : p.cs_of;
+  const int cs_sel = p.sets[zb / p.nper].cs_of;
   const bool cs_a = cs_sel == 1 && prod < 2 && wn == 0;
   const bool cs_b = cs_sel == 2 && prod < 2 && wm == 0;
   const int half = prod == 1 ? TG_BS : 0;               // P2 reads the imaginary halves; P3 reads both (half = 0, + TG_BS)
@@ -653,16 +684,15 @@ int dpot_gemm_tn_try(const dpot_gemm_desc* d, hipStream_t s) {
     return -1;
   const int nslab = d->K / TN_TOK;
   if (d->splitk > nslab || (long long)d->batch * d->splitk > 65535) return -1;
-  TnArgs p;
-  p.A = d->A; p.B = d->B; p.lda = d->lda; p.ldb = d->ldb; p.sA = d->strideA; p.sB = d->strideB;
-  p.A2 = nullptr; p.B2 = nullptr; p.batch1 = d->batch; p.cs_of2 = d->colsum_of; p.csL = 0;
+  TnArgs p{};
+  p.sets[0] = TnSet{d->A, d->B, d->colsum_of, 0};
+  p.nper = d->batch; p.lda = d->lda; p.ldb = d->ldb; p.sA = d->strideA; p.sB = d->strideB; p.csL = 0;
   p.N1 = d->M; p.N2 = d->N; p.T = d->K; p.batch = d->batch;
   p.tiles1 = d->M / TN_W; p.tiles2 = d->N / TN_W;
   p.splits = d->splitk;
   p.slabs_per_split = (nslab + d->splitk - 1) / d->splitk;
   if ((long long)p.slabs_per_split * (d->splitk - 1) >= nslab) return -1;      // an empty split would leave its partial unwritten
   p.ws = d->workspace;
-  p.cs_of = d->colsum_of;
   p.gauss = 0; p.splits12 = p.splits; p.slabs_per_split12 = p.slabs_per_split;
   hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)(p.tiles1 * p.tiles2), 1, (unsigned)(d->batch * d->splitk)), dim3(384),
                      0, s, p);
@@ -788,6 +818,12 @@ extern "C" int dpot_afno_wgrad2_splitk(int Mm, int nb, int bs) {
   return (int)s;
 }
 
+// token ranges of the products P1 / P2 of the three-product form when the sum product is cut into `splitk` (= splitk for the
+// other forms): what dpot_afno_wgrad2 launches and dpot_block_finalize reduces
+extern "C" int dpot_afno_wgrad2_splits12(int bs, int splitk) {
+  return tn_gauss(bs) ? tn_gauss_s12(bs, splitk) : splitk;
+}
+
 extern "C" int64_t dpot_afno_wgrad2_ws_elems(int nb, int bs, int splitk) {
   const int64_t N = 2 * bs;
   return (int64_t)splitk * 2 * nb * ((tn_gauss(bs) ? 3 * (int64_t)bs * bs : N * N) + N);
@@ -805,8 +841,10 @@ extern "C" int dpot_afno_wgrad2(const float* S, const float* dO1pre, const float
                "afno_wgrad2: operands must be 16-byte aligned");
   const int nslab = Mm / TN_TOK;
   DPOT_REQUIRE(splitk >= 1 && splitk <= nslab && (long long)2 * nb * splitk <= 65535, "afno_wgrad2: bad split factor");
-  TnArgs p;
-  p.A = S; p.B = dO1pre; p.A2 = O1; p.B2 = dO2; p.batch1 = nb; p.cs_of2 = 2; p.csL = 0;
+  TnArgs p{};
+  p.sets[0] = TnSet{S, dO1pre, 2, 0};
+  p.sets[1] = TnSet{O1, dO2, 2, 0};
+  p.nper = nb; p.csL = 0;
   p.lda = ld; p.ldb = ld; p.sA = N; p.sB = N;
   p.N1 = N; p.N2 = N; p.T = Mm; p.batch = 2 * nb;
   p.tiles1 = N / TN_W; p.tiles2 = N / TN_W;
@@ -814,7 +852,6 @@ extern "C" int dpot_afno_wgrad2(const float* S, const float* dO1pre, const float
   p.slabs_per_split = (nslab + splitk - 1) / splitk;
   DPOT_REQUIRE((long long)p.slabs_per_split * (splitk - 1) < nslab, "afno_wgrad2: split factor leaves an empty split");
   p.ws = workspace;
-  p.cs_of = 2;
   p.gauss = tn_gauss(bs);
   p.splits12 = p.gauss ? tn_gauss_s12(bs, splitk) : splitk;
   p.slabs_per_split12 = (nslab + p.splits12 - 1) / p.splits12;
@@ -1014,8 +1051,10 @@ extern "C" int dpot_mlp_wgrad2(const float* do2, const float* Hh, const float* x
                "mlp_wgrad2: operands must be 16-byte aligned");
   const int nslab = T / TN_TOK;
   DPOT_REQUIRE(splitk >= 1 && splitk <= nslab && 2ll * splitk <= 65535, "mlp_wgrad2: bad split factor");
-  TnArgs p;
-  p.A = do2; p.B = Hh; p.A2 = xn2; p.B2 = dHpre; p.batch1 = 1;
+  TnArgs p{};
+  p.sets[0] = TnSet{do2, Hh, 1, 0};
+  p.sets[1] = TnSet{xn2, dHpre, 2, 0};
+  p.nper = 1;
   p.lda = E; p.ldb = mh; p.sA = 0; p.sB = 0;
   p.N1 = E; p.N2 = mh; p.T = T; p.batch = 2;
   p.tiles1 = E / TN_W; p.tiles2 = mh / TN_W;
@@ -1023,7 +1062,7 @@ extern "C" int dpot_mlp_wgrad2(const float* do2, const float* Hh, const float* x
   p.slabs_per_split = (nslab + splitk - 1) / splitk;
   DPOT_REQUIRE((long long)p.slabs_per_split * (splitk - 1) < nslab, "mlp_wgrad2: split factor leaves an empty split");
   p.ws = workspace;
-  p.cs_of = 1; p.cs_of2 = 2; p.csL = E > mh ? E : mh;
+  p.csL = E > mh ? E : mh;
   p.gauss = 0; p.splits12 = p.splits; p.slabs_per_split12 = p.slabs_per_split;
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)(p.tiles1 * p.tiles2), 1, (unsigned)(2 * splitk)), dim3(384), 0, s, p);
@@ -1076,4 +1115,258 @@ extern "C" int dpot_block_finalize(const float* afno_ws, int afno_splitk, int nb
   DPOT_REQUIRE(total > 0, "block_finalize: nothing to do");
   hipLaunchKernelGGL(block_finalize_kernel, dim3((unsigned)total), dim3(256), 0, as_stream(stream), a);
   return check_launch("block_finalize_kernel");
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Weight gradients of SEVERAL DPOT blocks in one launch.  Nothing on the backward's data path reads a weight gradient - only
+// the optimiser does, after the last block - so the blocks' small problems need not run (and fill 256 CUs by deep token
+// splits) one block at a time: the operands of n blocks go into the problem table of ONE gemm_tn_kernel launch, and ONE
+// finalising launch reduces every block's partials, bias column sums and GroupNorm parameter-gradient partials.  Every block
+// keeps a workspace in the layout of its per-block launch, so the reduce bodies above run unchanged; every sum has a fixed
+// order.  The caller chooses the split factors: those of the per-block entries (several rounds of workgroups in one launch; the
+// same partials and sums - bit-identical results, the model's default) or the one-round rules below, which need 1/n of the
+// split factor (longer token ranges per workgroup, 1/n of the partial-sum traffic; another summation order).
+// ---------------------------------------------------------------------------------------------------------------------
+namespace dpot {
+constexpr int WB_MAXBLK = TN_MAXSETS / 2;             // blocks per launch (two sets each)
+
+// the largest split count <= s that leaves no token range empty (ranges of ceil(nslab / s) slabs)
+static int tn_no_empty(int nslab, long long s) {
+  if (s > nslab) s = nslab;
+  if (s < 1) s = 1;
+  while (s > 1 && ((nslab + s - 1) / s) * (s - 1) >= nslab) --s;
+  return (int)s;
+}
+// n blocks that do not fit one problem table are cut into equal launches
+static int wb_per_launch(int n) {
+  const int launches = (n + WB_MAXBLK - 1) / WB_MAXBLK;
+  return (n + launches - 1) / launches;
+}
+static bool mlp_batch_shape_ok(int T, int E, int mh) {
+  return T > 0 && E > 0 && mh > 0 && E % TN_W == 0 && mh % TN_W == 0 && T % TN_TOK == 0;
+}
+// (splits12, splits) of a three-product launch of `per` blocks: the largest split count whose workgroups fit one round of 256
+// with at least four slabs per range; 0: not even one range per tile fits
+static int afno_batch_splits(int nslab, int nb, int bs, int per, int* s12_out) {
+  const long long P = 2ll * per * nb;
+  const int smax = nslab / 4 > 1 ? nslab / 4 : 1;
+  int best = 0, best12 = 0;
+  for (int c = 1; c <= smax && c <= 64; ++c) {
+    if (tn_no_empty(nslab, c) != c) continue;
+    const int s12 = tn_no_empty(nslab, tn_gauss_s12(bs, c));
+    if (P * (2 * s12 + c) <= 256) { best = c; best12 = s12; }
+  }
+  *s12_out = best12;
+  return best;
+}
+
+struct WgradFinalizeArgs {
+  dpot_wgrad_block blk[WB_MAXBLK];                    // 128 bytes each
+  int a_splits, a_nb, a_bs, a_gauss, nA;              // slice A of every block: afno_wgrad2_reduce_body
+  int m_splits, m_E, m_mh, nM;                        // slice M: mlp_wgrad2_reduce_body
+  int g_jobs, g_B, g_E, nG;                           // slice G: gn_param_grad_body
+};
+// grid = blocks x (nA + nM + nG) workgroups, block-major: the slices of block_finalize_kernel, once per DPOT block
+__global__ __launch_bounds__(256) void wgrad_batch_finalize_kernel(const WgradFinalizeArgs a) {
+  const int per = a.nA + a.nM + a.nG;
+  const int k = blockIdx.x / per, b = blockIdx.x - k * per;
+  const dpot_wgrad_block& w = a.blk[k];
+  if (b < a.nA) {
+    afno_wgrad2_reduce_body(b, a.nA, w.afno_ws, a.a_splits, a.a_nb, a.a_bs, w.dw1, w.db1, w.dw2, w.db2, a.a_gauss);
+  } else if (b < a.nA + a.nM) {
+    mlp_wgrad2_reduce_body(b - a.nA, a.nM, w.mlp_ws, a.m_splits, a.m_E, a.m_mh, w.dW2, w.dW1, w.dfb2, w.dfb1);
+  } else {
+    const int g = b - a.nA - a.nM, pj = (a.g_E + 63) / 64;
+    const int job = g / pj;
+    gn_param_grad_body(g - job * pj, w.gn_part[job], w.gn_dgamma[job], w.gn_dbeta[job], a.g_B, a.g_E);
+  }
+}
+}  // namespace dpot
+
+extern "C" int dpot_wgrad_batch_max_blocks(void) { return WB_MAXBLK; }
+
+extern "C" int dpot_tn_split_range(int T, int splits, int i, int* first_tok, int* ntok) {
+  DPOT_REQUIRE(T > 0 && T % TN_TOK == 0 && splits >= 1 && i >= 0 && i < splits && first_tok && ntok, "tn_split_range: bad arguments");
+  // as gemm_tn_kernel cuts the slabs: ranges of ceil(nslab / splits) slabs, the last one shorter
+  const int nslab = T / TN_TOK, sps = (nslab + splits - 1) / splits;
+  int n = nslab - i * sps;
+  n = n < sps ? n : sps;
+  if (n < 0) n = 0;
+  *first_tok = i * sps * TN_TOK;
+  *ntok = n * TN_TOK;
+  return DPOT_OK;
+}
+
+// split factor of a batched channel-MLP launch over n blocks (0: shape not covered): max(1, 256 / tiles) token ranges of at
+// least four slabs - DPOT-Tiny, 4 blocks: 128 tiles x 2
+extern "C" int dpot_mlp_wgrad_batch_splitk(int T, int E, int mh, int n) {
+  static const int enabled = tune("panel", 1);
+  if (!enabled || n < 1 || !mlp_batch_shape_ok(T, E, mh)) return 0;
+  const long long tiles = 2ll * wb_per_launch(n) * (E / TN_W) * (mh / TN_W);
+  const int nslab = T / TN_TOK;
+  long long s = 256 / tiles;
+  const long long smax = nslab / 4;
+  if (s > smax) s = smax;
+  return tn_no_empty(nslab, s);
+}
+
+extern "C" int64_t dpot_mlp_wgrad_batch_ws_elems(int E, int mh, int splitk, int n) {
+  return (int64_t)n * dpot_mlp_wgrad2_ws_elems(E, mh, splitk);
+}
+
+extern "C" int dpot_mlp_wgrad_batch(const float* const* do2, const float* const* Hh, const float* const* xn2,
+                                    const float* const* dHpre, int n, int T, int E, int mh, float* workspace, int splitk,
+                                    dpot_stream_t stream) {
+  DPOT_REQUIRE(do2 && Hh && xn2 && dHpre && workspace && n >= 1, "mlp_wgrad_batch: null pointer");
+  DPOT_REQUIRE(mlp_batch_shape_ok(T, E, mh), "mlp_wgrad_batch: needs E, mh %% 128 == 0, T %% 32 == 0");
+  const int nslab = T / TN_TOK;
+  DPOT_REQUIRE(splitk >= 1 && splitk <= nslab && tn_no_empty(nslab, splitk) == splitk,
+               "mlp_wgrad_batch: split factor %d leaves an empty token range (%d slabs)", splitk, nslab);
+  DPOT_REQUIRE(aligned16(workspace), "mlp_wgrad_batch: workspace must be 16-byte aligned");
+  const int per = wb_per_launch(n);
+  const long long wsb = dpot_mlp_wgrad2_ws_elems(E, mh, splitk);
+  hipStream_t s = as_stream(stream);
+  for (int b0 = 0; b0 < n; b0 += per) {
+    const int nb_l = n - b0 < per ? n - b0 : per;
+    TnArgs p{};
+    for (int i = 0; i < nb_l; ++i) {
+      const int k = b0 + i;
+      DPOT_REQUIRE(do2[k] && Hh[k] && xn2[k] && dHpre[k] && aligned16(do2[k]) && aligned16(Hh[k]) && aligned16(xn2[k]) &&
+                       aligned16(dHpre[k]), "mlp_wgrad_batch: operands of block %d must be non-null and 16-byte aligned", k);
+      p.sets[2 * i] = TnSet{do2[k], Hh[k], 1, 0};
+      p.sets[2 * i + 1] = TnSet{xn2[k], dHpre[k], 2, 0};
+    }
+    p.nper = 1;
+    p.lda = E; p.ldb = mh; p.sA = 0; p.sB = 0;
+    p.N1 = E; p.N2 = mh; p.T = T; p.batch = 2;
+    p.tiles1 = E / TN_W; p.tiles2 = mh / TN_W;
+    p.splits = splitk;
+    p.slabs_per_split = (nslab + splitk - 1) / splitk;
+    p.ws = workspace + (long long)b0 * wsb;
+    p.ws_group = wsb;
+    p.csL = E > mh ? E : mh;
+    p.gauss = 0; p.splits12 = p.splits; p.slabs_per_split12 = p.slabs_per_split;
+    const long long nwg = 2ll * nb_l * p.tiles1 * p.tiles2 * splitk;
+    DPOT_REQUIRE(nwg <= 0x7fffffff, "mlp_wgrad_batch: grid too large");
+    p.raster = 1; p.nwg = (int)nwg;
+    hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)nwg), dim3(384), 0, s, p);
+    int rc = check_launch("gemm_tn_kernel");
+    if (rc) return rc;
+  }
+  return DPOT_OK;
+}
+
+// blocks per launch of the batched three-product AFNO weight gradient (0: shape not covered - per-block launches) and its
+// split factors.  The workgroups sets * nb * (2 * splits12 + splits) must fit one round of 256, and the P1 / P2 ranges must
+// keep the 5 / 6 proportion to the sum-product ranges (profiles/r05_tn_skew.txt) unless the tokens, not the chip, limit the
+// split: DPOT-Tiny (nb = 4) two blocks per launch at (5, 6) - three or four blocks leave (3, 4) / (2, 3); nb = 8: one block
+extern "C" int dpot_afno_wgrad_batch_plan(int Mm, int nb, int bs, int n, int* splits12, int* splits) {
+  static const int enabled = tune("panel", 1);
+  if (!enabled || !splits12 || !splits || n < 1 || nb <= 0 || bs != TN_W || !tn_gauss(bs) || Mm <= 0 || Mm % TN_TOK) return 0;
+  const int nslab = Mm / TN_TOK;
+  const int smax = tn_no_empty(nslab, nslab / 4);
+  for (int per = n < WB_MAXBLK ? n : WB_MAXBLK; per >= 1; --per) {
+    int s12 = 0;
+    const int c = afno_batch_splits(nslab, nb, bs, per, &s12);
+    if (!c) continue;
+    const bool balanced = 6 * s12 == 5 * c, token_limited = c == smax;
+    if (balanced || token_limited || per == 1) {
+      *splits12 = s12; *splits = c;
+      return per;
+    }
+  }
+  return 0;
+}
+
+extern "C" int64_t dpot_afno_wgrad_batch_ws_elems(int nb, int bs, int splitk, int n) {
+  return (int64_t)n * dpot_afno_wgrad2_ws_elems(nb, bs, splitk);
+}
+
+extern "C" int dpot_afno_wgrad_batch(const float* const* S, const float* const* dO1pre, const float* const* O1,
+                                     const float* const* dO2, int n, int ld, int Mm, int nb, int bs, float* workspace,
+                                     int per_launch, int splits12, int splitk, dpot_stream_t stream) {
+  DPOT_REQUIRE(S && dO1pre && O1 && dO2 && workspace && n >= 1, "afno_wgrad_batch: null pointer");
+  const int N = 2 * bs;
+  DPOT_REQUIRE(nb > 0 && bs == TN_W && tn_gauss(bs) && Mm > 0 && Mm % TN_TOK == 0 && ld >= nb * N && ld % 4 == 0,
+               "afno_wgrad_batch: needs the three-product form (bs == 128, DPOT_TUNE wgrad_gauss != 0), Mm %% 32 == 0");
+  const int nslab = Mm / TN_TOK;
+  DPOT_REQUIRE(per_launch >= 1 && per_launch <= WB_MAXBLK, "afno_wgrad_batch: 1 .. %d blocks per launch", WB_MAXBLK);
+  DPOT_REQUIRE(splitk >= 1 && splits12 >= 1 && splits12 <= splitk && tn_no_empty(nslab, splitk) == splitk &&
+                   tn_no_empty(nslab, splits12) == splits12,
+               "afno_wgrad_batch: split factors (%d, %d) leave an empty token range (%d slabs)", splits12, splitk, nslab);
+  DPOT_REQUIRE(aligned16(workspace), "afno_wgrad_batch: workspace must be 16-byte aligned");
+  const long long wsb = dpot_afno_wgrad2_ws_elems(nb, bs, splitk);
+  hipStream_t s = as_stream(stream);
+  for (int b0 = 0; b0 < n; b0 += per_launch) {
+    const int nb_l = n - b0 < per_launch ? n - b0 : per_launch;
+    TnArgs p{};
+    for (int i = 0; i < nb_l; ++i) {
+      const int k = b0 + i;
+      DPOT_REQUIRE(S[k] && dO1pre[k] && O1[k] && dO2[k] && aligned16(S[k]) && aligned16(dO1pre[k]) && aligned16(O1[k]) &&
+                       aligned16(dO2[k]), "afno_wgrad_batch: operands of block %d must be non-null and 16-byte aligned", k);
+      p.sets[2 * i] = TnSet{S[k], dO1pre[k], 2, 0};
+      p.sets[2 * i + 1] = TnSet{O1[k], dO2[k], 2, 0};
+    }
+    p.nper = nb; p.csL = 0;
+    p.lda = ld; p.ldb = ld; p.sA = N; p.sB = N;
+    p.N1 = N; p.N2 = N; p.T = Mm; p.batch = 2 * nb;
+    p.tiles1 = N / TN_W; p.tiles2 = N / TN_W;
+    p.splits = splitk;
+    p.slabs_per_split = (nslab + splitk - 1) / splitk;
+    p.gauss = 1;
+    p.splits12 = splits12;
+    p.slabs_per_split12 = (nslab + splits12 - 1) / splits12;
+    p.ws = workspace + (long long)b0 * wsb;
+    p.ws_group = wsb;
+    const long long nwg = 2ll * nb_l * nb * (2 * splits12 + splitk);
+    DPOT_REQUIRE(nwg <= 0x7fffffff, "afno_wgrad_batch: grid too large");
+    p.raster = 1; p.nwg = (int)nwg;
+    hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)nwg), dim3(384), 0, s, p);
+    int rc = check_launch("gemm_tn_kernel");
+    if (rc) return rc;
+  }
+  return DPOT_OK;
+}
+
+extern "C" int dpot_wgrad_batch_finalize(const dpot_wgrad_block* blocks, int n, int afno_splits12, int afno_splitk, int nb,
+                                         int bs, int mlp_splitk, int E, int mh, int gn_jobs, int B, int Egn,
+                                         dpot_stream_t stream) {
+  DPOT_REQUIRE(blocks && n >= 1, "wgrad_batch_finalize: no blocks");
+  DPOT_REQUIRE(gn_jobs >= 0 && gn_jobs <= 2, "wgrad_batch_finalize: at most two GroupNorm jobs per block");
+  WgradFinalizeArgs a{};
+  if (afno_splitk > 0) {
+    DPOT_REQUIRE(nb > 0 && bs == TN_W && afno_splits12 >= 1 && afno_splits12 <= afno_splitk, "wgrad_batch_finalize: bad AFNO slice");
+    a.a_splits = afno_splitk; a.a_nb = nb; a.a_bs = bs; a.a_gauss = afno_splits12;
+    long long blocksA = (2ll * nb * bs * bs + 255) / 256;
+    a.nA = (int)(blocksA > 4096 ? 4096 : blocksA);
+  }
+  if (mlp_splitk > 0) {
+    DPOT_REQUIRE(E > 0 && mh > 0 && E % 32 == 0 && mh % 32 == 0, "wgrad_batch_finalize: bad channel-MLP slice");
+    a.m_splits = mlp_splitk; a.m_E = E; a.m_mh = mh;
+    const long long blocksM = 2ll * (E / 32) * (mh / 32);
+    a.nM = (int)(blocksM > 2048 ? 2048 : blocksM);
+  }
+  if (gn_jobs > 0) {
+    DPOT_REQUIRE(B > 0 && Egn > 0, "wgrad_batch_finalize: bad GroupNorm slice");
+    a.g_jobs = gn_jobs; a.g_B = B; a.g_E = Egn; a.nG = gn_jobs * ((Egn + 63) / 64);
+  }
+  const int per = a.nA + a.nM + a.nG;
+  DPOT_REQUIRE(per > 0, "wgrad_batch_finalize: nothing to do");
+  hipStream_t s = as_stream(stream);
+  for (int b0 = 0; b0 < n; b0 += WB_MAXBLK) {
+    const int nl = n - b0 < WB_MAXBLK ? n - b0 : WB_MAXBLK;
+    for (int i = 0; i < nl; ++i) {
+      const dpot_wgrad_block& w = blocks[b0 + i];
+      DPOT_REQUIRE(!a.nA || (w.afno_ws && w.dw1 && w.db1 && w.dw2 && w.db2), "wgrad_batch_finalize: null AFNO pointer, block %d", b0 + i);
+      DPOT_REQUIRE(!a.nM || (w.mlp_ws && w.dW2 && w.dfb2 && w.dW1 && w.dfb1), "wgrad_batch_finalize: null channel-MLP pointer, block %d", b0 + i);
+      for (int j = 0; j < gn_jobs; ++j)
+        DPOT_REQUIRE(w.gn_part[j] && w.gn_dgamma[j] && w.gn_dbeta[j], "wgrad_batch_finalize: null GroupNorm pointer, block %d", b0 + i);
+      a.blk[i] = w;
+    }
+    hipLaunchKernelGGL(wgrad_batch_finalize_kernel, dim3((unsigned)(nl * per)), dim3(256), 0, s, a);
+    int rc = check_launch("wgrad_batch_finalize_kernel");
+    if (rc) return rc;
+  }
+  return DPOT_OK;
 }

@@ -75,6 +75,90 @@ class _Sink:
             fp.fire(i)
 
 
+class WgradBatch:
+    """The weight gradients of all Blocks of ONE forward pass, computed when the last of them has run its backward.
+
+    No data gradient reads a weight gradient - only the optimiser does - so a Block's backward need not launch its own small
+    weight-gradient problems (split deeply along the tokens to fill the chip) and its own finalising launch: it leaves its
+    operands and sinks here, and the flush runs the channel-MLP problems of all Blocks in one launch, the AFNO ones in as many
+    launches as `ops.afno_wgrad_batch_plan` balances, and ONE finalising launch (csrc/gemm_tn.hip).  DPOTNet creates one per
+    forward (an auto-regressive rollout: one per pass) and hands it to its Blocks; a Block registers in its forward when all
+    its parameters are bound to FlatParams slots (a gradient returned to autograd would have to exist when the Block's
+    backward returns).  Blocks are counted, not ordered.  The deferred operands are the Block's saved activations and
+    gradients its backward allocated; nothing writes them again, and the jobs keep them alive until the flush.
+
+    By default the batched launches cut the tokens exactly as the per-block launches do (several rounds of workgroups in one
+    launch): every partial and every sum is the same, the gradients are bit-identical to the per-block schedule's.
+    DPOT_TUNE fused_small=3 selects the one-round rules instead (fewer, longer token ranges: less partial traffic, another
+    summation order)."""
+
+    def __init__(self):
+        self.expected = 0
+        self.delivered = 0
+        self.jobs = []
+
+    def register(self) -> None:
+        self.expected += 1
+
+    def withdraw(self) -> None:
+        """a registered Block whose backward took the per-block route after all"""
+        self.delivered += 1
+        self._maybe_flush()
+
+    def deliver(self, job: dict) -> None:
+        self.jobs.append(job)
+        self.delivered += 1
+        self._maybe_flush()
+
+    def _maybe_flush(self) -> None:
+        if self.delivered < self.expected:
+            return
+        jobs, self.jobs, self.delivered = self.jobs, [], 0
+        groups = {}
+        for j in jobs:
+            groups.setdefault(j["key"], []).append(j)
+        for g in groups.values():
+            self._flush_group(g)
+
+    @staticmethod
+    def splits(n, M, E, mh, mp, Mm, nb, bs):
+        """(channel-MLP splits, AFNO blocks per launch, splits12, splits) of a batch of n Blocks; a zero: not covered"""
+        if ops.wgrad_batch_one_round():
+            per, s12, sk = ops.afno_wgrad_batch_plan(Mm, nb, bs, n)
+            return ops.mlp_wgrad_batch_splitk(M, E, mh, n, mp), (per if per >= 2 else 0), s12, sk
+        covered = ops.afno_wgrad_batch_plan(Mm, nb, bs, 1)[0] >= 1          # the three-product form at 128 channels per block
+        sk = ops.afno_wgrad2_splitk(Mm, nb, bs) if covered else 0
+        s12 = ops.afno_wgrad2_splits12(Mm, bs, sk) if sk else 0
+        return ops.mlp_wgrad2_splitk(M, E, mh, mp), min(n, ops.wgrad_batch_max_blocks()), s12, sk
+
+    @staticmethod
+    def _flush_group(g) -> None:
+        n = len(g)
+        M, E, mh, mp, adims, _ = g[0]["key"]
+        dev = g[0]["mlp"][0].device
+        skm, per, s12, sk = WgradBatch.splits(n, M, E, mh, mp, *adims)
+        mws = ops.mlp_wgrad_batch(*[[j["mlp"][k] for j in g] for k in range(4)], skm)
+        # outputs: the parameters' gradient slots where this is the step's first contribution, temporaries otherwise
+        mouts = [tuple(ops._out(sk.out(), shp, dev) for sk, shp in zip(j["mlp_sinks"], ((E, mh), (E,), (mh, E), (mh,))))
+                 for j in g]
+        Mm, nb, bs = adims
+        aws = ops.afno_wgrad_batch(*[[j["afno"][k] for j in g] for k in range(4)], nb, bs, per, s12, sk)
+        aouts = [tuple(ops._out(sk_.out(), shp, dev)
+                       for sk_, shp in zip(j["afno_sinks"], ((2, nb, bs, bs), (2, nb, bs), (2, nb, bs, bs), (2, nb, bs))))
+                 for j in g]
+        afno = (aws, s12, sk, nb, bs, aouts)
+        gn = [[(part, ops._out(sg.out(), (E,), dev), ops._out(sb.out(), (E,), dev)) for part, sg, sb in j["gn"]] for j in g]
+        ops.wgrad_batch_finalize(afno, (mws, skm, E, mh, mouts), gn)
+        for i, j in enumerate(g):
+            dW2, db2, dW1, db1 = mouts[i]
+            s_f2w, s_f2b, s_f1w, s_f1b = j["mlp_sinks"]
+            s_f2w.done(dW2.view(E, mh, 1, 1)), s_f2b.done(db2), s_f1w.done(dW1.view(mh, E, 1, 1)), s_f1b.done(db1)
+            for sk_, t in zip(j["afno_sinks"], aouts[i]):
+                sk_.done(t)
+            for (_, sg, sb), (_, dg, db) in zip(j["gn"], gn[i]):
+                sg.done(dg), sb.done(db)
+
+
 def _epoch_of(sinks):
     """(FlatParams, its weights epoch) of the first flat-bound parameter, or None.  DPOTNet keeps its derived weights
     (AFNO packs, panel packs, the de-embed matrix) in PERSISTENT buffers that every forward outside a weights_scope
@@ -364,7 +448,9 @@ def _mixer_core_bwd(dO2, S, O1pre, O1, wb1, wb2, dims, fused, afno_layout, sinks
     """backward of _mixer_core: dO2 [Mm, 2E] -> (dS, dw1, db1, dw2, db2); wb1 / wb2: the fragment-block-major W^T (fused
     kernel) or the plain Wbig (generic GEMM); sinks = (s_w1, s_b1, s_w2, s_b2).  pending (a dict, BlockFn): the fused
     weight-gradient launch leaves its split-K partials for the block's ONE finalising launch (pending["afno"] = the job)
-    and the four gradients are returned as plain tensors - the caller calls the sinks' done() after that launch"""
+    and the four gradients are returned as plain tensors - the caller calls the sinks' done() after that launch; with
+    pending["batch"] set (the Block delivers to a WgradBatch) only the operands are recorded (pending["afno_ops"]) and the
+    four gradients are returned as None"""
     B, tok, E, h, w, nb, bs, mx, my, mh, act = dims
     s_w1, s_b1, s_w2, s_b2 = sinks
     Mm = B * mx * my
@@ -392,10 +478,14 @@ def _mixer_core_bwd(dO2, S, O1pre, O1, wb1, wb2, dims, fused, afno_layout, sinks
         dO1pre = torch.empty(Mm, 2 * E, dtype=torch.float32, device=dev)
         ops.gemm(dO2, wb2, dO1pre, Mm, 2 * bs, 2 * bs, transB=True, act=act, mode=EPI_DACT, aux=O1pre,
                  ldaux=2 * E, strideAux=2 * bs, **kw)
-    if sk2:
+    if sk2 and pending is not None and pending.get("batch"):
+        # the Block's WgradBatch computes both weight gradients with those of the other Blocks: only the operands are recorded
+        pending["afno_ops"] = (S, dO1pre, O1, dO2)
+        dw1 = db1 = dw2 = db2 = None
+    elif sk2:
         dw1, db1 = ops._out(s_w1.out(), (2, nb, bs, bs), dev), ops._out(s_b1.out(), (2, nb, bs), dev)
         dw2, db2 = ops._out(s_w2.out(), (2, nb, bs, bs), dev), ops._out(s_b2.out(), (2, nb, bs), dev)
-        if pending is not None:
+        if pending is not None and not pending.get("batch"):
             pending["afno"] = ops.afno_wgrad2(S, dO1pre, O1, dO2, nb, bs, dw1, db1, dw2, db2, sk2, defer=True)
         else:
             ops.afno_wgrad2(S, dO1pre, O1, dO2, nb, bs, dw1, db1, dw2, db2, sk2)
@@ -591,7 +681,7 @@ class BlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, n1w, n1b, w1, b1, w2, b2, n2w, n2b, f1w, f1b, f2w, f2b, h: int, w: int, nb: int, modes: int,
                 act: int, packed=None, recompute: bool = False, mlp_pk=None, grad_enabled: bool = True,
-                emit_grad_packs: bool = False):
+                emit_grad_packs: bool = False, wgrad_batch: Optional[WgradBatch] = None):
         x = x.contiguous()
         B, tok, E = x.shape
         bs = E // nb
@@ -626,6 +716,11 @@ class BlockFn(torch.autograd.Function):
         ctx.gemm_precision = ops._cur_gemm()
         ctx.sinks = _sinks(ctx, (n1w, n1b, w1, b1, w2, b2, n2w, n2b, f1w, f1b, f2w, f2b), 1)
         ctx.weights_epoch = _epoch_of(ctx.sinks)
+        # deferred weight gradients (WgradBatch): every parameter gradient must have a FlatParams slot to land in later
+        ctx.wgrad_batch = None
+        if wgrad_batch is not None and keep and all(sk.fp is not None for sk in ctx.sinks):
+            wgrad_batch.register()
+            ctx.wgrad_batch = wgrad_batch
         return out.view(B, tok, E)
 
     @staticmethod
@@ -667,6 +762,18 @@ class BlockFn(torch.autograd.Function):
         mlp_pk = ctx.mlp_pk
         bf16p = mlp_pk is not None and mlp_pk.kind != "f32"
         npl = mlp_pk.planes if bf16p else 0
+        # weight gradients with those of the other Blocks (WgradBatch): the native fp32 two-layer weight-gradient launches only,
+        # three-product AFNO form
+        batch = ctx.wgrad_batch
+        if batch is not None:
+            if (pending is not None and not bf16p and do2.is_contiguous() and Hh.is_contiguous() and xn2.is_contiguous()
+                    and ops.mlp_wgrad2_splitk(M, E, mh, mp) and ctx.fused_mixer and S.stride(0) == 2 * E
+                    and ops.afno_wgrad2_splitk(Mm, nb, bs)
+                    and all(WgradBatch.splits(batch.expected, M, E, mh, mp, Mm, nb, bs))):
+                pending["batch"] = True
+            else:
+                batch.withdraw()
+                batch = None
 
         def wgrad(dy, xin, s_w, s_b, shape):
             n, k = dy.shape[1], xin.shape[1]
@@ -726,7 +833,10 @@ class BlockFn(torch.autograd.Function):
                 dHpre, _ = ops.gemm_panel(do2, mlp_pk[3], mh, act=act, mode=EPI_DACT, aux=Hpre)       # do2 W2, * act'(Hpre)
             else:
                 dHpre = ops.linear_bwd_data(do2, f2w, act=act, aux=Hpre, precision=mp)  # [M, mh]
-            if skm:
+            if skm and batch is not None:
+                mlp_ops = (do2, Hh, xn2.view(M, E), dHpre)
+                df2w = df2b = df1w = df1b = None
+            elif skm:
                 df2w, df2b = ops._out(s_f2w.out(), (E, mh), dev), ops._out(s_f2b.out(), (E,), dev)
                 df1w, df1b = ops._out(s_f1w.out(), (mh, E), dev), ops._out(s_f1b.out(), (mh,), dev)
                 if pending is not None:      # partials only: reduced by the block's finalising launch below
@@ -774,6 +884,13 @@ class BlockFn(torch.autograd.Function):
             # there the staging + two barriers per 32-token sub-tile cost what the saved pack pass did: DPOT-L 91.2 -> 90.9 ms,
             # L20 2.185 -> 2.211 s, profiles/r05_grad_packs_step_ab_L.txt; the opt-in of round 5 is gone)
             dx, gn1_part = ops.groupnorm_bwd(dxn1, x, mean1, rstd1, n1w, add=dout, defer=True)
+        if batch is not None:
+            aops = pending["afno_ops"]
+            batch.deliver({"key": (M, E, mh, mp, (Mm, nb, bs), tuple(gn1_part.shape)),
+                           "mlp": mlp_ops, "mlp_sinks": (s_f2w, s_f2b, s_f1w, s_f1b),
+                           "afno": aops, "afno_sinks": (s_w1, s_b1, s_w2, s_b2),
+                           "gn": [(gn1_part, s_n1w, s_n1b), (gn2_part, s_n2w, s_n2b)]})
+            return (dx,) + (None,) * 23
         gn_jobs = [(gn1_part, s_n1w.out(), s_n1b.out()), (gn2_part, s_n2w.out(), s_n2b.out())]
         if pending:
             (dn1w, dn1b), (dn2w, dn2b) = ops.block_finalize(pending.get("afno"), pending.get("mlp"), gn_jobs,
@@ -790,7 +907,7 @@ class BlockFn(torch.autograd.Function):
         dn1w, dn1b = s_n1w.done(dn1w), s_n1b.done(dn1b)
         dn2w, dn2b = s_n2w.done(dn2w), s_n2b.done(dn2b)
         return (dx, dn1w, dn1b, dw1, db1, dw2, db2, dn2w, dn2b, df1w, df1b, df2w, df2b, None, None, None, None, None,
-                None, None, None, None, None)
+                None, None, None, None, None, None)
 
 
 # ======================================================================================================

@@ -22,7 +22,7 @@ import torch.nn as nn
 from . import _lib, ops
 import contextlib
 
-from .functional import AdaINFn, BlockFn, EmbedFn, HeadFn
+from .functional import AdaINFn, BlockFn, EmbedFn, HeadFn, WgradBatch
 from .packs import ModelPacks
 
 ACTIVATIONS = ("gelu", "tanh", "sigmoid", "relu", "leaky_relu", "softplus", "ELU", "silu")
@@ -184,6 +184,11 @@ class DPOTNet(nn.Module):
                 and self._ar_pos[0] >= self._ar_pos[1] - self.recompute_keep_last:
             recompute = False
         hook = self._boundary_hook
+        # the Blocks' weight gradients in batched launches after the last Block's backward (functional.WgradBatch) - not
+        # with a boundary hook (the segmented data-parallel step wants every bucket's gradients final as the backward passes
+        # it) and not under recomputation (a recomputing Block must not keep its re-derived activations alive)
+        wb = WgradBatch() if (hook is None and not recompute and torch.is_grad_enabled()
+                              and ops.wgrad_batch_enabled()) else None
         for i, blk in enumerate(self.blocks):
             cut = False
             if hook is not None:
@@ -195,7 +200,7 @@ class DPOTNet(nn.Module):
                                 blk.norm2.bias, blk.mlp[0].weight, blk.mlp[0].bias, blk.mlp[2].weight,
                                 blk.mlp[2].bias, h, h, self.n_blocks, self.modes, self._act,
                                 (pk[2 * i], pk[2 * i + 1]), recompute, mlp_pk[i] if mlp_pk is not None else None,
-                                torch.is_grad_enabled(), i > 0 and not cut)
+                                torch.is_grad_enabled(), i > 0 and not cut, wb)
         if hook is not None:
             lat = hook(len(self.blocks) + 1, lat)
         ol, ch = self.out_layer, self.cls_head

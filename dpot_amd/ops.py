@@ -165,7 +165,9 @@ TUNE_KEYS = {
                        "un-paired weight gradients"),
     "packs": (1, "0 = bf16 packs by separate pack passes only: none from the one-launch AFNO layer, the GroupNorm backward or Adam"),
     "pack_both": (1, "0 = bf16 channel MLP without the pack-both path (one pack pass per operand form, fp32 pre-activation saved)"),
-    "fused_small": (1, "0 = separate small launches: per-block reduce launches, eight layout launches, torch ops for the cls head"),
+    "fused_small": (1, "0 = separate small launches: per-block reduce launches, eight layout launches, torch ops for the cls head; "
+                       "2 = as 1, but the blocks' weight gradients and their finalising launch per block instead of batched; "
+                       "3 = as 1 with the batched launches cut by the one-round rules (another summation order)"),
     "embed_implicit": (1, "0 = explicit patch matrix + GEMM instead of the implicit-GEMM patch embedding"),
     "mixer6": (1, "bf16x6 mixer kernel afno_mlp6 under gemm_precision 'auto' / 'bf16x6': 1 = where it measured faster (96 channels "
                   "per block: DPOT-L), 2 = wherever supported (also 128), 0 = never (the fp32 matrix-core kernels)"),
@@ -785,6 +787,106 @@ def block_finalize(afno_job, mlp_job, gn_jobs, cs_jobs=()):
 
 def block_finalize_enabled() -> bool:
     return tune("fused_small") != 0
+
+
+def wgrad_batch_enabled() -> bool:
+    """the weight gradients of all blocks in batched launches + one finalising launch (DPOT_TUNE fused_small=2: per block)"""
+    return tune("fused_small") in (1, 3)
+
+
+def wgrad_batch_one_round() -> bool:
+    """DPOT_TUNE fused_small=3: the batched launches cut the tokens by the one-round rules (`mlp_wgrad_batch_splitk`,
+    `afno_wgrad_batch_plan`) - another summation order than the per-block launches; default: the per-block split factors,
+    bit-identical gradients"""
+    return tune("fused_small") == 3
+
+
+def wgrad_batch_max_blocks() -> int:
+    return _lib.load().dpot_wgrad_batch_max_blocks()
+
+
+def afno_wgrad2_splits12(Mm: int, bs: int, splitk: int) -> int:
+    """token ranges of P1 / P2 in `afno_wgrad2` at `splitk`; 0 if one of them would be empty (TN_TOK = 32 tokens per slab)"""
+    s12 = _lib.load().dpot_afno_wgrad2_splits12(bs, splitk)
+    nslab = Mm // 32
+    return s12 if s12 >= 1 and -(-nslab // s12) * (s12 - 1) < nslab else 0
+
+
+def _ptr_array(tensors):
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def mlp_wgrad_batch_splitk(T: int, E: int, mh: int, n: int, precision: Optional[int] = None) -> int:
+    """split factor of the channel-MLP weight gradients of n blocks in one launch (0: not covered)"""
+    prec = _cur_gemm() if precision is None else precision
+    return _lib.load().dpot_mlp_wgrad_batch_splitk(T, E, mh, n) if prec == GEMM_F32 else 0
+
+
+def mlp_wgrad_batch(do2, Hh, xn2, dHpre, splitk: int) -> Tensor:
+    """partials of both channel-MLP weight gradients of len(do2) blocks (lists of per-block operands, as `mlp_wgrad2`):
+    returns the workspace [n, elems] - row i in the layout `mlp_wgrad2(defer=True)` leaves, for `wgrad_batch_finalize`"""
+    lib = _lib.load()
+    n = len(do2)
+    T, E = do2[0].shape
+    mh = Hh[0].shape[1]
+    for a, b, c, d in zip(do2, Hh, xn2, dHpre):
+        assert a.shape == (T, E) and c.shape == (T, E) and b.shape == (T, mh) and d.shape == (T, mh)
+        assert a.is_contiguous() and b.is_contiguous() and c.is_contiguous() and d.is_contiguous()
+    ws = torch.empty(n, lib.dpot_mlp_wgrad2_ws_elems(E, mh, splitk), dtype=torch.float32, device=do2[0].device)
+    check(lib.dpot_mlp_wgrad_batch(_ptr_array(do2), _ptr_array(Hh), _ptr_array(xn2), _ptr_array(dHpre), n, T, E, mh,
+                                   ws.data_ptr(), splitk, _stream()), "mlp_wgrad_batch")
+    return ws
+
+
+def afno_wgrad_batch_plan(Mm: int, nb: int, bs: int, n: int) -> Tuple[int, int, int]:
+    """(blocks per launch, splits12, splits) of the batched three-product AFNO weight gradient; blocks per launch 0: the
+    shape is not covered (per-block launches)"""
+    if _cur_gemm() not in (GEMM_F32, GEMM_AUTO):
+        return 0, 0, 0
+    s12, s = C.c_int(0), C.c_int(0)
+    per = _lib.load().dpot_afno_wgrad_batch_plan(Mm, nb, bs, n, C.byref(s12), C.byref(s))
+    return per, s12.value, s.value
+
+
+def afno_wgrad_batch(S, dO1pre, O1, dO2, nb: int, bs: int, per_launch: int, splits12: int, splitk: int) -> Tensor:
+    """partials of both AFNO weight gradients of len(S) blocks (lists of per-block operands, as `afno_wgrad2`), `per_launch`
+    blocks per launch: returns the workspace [n, elems], row i in the layout of `afno_wgrad2(defer=True)`"""
+    lib = _lib.load()
+    n = len(S)
+    Mm, ld = S[0].shape
+    for ts in (S, dO1pre, O1, dO2):
+        for t in ts:
+            assert t.shape == (Mm, ld) and t.is_contiguous()
+    ws = torch.empty(n, lib.dpot_afno_wgrad2_ws_elems(nb, bs, splitk), dtype=torch.float32, device=S[0].device)
+    check(lib.dpot_afno_wgrad_batch(_ptr_array(S), _ptr_array(dO1pre), _ptr_array(O1), _ptr_array(dO2), n, ld, Mm, nb, bs,
+                                    ws.data_ptr(), per_launch, splits12, splitk, _stream()), "afno_wgrad_batch")
+    return ws
+
+
+def wgrad_batch_finalize(afno, mlp, gn):
+    """ONE launch that finalises n blocks (csrc/gemm_tn.hip wgrad_batch_finalize_kernel).
+    afno: None | (ws [n, .], splits12, splitk, nb, bs, [(dw1, db1, dw2, db2)] * n);
+    mlp:  None | (ws [n, .], splitk, E, mh, [(dW2, db2, dW1, db1)] * n);
+    gn:   [[(part [2, B, E], dgamma, dbeta)] * jobs] * n  (jobs <= 2, outputs allocated by the caller)"""
+    n = len(gn)
+    blocks = (_lib.WgradBlock * n)()
+    jobs, B, Eg = len(gn[0]), 0, 0
+    for i in range(n):
+        w = blocks[i]
+        if afno is not None:
+            w.afno_ws = afno[0][i].data_ptr()
+            w.dw1, w.db1, w.dw2, w.db2 = (t.data_ptr() for t in afno[5][i])
+        if mlp is not None:
+            w.mlp_ws = mlp[0][i].data_ptr()
+            w.dW2, w.dfb2, w.dW1, w.dfb1 = (t.data_ptr() for t in mlp[4][i])
+        assert len(gn[i]) == jobs
+        for j, (part, dg, db) in enumerate(gn[i]):
+            _, B, Eg = part.shape
+            w.gn_part[j], w.gn_dgamma[j], w.gn_dbeta[j] = part.data_ptr(), dg.data_ptr(), db.data_ptr()
+    a = afno if afno is not None else (None, 0, 0, 0, 0)
+    m = mlp if mlp is not None else (None, 0, 0, 0)
+    check(_lib.load().dpot_wgrad_batch_finalize(blocks, n, a[1], a[2], a[3], a[4], m[1], m[2], m[3], jobs, B, Eg, _stream()),
+          "wgrad_batch_finalize")
 
 
 def afno_mlp2_supported(nb: int, bs: int) -> bool:

@@ -162,6 +162,8 @@ int dpot_mlp_wgrad2(const float* do2, const float* Hh, const float* xn2, const f
                     float* dW2, float* db2, float* dW1, float* db1, float* workspace, int splitk, dpot_stream_t stream);
 int dpot_afno_wgrad2_splitk(int Mm, int nb, int bs);
 int64_t dpot_afno_wgrad2_ws_elems(int nb, int bs, int splitk);
+/* token ranges of the products P1 / P2 of the three-product form at `splitk` ranges of the sum product (else splitk) */
+int dpot_afno_wgrad2_splits12(int bs, int splitk);
 int dpot_afno_wgrad2(const float* S, const float* dO1pre, const float* O1, const float* dO2, int ld, int Mm, int nb,
                      int bs, float* dw1, float* db1, float* dw2, float* db2, float* workspace, int splitk,
                      dpot_stream_t stream);
@@ -177,6 +179,40 @@ int dpot_block_finalize(const float* afno_ws, int afno_splitk, int nb, int bs, f
                         float* dfb1, const float* const* gn_parts, float* const* gn_dgammas, float* const* gn_dbetas,
                         int gn_jobs, int B, int Egn, const float* const* cs_parts, float* const* cs_outs, const int* cs_rows,
                         const int* cs_cols, int cs_jobs, dpot_stream_t stream);
+/* The weight gradients of SEVERAL DPOT blocks per launch (csrc/gemm_tn.hip).  No data gradient reads a weight gradient, so the
+ * blocks' small problems need not fill the chip one block at a time: n blocks in the problem table of one launch need 1/n of
+ * the split factor - longer token ranges per workgroup, 1/n of the partial-sum traffic - and ONE launch finalises them all.
+ * Each entry takes the per-block operand pointers (host arrays of n device pointers) and writes PARTIALS ONLY: block i's
+ * workspace is the i-th slice of `workspace`, in the layout of the per-block entry at the same split factor.  More blocks
+ * than dpot_wgrad_batch_max_blocks() are cut into several launches.  Fixed summation orders, no atomics.  At the split
+ * factors of the per-block entries (dpot_mlp_wgrad2_splitk; dpot_afno_wgrad2_splitk with dpot_afno_wgrad2_splits12) every
+ * partial and every sum is the per-block entries': bit-identical results, the launch runs several rounds of workgroups.  The
+ * ONE-ROUND rules below cut the tokens less deeply (less partial traffic, longer ranges): another summation order.
+ * dpot_mlp_wgrad_batch_splitk: max(1, 256 / tiles of a launch) token ranges of >= 4 slabs, none empty (0: shape not covered).
+ * dpot_afno_wgrad_batch_plan: blocks per launch and the split factors (splits12 token ranges for the products P1 / P2, splits
+ * for the sum product) such that sets * nb * (2 * splits12 + splits) <= 256 with splits12 : splits = 5 : 6 unless the tokens
+ * limit the split; 0: not covered (bs != 128 or DPOT_TUNE wgrad_gauss=0) - use the per-block entries.
+ * dpot_tn_split_range: the tokens [first_tok, first_tok + ntok) of range i when T tokens are cut into `splits` ranges. */
+typedef struct dpot_wgrad_block {
+  const float* afno_ws; float *dw1, *db1, *dw2, *db2;     /* as dpot_afno_wgrad2 */
+  const float* mlp_ws; float *dW2, *dfb2, *dW1, *dfb1;    /* as dpot_mlp_wgrad2 */
+  const float* gn_part[2]; float* gn_dgamma[2]; float* gn_dbeta[2];   /* as dpot_groupnorm_param_grads */
+} dpot_wgrad_block;
+int dpot_wgrad_batch_max_blocks(void);
+int dpot_tn_split_range(int T, int splits, int i, int* first_tok, int* ntok);
+int dpot_mlp_wgrad_batch_splitk(int T, int E, int mh, int n);
+int64_t dpot_mlp_wgrad_batch_ws_elems(int E, int mh, int splitk, int n);
+int dpot_mlp_wgrad_batch(const float* const* do2, const float* const* Hh, const float* const* xn2, const float* const* dHpre,
+                         int n, int T, int E, int mh, float* workspace, int splitk, dpot_stream_t stream);
+int dpot_afno_wgrad_batch_plan(int Mm, int nb, int bs, int n, int* splits12, int* splits);
+int64_t dpot_afno_wgrad_batch_ws_elems(int nb, int bs, int splitk, int n);
+int dpot_afno_wgrad_batch(const float* const* S, const float* const* dO1pre, const float* const* O1, const float* const* dO2,
+                          int n, int ld, int Mm, int nb, int bs, float* workspace, int per_launch, int splits12, int splitk,
+                          dpot_stream_t stream);
+/* ONE finalising launch for n blocks: per block the slices of dpot_block_finalize (AFNO partials when afno_splitk > 0,
+ * channel-MLP partials when mlp_splitk > 0, gn_jobs <= 2 GroupNorm parameter gradients), the same reduction bodies. */
+int dpot_wgrad_batch_finalize(const dpot_wgrad_block* blocks, int n, int afno_splits12, int afno_splitk, int nb, int bs,
+                              int mlp_splitk, int E, int mh, int gn_jobs, int B, int Egn, dpot_stream_t stream);
 /* Small weight-only layout jobs (zero-padded copies, small transposes, bias broadcasts, "+ bias") in ONE launch from a DEVICE
  * table: dst[i0][i1][i2] (contiguous d0 x d1 x d2) = (inside v0 x v1 x v2 ? src[i0 s0 + i1 s1 + i2 s2] : 0) + (add ? add[i2] : 0).
  * The pieces DPOTNet derives from its parameters once per optimiser step (models/dpot.py:198-202 padded for the MFMA
