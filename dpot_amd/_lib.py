@@ -108,6 +108,9 @@ SIGNATURES = {
     "dpot_rfft2_norm": (c_i, [c_fp] * 5 + [c_i, c_fp] + [c_i] * 8 + [c_fp]),
     "dpot_irfft2_norm": (c_i, [c_fp] * 6 + [c_i, c_fp] + [c_i] * 8 + [c_fp]),
     "dpot_irfft2": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 8 + [c_fp]),
+    "dpot_dft3_supported": (c_i, [c_i] * 7),
+    "dpot_rfft3": (c_i, [c_fp, c_fp] + [c_i] * 10 + [c_fp]),
+    "dpot_irfft3": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 10 + [c_fp]),
     "dpot_afno_pack": (c_i, [c_fp] * 4 + [c_i, c_i, c_fp]),
     "dpot_afno_pack_multi": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i, c_i, c_i, c_fp]),
     "dpot_afno_unpack_grad": (c_i, [c_fp] * 4 + [c_i, c_i, c_fp]),

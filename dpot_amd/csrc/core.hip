@@ -45,7 +45,8 @@ int tune(const char* key, int dflt) {
  * dpot_afno_fused_bwd removed; every fallback selector behind DPOT_TUNE
  * 264: dpot_spectral_resize, dpot_spectral_resize_pad (csrc/resize.hip)
  * 266: dpot_mlp_wgrad_batch, dpot_afno_wgrad_batch, dpot_wgrad_batch_finalize and their queries (csrc/gemm_tn.hip): the weight
- * gradients of several DPOT blocks per launch */
-extern "C" int dpot_version(void) { return 266; }
+ * gradients of several DPOT blocks per launch
+ * 267: dpot_dft3_supported, dpot_rfft3, dpot_irfft3 (csrc/dft3.hip): the transforms of the 3-D model's AFNO3D */
+extern "C" int dpot_version(void) { return 267; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

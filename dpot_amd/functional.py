@@ -5,6 +5,7 @@ kernels directly (no autograd tracing inside a stage, no eager-PyTorch math):
   BlockFn   GroupNorm -> AFNO mixer -> GroupNorm -> channel MLP -> +residual                        models/dpot.py:165-180
   HeadFn    out_layer (ConvTranspose as GEMM + pixel tail) and cls_head                             models/dpot.py:394-398
   RelL2Fn   masked relative L2 loss                                                                 utils/criterion.py:38-59
+  AFNO3DFn, GroupNormFn, Mlp2Fn, TimeAggFn, Head3DFn, block3d   the 3-D model's stages          models/dpot3d.py
 
 Internal activation layout: channels-last tokens [B, h*w, E] (row-major [B*h*w, E]).
 
@@ -1149,3 +1150,224 @@ def cls_ce_loss(logits: Tensor, labels: Tensor, out: Optional[Tensor] = None):
     the logits) and the count of rows whose first maximal logit is the label.  Rows with a label outside [0, n_cls) add
     nothing to either and get a zero gradient; `out` (optional 4-word int64 slot) then holds their count in word 3."""
     return ClsCEFn.apply(logits, labels, [out] if out is not None else None)
+
+
+# ======================================================================================================
+# 3-D model (models/dpot3d.py): AFNO3D on the kernels of csrc/dft3.hip, and the plain stages of DPOTNet3D
+# ======================================================================================================
+def _mixer3_dims(B: int, tok: int, E: int, nb: int, m3, act: int):
+    """the `dims` tuple of _mixer_core / _mixer_core_bwd for a 3-D box: they read only B * mx * my (the kept-mode rows), so the
+    two mode slots carry (mx * my, mz); the grid slots are unused"""
+    mx, my, mz = m3
+    return (B, tok, E, 0, 0, nb, E // nb, mx * my, mz, 0, act)
+
+
+class AFNO3DFn(torch.autograd.Function):
+    """The reference's ``AFNO3D`` (models/dpot3d.py:46-97) on a channels-last field x[B, X*Y*Z, E] (z fastest):
+    irfftn(MLP(rfftn(x)[:modes, :modes, :8])) + x.  The 3-D twin of AFNO2DFn: rfft3 -> _mixer_core -> irfft3 (+ x); backward
+    rfft3(dy, w(kz)) -> _mixer_core_bwd -> irfft3(dS, w = 1) + dy."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, dims3, nb: int, modes: int, act: int, packed=None):
+        ops.capture_precision(ctx)
+        x = x.contiguous()
+        B, tok, E = x.shape
+        dims3 = tuple(int(d) for d in dims3)
+        assert tok == dims3[0] * dims3[1] * dims3[2], f"{tok} tokens are not a {dims3} grid"
+        m3 = ops.kept_modes3(dims3, modes)
+        if packed is None:
+            packed = tuple(ops.AfnoPacks([(w1, b1), (w2, b2)]).refresh())
+        dims = _mixer3_dims(B, tok, E, nb, m3, act)
+        S = ops.rfft3(x, dims3, nb, m3, 0)                                   # [Mm, 2E]
+        O2, O1pre, O1 = _mixer_core(S, packed, dims)
+        y = ops.irfft3(O2, B, dims3, E, nb, m3, 1, res=x)                    # + x_orig
+        ctx.fused = packed[0][2] is not None
+        wb1, wb2 = (packed[0][3], packed[1][3]) if ctx.fused else (packed[0][0], packed[1][0])
+        ctx.afno_layout = getattr(packed[0], "layout", 0) if ctx.fused else 0
+        ctx.p6b = _p6_of(packed, 1) if ctx.fused else None
+        ctx.save_for_backward(S, O1pre, O1, wb1, wb2)
+        ctx.dims, ctx.dims3, ctx.m3 = dims, dims3, m3
+        ctx.sinks = _sinks(ctx, (w1, b1, w2, b2), 1)
+        ctx.weights_epoch = _epoch_of(ctx.sinks)
+        return y
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dy):
+        _check_epoch(ctx, "AFNO3DFn")
+        S, O1pre, O1, wb1, wb2 = ctx.saved_tensors
+        lay = ctx.afno_layout
+        if ctx.p6b is not None:
+            (wb1, wb2), lay = ctx.p6b, 2
+        dy = dy.contiguous()
+        B, _, E = dy.shape
+        nb = ctx.dims[5]
+        dO2 = ops.rfft3(dy, ctx.dims3, nb, ctx.m3, 1)                        # adjoint of irfft3
+        dS, dw1, db1, dw2, db2 = _mixer_core_bwd(dO2, S, O1pre, O1, wb1, wb2, ctx.dims, ctx.fused, lay, ctx.sinks)
+        dx = ops.irfft3(dS, B, ctx.dims3, E, nb, ctx.m3, 0, res=dy)          # adjoint of rfft3, + skip path
+        return dx, dw1, db1, dw2, db2, None, None, None, None, None
+
+
+class GroupNormFn(torch.autograd.Function):
+    """GroupNorm(G, E) of a channels-last field x[B, tokens, E] (any number of spatial axes flattened into the tokens)"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, G: int = 8):
+        x = x.contiguous()
+        y, mean, rstd = ops.groupnorm_fwd(x, gamma, beta, G)
+        ctx.save_for_backward(x, mean, rstd, gamma)
+        ctx.G = G
+        ctx.sinks = _sinks(ctx, (gamma, beta), 1)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, rstd, gamma = ctx.saved_tensors
+        s_g, s_b = ctx.sinks
+        dx, dg, db = ops.groupnorm_bwd(dy.contiguous(), x, mean, rstd, gamma, ctx.G, out_dgamma=s_g.out(),
+                                       out_dbeta=s_b.out())
+        return dx, s_g.done(dg), s_b.done(db), None
+
+
+class Mlp2Fn(torch.autograd.Function):
+    """y[M, N] = act(x[M, K] W1[H, K]^T + b1) W2[N, H]^T + b2 (+ res): two 1x1 convolutions / Linears with the activation in
+    the first GEMM's epilogue.  res [M, N] is added row by row; res [R, N] with res_mod = R is added to row m as res[m % R]
+    (a per-token table under a batch).  Weights are 2-D views of the parameters."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2, act: int, res=None, res_mod: int = 0):
+        ops.capture_precision(ctx)
+        x, W1, W2 = x.contiguous(), W1.contiguous(), W2.contiguous()
+        res = res.contiguous() if res is not None else None
+        Hh, Hpre = ops.linear_fwd(x, W1, b1, act=act, save_pre=True)
+        y, _ = ops.linear_fwd(Hh, W2, b2, res=res, res_mod=res_mod)
+        ctx.save_for_backward(x, Hh, Hpre, W1, W2)
+        ctx.act, ctx.res_mod, ctx.has_res = act, res_mod, res is not None
+        return y
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dy):
+        x, Hh, Hpre, W1, W2 = ctx.saved_tensors
+        dy = dy.contiguous()
+        M, N = dy.shape
+        dHpre = ops.linear_bwd_data(dy, W2, act=ctx.act, aux=Hpre)          # (dy W2) * act'(Hpre)
+        dW2, db2 = ops.linear_bwd_wb(dy, Hh)
+        dW1, db1 = ops.linear_bwd_wb(dHpre, x)
+        dx = ops.linear_bwd_data(dHpre, W1) if ctx.needs_input_grad[0] else None
+        dres = None
+        if ctx.has_res and ctx.needs_input_grad[6]:
+            dres = dy if not ctx.res_mod else ops.group_rowsum(dy, M // ctx.res_mod, ctx.res_mod, 1, N)
+        return dx, dW1, db1, dW2, db2, None, dres, None
+
+
+class TimeAggFn(torch.autograd.Function):
+    """TimeAggregator (models/dpot3d.py:143-151) on rows A[M, T*E] (columns (t, i)): y[m, j] = sum_{t,i} A[m, (t,i)] ws[t,i,j]
+    with ws = w (time_agg 'mlp') or w * cos(t gamma_i) ('exp_mlp': gamma given)"""
+
+    @staticmethod
+    def forward(ctx, A, w, gamma, tt):
+        ops.capture_precision(ctx)
+        A = A.contiguous()
+        T, E, _ = w.shape
+        M = A.shape[0]
+        ws = ops.timeagg_scale_w(w, gamma, tt) if gamma is not None else w
+        y = torch.empty(M, E, dtype=torch.float32, device=A.device)
+        ops.gemm(A, ws, y, M, E, T * E, lda=T * E, ldb=E, ldc=E)
+        ctx.save_for_backward(A, ws, w, gamma, tt)
+        ctx.sinks = _sinks(ctx, (w, gamma), 1)
+        ctx.weights_epoch = _epoch_of(ctx.sinks)
+        return y
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dy):
+        A, ws, w, gamma, tt = ctx.saved_tensors
+        s_w, s_g = ctx.sinks
+        T, E, _ = w.shape
+        M = A.shape[0]
+        dy = dy.contiguous()
+        dev = dy.device
+        dA = None
+        if ctx.needs_input_grad[0]:
+            dA = torch.empty(M, T * E, dtype=torch.float32, device=dev)
+            ops.gemm(dy, ws, dA, M, T * E, E, transB=True, lda=E, ldb=E, ldc=T * E)
+        dws = ops._out(s_w.out() if gamma is None else None, (T, E, E), dev)
+        ops.gemm(A, dy, dws, T * E, E, M, transA=True, lda=T * E, ldb=E, ldc=E,
+                 splitk=ops.auto_splitk(T * E, E, M, tn=True))
+        if gamma is not None:
+            dw, dgamma = ops.timeagg_scale_w_bwd(dws, w, gamma, tt, out_dw=s_w.out(), out_dgamma=s_g.out())
+            dw, dgamma = s_w.done(dw), s_g.done(dgamma)
+        else:
+            dw, dgamma = s_w.done(dws), None
+        return dA, dw, dgamma, None
+
+
+def _unfold3(t: Tensor, B: int, h: int, P: int, old: int) -> Tensor:
+    """[B*h^3, old*P^3] (rows (b, hx, hy, hz), columns (o, i, j, k)) -> [B*(hP)^3, old] (rows (b, x, y, z)): the scatter of a
+    k = s = P transposed convolution"""
+    return t.view(B, h, h, h, old, P, P, P).permute(0, 1, 5, 2, 6, 3, 7, 4).reshape(B * (h * P) ** 3, old)
+
+
+def _fold3(t: Tensor, B: int, h: int, P: int, old: int) -> Tensor:
+    """inverse of _unfold3"""
+    return t.view(B, h, P, h, P, h, P, old).permute(0, 1, 3, 5, 7, 2, 4, 6).reshape(B * h ** 3, old * P ** 3)
+
+
+class Head3DFn(torch.autograd.Function):
+    """out_layer of DPOTNet3D (models/dpot3d.py:301-307): ConvTranspose3d(E -> old, k = s = P), act, Conv3d(old -> old, 1), act,
+    Conv3d(old -> Co, 1) on latent rows x[B*h^3, E] -> [B*(hP)^3, Co] (rows (b, x, y, z)).  W0 [E, old*P^3] is the transposed
+    convolution's weight viewed 2-D, b0e its bias repeated over the P^3 taps (column order (o, i, j, k))."""
+
+    @staticmethod
+    def forward(ctx, x, W0, b0e, W2, b2, W4, b4, B: int, h: int, P: int, act: int):
+        ops.capture_precision(ctx)
+        x, W0, W2, W4 = x.contiguous(), W0.contiguous(), W2.contiguous(), W4.contiguous()
+        M, E = x.shape
+        old = W2.shape[0]
+        N0 = old * P ** 3
+        H1 = torch.empty(M, N0, dtype=torch.float32, device=x.device)
+        H1pre = torch.empty_like(H1)
+        ops.gemm(x, W0, H1, M, N0, E, lda=E, ldb=N0, ldc=N0, bias=b0e.contiguous(), act=act, mode=EPI_ACT, preact=H1pre,
+                 ldpre=N0)
+        H1p, H1pre_p = _unfold3(H1, B, h, P, old), _unfold3(H1pre, B, h, P, old)
+        del H1, H1pre
+        H2, H2pre = ops.linear_fwd(H1p, W2, b2, act=act, save_pre=True)
+        out, _ = ops.linear_fwd(H2, W4, b4)
+        ctx.save_for_backward(x, W0, W2, W4, H1p, H1pre_p, H2, H2pre)
+        ctx.dims = (B, h, P, old, act)
+        return out
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dout):
+        x, W0, W2, W4, H1p, H1pre_p, H2, H2pre = ctx.saved_tensors
+        B, h, P, old, act = ctx.dims
+        M, E = x.shape
+        N0 = old * P ** 3
+        dev = x.device
+        dout = dout.contiguous()
+        dH2pre = ops.linear_bwd_data(dout, W4, act=act, aux=H2pre)
+        dW4, db4 = ops.linear_bwd_wb(dout, H2)
+        dH1pre_p = ops.linear_bwd_data(dH2pre, W2, act=act, aux=H1pre_p)
+        dW2, db2 = ops.linear_bwd_wb(dH2pre, H1p)
+        dH1pre = _fold3(dH1pre_p, B, h, P, old)                             # [M, old*P^3]
+        dW0 = torch.empty(E, N0, dtype=torch.float32, device=dev)
+        ops.gemm(x, dH1pre, dW0, E, N0, M, transA=True, lda=E, ldb=N0, ldc=N0, splitk=ops.auto_splitk(E, N0, M, tn=True))
+        db0e = ops.colsum(dH1pre, M, N0)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(M, E, dtype=torch.float32, device=dev)
+            ops.gemm(dH1pre, W0, dx, M, E, N0, transB=True, lda=N0, ldb=N0, ldc=E)
+        return dx, dW0, db0e, dW2, db2, dW4, db4, None, None, None, None
+
+
+def block3d(x, n1w, n1b, w1, b1, w2, b2, n2w, n2b, f1w, f1b, f2w, f2b, dims3, nb: int, modes: int, act: int, packed=None):
+    """``Block`` of models/dpot3d.py:208-225 (double_skip=False) on x[B, X*Y*Z, E]:  MLP(GN2(AFNO3D(GN1(x)))) + x"""
+    B, tok, E = x.shape
+    mh = f1w.shape[0]
+    xn1 = GroupNormFn.apply(x, n1w, n1b, 8)
+    y1 = AFNO3DFn.apply(xn1, w1, b1, w2, b2, dims3, nb, modes, act, packed)
+    xn2 = GroupNormFn.apply(y1, n2w, n2b, 8)
+    out = Mlp2Fn.apply(xn2.view(B * tok, E), f1w.view(mh, E), f1b, f2w.view(E, mh), f2b, act, x.reshape(B * tok, E), 0)
+    return out.view(B, tok, E)

@@ -4,6 +4,8 @@
   utils/utilities.py:99-166 (``module.`` prefix of DDP checkpoints stripped; fine-tuning may take only some
   components from a pretrained state_dict), written against the same sub-module names, so a pretrained ``.pth``
   (``torch.load(path)['model']``, README.md:30) loads unchanged.
+* ``load_3d_components_from_2d`` - utils/utilities.py:170-207: the blocks and the time aggregator of a pretrained 2-D
+  checkpoint into a ``DPOTNet3D`` (the 3-D fine-tuning path of finetune3d.py).
 * ``rollout_eval`` / ``GraphedRollout`` - the no-grad rollout of evaluate.py:183-222: the model's own prediction is
   appended to the input window step after step; returns the prediction, the per-step loss sum and the loss of the
   whole trajectory (both SimpleLpLoss(size_average=False)).  With fixed shapes the single forward step is one
@@ -88,6 +90,32 @@ def load_components_from_pretrained(model: nn.Module, state_dict: Union[str, Map
             warnings.warn(f"load_components_from_pretrained: this model has no {name!r} component - skipped")
         else:
             raise KeyError(f"unknown component {name!r} (known: {COMPONENTS})")
+
+
+def load_3d_components_from_2d(model: nn.Module, state_dict: Union[str, Mapping],
+                               components: Union[str, Iterable[str]] = "all") -> None:
+    """utils/utilities.py:170-207: a DPOTNet3D takes components of a pretrained 2-D checkpoint.  'all' loads the whole state
+    dict (it must then be a 3-D one), 'blocks' copies every block - the 1 x 1 Conv2d weights of the channel MLP (keys holding
+    both 'mlp' and 'weight') gain a trailing axis and become Conv3d weights - and 'time_agg' the time aggregator; any other
+    name is reported and skipped, as the reference prints 'Submodule does not exists' and carries on.  Values are copied in
+    place (load_state_dict), so an existing FlatParams binding stays valid."""
+    sd = _plain_state_dict(state_dict)
+    if components == "all" or "all" in components:
+        model.load_state_dict(sd)
+        return
+    for name in components:
+        if name == "blocks" and hasattr(model, "blocks"):
+            for i, block in enumerate(model.blocks):
+                bsd = _sub(sd, f"blocks.{i}.")
+                for k, v in bsd.items():
+                    if "mlp" in k and "weight" in k:
+                        bsd[k] = v.unsqueeze(-1)                  # Conv2d [o, i, 1, 1] -> Conv3d [o, i, 1, 1, 1]
+                block.load_state_dict(bsd)
+        elif name == "time_agg" and hasattr(model, "time_agg_layer"):
+            model.time_agg_layer.load_state_dict(_sub(sd, "time_agg_layer."))
+        else:
+            warnings.warn(f"load_3d_components_from_2d: component {name!r} is not one a 3-D model takes from a 2-D checkpoint "
+                          "('blocks', 'time_agg') or this model does not have it - skipped")
 
 
 # ------------------------------------------------------------------------------------------------------

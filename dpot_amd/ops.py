@@ -611,6 +611,49 @@ def irfft2(spec: Tensor, B: int, h: int, w: int, E: int, nb: int, mx: int, my: i
     return y
 
 
+def kept_modes3(dims, modes: int, temporal_modes: int = 8) -> Tuple[int, int, int]:
+    """the box AFNO3D keeps of rfftn's half spectrum (models/dpot3d.py:64): [:modes, :modes, :temporal_modes]"""
+    X, Y, Z = dims
+    return min(modes, X), min(modes, Y), min(temporal_modes, Z // 2 + 1)
+
+
+def dft3_supported(dims, E: int, modes3) -> bool:
+    """whether one sample's channel slab of an X x Y x Z latent cube fits the LDS (host only, no GPU needed)"""
+    X, Y, Z = dims
+    mx, my, mz = modes3
+    return bool(_lib.load().dpot_dft3_supported(X, Y, Z, E, mx, my, mz))
+
+
+def rfft3(x: Tensor, dims, nb: int, modes3, col_weights: int = 0) -> Tensor:
+    """x[B, X*Y*Z, E] -> spec[B*mx*my*mz, 2E] (rows (b, kx, ky, kz), planar per channel block): w(kz) * rfftn(x, ortho) on
+    the kept box; col_weights = 1: the adjoint of irfft3"""
+    X, Y, Z = dims
+    mx, my, mz = modes3
+    B, E = x.shape[0], x.shape[-1]
+    if not dft3_supported(dims, E, modes3):
+        raise ValueError(f"rfft3: the latent grid {X}x{Y}x{Z} (kept modes {mx}x{my}x{mz}, {E} channels) is not supported: "
+                         "one sample's channel slab does not fit the LDS")
+    spec = torch.empty(B * mx * my * mz, 2 * E, dtype=torch.float32, device=x.device)
+    check(_lib.load().dpot_rfft3(_req(x, "x").data_ptr(), spec.data_ptr(), B, X, Y, Z, E, nb, mx, my, mz, col_weights,
+                                 _stream()), "rfft3")
+    return spec
+
+
+def irfft3(spec: Tensor, B: int, dims, E: int, nb: int, modes3, col_weights: int = 1,
+           res: Optional[Tensor] = None) -> Tensor:
+    """spec[B*mx*my*mz, 2E] -> y[B, X*Y*Z, E]: what irfftn(s=(X, Y, Z), ortho) gives for the zero-padded box, also for a
+    spectrum that is not Hermitian (col_weights = 1); col_weights = 0: the adjoint of rfft3.  `res` is added"""
+    X, Y, Z = dims
+    mx, my, mz = modes3
+    if not dft3_supported(dims, E, modes3):
+        raise ValueError(f"irfft3: the latent grid {X}x{Y}x{Z} (kept modes {mx}x{my}x{mz}, {E} channels) is not supported: "
+                         "one sample's channel slab does not fit the LDS")
+    y = torch.empty(B, X * Y * Z, E, dtype=torch.float32, device=spec.device)
+    check(_lib.load().dpot_irfft3(_req(spec, "spec").data_ptr(), _p(res), y.data_ptr(), B, X, Y, Z, E, nb, mx, my, mz,
+                                  col_weights, _stream()), "irfft3")
+    return y
+
+
 def afno_pack(w: Tensor, b: Tensor) -> Tuple[Tensor, Tensor]:
     _, nb, bs, _ = w.shape
     wbig = torch.empty(nb, 2 * bs, 2 * bs, dtype=torch.float32, device=w.device)

@@ -263,6 +263,29 @@ int dpot_irfft2_norm(const float* spec, const float* res, const float* mean, con
                      const float* beta, int G, float* y, int B, int h, int w, int E, int nb, int mx, int my,
                      int col_weights, dpot_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * rfftn / irfftn, norm="ortho", over the three spatial axes of a channels-last latent cube with the box
+ * truncation of models/dpot3d.py:46-97 (AFNO3D), as three in-LDS direct DFT passes (csrc/dft3.hip).
+ *
+ * field    x[B, X*Y*Z, E]          channels last, z fastest among the spatial axes ('b x y z c')
+ * spectrum spec[B*mx*my*mz, 2E]    rows (b, kx, ky, kz), columns per channel block [re(bs) | im(bs)] - the layout of
+ *                                  dpot_rfft2, so the same mixer kernels consume it
+ * kept box kx < mx <= X, ky < my <= Y (rows 0..m-1 only, no negative frequencies), kz < mz <= Z/2 + 1.
+ *
+ * col_weights applies w(kz): 0 -> w = 1; 1 -> w = 1 at kz = 0 and (Z even) kz = Z/2, else 2.
+ *   dpot_rfft3 (x, w=0) = rfftn(x)[:, :mx, :my, :mz]     dpot_rfft3 (g, w=1) = adjoint of irfftn applied to g
+ *   dpot_irfft3(S, w=1) = Re sum_k w(kz) S e^{+2 pi i (kx x/X + ky y/Y + kz z/Z)} / sqrt(XYZ) - what torch.fft.irfftn
+ *     gives for the zero-padded box, also where S is not Hermitian on the kz = 0 / Nyquist planes
+ *   dpot_irfft3(G, w=0) = adjoint of rfftn applied to G.      `res` ([B, X*Y*Z, E], may be NULL) is added.
+ * Any X, Y, Z (odd, non-cubic).  A slab of one sample must fit the LDS: dpot_dft3_supported (host only; 8^3 and 16^3 cubes
+ * are covered, 64^3 is not) - otherwise the launchers return DPOT_EUNSUP and launch nothing.
+ * ------------------------------------------------------------------------------------------------ */
+int dpot_dft3_supported(int X, int Y, int Z, int E, int mx, int my, int mz);
+int dpot_rfft3(const float* x, float* spec, int B, int X, int Y, int Z, int E, int nb, int mx, int my, int mz,
+               int col_weights, dpot_stream_t stream);
+int dpot_irfft3(const float* spec, const float* res, float* y, int B, int X, int Y, int Z, int E, int nb, int mx,
+                int my, int mz, int col_weights, dpot_stream_t stream);
+
 /* AFNO weight packing: w[2,nb,bs,bs], b[2,nb,bs] -> Wbig[nb,2bs,2bs] = [[Wr,Wi],[-Wi,Wr]], bbig[nb,2,bs]
  * and the adjoint (gradients back to the reference layout).  models/dpot.py:45-48,72-94 */
 int dpot_afno_pack(const float* w, const float* b, float* wbig, float* bbig, int nb, int bs,
