@@ -16,8 +16,8 @@ kernels, and the data-parallel reducer is notified the moment a parameter's grad
 from __future__ import annotations
 
 import os
-from collections import OrderedDict
-from typing import Optional
+from collections import OrderedDict, namedtuple
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -76,6 +76,15 @@ class _Sink:
             fp.fire(i)
 
 
+_AFNO_PARAMS = ("w1", "b1", "w2", "b2")
+_MLP_PARAMS = ("f2w", "f2b", "f1w", "f1b")                # in the order of the weight-gradient launches' outputs
+_GN_PARAMS = (("n1w", "n1b"), ("n2w", "n2b"))
+_BLOCK_PARAMS = _GN_PARAMS[0] + _AFNO_PARAMS + _GN_PARAMS[1] + ("f1w", "f1b", "f2w", "f2b")          # BlockFn's order
+# a Block's entry in its forward pass's WgradBatch: key = (M, E, mh, mp, (Mm, nb, bs), shape of a GroupNorm partial),
+# mlp = (do2, Hh, xn2, dHpre), afno = (S, dO1pre, O1, dO2), gn = the partials of norm1, norm2, sinks = {parameter name: _Sink}
+WgradJob = namedtuple("WgradJob", "key mlp afno gn sinks")
+
+
 class WgradBatch:
     """The weight gradients of all Blocks of ONE forward pass, computed when the last of them has run its backward.
 
@@ -94,8 +103,7 @@ class WgradBatch:
     summation order)."""
 
     def __init__(self):
-        self.expected = 0
-        self.delivered = 0
+        self.expected = self.delivered = 0
         self.jobs = []
 
     def register(self) -> None:
@@ -106,7 +114,7 @@ class WgradBatch:
         self.delivered += 1
         self._maybe_flush()
 
-    def deliver(self, job: dict) -> None:
+    def deliver(self, job: WgradJob) -> None:
         self.jobs.append(job)
         self.delivered += 1
         self._maybe_flush()
@@ -117,7 +125,7 @@ class WgradBatch:
         jobs, self.jobs, self.delivered = self.jobs, [], 0
         groups = {}
         for j in jobs:
-            groups.setdefault(j["key"], []).append(j)
+            groups.setdefault(j.key, []).append(j)
         for g in groups.values():
             self._flush_group(g)
 
@@ -134,30 +142,24 @@ class WgradBatch:
 
     @staticmethod
     def _flush_group(g) -> None:
-        n = len(g)
-        M, E, mh, mp, adims, _ = g[0]["key"]
-        dev = g[0]["mlp"][0].device
-        skm, per, s12, sk = WgradBatch.splits(n, M, E, mh, mp, *adims)
-        mws = ops.mlp_wgrad_batch(*[[j["mlp"][k] for j in g] for k in range(4)], skm)
-        # outputs: the parameters' gradient slots where this is the step's first contribution, temporaries otherwise
-        mouts = [tuple(ops._out(sk.out(), shp, dev) for sk, shp in zip(j["mlp_sinks"], ((E, mh), (E,), (mh, E), (mh,))))
-                 for j in g]
+        M, E, mh, mp, adims, _ = g[0].key
+        dev = g[0].mlp[0].device
+        skm, per, s12, sk = WgradBatch.splits(len(g), M, E, mh, mp, *adims)
+        mws = ops.mlp_wgrad_batch(*[[j.mlp[k] for j in g] for k in range(4)], skm)
+        def outs(j, names, shapes):      # the gradient slots where this is the step's first contribution, else temporaries
+            return tuple(ops._out(j.sinks[nm].out(), shp, dev) for nm, shp in zip(names, shapes))
+        mouts = [outs(j, _MLP_PARAMS, ((E, mh), (E,), (mh, E), (mh,))) for j in g]
         Mm, nb, bs = adims
-        aws = ops.afno_wgrad_batch(*[[j["afno"][k] for j in g] for k in range(4)], nb, bs, per, s12, sk)
-        aouts = [tuple(ops._out(sk_.out(), shp, dev)
-                       for sk_, shp in zip(j["afno_sinks"], ((2, nb, bs, bs), (2, nb, bs), (2, nb, bs, bs), (2, nb, bs))))
-                 for j in g]
-        afno = (aws, s12, sk, nb, bs, aouts)
-        gn = [[(part, ops._out(sg.out(), (E,), dev), ops._out(sb.out(), (E,), dev)) for part, sg, sb in j["gn"]] for j in g]
-        ops.wgrad_batch_finalize(afno, (mws, skm, E, mh, mouts), gn)
+        aws = ops.afno_wgrad_batch(*[[j.afno[k] for j in g] for k in range(4)], nb, bs, per, s12, sk)
+        aouts = [outs(j, _AFNO_PARAMS, ((2, nb, bs, bs), (2, nb, bs)) * 2) for j in g]
+        gn = [[(part,) + outs(j, names, ((E,), (E,))) for part, names in zip(j.gn, _GN_PARAMS)] for j in g]
+        ops.wgrad_batch_finalize((aws, s12, sk, nb, bs, aouts), (mws, skm, E, mh, mouts), gn)
         for i, j in enumerate(g):
             dW2, db2, dW1, db1 = mouts[i]
-            s_f2w, s_f2b, s_f1w, s_f1b = j["mlp_sinks"]
-            s_f2w.done(dW2.view(E, mh, 1, 1)), s_f2b.done(db2), s_f1w.done(dW1.view(mh, E, 1, 1)), s_f1b.done(db1)
-            for sk_, t in zip(j["afno_sinks"], aouts[i]):
-                sk_.done(t)
-            for (_, sg, sb), (_, dg, db) in zip(j["gn"], gn[i]):
-                sg.done(dg), sb.done(db)
+            (_, dg1, db1n), (_, dg2, db2n) = gn[i]
+            final = (dW2.view(E, mh, 1, 1), db2, dW1.view(mh, E, 1, 1), db1) + aouts[i] + (dg1, db1n, dg2, db2n)
+            for nm, t in zip(_MLP_PARAMS + _AFNO_PARAMS + _GN_PARAMS[0] + _GN_PARAMS[1], final):
+                j.sinks[nm].done(t)
 
 
 def _epoch_of(sinks):
@@ -350,9 +352,6 @@ class EmbedFn(torch.autograd.Function):
 
 
 # ======================================================================================================
-X6_MIN_FLOP = 3.0e9      # 'auto': GEMMs below this stay on the native fp32 kernels (launch / pack overheads dominate)
-
-
 def mlp_pack_kind(E: int, mh: int, M: Optional[int] = None) -> Optional[str]:
     """which pre-packed-weight kernel family the channel MLP of a model uses under the current precision settings:
     'bf16' (opt-in reduced precision), 'bf16x6' (fp32-accurate operand split; precision 'bf16x6', or 'auto' for GEMMs of
@@ -387,127 +386,243 @@ def _mlp_panel_mode(mlp_pk, M, E, mh, mp) -> int:
     return 2 if ok else 0
 
 
-def _p6_of(packed, which: int):
-    """the bf16x6 mixer packs (csrc/afno_mlp6.hip) of a filter's two AfnoItems - which = 0: forward operands, 1: backward-data
-    operands - when the GEMM precision in effect asks for them ('auto' / 'bf16x6'), else None"""
-    a, b = getattr(packed[0], "p6", None), getattr(packed[1], "p6", None)
-    if a is None or b is None or a[which] is None or b[which] is None or not ops.afno_mlp6_wanted():
-        return None
-    return a[which], b[which]
+class MixerWeights(NamedTuple):
+    """One filter's two packed layers (a pair of ops.AfnoItem) resolved ONCE per forward, under the precision in effect, into the
+    operands each launch takes.  The packs are epoch-checked persistent buffers: the ctx keeps the view (`for_backward`)."""
+    fused: bool               # both layers in one launch (ops.afno_mlp2, csrc/afno_mlp.hip); else the generic batched GEMM
+    fwd: Optional[tuple]      # (w1T, b1, w2T, b2) of the forward: fragment packs (fused) or the plain Wbig / bbig (generic)
+    layout: int               # of fwd's and bwd's packs: 0 fragment-block-major Wbig, 1 (Wr, Wi) fragments, 2 bf16x6
+    bwd: tuple                # (w1, w2) the backward data path multiplies by: packs of W^T (fused) or the plain Wbig
+    base: Optional[tuple]     # (w1T, b1, w2T, b2) for the one-launch AFNO layer (ops.afno_fused_fwd): never the bf16x6 packs
+    base_layout: int
+
+    @classmethod
+    def of(cls, packed) -> "MixerWeights":
+        a, b = packed
+        if a.fwd is None:
+            return cls(False, (a.wbig, a.bbig, b.wbig, b.bbig), 0, (a.wbig, b.wbig), None, 0)
+        base = (a.fwd, a.bbig, b.fwd, b.bbig)
+        if a.p6 is not None and b.p6 is not None and ops.afno_mlp6_wanted():
+            # fp32-accurate on the bf16 matrix cores (gemm_precision 'auto' / 'bf16x6', csrc/afno_mlp6.hip): same contract
+            return cls(True, (a.p6[0], a.bbig, b.p6[0], b.bbig), 2, (a.p6[1], b.p6[1]), base, a.layout)
+        return cls(True, base, a.layout, (a.bwd, b.bwd), base, a.layout)
+
+    def for_backward(self, recompute: bool) -> "MixerWeights":
+        """what the ctx keeps: all of it when the backward runs the forward again, else the backward-data operands only"""
+        return self if recompute else self._replace(fwd=None, base=None)
 
 
-def _mixer_core(S, packed, dims, afno_layout=None):
-    """the block-diagonal complex 2-layer MLP on the kept modes (models/dpot.py:72-94): spectrum S [Mm, 2E] ->
-    (O2, O1pre, O1)"""
-    B, tok, E, h, w, nb, bs, mx, my, mh, act = dims
-    Mm = B * mx * my
-    dev = S.device
-    (wb1, bb1, wb1T, _), (wb2, bb2, wb2T, _) = packed          # w*T: fragment-block-major W for the fused kernel
-    if wb1T is not None:
+class BlockDims(NamedTuple("BlockDims", [(n, int) for n in "B tok E h w nb mx my mh act".split()])):
+    """shapes of one Block: x [B, tok = h*w, E], nb diagonal blocks of E // nb channels, mx x my kept modes, hidden width mh"""
+    M = property(lambda d: d.B * d.tok)               # token rows of the channel MLP
+    Mm = property(lambda d: d.B * d.mx * d.my)        # kept-mode rows of the spectrum
+
+
+class _WgradRoute:
+    """Where the parameter gradients of ONE backward are delivered; the route is decided once, here:
+      at once    every producer finalises its gradients itself (`put`): AFNO2DFn / AFNO3DFn, and DPOT_TUNE fused_small=0;
+      `defer`    the fused weight-gradient launches leave their split-K partials, and ONE launch per block (csrc/gemm_tn.hip
+                 block_finalize_kernel) reduces them together with the GroupNorm partials;
+      `batch`    only operands are recorded: the forward pass's WgradBatch computes them with those of the other Blocks.
+    The producers' generic split-K fallbacks `put` at once on every route.  `finish()` -> the gradients in the sinks' order."""
+
+    def __init__(self, names, sinks):
+        self.sinks = dict(zip(names, sinks))
+        self.grads = dict.fromkeys(names)
+        self.defer, self.batch = False, None
+        self.afno_job = self.mlp_job = self.gn_parts = None
+        self.mp = self.mlp_ops = self.afno_ops = self.afno_dims = None       # the batch route's record (of_block, mlp, afno)
+        self.cs_jobs, self.late = (), []  # late: (name, tensor) final once the block's finalising launch has run
+
+    @classmethod
+    def of_block(cls, ctx, do2, Hh, xn2, S, bf16p: bool) -> "_WgradRoute":
+        self = cls(_BLOCK_PARAMS, ctx.sinks)
+        d, self.mp = ctx.dims, ctx.mlp_precision
+        self.defer = ops.block_finalize_enabled()
+        batch = ctx.wgrad_batch      # only the native fp32 two-layer weight-gradient launches, three-product AFNO form
+        if batch is not None:
+            bs = d.E // d.nb
+            if (self.defer and not bf16p and do2.is_contiguous() and Hh.is_contiguous() and xn2.is_contiguous()
+                    and ops.mlp_wgrad2_splitk(d.M, d.E, d.mh, self.mp) and ctx.mixer.fused and S.stride(0) == 2 * d.E
+                    and ops.afno_wgrad2_splitk(d.Mm, d.nb, bs)
+                    and all(WgradBatch.splits(batch.expected, d.M, d.E, d.mh, self.mp, d.Mm, d.nb, bs))):
+                self.batch = batch
+            else:
+                batch.withdraw()
+        return self
+
+    def out(self, name: str, shape, dev) -> Tensor:
+        return ops._out(self.sinks[name].out(), shape, dev)
+
+    def put(self, name: str, t: Optional[Tensor]) -> None:
+        self.grads[name] = self.sinks[name].done(t)
+
+    def _launched(self, names, outs, job):
+        if job is None:
+            for n, t in zip(names, outs):
+                self.put(n, t)
+        else:
+            self.late += zip(names, outs)
+        return job
+
+    def afno(self, S, dO1pre, O1, dO2, nb: int, bs: int, sk2: int) -> None:
+        """both weight gradients of the mixer in ONE launch (csrc/gemm_tn.hip, dpot_afno_wgrad2)"""
+        if self.batch is not None:
+            self.afno_ops, self.afno_dims = (S, dO1pre, O1, dO2), (S.shape[0], nb, bs)
+            return
+        outs = [self.out(n, shp, S.device) for n, shp in zip(_AFNO_PARAMS, ((2, nb, bs, bs), (2, nb, bs)) * 2)]
+        self.afno_job = self._launched(_AFNO_PARAMS, outs,
+                                       ops.afno_wgrad2(S, dO1pre, O1, dO2, nb, bs, *outs, sk2, defer=self.defer))
+
+    def mlp(self, do2, Hh, xn2, dHpre, skm: int) -> None:
+        """both weight gradients of the channel MLP in ONE launch (csrc/gemm_tn.hip, dpot_mlp_wgrad2)"""
+        if self.batch is not None:
+            self.mlp_ops = (do2, Hh, xn2, dHpre)
+            return
+        (M, E), mh, dev = do2.shape, Hh.shape[1], do2.device
+        df2w, df2b = self.out("f2w", (E, mh), dev), self.out("f2b", (E,), dev)
+        df1w, df1b = self.out("f1w", (mh, E), dev), self.out("f1b", (mh,), dev)
+        self.mlp_job = self._launched(_MLP_PARAMS, (df2w.view(E, mh, 1, 1), df2b, df1w.view(mh, E, 1, 1), df1b),
+                                      ops.mlp_wgrad2(do2, Hh, xn2, dHpre, df2w, df2b, df1w, df1b, skm, defer=self.defer))
+
+    def bias_colsums(self, df2b, df1b) -> None:
+        """pack-both path: finished column sums, or with `defer` the pack passes' jobs (partials, rows, n, out)"""
+        if self.defer:
+            self.cs_jobs = [df2b, df1b]
+            self.late += [("f2b", df2b[3]), ("f1b", df1b[3])]
+        else:
+            self.put("f2b", df2b), self.put("f1b", df1b)
+
+    def groupnorm(self, gn1_part, gn2_part) -> None:
+        self.gn_parts = (gn1_part, gn2_part)
+
+    def finish(self) -> tuple:
+        s = self.sinks
+        if self.batch is not None:
+            (M, E), mh = self.mlp_ops[0].shape, self.mlp_ops[1].shape[1]
+            self.batch.deliver(WgradJob((M, E, mh, self.mp, self.afno_dims, tuple(self.gn_parts[0].shape)),
+                                        self.mlp_ops, self.afno_ops, self.gn_parts, s))
+        elif self.gn_parts is not None:
+            gn_jobs = [(part, s[g].out(), s[b].out()) for part, (g, b) in zip(self.gn_parts, _GN_PARAMS)]
+            if self.afno_job is not None or self.mlp_job is not None or self.cs_jobs:
+                outs = ops.block_finalize(self.afno_job, self.mlp_job, gn_jobs, self.cs_jobs)
+                for n, t in self.late:
+                    self.put(n, t)
+            else:
+                outs = ops.groupnorm_param_grads(gn_jobs)
+            for (g, b), (dg, db) in zip(_GN_PARAMS, outs):
+                self.put(g, dg), self.put(b, db)
+        return tuple(self.grads.values())
+
+
+def _mixer_core(S, mw: MixerWeights, nb: int, act: int):
+    """the block-diagonal complex 2-layer MLP on the kept modes (models/dpot.py:72-94): spectrum S [Mm, 2E] -> (O2, O1pre, O1)"""
+    Mm, E, bs = S.shape[0], S.shape[1] // 2, S.shape[1] // 2 // nb
+    w1, b1, w2, b2 = mw.fwd
+    if mw.fused:
         # both layers of the block-diagonal complex MLP in ONE launch; the activated spectrum never leaves the CU
         # except as the copy saved for the backward (csrc/afno_mlp.hip)
-        # (layout 1: the (Wr, Wi) fragment packs of the three-product kernel; ops.AfnoItem carries the tag)
-        lay = afno_layout if afno_layout is not None else getattr(packed[0], "layout", 0)
-        p6 = _p6_of(packed, 0)
-        if p6 is not None:       # fp32-accurate on the bf16 matrix cores (gemm_precision 'auto' / 'bf16x6'): same contract
-            wb1T, wb2T, lay = p6[0], p6[1], 2
         # only the pre-activation is saved: the activated layer-1 output (operand of the layer-2 weight gradient) is
         # re-derived by the backward launch from it (O1 = None here; one spectrum-sized store and 18.9 MB per block less)
-        O2, O1pre, O1 = ops.afno_mlp2(S, wb1T, bb1, wb2T, bb2, nb, bs, act, mode=0, want_pre=True, want_mid=False,
-                                      layout=lay)
-    else:
-        O1 = torch.empty(Mm, 2 * E, dtype=torch.float32, device=dev)
-        O1pre = torch.empty_like(O1)
-        kw = dict(lda=2 * E, ldb=2 * bs, ldc=2 * E, batch=nb, strideA=2 * bs, strideB=4 * bs * bs, strideC=2 * bs,
-                  strideBias=2 * bs, tag=1)
-        ops.gemm(S, wb1, O1, Mm, 2 * bs, 2 * bs, bias=bb1, act=act, mode=EPI_ACT, preact=O1pre, ldpre=2 * E,
-                 stridePre=2 * bs, **kw)
-        O2 = torch.empty_like(O1)
-        ops.gemm(O1, wb2, O2, Mm, 2 * bs, 2 * bs, bias=bb2, **kw)
+        return ops.afno_mlp2(S, w1, b1, w2, b2, nb, bs, act, mode=0, want_pre=True, want_mid=False, layout=mw.layout)
+    O1 = torch.empty(Mm, 2 * E, dtype=torch.float32, device=S.device)
+    O1pre = torch.empty_like(O1)
+    kw = dict(lda=2 * E, ldb=2 * bs, ldc=2 * E, batch=nb, strideA=2 * bs, strideB=4 * bs * bs, strideC=2 * bs,
+              strideBias=2 * bs, tag=1)
+    ops.gemm(S, w1, O1, Mm, 2 * bs, 2 * bs, bias=b1, act=act, mode=EPI_ACT, preact=O1pre, ldpre=2 * E,
+             stridePre=2 * bs, **kw)
+    O2 = torch.empty_like(O1)
+    ops.gemm(O1, w2, O2, Mm, 2 * bs, 2 * bs, bias=b2, **kw)
     return O2, O1pre, O1
 
 
-def _mixer_fwd(xn1, packed, dims, afno_layout=None, norm=None):
-    """AFNO2D.forward on a [B, tok, E] field (models/dpot.py:51-110): rfft2 -> block-diagonal complex 2-layer MLP on the
-    kept modes -> irfft2 + x_orig.  Returns (y1, S, O1pre, O1); shared by BlockFn and AFNO2DFn.
+def _mixer_one_launch(x, mw: MixerWeights, d: BlockDims):
+    """the whole mixer in ONE launch (csrc/afno_fused.hip), spectrum and hidden layer on chip; None: not covered"""
+    if not (mw.fused and ops.afno_fused_supported(d.h, d.w, d.E, d.nb, d.mx, d.my, G=0, B=d.B, layout=mw.base_layout)):
+        return None
+    S, O1pre, y1 = ops.afno_fused_fwd(x, None, None, *mw.base, None, None, d.h, d.w, d.nb, d.mx, d.my, d.act)[:3]
+    return y1, S, O1pre, None
+
+
+def _mixer_fwd(xn1, mw: MixerWeights, d: BlockDims, norm=None):
+    """AFNO2D.forward on [B, tok, E] (models/dpot.py:51-110): rfft2 -> _mixer_core -> irfft2 + x_orig -> (y1, S, O1pre, O1).
     norm = (mean, rstd, gamma, beta): xn1 is the UN-normalised block input and both DFT kernels apply GroupNorm1 on their
     loads (the transform's input and the residual) - the normalised field is never written"""
-    B, tok, E, h, w, nb, bs, mx, my, mh, act = dims
-    lay = afno_layout if afno_layout is not None else getattr(packed[0], "layout", 0)
-    if norm is None and packed[0][2] is not None and ops.afno_fused_supported(h, w, E, nb, mx, my, G=0, B=B, layout=lay):
-        # the whole mixer in ONE launch (csrc/afno_fused.hip, SURVEY 8 f4), spectrum and hidden layer on chip
-        S, O1pre, y1 = ops.afno_fused_fwd(xn1, None, None, packed[0][2], packed[0][1], packed[1][2], packed[1][1], None,
-                                          None, h, w, nb, mx, my, act)[:3]
-        return y1, S, O1pre, None
-    S = ops.rfft2(xn1, h, w, nb, mx, my, 0, norm=norm)                     # [Mm, 2E]
-    O2, O1pre, O1 = _mixer_core(S, packed, dims, afno_layout)
-    y1 = ops.irfft2(O2, B, h, w, E, nb, mx, my, 1, res=xn1, res_norm=norm)  # + x_orig (the normalised input)
+    one = _mixer_one_launch(xn1, mw, d) if norm is None else None
+    if one is not None:
+        return one
+    S = ops.rfft2(xn1, d.h, d.w, d.nb, d.mx, d.my, 0, norm=norm)                     # [Mm, 2E]
+    O2, O1pre, O1 = _mixer_core(S, mw, d.nb, d.act)
+    y1 = ops.irfft2(O2, d.B, d.h, d.w, d.E, d.nb, d.mx, d.my, 1, res=xn1, res_norm=norm)  # + x_orig (the normalised input)
     return y1, S, O1pre, O1
 
 
-def _mixer_core_bwd(dO2, S, O1pre, O1, wb1, wb2, dims, fused, afno_layout, sinks, pending=None):
-    """backward of _mixer_core: dO2 [Mm, 2E] -> (dS, dw1, db1, dw2, db2); wb1 / wb2: the fragment-block-major W^T (fused
-    kernel) or the plain Wbig (generic GEMM); sinks = (s_w1, s_b1, s_w2, s_b2).  pending (a dict, BlockFn): the fused
-    weight-gradient launch leaves its split-K partials for the block's ONE finalising launch (pending["afno"] = the job)
-    and the four gradients are returned as plain tensors - the caller calls the sinks' done() after that launch; with
-    pending["batch"] set (the Block delivers to a WgradBatch) only the operands are recorded (pending["afno_ops"]) and the
-    four gradients are returned as None"""
-    B, tok, E, h, w, nb, bs, mx, my, mh, act = dims
-    s_w1, s_b1, s_w2, s_b2 = sinks
-    Mm = B * mx * my
-    dev = dO2.device
+def _mixer_core_bwd(dO2, S, O1pre, O1, mw: MixerWeights, nb: int, act: int, wg: _WgradRoute):
+    """backward of _mixer_core: dO2 [Mm, 2E] -> dS; the four weight gradients go to `wg`"""
+    Mm, E, bs, dev = dO2.shape[0], dO2.shape[1] // 2, dO2.shape[1] // 2 // nb, dO2.device
+    wb1, wb2 = mw.bwd
     kw = dict(lda=2 * E, ldb=2 * bs, ldc=2 * E, batch=nb, strideA=2 * bs, strideB=4 * bs * bs, strideC=2 * bs)
     sk = max(2, ops.auto_splitk(2 * bs, 2 * bs, Mm, nb, tn=True))
     wkw = dict(transA=True, lda=2 * E, ldb=2 * E, ldc=2 * bs, batch=nb, strideA=2 * bs, strideB=2 * bs,
                strideC=4 * bs * bs, splitk=sk, mode=ops.EPI_AFNO_WGRAD)
-    # both weight gradients of the mixer in ONE launch (csrc/gemm_tn.hip, dpot_afno_wgrad2) once dO1pre exists
-    sk2 = ops.afno_wgrad2_splitk(Mm, nb, bs) if fused and S.stride(0) == 2 * E else 0
-    if fused:
-        # data path of both layers in one launch: dO1pre = (dO2 W2^T) * act'(O1pre), dS = dO1pre W1^T
-        # (wb1 / wb2 hold the fragment-block-major W^T here); the same launch re-derives O1 = act(O1pre) when the forward
-        # did not keep it
-        dS, O1r, dO1pre = ops.afno_mlp2(dO2, wb2, None, wb1, None, nb, bs, act, mode=1, aux=O1pre, want_mid=True,
-                                        want_pre=O1 is None, layout=afno_layout)
-        if O1 is None:
-            O1 = O1r
-    if not sk2:
+
+    def wgrad(a, dy, w: str, b: str):
         # wgrad of Wbig; its split-K reduction writes dw / db in the parameters' own [2, nb, bs, ...] layout
-        dw2, db2 = ops._out(s_w2.out(), (2, nb, bs, bs), dev), ops._out(s_b2.out(), (2, nb, bs), dev)
-        ops.gemm(O1, dO2, dw2, 2 * bs, 2 * bs, Mm, colsum_out=db2, colsum_of=2, **wkw)
-        dw2, db2 = s_w2.done(dw2), s_b2.done(db2)
-    if not fused:
+        dw, db = wg.out(w, (2, nb, bs, bs), dev), wg.out(b, (2, nb, bs), dev)
+        ops.gemm(a, dy, dw, 2 * bs, 2 * bs, Mm, colsum_out=db, colsum_of=2, **wkw)
+        wg.put(w, dw), wg.put(b, db)
+
+    sk2 = ops.afno_wgrad2_splitk(Mm, nb, bs) if mw.fused and S.stride(0) == 2 * E else 0
+    if mw.fused:
+        # data path of both layers in one launch: dO1pre = (dO2 W2^T) * act'(O1pre), dS = dO1pre W1^T; the same launch
+        # re-derives O1 = act(O1pre) when the forward did not keep it
+        dS, O1r, dO1pre = ops.afno_mlp2(dO2, wb2, None, wb1, None, nb, bs, act, mode=1, aux=O1pre, want_mid=True,
+                                        want_pre=O1 is None, layout=mw.layout)
+        O1 = O1r if O1 is None else O1
+    if not sk2:
+        wgrad(O1, dO2, "w2", "b2")
+    if not mw.fused:
         dO1pre = torch.empty(Mm, 2 * E, dtype=torch.float32, device=dev)
         ops.gemm(dO2, wb2, dO1pre, Mm, 2 * bs, 2 * bs, transB=True, act=act, mode=EPI_DACT, aux=O1pre,
                  ldaux=2 * E, strideAux=2 * bs, **kw)
-    if sk2 and pending is not None and pending.get("batch"):
-        # the Block's WgradBatch computes both weight gradients with those of the other Blocks: only the operands are recorded
-        pending["afno_ops"] = (S, dO1pre, O1, dO2)
-        dw1 = db1 = dw2 = db2 = None
-    elif sk2:
-        dw1, db1 = ops._out(s_w1.out(), (2, nb, bs, bs), dev), ops._out(s_b1.out(), (2, nb, bs), dev)
-        dw2, db2 = ops._out(s_w2.out(), (2, nb, bs, bs), dev), ops._out(s_b2.out(), (2, nb, bs), dev)
-        if pending is not None and not pending.get("batch"):
-            pending["afno"] = ops.afno_wgrad2(S, dO1pre, O1, dO2, nb, bs, dw1, db1, dw2, db2, sk2, defer=True)
-        else:
-            ops.afno_wgrad2(S, dO1pre, O1, dO2, nb, bs, dw1, db1, dw2, db2, sk2)
-            dw1, db1, dw2, db2 = s_w1.done(dw1), s_b1.done(db1), s_w2.done(dw2), s_b2.done(db2)
+    if sk2:
+        wg.afno(S, dO1pre, O1, dO2, nb, bs, sk2)
     else:
-        dw1, db1 = ops._out(s_w1.out(), (2, nb, bs, bs), dev), ops._out(s_b1.out(), (2, nb, bs), dev)
-        ops.gemm(S, dO1pre, dw1, 2 * bs, 2 * bs, Mm, colsum_out=db1, colsum_of=2, **wkw)
-        dw1, db1 = s_w1.done(dw1), s_b1.done(db1)
-    if not fused:
+        wgrad(S, dO1pre, "w1", "b1")
+    if not mw.fused:
         dS = torch.empty(Mm, 2 * E, dtype=torch.float32, device=dev)
         ops.gemm(dO1pre, wb1, dS, Mm, 2 * bs, 2 * bs, transB=True, **kw)
-    return dS, dw1, db1, dw2, db2
+    return dS
 
 
-def _mixer_bwd(dy1, S, O1pre, O1, wb1, wb2, dims, fused, afno_layout, sinks, pending=None):
-    """backward of _mixer_fwd: returns (dxn1 = adjoint-rfft2(dS) + dy1, dw1, db1, dw2, db2); pending: see _mixer_core_bwd"""
-    B, tok, E, h, w, nb, bs, mx, my, mh, act = dims
-    dO2 = ops.rfft2(dy1, h, w, nb, mx, my, 1)                              # adjoint of irfft2
-    dS, dw1, db1, dw2, db2 = _mixer_core_bwd(dO2, S, O1pre, O1, wb1, wb2, dims, fused, afno_layout, sinks, pending)
-    dxn1 = ops.irfft2(dS, B, h, w, E, nb, mx, my, 0, res=dy1)              # adjoint of rfft2, + skip path
-    return dxn1, dw1, db1, dw2, db2
+def _afno_forward(ctx, x, weights, packed, nb: int, act: int, rfft, irfft, one_launch=None):
+    """AFNO2DFn / AFNO3DFn: transform -> _mixer_core -> inverse transform + x.  rfft(t, col_weights) and
+    irfft(spec, col_weights, res) are the pair of transform calls (kept for the backward: they hold shapes only)"""
+    if packed is None:
+        packed = tuple(ops.AfnoPacks([weights[:2], weights[2:]]).refresh())
+    mw = MixerWeights.of(packed)
+    out = one_launch(mw) if one_launch is not None else None
+    if out is None:
+        S = rfft(x, 0)                                                       # [Mm, 2E]
+        O2, O1pre, O1 = _mixer_core(S, mw, nb, act)
+        out = irfft(O2, 1, x), S, O1pre, O1                                  # + x_orig
+    y, *saved = out
+    ctx.save_for_backward(*saved)
+    ctx.mixer, ctx.mixer_args, ctx.transforms = mw.for_backward(False), (nb, act), (rfft, irfft)
+    ctx.sinks = _sinks(ctx, weights, 1)
+    ctx.weights_epoch = _epoch_of(ctx.sinks)
+    return y
+
+
+def _afno_backward(ctx, dy, what: str):
+    """adjoint of _afno_forward: (dx, dw1, db1, dw2, db2)"""
+    _check_epoch(ctx, what)
+    rfft, irfft = ctx.transforms
+    dy = dy.contiguous()
+    wg = _WgradRoute(_AFNO_PARAMS, ctx.sinks)
+    dO2 = rfft(dy, 1)                                                        # adjoint of the inverse transform
+    dS = _mixer_core_bwd(dO2, *ctx.saved_tensors, ctx.mixer, *ctx.mixer_args, wg)
+    return (irfft(dS, 0, dy),) + wg.finish()                                 # adjoint of the transform, + skip path
 
 
 class AFNO2DFn(torch.autograd.Function):
@@ -520,97 +635,85 @@ class AFNO2DFn(torch.autograd.Function):
         ops.capture_precision(ctx)       # re-applied around backward (ops.with_ctx_precision)
         x = x.contiguous()
         B, tok, E = x.shape
-        bs = E // nb
-        mx, my = min(modes, h), min(modes, w // 2 + 1)
-        if packed is None:
-            packed = tuple(ops.AfnoPacks([(w1, b1), (w2, b2)]).refresh())
-        dims = (B, tok, E, h, w, nb, bs, mx, my, 0, act)
-        y1, S, O1pre, O1 = _mixer_fwd(x, packed, dims)
-        ctx.fused = packed[0][2] is not None
-        wb1, wb2 = (packed[0][3], packed[1][3]) if ctx.fused else (packed[0][0], packed[1][0])
-        ctx.afno_layout = getattr(packed[0], "layout", 0) if ctx.fused else 0
-        ctx.p6b = _p6_of(packed, 1) if ctx.fused else None     # persistent buffers of the pack object (epoch-checked)
-        ctx.save_for_backward(S, O1pre, O1, wb1, wb2)
-        ctx.dims = dims
-        ctx.sinks = _sinks(ctx, (w1, b1, w2, b2), 1)
-        ctx.weights_epoch = _epoch_of(ctx.sinks)
-        return y1
+        d = BlockDims(B, tok, E, h, w, nb, min(modes, h), min(modes, w // 2 + 1), 0, act)
+        return _afno_forward(ctx, x, (w1, b1, w2, b2), packed, nb, act,
+                             lambda t, cw: ops.rfft2(t, h, w, nb, d.mx, d.my, cw),
+                             lambda s, cw, res: ops.irfft2(s, B, h, w, E, nb, d.mx, d.my, cw, res=res),
+                             lambda mw: _mixer_one_launch(x, mw, d))
 
     @staticmethod
     @ops.with_ctx_precision
     def backward(ctx, dy):
-        _check_epoch(ctx, "AFNO2DFn")
-        S, O1pre, O1, wb1, wb2 = ctx.saved_tensors
-        lay = ctx.afno_layout
-        if ctx.p6b is not None:
-            (wb1, wb2), lay = ctx.p6b, 2
-        dx, dw1, db1, dw2, db2 = _mixer_bwd(dy.contiguous(), S, O1pre, O1, wb1, wb2, ctx.dims, ctx.fused, lay, ctx.sinks)
-        return dx, dw1, db1, dw2, db2, None, None, None, None, None, None
+        return _afno_backward(ctx, dy, "AFNO2DFn") + (None,) * 6
 
 
-def _block_parts(x, n1w, n1b, n2w, n2b, f1w, f1b, packed, dims, mp, need_out, f2w=None, f2b=None, mlp_pk=None,
-                 afno_layout=None, save=True):
-    """forward of one Block up to (and optionally including) the second channel-MLP GEMM; returns every intermediate
-    the backward needs.  Called by BlockFn.forward, and again by BlockFn.backward when activations are recomputed."""
-    B, tok, E, h, w, nb, bs, mx, my, mh, act = dims
-    Mm, M = B * mx * my, B * tok
-    dev = x.device
-    panel = _mlp_panel_mode(mlp_pk, M, E, mh, mp)
-    npl = mlp_pk.planes if panel == 2 else 0
-    both = (panel == 2 and npl == 1 and ops.tune("pack_both") != 0
-            and ops.bf16_pack_both_supported(M, E) and ops.bf16_pack_both_supported(M, mh))
-    # GroupNorm applied ON THE LOAD of its consumer (DPOT_TUNE gn_fuse=0 disables): norm2 inside the pack pass of the bf16
-    # channel MLP (the fp32 GroupNorm2(y1) is never written); norm1 inside both DFT kernels where they are not fused with
-    # the statistics anyway (32x32 latent grid: statistics-only GroupNorm launches, no normalised tensor)
-    onload = ops.tune("gn_fuse") != 0
-    pack_norm = both and onload and tok % 64 == 0 and (E // 8) % 4 == 0
-    lay = afno_layout if afno_layout is not None else getattr(packed[0], "layout", 0)
+# every intermediate of a Block's forward that its backward reads.  xn2 / Hh are the fp32 GroupNorm2 output and hidden layer,
+# or on the pack-both bf16 path their TRANSPOSED bf16 packs (Hpre then: act'(pre-activation) as a bf16 pack)
+_Parts = namedtuple("_Parts", "mean1 rstd1 S O1pre O1 y1 mean2 rstd2 xn2 Hpre Hh")
+
+
+def _norms_mixer_fwd(x, n1w, n1b, n2w, n2b, mw: MixerWeights, d: BlockDims, pack_norm: bool, save: bool):
+    """norm1 -> AFNO mixer -> norm2 by the fewest launches the shape allows: the first nine fields of _Parts, and fused_xp.
+    pack_norm (the channel MLP's pack pass applies norm2 on its load): xn2 = None, or the one-launch layer wrote fused_xp"""
+    B, tok, E, h, w, nb, mx, my = d[:8]
     fused_xp = None
-    if packed[0][2] is not None and ops.afno_fused_supported(h, w, E, nb, mx, my, B=B, layout=lay):
+    if mw.fused and ops.afno_fused_supported(h, w, E, nb, mx, my, B=B, layout=mw.base_layout):
         # the whole AFNO layer - norm1, rfft2, both MLP layers, irfft2, + x_orig, norm2 - in ONE launch (csrc/afno_fused.hip,
         # SURVEY 8 f4): spectrum and hidden layer stay on chip; save=False (nothing will run a backward on these
         # intermediates: inference, or a forward whose Block recomputes): S / O1pre are not even written
         # (round 5: with the bf16 channel MLP the same launch also writes GroupNorm2(y1) as the two bf16 operand packs -
         # DPOT_TUNE packs=0: the separate pack pass over y1 instead)
         fused_packs = pack_norm and ops.tune("packs") != 0
+        w1T, b1, w2T, b2 = mw.base
         res = ops.afno_fused_fwd(
-            x, n1w, n1b, packed[0][2], packed[0][1], packed[1][2], packed[1][1], n2w, n2b, h, w, nb, mx, my, act, save=save,
+            x, n1w, n1b, w1T, b1, w2T, b2, n2w, n2b, h, w, nb, mx, my, d.act, save=save,
             want_y1=save or (pack_norm and not fused_packs), want_xn2=not pack_norm, want_packs=fused_packs,
             packs_trans=save)
         S, O1pre, y1, xn2, mean1, rstd1, mean2, rstd2 = res[:8]
-        fused_xp = res[8:] if fused_packs else None
-        O1 = None
+        O1, fused_xp = None, (res[8:] if fused_packs else None)
     elif ops.gn_dft_supported(h, w, E):
         # GroupNorm fused with the neighbouring DFT (csrc/gn_dft.hip): norm1 + rfft2, and irfft2 + x_orig + norm2 -
         # two launches around the mixer instead of four, GroupNorm1(x) never written
         S, mean1, rstd1 = ops.gn_rfft2(x, n1w, n1b, h, w, nb, mx, my)
-        O2, O1pre, O1 = _mixer_core(S, packed, dims, afno_layout)
+        O2, O1pre, O1 = _mixer_core(S, mw, nb, d.act)
         y1, xn2, mean2, rstd2 = ops.irfft2_gn(O2, x, mean1, rstd1, n1w, n1b, n2w, n2b, h, w, nb, mx, my,
                                               want_xn2=not pack_norm)
-        del O2
     else:
-        stats = onload and ops.groupnorm_stats_supported(B, tok, E)
+        # norm1 inside both DFT kernels where they are not fused with the statistics anyway (32x32 latent grid:
+        # statistics-only GroupNorm launches, no normalised tensor)
+        stats = ops.tune("gn_fuse") != 0 and ops.groupnorm_stats_supported(B, tok, E)
         if stats and ops.rfft2_norm_supported(h, w, E):
             mean1, rstd1 = ops.groupnorm_stats(x, n1w, n1b)
-            y1, S, O1pre, O1 = _mixer_fwd(x, packed, dims, afno_layout, norm=(mean1, rstd1, n1w, n1b))
+            y1, S, O1pre, O1 = _mixer_fwd(x, mw, d, norm=(mean1, rstd1, n1w, n1b))
         else:
             xn1, mean1, rstd1 = ops.groupnorm_fwd(x, n1w, n1b)
-            y1, S, O1pre, O1 = _mixer_fwd(xn1, packed, dims, afno_layout)
+            y1, S, O1pre, O1 = _mixer_fwd(xn1, mw, d)
             del xn1
-        pack_norm = pack_norm and stats
-        if pack_norm:
+        if pack_norm and stats:
             xn2 = None
             mean2, rstd2 = ops.groupnorm_stats(y1, n2w, n2b)
         else:
             xn2, mean2, rstd2 = ops.groupnorm_fwd(y1, n2w, n2b)
+    return mean1, rstd1, S, O1pre, O1, y1, mean2, rstd2, xn2, fused_xp
+
+
+def _mlp_fwd(x, front: list, n2w, n2b, f1w, f1b, f2w, f2b, mlp_pk, panel: int, both: bool, d: BlockDims, mp, need_out: bool):
+    """the channel MLP + outer residual on kernel family `panel` (_mlp_panel_mode): (out | None, xn2, Hpre, Hh) as _Parts
+    keeps them.  Takes xn2 and fused_xp OUT of `front` (what _norms_mixer_fwd returned), so that the fp32 xn2 can be dropped
+    here; xn2 = None (only with `both`): the pack pass applies GroupNorm2 on its load, or fused_xp exists"""
+    M, E, mh, act = d.M, d.E, d.mh, d.act
+    fused_xp, xn2 = front.pop(), front.pop()
+    y1, mean2, rstd2 = front[5:]
+    npl = mlp_pk.planes if panel == 2 else 0
+    out = None
     if both:
         # plain-bf16 channel MLP, one pack pass per activation: the pass that packs xn2 / Hh as the A operand of the
         # next GEMM also writes the TRANSPOSED pack the weight gradient will need - that (bf16, half the bytes) is what
         # the backward keeps; the fp32 xn2 / Hh are dropped right here
         if fused_xp is not None:
             xp, xpT = fused_xp                      # written by the one-launch AFNO layer itself
-        elif pack_norm:
-            xp, xpT, _ = ops.bf16_pack_both(y1.view(M, E), norm=(mean2, rstd2, n2w, n2b, tok))
+        elif xn2 is None:
+            xp, xpT, _ = ops.bf16_pack_both(y1.view(M, E), norm=(mean2, rstd2, n2w, n2b, d.tok))
         else:
             xp, xpT, _ = ops.bf16_pack_both(xn2.view(M, E))
         del xn2
@@ -619,10 +722,9 @@ def _block_parts(x, n1w, n1b, n2w, n2b, f1w, f1b, packed, dims, mp, need_out, f2
         # pre-activation and without a second activation evaluation)
         _, Hpre, hp, hpT, _ = ops.gemm_bf16p_packed(xp, mlp_pk[0], M, mh, E, bias=f1b, act=act, mode=EPI_ACT,
                                                     save_dact=True, pack_rows=need_out, pack_trans=True, store=False)
-        out = None
         if need_out:
             out, _ = ops.gemm_bf16p(hp, mlp_pk[2], M, E, mh, bias=f2b, res=x.view(M, E))
-        return out, (mean1, rstd1, S, O1pre, O1, y1, mean2, rstd2, xpT, Hpre, hpT)
+        return out, xpT, Hpre, hpT
     if panel == 2:   # bf16 matrix cores: weights pre-packed bf16 once per step, activations packed in one pass each
         Hh, Hpre = ops.gemm_bf16p(ops.bf16_pack_rows(xn2.view(M, E), planes=npl), mlp_pk[0], M, mh, E, bias=f1b, act=act,
                                   mode=EPI_ACT, save_pre=True, planes=npl)
@@ -630,7 +732,6 @@ def _block_parts(x, n1w, n1b, n2w, n2b, f1w, f1b, packed, dims, mp, need_out, f2
         Hh, Hpre = ops.gemm_panel(xn2.view(M, E), mlp_pk[0], mh, bias=f1b, act=act, mode=EPI_ACT, save_pre=True)
     else:
         Hh, Hpre = ops.linear_fwd(xn2.view(M, E), f1w, f1b, act=act, save_pre=True, precision=mp)
-    out = None
     if need_out:
         if panel == 2:
             out, _ = ops.gemm_bf16p(ops.bf16_pack_rows(Hh, planes=npl), mlp_pk[2], M, E, mh, bias=f2b, res=x.view(M, E),
@@ -639,7 +740,22 @@ def _block_parts(x, n1w, n1b, n2w, n2b, f1w, f1b, packed, dims, mp, need_out, f2
             out, _ = ops.gemm_panel(Hh, mlp_pk[2], E, bias=f2b, res=x.view(M, E))
         else:
             out, _ = ops.linear_fwd(Hh, f2w, f2b, res=x.view(M, E), precision=mp)
-    return out, (mean1, rstd1, S, O1pre, O1, y1, mean2, rstd2, xn2, Hpre, Hh)
+    return out, xn2, Hpre, Hh
+
+
+def _block_parts(x, n1w, n1b, n2w, n2b, f1w, f1b, mw: MixerWeights, d: BlockDims, mp, need_out, f2w=None, f2b=None,
+                 mlp_pk=None, save=True):
+    """forward of one Block up to (and optionally including) the second channel-MLP GEMM; returns (out | None, _Parts).
+    Called by BlockFn.forward, and again by BlockFn.backward when activations are recomputed."""
+    # GroupNorm2 applied ON THE LOAD of its consumer (DPOT_TUNE gn_fuse=0 disables): inside the pack pass of the bf16
+    # channel MLP (the fp32 GroupNorm2(y1) is never written)
+    panel = _mlp_panel_mode(mlp_pk, d.M, d.E, d.mh, mp)
+    both = (panel == 2 and mlp_pk.planes == 1 and ops.tune("pack_both") != 0
+            and ops.bf16_pack_both_supported(d.M, d.E) and ops.bf16_pack_both_supported(d.M, d.mh))
+    pack_norm = both and ops.tune("gn_fuse") != 0 and d.tok % 64 == 0 and (d.E // 8) % 4 == 0
+    front = list(_norms_mixer_fwd(x, n1w, n1b, n2w, n2b, mw, d, pack_norm, save))
+    out, *back = _mlp_fwd(x, front, n2w, n2b, f1w, f1b, f2w, f2b, mlp_pk, panel, both, d, mp, need_out)
+    return out, _Parts(*front, *back)
 
 
 # The gradient a Block's backward returns (dx) is the `dout` of the PREVIOUS Block's backward, whose bf16 channel MLP first packs
@@ -684,35 +800,25 @@ class BlockFn(torch.autograd.Function):
                 act: int, packed=None, recompute: bool = False, mlp_pk=None, grad_enabled: bool = True,
                 emit_grad_packs: bool = False, wgrad_batch: Optional[WgradBatch] = None):
         x = x.contiguous()
-        B, tok, E = x.shape
-        bs = E // nb
-        mx, my = min(modes, h), min(modes, w // 2 + 1)
-        mh = f1w.shape[0]
-        if packed is None:      # ((Wbig1, bbig1, blocked W1, blocked W1^T), (...)); normally packed by the model
+        (B, tok, E), mh = x.shape, f1w.shape[0]
+        if packed is None:      # normally packed by the model (packs.DerivedWeights)
             packed = (ops.afno_pack3(w1, b1), ops.afno_pack3(w2, b2))
-        dims = (B, tok, E, h, w, nb, bs, mx, my, mh, act)
+        mw = MixerWeights.of(packed)
+        d = BlockDims(B, tok, E, h, w, nb, min(modes, h), min(modes, w // 2 + 1), mh, act)
         mp = ops.mlp_precision()                                               # channel-MLP GEMM precision override
         # (no input needs a gradient or the caller runs under no_grad - inference - or the Block recomputes: the
         # intermediates are dropped right below.  grad_enabled comes from the CALLER: inside forward() autograd is always off,
         # and needs_input_grad mirrors requires_grad of the inputs whatever the grad mode)
         keep = grad_enabled and any(ctx.needs_input_grad) and not recompute
-        out, parts = _block_parts(x, n1w, n1b, n2w, n2b, f1w, f1b, packed, dims, mp, True, f2w, f2b, mlp_pk, save=keep)
-        ctx.mlp_pk = mlp_pk if _mlp_panel_mode(mlp_pk, B * tok, E, mh, mp) else None
-        ctx.fused_mixer = packed[0][2] is not None
-        # weights the backward data path multiplies by: blocked W^T (fused kernel) or the plain Wbig (generic GEMM)
-        wb1, wb2 = (packed[0][3], packed[1][3]) if ctx.fused_mixer else (packed[0][0], packed[1][0])
-        opt_t = (packed[0][2], packed[1][2]) if ctx.fused_mixer else ()
+        out, parts = _block_parts(x, n1w, n1b, n2w, n2b, f1w, f1b, mw, d, mp, True, f2w, f2b, mlp_pk, save=keep)
+        ctx.mlp_pk = mlp_pk if _mlp_panel_mode(mlp_pk, d.M, E, mh, mp) else None
+        ctx.mixer = mw.for_backward(recompute)
         if recompute:
-            ctx.save_for_backward(x, wb1, packed[0][1], wb2, packed[1][1], n1w, n1b, n2w, n2b, f1w, f1b, f2w, *opt_t)
+            ctx.save_for_backward(x, n1w, n1b, n2w, n2b, f1w, f1b, f2w)
         else:
-            ctx.save_for_backward(x, *parts, wb1, wb2, n1w, n2w, f1w, f2w)
-        ctx.recompute = recompute
+            ctx.save_for_backward(x, *parts, n1w, n2w, f1w, f2w)
+        ctx.recompute, ctx.dims = recompute, d
         ctx.emit_grad_packs = emit_grad_packs     # a Block precedes this one: its bf16 channel-MLP backward wants dx packed
-        ctx.dims = dims
-        ctx.afno_layout = getattr(packed[0], "layout", 0) if ctx.fused_mixer else 0
-        # bf16x6 mixer packs (persistent buffers of the model's AfnoPacks, epoch-checked like every derived weight)
-        ctx.p6f = _p6_of(packed, 0) if ctx.fused_mixer else None
-        ctx.p6b = _p6_of(packed, 1) if ctx.fused_mixer else None
         ctx.mlp_precision = ops.effective_mlp_precision()    # a concrete code: the backward reproduces the forward's mode
         ctx.gemm_precision = ops._cur_gemm()
         ctx.sinks = _sinks(ctx, (n1w, n1b, w1, b1, w2, b2, n2w, n2b, f1w, f1b, f2w, f2b), 1)
@@ -728,187 +834,133 @@ class BlockFn(torch.autograd.Function):
     def backward(ctx, dout):
         # the modes the forward ran in (per-model attributes), whatever thread autograd runs this on
         with ops.precision_scope(getattr(ctx, "gemm_precision", None), ctx.mlp_precision):
-            return BlockFn._backward(ctx, dout)
+            _check_epoch(ctx, "BlockFn")
+            d, mp, mlp_pk = ctx.dims, ctx.mlp_precision, ctx.mlp_pk
+            if ctx.recompute:
+                x, n1w, n1b, n2w, n2b, f1w, f1b, f2w = ctx.saved_tensors
+                with torch.no_grad():
+                    _, p = _block_parts(x, n1w, n1b, n2w, n2b, f1w, f1b, ctx.mixer, d, mp, False, mlp_pk=mlp_pk)
+            else:
+                x, *parts, n1w, n2w, f1w, f2w = ctx.saved_tensors
+                p = _Parts(*parts)
+            dout = dout.contiguous()
+            do2 = dout.view(d.M, d.E)
+            bf16p = mlp_pk is not None and mlp_pk.kind != "f32"
+            both = bf16p and p.xn2.dtype == torch.bfloat16       # pack-both path: xn2 / Hh ARE the transposed bf16 packs
+            wg = _WgradRoute.of_block(ctx, do2, p.Hh, p.xn2, p.S, bf16p)
+            dxn2 = _mlp_bwd_packed(do2, p, mlp_pk, d, wg) if both else _mlp_bwd(do2, p, f1w, f2w, mlp_pk, d, mp, wg)
+            pack_dx = both and ctx.emit_grad_packs and ctx.needs_input_grad[0]      # the previous Block wants dx packed as well
+            dx = _norms_mixer_bwd(dout, dxn2, x, p, n1w, n2w, ctx.mixer, d, pack_dx, wg)
+            return (dx,) + wg.finish() + (None,) * 11
 
-    @staticmethod
-    def _backward(ctx, dout):
-        _check_epoch(ctx, "BlockFn")
-        mp = ctx.mlp_precision
-        if ctx.recompute:
-            x, wb1, bb1, wb2, bb2, n1w, n1b, n2w, n2b, f1w, f1b, f2w, *wts = ctx.saved_tensors
-            wb1T, wb2T = wts if ctx.fused_mixer else (None, None)
-            p6f = ctx.p6f if ctx.p6f is not None else (None, None)
-            with torch.no_grad():
-                _, parts = _block_parts(x, n1w, n1b, n2w, n2b, f1w, f1b,
-                                        (ops.AfnoItem((wb1, bb1, wb1T, None), ctx.afno_layout, (p6f[0], None)),
-                                         ops.AfnoItem((wb2, bb2, wb2T, None), ctx.afno_layout, (p6f[1], None))),
-                                        ctx.dims, mp, False, mlp_pk=ctx.mlp_pk, afno_layout=ctx.afno_layout)
-            mean1, rstd1, S, O1pre, O1, y1, mean2, rstd2, xn2, Hpre, Hh = parts
-        else:
-            (x, mean1, rstd1, S, O1pre, O1, y1, mean2, rstd2, xn2, Hpre, Hh, wb1, wb2, n1w, n2w, f1w,
-             f2w) = ctx.saved_tensors
-        B, tok, E, h, w, nb, bs, mx, my, mh, act = ctx.dims
-        s_n1w, s_n1b, s_w1, s_b1, s_w2, s_b2, s_n2w, s_n2b, s_f1w, s_f1b, s_f2w, s_f2b = ctx.sinks
-        afno_lay = ctx.afno_layout
-        if ctx.p6b is not None:      # the mixer's data gradient on the bf16 matrix cores (bf16x6), csrc/afno_mlp6.hip
-            (wb1, wb2), afno_lay = ctx.p6b, 2
-        M, Mm = B * tok, B * mx * my
-        dev = dout.device
-        dout = dout.contiguous()
-        do2 = dout.view(M, E)
-        # one finalising launch per block (csrc/gemm_tn.hip block_finalize_kernel): the fused weight-gradient launches leave
-        # their split-K partials, and those are reduced together with the GroupNorm parameter-gradient partials at the end
-        pending = {} if ops.block_finalize_enabled() else None
-        # channel MLP
-        mlp_pk = ctx.mlp_pk
-        bf16p = mlp_pk is not None and mlp_pk.kind != "f32"
-        npl = mlp_pk.planes if bf16p else 0
-        # weight gradients with those of the other Blocks (WgradBatch): the native fp32 two-layer weight-gradient launches only,
-        # three-product AFNO form
-        batch = ctx.wgrad_batch
-        if batch is not None:
-            if (pending is not None and not bf16p and do2.is_contiguous() and Hh.is_contiguous() and xn2.is_contiguous()
-                    and ops.mlp_wgrad2_splitk(M, E, mh, mp) and ctx.fused_mixer and S.stride(0) == 2 * E
-                    and ops.afno_wgrad2_splitk(Mm, nb, bs)
-                    and all(WgradBatch.splits(batch.expected, M, E, mh, mp, Mm, nb, bs))):
-                pending["batch"] = True
-            else:
-                batch.withdraw()
-                batch = None
 
-        def wgrad(dy, xin, s_w, s_b, shape):
-            n, k = dy.shape[1], xin.shape[1]
-            if bf16p:   # dW[n, k] = dy^T xin on the bf16 matrix cores: both operands packed transposed (k-dim = tokens),
-                #         split-K over the tokens with a fixed-order reduction; the bias gradient is a column sum
-                dw, _ = ops.gemm_bf16p(ops.bf16_pack_rows(dy, trans=True, planes=npl),
-                                       ops.bf16_pack_rows(xin, trans=True, planes=npl), n, k, M, out=s_w.out(),
-                                       planes=npl)
-                db = ops.colsum(dy, M, n, out=s_b.out())
-            else:
-                dw, db = ops.linear_bwd_wb(dy, xin, s_w.out(), s_b.out(), precision=mp)
-            return s_w.done(dw.view(shape)), s_b.done(db)
+def _mlp_bwd_packed(do2, p: _Parts, mlp_pk, d: BlockDims, wg: _WgradRoute):
+    """channel-MLP backward on the pack-both bf16 path (see _mlp_fwd) -> dxn2 [M, E]: each gradient is packed once, in both forms,
+    and its bias column sums come out of the same pass (with wg.defer: partials now, summed by the block's finalising launch)"""
+    M, E, mh = d.M, d.E, d.mh
+    s_f2b, s_f1b = wg.sinks["f2b"], wg.sinks["f1b"]
+    taken = _take_grad_packs(do2)
+    if taken is not None:              # packed by the kernel that produced this gradient (the next Block's backward)
+        dop, dopT, cs_b = taken             # cs_b: [B * token ranges, E] partial column sums
+        df2b = ((cs_b, cs_b.shape[0], E, wg.out("f2b", (E,), do2.device)) if wg.defer
+                else ops.colsum(cs_b, cs_b.shape[0], E, out=s_f2b.out()))
+    else:
+        dop, dopT, df2b = ops.bf16_pack_both(do2, want_colsum=True, colsum_out=s_f2b.out(), defer_colsum=wg.defer)
+    # both weight gradients in ONE launch once dHpre's pack exists, when each alone would need split-K
+    pair = ops.gemm_bf16p_pair_wanted(E, mh, mh, E, M)
+    if not pair:
+        df2w, _ = ops.gemm_bf16p(dopT, p.Hh, E, mh, M, out=wg.sinks["f2w"].out())
+    # dHpre = (do2 W2) * act'(Hpre) leaves the GEMM as its packs + bias column sums only
+    _, _, dhp, dhpT, df1b = ops.gemm_bf16p_packed(dop, mlp_pk[3], M, mh, E, act=d.act, mode=EPI_DACT, dact=p.Hpre,
+                                                  pack_rows=True, pack_trans=True, colsum=True,
+                                                  colsum_out=s_f1b.out(), store=False, defer_colsum=wg.defer)
+    if pair:
+        df2w, df1w = ops.gemm_bf16p_pair(dopT, p.Hh, E, mh, dhpT, p.xn2, mh, E, M, out0=wg.sinks["f2w"].out(),
+                                         out1=wg.sinks["f1w"].out())
+    else:
+        df1w, _ = ops.gemm_bf16p(dhpT, p.xn2, mh, E, M, out=wg.sinks["f1w"].out())
+    del dop, dopT
+    wg.put("f2w", df2w.view(E, mh, 1, 1)), wg.put("f1w", df1w.view(mh, E, 1, 1))
+    wg.bias_colsums(df2b, df1b)
+    return ops.gemm_bf16p(dhp, mlp_pk[1], M, E, mh)[0]
 
-        if bf16p and xn2.dtype == torch.bfloat16:
-            # pack-both path (see _block_parts): xn2 / Hh ARE the transposed bf16 packs; each gradient is packed once, in
-            # both forms, and its bias column sums come out of the same pass
-            dcs = pending is not None          # bias column sums: partials now, summed by the block's finalising launch
-            taken = _take_grad_packs(do2)
-            if taken is not None:              # packed by the kernel that produced this gradient (the next Block's backward)
-                dop, dopT, cs_b = taken             # cs_b: [B * token ranges, E] partial column sums
-                df2b = ((cs_b, cs_b.shape[0], E, ops._out(s_f2b.out(), (E,), dev)) if dcs
-                        else ops.colsum(cs_b, cs_b.shape[0], E, out=s_f2b.out()))
-            else:
-                dop, dopT, df2b = ops.bf16_pack_both(do2, want_colsum=True, colsum_out=s_f2b.out(), defer_colsum=dcs)
-            # both weight gradients in ONE launch once dHpre's pack exists, when each alone would need split-K
-            pair = ops.gemm_bf16p_pair_wanted(E, mh, mh, E, M)
-            if not pair:
-                df2w, _ = ops.gemm_bf16p(dopT, Hh, E, mh, M, out=s_f2w.out())
-            # dHpre = (do2 W2) * act'(Hpre) leaves the GEMM as its packs + bias column sums only
-            _, _, dhp, dhpT, df1b = ops.gemm_bf16p_packed(dop, mlp_pk[3], M, mh, E, act=act, mode=EPI_DACT, dact=Hpre,
-                                                          pack_rows=True, pack_trans=True, colsum=True,
-                                                          colsum_out=s_f1b.out(), store=False, defer_colsum=dcs)
-            if dcs:
-                pending["cs"] = [df2b, df1b]
-                df2b, df1b = df2b[3], df1b[3]
-            if pair:
-                df2w, df1w = ops.gemm_bf16p_pair(dopT, Hh, E, mh, dhpT, xn2, mh, E, M, out0=s_f2w.out(), out1=s_f1w.out())
-            else:
-                df1w, _ = ops.gemm_bf16p(dhpT, xn2, mh, E, M, out=s_f1w.out())
-            del dop, dopT
-            df2w, df1w = s_f2w.done(df2w.view(E, mh, 1, 1)), s_f1w.done(df1w.view(mh, E, 1, 1))
-            if not dcs:
-                df2b, df1b = s_f2b.done(df2b), s_f1b.done(df1b)
-            dxn2, _ = ops.gemm_bf16p(dhp, mlp_pk[1], M, E, mh)
-            del dhp, dhpT
+
+def _mlp_bwd(do2, p: _Parts, f1w, f2w, mlp_pk, d: BlockDims, mp, wg: _WgradRoute):
+    """channel-MLP backward with fp32 activations -> dxn2 [M, E]: generic GEMMs, fp32 panels, or bf16 / bf16x6 panels"""
+    M, E, mh, act = d.M, d.E, d.mh, d.act
+    xn2 = p.xn2.view(M, E)
+    bf16p = mlp_pk is not None and mlp_pk.kind != "f32"
+    npl = mlp_pk.planes if bf16p else 0
+
+    def wgrad(dy, xin, w: str, b: str, shape):
+        n, k = dy.shape[1], xin.shape[1]
+        if bf16p:   # dW[n, k] = dy^T xin on the bf16 matrix cores: both operands packed transposed (k-dim = tokens),
+            #         split-K over the tokens with a fixed-order reduction; the bias gradient is a column sum
+            dw, _ = ops.gemm_bf16p(ops.bf16_pack_rows(dy, trans=True, planes=npl),
+                                   ops.bf16_pack_rows(xin, trans=True, planes=npl), n, k, M, out=wg.sinks[w].out(),
+                                   planes=npl)
+            db = ops.colsum(dy, M, n, out=wg.sinks[b].out())
         else:
-            # native fp32: both weight gradients in ONE launch once dHpre exists (csrc/gemm_tn.hip, dpot_mlp_wgrad2)
-            skm = 0 if bf16p else ops.mlp_wgrad2_splitk(M, E, mh, mp)
-            if skm and not (do2.is_contiguous() and Hh.is_contiguous() and xn2.is_contiguous()):
-                skm = 0
-            if not skm:
-                df2w, df2b = wgrad(do2, Hh, s_f2w, s_f2b, (E, mh, 1, 1))
-            if bf16p:
-                dHpre, _ = ops.gemm_bf16p(ops.bf16_pack_rows(do2, planes=npl), mlp_pk[3], M, mh, E, act=act, mode=EPI_DACT,
-                                          aux=Hpre, planes=npl)
-            elif mlp_pk is not None:
-                dHpre, _ = ops.gemm_panel(do2, mlp_pk[3], mh, act=act, mode=EPI_DACT, aux=Hpre)       # do2 W2, * act'(Hpre)
-            else:
-                dHpre = ops.linear_bwd_data(do2, f2w, act=act, aux=Hpre, precision=mp)  # [M, mh]
-            if skm and batch is not None:
-                mlp_ops = (do2, Hh, xn2.view(M, E), dHpre)
-                df2w = df2b = df1w = df1b = None
-            elif skm:
-                df2w, df2b = ops._out(s_f2w.out(), (E, mh), dev), ops._out(s_f2b.out(), (E,), dev)
-                df1w, df1b = ops._out(s_f1w.out(), (mh, E), dev), ops._out(s_f1b.out(), (mh,), dev)
-                if pending is not None:      # partials only: reduced by the block's finalising launch below
-                    pending["mlp"] = ops.mlp_wgrad2(do2, Hh, xn2.view(M, E), dHpre, df2w, df2b, df1w, df1b, skm, defer=True)
-                else:
-                    ops.mlp_wgrad2(do2, Hh, xn2.view(M, E), dHpre, df2w, df2b, df1w, df1b, skm)
-                    df2w, df2b = s_f2w.done(df2w.view(E, mh, 1, 1)), s_f2b.done(df2b)
-                    df1w, df1b = s_f1w.done(df1w.view(mh, E, 1, 1)), s_f1b.done(df1b)
-            else:
-                df1w, df1b = wgrad(dHpre, xn2.view(M, E), s_f1w, s_f1b, (mh, E, 1, 1))
-            if bf16p:
-                dxn2, _ = ops.gemm_bf16p(ops.bf16_pack_rows(dHpre, planes=npl), mlp_pk[1], M, E, mh, planes=npl)
-            elif mlp_pk is not None:
-                dxn2, _ = ops.gemm_panel(dHpre, mlp_pk[1], E)                      # dHpre W1
-            else:
-                dxn2 = ops.linear_bwd_data(dHpre, f1w, precision=mp)               # [M, E]
-        # parameter-gradient partials of norm2 are reduced together with norm1's at the end of the block (one launch)
-        if ops.gn_dft_supported(h, w, E):
-            # norm2 backward + rfft2 (adjoint of the forward irfft2), then irfft2 (adjoint) + skip + norm1 backward + outer
-            # skip: two launches around the mixer's backward (csrc/gn_dft.hip)
-            dy1, gn2_part, dO2 = ops.gn_bwd_rfft2(dxn2.view(B, tok, E), y1, mean2, rstd2, n2w, h, w, nb, mx, my,
-                                                  col_weights=1)
-            dS, dw1, db1, dw2, db2 = _mixer_core_bwd(dO2, S, O1pre, O1, wb1, wb2, ctx.dims, ctx.fused_mixer,
-                                                     afno_lay, (s_w1, s_b1, s_w2, s_b2), pending)
-            if E // 8 <= 64:
-                dx, gn1_part = ops.irfft2_gn_bwd(dS, dy1, x, mean1, rstd1, n1w, h, w, nb, mx, my, add=dout,
-                                                 col_weights=0)
-            else:
-                # 128 channels per group (DPOT-S / -M): this pair reads four fields with 4-byte accesses and runs at 64.7 us
-                # against 20.0 + 24.6 us for the separate kernels (profiles/r03_step_census_M_bf16_v1.txt) - not fused
-                dxn1 = ops.irfft2(dS, B, h, w, E, nb, mx, my, 0, res=dy1)
-                if (ctx.emit_grad_packs and ctx.needs_input_grad[0] and bf16p and xn2.dtype == torch.bfloat16 and ops.groupnorm_bwd_packs_supported(tok, E, B=B)
-                        and ops.tune("packs") != 0):
-                    # dx goes to the previous Block's bf16 channel-MLP backward: written here in its packed forms as well
-                    dx, gn1_part, gp_r, gp_t, gp_cs = ops.groupnorm_bwd_packs(dxn1, x, mean1, rstd1, n1w, add=dout)
-                    _stash_grad_packs(dx, gp_r, gp_t, gp_cs)
-                else:
-                    dx, gn1_part = ops.groupnorm_bwd(dxn1, x, mean1, rstd1, n1w, add=dout, defer=True)
+            dw, db = ops.linear_bwd_wb(dy, xin, wg.sinks[w].out(), wg.sinks[b].out(), precision=mp)
+        wg.put(w, dw.view(shape)), wg.put(b, db)
+
+    # native fp32: both weight gradients in ONE launch once dHpre exists (csrc/gemm_tn.hip, dpot_mlp_wgrad2)
+    skm = 0 if bf16p else ops.mlp_wgrad2_splitk(M, E, mh, mp)
+    if skm and not (do2.is_contiguous() and p.Hh.is_contiguous() and p.xn2.is_contiguous()):
+        skm = 0
+    if not skm:
+        wgrad(do2, p.Hh, "f2w", "f2b", (E, mh, 1, 1))
+    if bf16p:
+        dHpre, _ = ops.gemm_bf16p(ops.bf16_pack_rows(do2, planes=npl), mlp_pk[3], M, mh, E, act=act, mode=EPI_DACT,
+                                  aux=p.Hpre, planes=npl)
+    elif mlp_pk is not None:
+        dHpre, _ = ops.gemm_panel(do2, mlp_pk[3], mh, act=act, mode=EPI_DACT, aux=p.Hpre)       # do2 W2, * act'(Hpre)
+    else:
+        dHpre = ops.linear_bwd_data(do2, f2w, act=act, aux=p.Hpre, precision=mp)  # [M, mh]
+    if skm:
+        wg.mlp(do2, p.Hh, xn2, dHpre, skm)
+    else:
+        wgrad(dHpre, xn2, "f1w", "f1b", (mh, E, 1, 1))
+    if bf16p:
+        return ops.gemm_bf16p(ops.bf16_pack_rows(dHpre, planes=npl), mlp_pk[1], M, E, mh, planes=npl)[0]
+    if mlp_pk is not None:
+        return ops.gemm_panel(dHpre, mlp_pk[1], E)[0]                      # dHpre W1
+    return ops.linear_bwd_data(dHpre, f1w, precision=mp)                   # [M, E]
+
+
+def _norms_mixer_bwd(dout, dxn2, x, p: _Parts, n1w, n2w, mw: MixerWeights, d: BlockDims, pack_dx: bool, wg: _WgradRoute):
+    """norm2 backward, mixer backward, norm1 backward + outer skip: dxn2 [M, E] -> dx; both norms' partials go to `wg`"""
+    B, tok, E, h, w, nb, mx, my = d[:8]
+    if ops.gn_dft_supported(h, w, E):
+        # norm2 backward + rfft2 (adjoint of the forward irfft2), then irfft2 (adjoint) + skip + norm1 backward + outer
+        # skip: two launches around the mixer's backward (csrc/gn_dft.hip)
+        dy1, gn2_part, dO2 = ops.gn_bwd_rfft2(dxn2.view(B, tok, E), p.y1, p.mean2, p.rstd2, n2w, h, w, nb, mx, my,
+                                              col_weights=1)
+        dS = _mixer_core_bwd(dO2, p.S, p.O1pre, p.O1, mw, nb, d.act, wg)
+        if E // 8 <= 64:
+            dx, gn1_part = ops.irfft2_gn_bwd(dS, dy1, x, p.mean1, p.rstd1, n1w, h, w, nb, mx, my, add=dout,
+                                             col_weights=0)
         else:
-            dy1, gn2_part = ops.groupnorm_bwd(dxn2.view(B, tok, E), y1, mean2, rstd2, n2w, defer=True)
-            # AFNO mixer
-            dxn1, dw1, db1, dw2, db2 = _mixer_bwd(dy1, S, O1pre, O1, wb1, wb2, ctx.dims, ctx.fused_mixer,
-                                                  afno_lay, (s_w1, s_b1, s_w2, s_b2), pending)
-            # (DPOT-L: the CHUNKED GroupNorm backward could write the gradient's packs too - see the 128-channel branch above - but
-            # there the staging + two barriers per 32-token sub-tile cost what the saved pack pass did: DPOT-L 91.2 -> 90.9 ms,
-            # L20 2.185 -> 2.211 s, profiles/r05_grad_packs_step_ab_L.txt; the opt-in of round 5 is gone)
-            dx, gn1_part = ops.groupnorm_bwd(dxn1, x, mean1, rstd1, n1w, add=dout, defer=True)
-        if batch is not None:
-            aops = pending["afno_ops"]
-            batch.deliver({"key": (M, E, mh, mp, (Mm, nb, bs), tuple(gn1_part.shape)),
-                           "mlp": mlp_ops, "mlp_sinks": (s_f2w, s_f2b, s_f1w, s_f1b),
-                           "afno": aops, "afno_sinks": (s_w1, s_b1, s_w2, s_b2),
-                           "gn": [(gn1_part, s_n1w, s_n1b), (gn2_part, s_n2w, s_n2b)]})
-            return (dx,) + (None,) * 23
-        gn_jobs = [(gn1_part, s_n1w.out(), s_n1b.out()), (gn2_part, s_n2w.out(), s_n2b.out())]
-        if pending:
-            (dn1w, dn1b), (dn2w, dn2b) = ops.block_finalize(pending.get("afno"), pending.get("mlp"), gn_jobs,
-                                                            pending.get("cs", ()))
-            if "cs" in pending:
-                df2b, df1b = s_f2b.done(df2b), s_f1b.done(df1b)
-            if "mlp" in pending:
-                df2w, df2b = s_f2w.done(df2w.view(E, mh, 1, 1)), s_f2b.done(df2b)
-                df1w, df1b = s_f1w.done(df1w.view(mh, E, 1, 1)), s_f1b.done(df1b)
-            if "afno" in pending:
-                dw1, db1, dw2, db2 = s_w1.done(dw1), s_b1.done(db1), s_w2.done(dw2), s_b2.done(db2)
-        else:
-            (dn1w, dn1b), (dn2w, dn2b) = ops.groupnorm_param_grads(gn_jobs)
-        dn1w, dn1b = s_n1w.done(dn1w), s_n1b.done(dn1b)
-        dn2w, dn2b = s_n2w.done(dn2w), s_n2b.done(dn2b)
-        return (dx, dn1w, dn1b, dw1, db1, dw2, db2, dn2w, dn2b, df1w, df1b, df2w, df2b, None, None, None, None, None,
-                None, None, None, None, None, None)
+            # 128 channels per group (DPOT-S / -M): this pair reads four fields with 4-byte accesses and runs at 64.7 us
+            # against 20.0 + 24.6 us for the separate kernels (profiles/r03_step_census_M_bf16_v1.txt) - not fused
+            dxn1 = ops.irfft2(dS, B, h, w, E, nb, mx, my, 0, res=dy1)
+            if pack_dx and ops.groupnorm_bwd_packs_supported(tok, E, B=B) and ops.tune("packs") != 0:
+                # dx goes to the previous Block's bf16 channel-MLP backward: written here in its packed forms as well
+                dx, gn1_part, gp_r, gp_t, gp_cs = ops.groupnorm_bwd_packs(dxn1, x, p.mean1, p.rstd1, n1w, add=dout)
+                _stash_grad_packs(dx, gp_r, gp_t, gp_cs)
+            else:
+                dx, gn1_part = ops.groupnorm_bwd(dxn1, x, p.mean1, p.rstd1, n1w, add=dout, defer=True)
+    else:
+        dy1, gn2_part = ops.groupnorm_bwd(dxn2.view(B, tok, E), p.y1, p.mean2, p.rstd2, n2w, defer=True)
+        dO2 = ops.rfft2(dy1, h, w, nb, mx, my, 1)                              # adjoint of irfft2
+        dS = _mixer_core_bwd(dO2, p.S, p.O1pre, p.O1, mw, nb, d.act, wg)
+        dxn1 = ops.irfft2(dS, B, h, w, E, nb, mx, my, 0, res=dy1)              # adjoint of rfft2, + skip path
+        # (DPOT-L: the CHUNKED GroupNorm backward could write the gradient's packs too - see the 128-channel branch above - but
+        # there the staging + two barriers per 32-token sub-tile cost what the saved pack pass did: DPOT-L 91.2 -> 90.9 ms,
+        # L20 2.185 -> 2.211 s, profiles/r05_grad_packs_step_ab_L.txt; the opt-in of round 5 is gone)
+        dx, gn1_part = ops.groupnorm_bwd(dxn1, x, p.mean1, p.rstd1, n1w, add=dout, defer=True)
+    wg.groupnorm(gn1_part, gn2_part)
+    return dx
 
 
 # ======================================================================================================
@@ -1155,13 +1207,6 @@ def cls_ce_loss(logits: Tensor, labels: Tensor, out: Optional[Tensor] = None):
 # ======================================================================================================
 # 3-D model (models/dpot3d.py): AFNO3D on the kernels of csrc/dft3.hip, and the plain stages of DPOTNet3D
 # ======================================================================================================
-def _mixer3_dims(B: int, tok: int, E: int, nb: int, m3, act: int):
-    """the `dims` tuple of _mixer_core / _mixer_core_bwd for a 3-D box: they read only B * mx * my (the kept-mode rows), so the
-    two mode slots carry (mx * my, mz); the grid slots are unused"""
-    mx, my, mz = m3
-    return (B, tok, E, 0, 0, nb, E // nb, mx * my, mz, 0, act)
-
-
 class AFNO3DFn(torch.autograd.Function):
     """The reference's ``AFNO3D`` (models/dpot3d.py:46-97) on a channels-last field x[B, X*Y*Z, E] (z fastest):
     irfftn(MLP(rfftn(x)[:modes, :modes, :8])) + x.  The 3-D twin of AFNO2DFn: rfft3 -> _mixer_core -> irfft3 (+ x); backward
@@ -1175,37 +1220,14 @@ class AFNO3DFn(torch.autograd.Function):
         dims3 = tuple(int(d) for d in dims3)
         assert tok == dims3[0] * dims3[1] * dims3[2], f"{tok} tokens are not a {dims3} grid"
         m3 = ops.kept_modes3(dims3, modes)
-        if packed is None:
-            packed = tuple(ops.AfnoPacks([(w1, b1), (w2, b2)]).refresh())
-        dims = _mixer3_dims(B, tok, E, nb, m3, act)
-        S = ops.rfft3(x, dims3, nb, m3, 0)                                   # [Mm, 2E]
-        O2, O1pre, O1 = _mixer_core(S, packed, dims)
-        y = ops.irfft3(O2, B, dims3, E, nb, m3, 1, res=x)                    # + x_orig
-        ctx.fused = packed[0][2] is not None
-        wb1, wb2 = (packed[0][3], packed[1][3]) if ctx.fused else (packed[0][0], packed[1][0])
-        ctx.afno_layout = getattr(packed[0], "layout", 0) if ctx.fused else 0
-        ctx.p6b = _p6_of(packed, 1) if ctx.fused else None
-        ctx.save_for_backward(S, O1pre, O1, wb1, wb2)
-        ctx.dims, ctx.dims3, ctx.m3 = dims, dims3, m3
-        ctx.sinks = _sinks(ctx, (w1, b1, w2, b2), 1)
-        ctx.weights_epoch = _epoch_of(ctx.sinks)
-        return y
+        return _afno_forward(ctx, x, (w1, b1, w2, b2), packed, nb, act,
+                             lambda t, cw: ops.rfft3(t, dims3, nb, m3, cw),
+                             lambda s, cw, res: ops.irfft3(s, B, dims3, E, nb, m3, cw, res=res))
 
     @staticmethod
     @ops.with_ctx_precision
     def backward(ctx, dy):
-        _check_epoch(ctx, "AFNO3DFn")
-        S, O1pre, O1, wb1, wb2 = ctx.saved_tensors
-        lay = ctx.afno_layout
-        if ctx.p6b is not None:
-            (wb1, wb2), lay = ctx.p6b, 2
-        dy = dy.contiguous()
-        B, _, E = dy.shape
-        nb = ctx.dims[5]
-        dO2 = ops.rfft3(dy, ctx.dims3, nb, ctx.m3, 1)                        # adjoint of irfft3
-        dS, dw1, db1, dw2, db2 = _mixer_core_bwd(dO2, S, O1pre, O1, wb1, wb2, ctx.dims, ctx.fused, lay, ctx.sinks)
-        dx = ops.irfft3(dS, B, ctx.dims3, E, nb, ctx.m3, 0, res=dy)          # adjoint of rfft3, + skip path
-        return dx, dw1, db1, dw2, db2, None, None, None, None, None
+        return _afno_backward(ctx, dy, "AFNO3DFn") + (None,) * 5
 
 
 class GroupNormFn(torch.autograd.Function):

@@ -663,37 +663,6 @@ def afno_pack(w: Tensor, b: Tensor) -> Tuple[Tensor, Tensor]:
     return wbig, bbig
 
 
-def afno_pack3(w: Tensor, b: Tensor):
-    """(Wbig, bbig, blocked W | None, blocked W^T | None): the per-layer form of what afno_pack_multi returns"""
-    _, nb, bs, _ = w.shape
-    wbig, bbig = afno_pack(w, b)
-    if afno_mlp2_supported(nb, bs):
-        wf, wb = afno_block_weights(wbig)
-        return wbig, bbig, wf, wb
-    return wbig, bbig, None, None
-
-
-def afno_pack_multi(pairs) -> list:
-    """pairs = [(w [2,nb,bs,bs], b [2,nb,bs]), ...] of equal shapes -> [(wbig, bbig), ...], ONE launch for all of them"""
-    n = len(pairs)
-    _, nb, bs, _ = pairs[0][0].shape
-    dev = pairs[0][0].device
-    wbig = torch.empty(n, nb, 2 * bs, 2 * bs, dtype=torch.float32, device=dev)
-    bbig = torch.empty(n, nb, 2 * bs, dtype=torch.float32, device=dev)
-    arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
-    check(_lib.load().dpot_afno_pack_multi(arr([_req(w, "w").data_ptr() for w, _ in pairs]),
-                                           arr([_req(b, "b").data_ptr() for _, b in pairs]),
-                                           arr([wbig[i].data_ptr() for i in range(n)]),
-                                           arr([bbig[i].data_ptr() for i in range(n)]), n, nb, bs, _stream()),
-          "afno_pack_multi")
-    # fragment-block-major copies for the fused 2-layer kernel (afno_mlp2): one launch for all layers
-    if afno_mlp2_supported(nb, bs):
-        wf, wb = afno_block_weights(wbig.view(n * nb, 2 * bs, 2 * bs))
-        wf, wb = wf.view(n, nb, 2 * bs, 2 * bs), wb.view(n, nb, 2 * bs, 2 * bs)
-        return [(wbig[i], bbig[i], wf[i], wb[i]) for i in range(n)]
-    return [(wbig[i], bbig[i], None, None) for i in range(n)]
-
-
 class AfnoItem(tuple):
     """(Wbig, bbig, fwd pack | None, bwd pack | None) of one AFNO layer + the layout of the packs (0: fragment-block-major
     Wbig for afno_mlp2's four-product kernel, 1: (Wr, Wi) fragments for the three-product kernel)"""
@@ -703,6 +672,16 @@ class AfnoItem(tuple):
         self.layout = layout
         self.p6 = p6          # (fwd6, bwd6): the bf16x6 packs of csrc/afno_mlp6.hip (layout 2 of afno_mlp2), or None
         return self
+
+    wbig, bbig, fwd, bwd = (property(lambda self, i=i: self[i]) for i in range(4))
+
+
+def afno_pack3(w: Tensor, b: Tensor) -> AfnoItem:
+    """one layer packed on its own: (Wbig, bbig, blocked W | None, blocked W^T | None), layout 0"""
+    _, nb, bs, _ = w.shape
+    wbig, bbig = afno_pack(w, b)
+    wf, wb = afno_block_weights(wbig) if afno_mlp2_supported(nb, bs) else (None, None)
+    return AfnoItem((wbig, bbig, wf, wb))
 
 
 class AfnoPacks:
@@ -729,7 +708,6 @@ class AfnoPacks:
         self.wbig = wbig
         self.fwd6 = self.bwd6 = None               # allocated by the first refresh that wants them (3 bytes per weight element
         self._p6_ok = fused and n % 2 == 0 and afno_mlp6_supported(nb, bs)   # each: nothing for a model that stays in 'f32')
-        self._fused = fused
         self._base = [(wbig[i], bbig[i], fwd[i] if fused else None, bwd[i] if fused else None) for i in range(n)]
         self.items = [AfnoItem(t, self.layout, None) for t in self._base]
 
@@ -1089,7 +1067,7 @@ def groupnorm_param_grads(jobs):
 # GroupNorm fused with the mixer's DFTs (csrc/gn_dft.hip)
 # ------------------------------------------------------------------------------------------------------
 def gn_dft_supported(h: int, w: int, E: int, G: int = 8) -> bool:
-    """16x16 latent grid and 64 / 128 channels per group (DPOT-Tiny / -Small / -Medium at 128^2); DPOT_GN_DFT=0 disables"""
+    """16x16 latent grid and 64 / 128 channels per group (DPOT-Tiny / -Small / -Medium at 128^2); DPOT_TUNE gn_fuse=0 disables"""
     return bool(_lib.load().dpot_gn_dft_supported(h, w, E, G))
 
 

@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from dpot_amd import ops  # noqa: E402
-from dpot_amd.functional import AFNO3DFn, _mixer3_dims, _mixer_core  # noqa: E402
+from dpot_amd.functional import _AFNO_PARAMS, AFNO3DFn, MixerWeights, _mixer_core, _mixer_core_bwd, _Sink, _WgradRoute  # noqa: E402
 
 SHAPES = [(4, (8, 8, 8), 512), (4, (8, 8, 8), 1024), (2, (16, 16, 16), 512)]
 NB, MODES = 8, 32
@@ -102,26 +102,21 @@ class ComposedAFNO3D(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, packed, dims3, nb, m3, act, ws):
         B, tok, E = x.shape
-        dims = _mixer3_dims(B, tok, E, nb, m3, act)
+        mw = MixerWeights.of(packed)
         S = fft_fwd(x, dims3, m3, nb, ws[0])
-        O2, O1pre, O1 = _mixer_core(S, packed, dims)
+        O2, O1pre, O1 = _mixer_core(S, mw, nb, act)
         y = fft_inv(O2, B, dims3, E, m3, nb, ws[0], x)
         ctx.save_for_backward(S, O1pre, O1)
-        ctx.args = (packed, dims, dims3, nb, m3, ws)
+        ctx.args = (mw.for_backward(False), act, dims3, nb, m3, ws)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        from dpot_amd.functional import _Sink, _mixer_core_bwd
-        S, O1pre, O1 = ctx.saved_tensors
-        packed, dims, dims3, nb, m3, ws = ctx.args
+        mw, act, dims3, nb, m3, ws = ctx.args
         B, _, E = dy.shape
-        fused = packed[0][2] is not None
-        wb1, wb2 = (packed[0][3], packed[1][3]) if fused else (packed[0][0], packed[1][0])
         dO2 = fft_fwd(dy.contiguous(), dims3, m3, nb, ws[1])
-        sinks = [_Sink(None, False) for _ in range(4)]
-        dS = _mixer_core_bwd(dO2, S, O1pre, O1, wb1, wb2, dims, fused,
-                             getattr(packed[0], "layout", 0) if fused else 0, sinks)[0]
+        wg = _WgradRoute(_AFNO_PARAMS, [_Sink(None, False) for _ in range(4)])
+        dS = _mixer_core_bwd(dO2, *ctx.saved_tensors, mw, nb, act, wg)
         return fft_inv(dS, B, dims3, E, m3, nb, ws[2], dy), None, None, None, None, None, None
 
 
