@@ -46,7 +46,9 @@ int tune(const char* key, int dflt) {
  * 264: dpot_spectral_resize, dpot_spectral_resize_pad (csrc/resize.hip)
  * 266: dpot_mlp_wgrad_batch, dpot_afno_wgrad_batch, dpot_wgrad_batch_finalize and their queries (csrc/gemm_tn.hip): the weight
  * gradients of several DPOT blocks per launch
- * 267: dpot_dft3_supported, dpot_rfft3, dpot_irfft3 (csrc/dft3.hip): the transforms of the 3-D model's AFNO3D */
-extern "C" int dpot_version(void) { return 267; }
+ * 267: dpot_dft3_supported, dpot_rfft3, dpot_irfft3 (csrc/dft3.hip): the transforms of the 3-D model's AFNO3D
+ * 268: dpot_wgrad_flush_async, dpot_wgrad_wait, dpot_wgrad_lane_* (csrc/gemm_tn.hip): the batched weight gradients on a
+ * library-owned stream beside the caller's */
+extern "C" int dpot_version(void) { return 268; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

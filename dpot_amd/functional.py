@@ -100,11 +100,17 @@ class WgradBatch:
     By default the batched launches cut the tokens exactly as the per-block launches do (several rounds of workgroups in one
     launch): every partial and every sum is the same, the gradients are bit-identical to the per-block schedule's.
     DPOT_TUNE fused_small=3 selects the one-round rules instead (fewer, longer token ranges: less partial traffic, another
-    summation order)."""
+    summation order).
+
+    The flush is the last thing block 0's backward does; the embed backward that follows is a chain of small launches that reads
+    none of its results.  By default (DPOT_TUNE fused_small=4, `ops.wgrad_lane_scope`) the three launch sets therefore go to the
+    library's weight-gradient lane, a stream of its own that is forked from this one and joined back when the backward ends
+    (`_lane_ok`, ops.wgrad_flush_async).  Same launches, same results."""
 
     def __init__(self):
         self.expected = self.delivered = 0
         self.jobs = []
+        self.lane = ops.wgrad_lane_enabled()     # read in the forward: the flush runs on the autograd engine's thread
 
     def register(self) -> None:
         self.expected += 1
@@ -141,19 +147,42 @@ class WgradBatch:
         return ops.mlp_wgrad2_splitk(M, E, mh, mp), min(n, ops.wgrad_batch_max_blocks()), s12, sk
 
     @staticmethod
-    def _flush_group(g) -> None:
+    def _lane_ok(g) -> bool:
+        """The flush may run beside the rest of the backward (ops.wgrad_flush_async) when nobody looks at its gradients before
+        the backward ends - no gradient-ready callbacks (a data-parallel reducer, hooks) - and every sink is the ONLY outstanding
+        use of its parameter and writes its slot directly: no temporary to add on the step's stream now, none by a later
+        contribution of this backward (a rollout's further passes).  The wait is the autograd engine's end-of-backward callback;
+        outside a backward there is none to queue."""
+        for j in g:
+            for sk in j.sinks.values():
+                if sk.fp.callbacks or sk.fp.pending[sk.i] != 1 or sk.out() is None:
+                    return False
+        try:
+            torch.autograd.Variable._execution_engine.queue_callback(ops.wgrad_lane_join)
+        except RuntimeError:
+            return False
+        return True
+
+    def _flush_group(self, g) -> None:
         M, E, mh, mp, adims, _ = g[0].key
         dev = g[0].mlp[0].device
         skm, per, s12, sk = WgradBatch.splits(len(g), M, E, mh, mp, *adims)
-        mws = ops.mlp_wgrad_batch(*[[j.mlp[k] for j in g] for k in range(4)], skm)
+        lane = self.lane and self._lane_ok(g)
+        if not lane:
+            ops.wgrad_lane_join()        # nothing pending in a backward of one schedule; a mixed one adds on this stream below
+        mops, aops = [[j.mlp[k] for j in g] for k in range(4)], [[j.afno[k] for j in g] for k in range(4)]
         def outs(j, names, shapes):      # the gradient slots where this is the step's first contribution, else temporaries
             return tuple(ops._out(j.sinks[nm].out(), shp, dev) for nm, shp in zip(names, shapes))
         mouts = [outs(j, _MLP_PARAMS, ((E, mh), (E,), (mh, E), (mh,))) for j in g]
         Mm, nb, bs = adims
-        aws = ops.afno_wgrad_batch(*[[j.afno[k] for j in g] for k in range(4)], nb, bs, per, s12, sk)
         aouts = [outs(j, _AFNO_PARAMS, ((2, nb, bs, bs), (2, nb, bs)) * 2) for j in g]
         gn = [[(part,) + outs(j, names, ((E,), (E,))) for part, names in zip(j.gn, _GN_PARAMS)] for j in g]
-        ops.wgrad_batch_finalize((aws, s12, sk, nb, bs, aouts), (mws, skm, E, mh, mouts), gn)
+        if lane:
+            ops.wgrad_flush_async(mops, skm, mouts, aops, nb, bs, per, s12, sk, aouts, gn)
+        else:
+            mws = ops.mlp_wgrad_batch(*mops, skm)
+            aws = ops.afno_wgrad_batch(*aops, nb, bs, per, s12, sk)
+            ops.wgrad_batch_finalize((aws, s12, sk, nb, bs, aouts), (mws, skm, E, mh, mouts), gn)
         for i, j in enumerate(g):
             dW2, db2, dW1, db1 = mouts[i]
             (_, dg1, db1n), (_, dg2, db2n) = gn[i]

@@ -165,9 +165,11 @@ TUNE_KEYS = {
                        "un-paired weight gradients"),
     "packs": (1, "0 = bf16 packs by separate pack passes only: none from the one-launch AFNO layer, the GroupNorm backward or Adam"),
     "pack_both": (1, "0 = bf16 channel MLP without the pack-both path (one pack pass per operand form, fp32 pre-activation saved)"),
-    "fused_small": (1, "0 = separate small launches: per-block reduce launches, eight layout launches, torch ops for the cls head; "
+    "fused_small": (4, "0 = separate small launches: per-block reduce launches, eight layout launches, torch ops for the cls head; "
                        "2 = as 1, but the blocks' weight gradients and their finalising launch per block instead of batched; "
-                       "3 = as 1 with the batched launches cut by the one-round rules (another summation order)"),
+                       "3 = as 1 with the batched launches cut by the one-round rules (another summation order); "
+                       "4 = as 1 with the batched launches on the library's own stream beside the embed backward "
+                       "(dpot_wgrad_flush_async); 1 = the batched launches on the step's stream, one after the other"),
     "embed_implicit": (1, "0 = explicit patch matrix + GEMM instead of the implicit-GEMM patch embedding"),
     "mixer6": (1, "bf16x6 mixer kernel afno_mlp6 under gemm_precision 'auto' / 'bf16x6': 1 = where it measured faster (96 channels "
                   "per block: DPOT-L), 2 = wherever supported (also 128), 0 = never (the fp32 matrix-core kernels)"),
@@ -811,8 +813,9 @@ def block_finalize_enabled() -> bool:
 
 
 def wgrad_batch_enabled() -> bool:
-    """the weight gradients of all blocks in batched launches + one finalising launch (DPOT_TUNE fused_small=2: per block)"""
-    return tune("fused_small") in (1, 3)
+    """the weight gradients of all blocks in batched launches + one finalising launch (DPOT_TUNE fused_small=2: per block;
+    4, the default: the batched launches on the weight-gradient lane, `wgrad_lane_enabled`)"""
+    return tune("fused_small") in (1, 3, 4)
 
 
 def wgrad_batch_one_round() -> bool:
@@ -820,6 +823,59 @@ def wgrad_batch_one_round() -> bool:
     `afno_wgrad_batch_plan`) - another summation order than the per-block launches; default: the per-block split factors,
     bit-identical gradients"""
     return tune("fused_small") == 3
+
+
+@contextlib.contextmanager
+def wgrad_lane_scope(on: Optional[bool]):
+    """whether the forward passes run on this thread inside hand their batched weight gradients to the library's lane
+    (functional.WgradBatch reads it when DPOTNet creates it, so the backward may run anywhere later): True / False, or None =
+    DPOT_TUNE fused_small (4, the default: the lane).  For one process that runs both schedules."""
+    prev = getattr(_tls, "wgrad_lane", None)
+    _tls.wgrad_lane = on
+    try:
+        yield
+    finally:
+        _tls.wgrad_lane = prev
+
+
+def wgrad_lane_enabled() -> bool:
+    v = getattr(_tls, "wgrad_lane", None)
+    return tune("fused_small") == 4 if v is None else bool(v)
+
+
+def wgrad_lane_init() -> None:
+    """create the current device's lane now (never legal while a stream of the device is capturing)"""
+    check(_lib.load().dpot_wgrad_lane_init(), "wgrad_lane_init")
+
+
+def wgrad_lane_ready() -> bool:
+    return bool(_lib.load().dpot_wgrad_lane_ready())
+
+
+def wgrad_lane_pending() -> int:
+    """flushes the current device's lane has taken since the last wait (tests, assertions)"""
+    return _lib.load().dpot_wgrad_lane_pending()
+
+
+def wgrad_lane_shutdown() -> None:
+    wgrad_lane_join()
+    check(_lib.load().dpot_wgrad_lane_shutdown(), "wgrad_lane_shutdown")
+
+
+# what the lane's queued launches read and write, [(stream, tensors)]: allocated on the step's stream and referenced from here
+# until the wait has been ISSUED on that stream - whatever the allocator hands out again afterwards is ordered behind the lane
+_lane_held = []
+_lane_lock = threading.Lock()
+
+
+def wgrad_lane_join() -> None:
+    """order the streams that flushed to the lane behind it (dpot_wgrad_wait) and release what the lane's launches use.  Nothing
+    when nothing is pending; the end-of-backward callback of functional.WgradBatch and FlatOptimizer.launch call it."""
+    with _lane_lock:
+        held = _lane_held[:]
+        del _lane_held[:]
+    for stream in dict.fromkeys(st for st, _ in held):
+        check(_lib.load().dpot_wgrad_wait(stream), "wgrad_wait")
 
 
 def wgrad_batch_max_blocks() -> int:
@@ -846,17 +902,22 @@ def mlp_wgrad_batch_splitk(T: int, E: int, mh: int, n: int, precision: Optional[
 def mlp_wgrad_batch(do2, Hh, xn2, dHpre, splitk: int) -> Tensor:
     """partials of both channel-MLP weight gradients of len(do2) blocks (lists of per-block operands, as `mlp_wgrad2`):
     returns the workspace [n, elems] - row i in the layout `mlp_wgrad2(defer=True)` leaves, for `wgrad_batch_finalize`"""
-    lib = _lib.load()
+    n, T, E, mh, ws = _mlp_wgrad_batch_ws(do2, Hh, xn2, dHpre, splitk)
+    check(_lib.load().dpot_mlp_wgrad_batch(_ptr_array(do2), _ptr_array(Hh), _ptr_array(xn2), _ptr_array(dHpre), n, T, E, mh,
+                                           ws.data_ptr(), splitk, _stream()), "mlp_wgrad_batch")
+    return ws
+
+
+def _mlp_wgrad_batch_ws(do2, Hh, xn2, dHpre, splitk: int):
+    """(n, T, E, mh, workspace [n, elems]) of `mlp_wgrad_batch` after its operand checks"""
     n = len(do2)
     T, E = do2[0].shape
     mh = Hh[0].shape[1]
     for a, b, c, d in zip(do2, Hh, xn2, dHpre):
         assert a.shape == (T, E) and c.shape == (T, E) and b.shape == (T, mh) and d.shape == (T, mh)
         assert a.is_contiguous() and b.is_contiguous() and c.is_contiguous() and d.is_contiguous()
-    ws = torch.empty(n, lib.dpot_mlp_wgrad2_ws_elems(E, mh, splitk), dtype=torch.float32, device=do2[0].device)
-    check(lib.dpot_mlp_wgrad_batch(_ptr_array(do2), _ptr_array(Hh), _ptr_array(xn2), _ptr_array(dHpre), n, T, E, mh,
-                                   ws.data_ptr(), splitk, _stream()), "mlp_wgrad_batch")
-    return ws
+    ws = torch.empty(n, _lib.load().dpot_mlp_wgrad2_ws_elems(E, mh, splitk), dtype=torch.float32, device=do2[0].device)
+    return n, T, E, mh, ws
 
 
 def afno_wgrad_batch_plan(Mm: int, nb: int, bs: int, n: int) -> Tuple[int, int, int]:
@@ -872,16 +933,21 @@ def afno_wgrad_batch_plan(Mm: int, nb: int, bs: int, n: int) -> Tuple[int, int, 
 def afno_wgrad_batch(S, dO1pre, O1, dO2, nb: int, bs: int, per_launch: int, splits12: int, splitk: int) -> Tensor:
     """partials of both AFNO weight gradients of len(S) blocks (lists of per-block operands, as `afno_wgrad2`), `per_launch`
     blocks per launch: returns the workspace [n, elems], row i in the layout of `afno_wgrad2(defer=True)`"""
-    lib = _lib.load()
+    n, Mm, ld, ws = _afno_wgrad_batch_ws(S, dO1pre, O1, dO2, nb, bs, splitk)
+    check(_lib.load().dpot_afno_wgrad_batch(_ptr_array(S), _ptr_array(dO1pre), _ptr_array(O1), _ptr_array(dO2), n, ld, Mm, nb,
+                                            bs, ws.data_ptr(), per_launch, splits12, splitk, _stream()), "afno_wgrad_batch")
+    return ws
+
+
+def _afno_wgrad_batch_ws(S, dO1pre, O1, dO2, nb: int, bs: int, splitk: int):
+    """(n, Mm, ld, workspace [n, elems]) of `afno_wgrad_batch` after its operand checks"""
     n = len(S)
     Mm, ld = S[0].shape
     for ts in (S, dO1pre, O1, dO2):
         for t in ts:
             assert t.shape == (Mm, ld) and t.is_contiguous()
-    ws = torch.empty(n, lib.dpot_afno_wgrad2_ws_elems(nb, bs, splitk), dtype=torch.float32, device=S[0].device)
-    check(lib.dpot_afno_wgrad_batch(_ptr_array(S), _ptr_array(dO1pre), _ptr_array(O1), _ptr_array(dO2), n, ld, Mm, nb, bs,
-                                    ws.data_ptr(), per_launch, splits12, splitk, _stream()), "afno_wgrad_batch")
-    return ws
+    ws = torch.empty(n, _lib.load().dpot_afno_wgrad2_ws_elems(nb, bs, splitk), dtype=torch.float32, device=S[0].device)
+    return n, Mm, ld, ws
 
 
 def wgrad_batch_finalize(afno, mlp, gn):
@@ -889,6 +955,15 @@ def wgrad_batch_finalize(afno, mlp, gn):
     afno: None | (ws [n, .], splits12, splitk, nb, bs, [(dw1, db1, dw2, db2)] * n);
     mlp:  None | (ws [n, .], splitk, E, mh, [(dW2, db2, dW1, db1)] * n);
     gn:   [[(part [2, B, E], dgamma, dbeta)] * jobs] * n  (jobs <= 2, outputs allocated by the caller)"""
+    blocks, n, jobs, B, Eg = _wgrad_block_table(afno, mlp, gn)
+    a = afno if afno is not None else (None, 0, 0, 0, 0)
+    m = mlp if mlp is not None else (None, 0, 0, 0)
+    check(_lib.load().dpot_wgrad_batch_finalize(blocks, n, a[1], a[2], a[3], a[4], m[1], m[2], m[3], jobs, B, Eg, _stream()),
+          "wgrad_batch_finalize")
+
+
+def _wgrad_block_table(afno, mlp, gn):
+    """(dpot_wgrad_block table, n, GroupNorm jobs per block, B, E of the GroupNorm partials) of `wgrad_batch_finalize`"""
     n = len(gn)
     blocks = (_lib.WgradBlock * n)()
     jobs, B, Eg = len(gn[0]), 0, 0
@@ -904,10 +979,24 @@ def wgrad_batch_finalize(afno, mlp, gn):
         for j, (part, dg, db) in enumerate(gn[i]):
             _, B, Eg = part.shape
             w.gn_part[j], w.gn_dgamma[j], w.gn_dbeta[j] = part.data_ptr(), dg.data_ptr(), db.data_ptr()
-    a = afno if afno is not None else (None, 0, 0, 0, 0)
-    m = mlp if mlp is not None else (None, 0, 0, 0)
-    check(_lib.load().dpot_wgrad_batch_finalize(blocks, n, a[1], a[2], a[3], a[4], m[1], m[2], m[3], jobs, B, Eg, _stream()),
-          "wgrad_batch_finalize")
+    return blocks, n, jobs, B, Eg
+
+
+def wgrad_flush_async(mlp_ops, skm: int, mouts, afno_ops, nb: int, bs: int, per_launch: int, splits12: int, splitk: int,
+                      aouts, gn) -> None:
+    """`mlp_wgrad_batch`, `afno_wgrad_batch` and `wgrad_batch_finalize` of one group of blocks on the library's lane, behind
+    the current stream (csrc/gemm_tn.hip dpot_wgrad_flush_async).  mlp_ops / afno_ops: the four operand lists of the two
+    launches; mouts, aouts, gn: the outputs per block as `wgrad_batch_finalize` takes them.  Everything the launches touch
+    stays referenced until `wgrad_lane_join` has ordered the stream behind the lane."""
+    n, T, E, mh, mws = _mlp_wgrad_batch_ws(*mlp_ops, skm)
+    _, Mm, ld, aws = _afno_wgrad_batch_ws(*afno_ops, nb, bs, splitk)
+    blocks, _, jobs, B, Eg = _wgrad_block_table((aws, splits12, splitk, nb, bs, aouts), (mws, skm, E, mh, mouts), gn)
+    stream = _stream()
+    with _lane_lock:
+        _lane_held.append((stream, (mlp_ops, afno_ops, aws, mws, mouts, aouts, gn)))
+    check(_lib.load().dpot_wgrad_flush_async(*[_ptr_array(t) for t in mlp_ops], n, T, E, mh, mws.data_ptr(), skm,
+                                             *[_ptr_array(t) for t in afno_ops], ld, Mm, nb, bs, aws.data_ptr(), per_launch,
+                                             splits12, splitk, blocks, jobs, B, Eg, stream), "wgrad_flush_async")
 
 
 def afno_mlp2_supported(nb: int, bs: int) -> bool:

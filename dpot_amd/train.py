@@ -158,6 +158,7 @@ class FlatOptimizer:
     def launch(self, grad_scale: float = 1.0) -> None:
         """device side of a step (capturable): ||g||^2 (with clipping), then the update launches"""
         use_clip = self.max_norm is not None
+        ops.wgrad_lane_join()         # the backward has joined the weight-gradient lane already; this costs a list lookup
         if use_clip:
             ops.sumsq(self.fp.grad[:self.n_active], self.sumsq, self._part)
         plan = self._pack_plan()

@@ -22,7 +22,8 @@
  *   - kernels are enqueued on `stream` (a hipStream_t passed as void*) and never synchronise, so every
  *     call is legal inside HIP stream capture (hipGraph)
  *   - return value: 0 on success, negative DPOT_E* on error; dpot_last_error() gives the message
- *   - re-entrant and stateless (no global state besides the thread-local error string)
+ *   - re-entrant and stateless (no global state besides the thread-local error string and the weight-gradient lane,
+ *     one stream and two events per device behind a mutex: dpot_wgrad_flush_async)
  */
 #ifndef DPOT_HIP_H
 #define DPOT_HIP_H
@@ -213,6 +214,29 @@ int dpot_afno_wgrad_batch(const float* const* S, const float* const* dO1pre, con
  * channel-MLP partials when mlp_splitk > 0, gn_jobs <= 2 GroupNorm parameter gradients), the same reduction bodies. */
 int dpot_wgrad_batch_finalize(const dpot_wgrad_block* blocks, int n, int afno_splits12, int afno_splitk, int nb, int bs,
                               int mlp_splitk, int E, int mh, int gn_jobs, int B, int Egn, dpot_stream_t stream);
+/* The weight-gradient LANE: the three launch sets above on a library-owned stream beside the caller's (csrc/gemm_tn.hip).
+ * Nothing reads a weight gradient before the optimiser, so the caller's stream can go on with the embed backward meanwhile.
+ * One lane per device - a non-blocking stream at the default priority (any other measured slower under graph replay) and two events
+ * without timing - created by dpot_wgrad_lane_init() or the first flush, never while the caller's stream is capturing (that
+ * flush runs on the caller's stream).  This is the library's only state; it is guarded by a mutex.
+ * dpot_wgrad_flush_async: the arguments of dpot_mlp_wgrad_batch, dpot_afno_wgrad_batch and dpot_wgrad_batch_finalize (n, the
+ *   split factors, nb, bs, E, mh once).  Records the fork event on `stream`, makes the lane wait for it, issues the three
+ *   launch sets on the lane through those entry points, records the done event on the lane and counts one pending flush.
+ *   Inside a stream capture the lane becomes a parallel branch of the capture; dpot_wgrad_wait joins it back.
+ *   The caller keeps every buffer the launches read or write alive, and unused by others, until it has called dpot_wgrad_wait.
+ * dpot_wgrad_wait: makes `stream` wait for the last done event and clears the pending count; nothing when nothing is pending.
+ * dpot_wgrad_lane_pending: flushes since the last wait (current device).  dpot_wgrad_lane_ready: 1 when the lane exists.
+ * dpot_wgrad_lane_shutdown: drains and destroys the lane of the current device (nothing may be pending). */
+int dpot_wgrad_lane_init(void);
+int dpot_wgrad_lane_ready(void);
+int dpot_wgrad_lane_pending(void);
+int dpot_wgrad_lane_shutdown(void);
+int dpot_wgrad_flush_async(const float* const* do2, const float* const* Hh, const float* const* xn2, const float* const* dHpre,
+                           int n, int T, int E, int mh, float* mlp_ws, int mlp_splitk, const float* const* S,
+                           const float* const* dO1pre, const float* const* O1, const float* const* dO2, int ld, int Mm, int nb,
+                           int bs, float* afno_ws, int per_launch, int afno_splits12, int afno_splitk,
+                           const dpot_wgrad_block* blocks, int gn_jobs, int B, int Egn, dpot_stream_t stream);
+int dpot_wgrad_wait(dpot_stream_t stream);
 /* Small weight-only layout jobs (zero-padded copies, small transposes, bias broadcasts, "+ bias") in ONE launch from a DEVICE
  * table: dst[i0][i1][i2] (contiguous d0 x d1 x d2) = (inside v0 x v1 x v2 ? src[i0 s0 + i1 s1 + i2 s2] : 0) + (add ? add[i2] : 0).
  * The pieces DPOTNet derives from its parameters once per optimiser step (models/dpot.py:198-202 padded for the MFMA
