@@ -140,6 +140,9 @@ SIGNATURES = {
     "dpot_patchify": (c_i, [c_fp] * 5 + [c_i] * 6 + [c_fp]),
     "dpot_unpatchify": (c_i, [c_fp] * 2 + [c_i] * 6 + [c_fp]),
     "dpot_pixel_shuffle": (c_i, [c_fp] * 2 + [c_i] * 6 + [c_fp]),
+    "dpot_patchify3": (c_i, [c_fp] * 4 + [c_i] * 5 + [c_fp]),
+    "dpot_unpatchify3": (c_i, [c_fp] * 2 + [c_i] * 5 + [c_fp]),
+    "dpot_fold3": (c_i, [c_fp] * 2 + [c_i] * 5 + [c_fp]),
     "dpot_copy2d_pad": (c_i, [c_fp, c_i, c_i, c_fp, c_i, c_i, c_fp]),
     "dpot_transpose2d": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp]),
     "dpot_colsum_parts": (c_i, [c_i]),

@@ -1312,6 +1312,44 @@ class Mlp2Fn(torch.autograd.Function):
         return dx, dW1, db1, dW2, db2, None, dres, None
 
 
+class PatchEmbed3DFn(torch.autograd.Function):
+    """PatchEmbed of DPOTNet3D (models/dpot3d.py:100-140) on the raw window x[B,S,S,S,T,C]: ops.patchify3 (the four coordinate
+    channels come from the tables gs[S], gt[T]), then the two GEMMs of Mlp2Fn - k = s = P convolution, act, 1x1 convolution,
+    + the pos_embed table ``pos`` [tok, E] - giving rows ((b, t), token).  The patch matrix ((C+4)/C times the window, per AR
+    step) is NOT kept for the backward: x is, and the backward gathers the matrix again for the weight gradient and frees it.
+    dx (an AR step whose input carries a gradient) comes from ops.unpatchify3."""
+
+    @staticmethod
+    def forward(ctx, x, gs, gt, W1, b1, W2, b2, pos, P: int, act: int):
+        ops.capture_precision(ctx)
+        x, W1, W2, pos = x.contiguous(), W1.contiguous(), W2.contiguous(), pos.contiguous()
+        A0 = ops.patchify3(x, gs, gt, P)
+        Hh, Hpre = ops.linear_fwd(A0, W1, b1, act=act, save_pre=True)
+        del A0
+        y, _ = ops.linear_fwd(Hh, W2, b2, res=pos, res_mod=pos.shape[0])
+        ctx.save_for_backward(x, gs, gt, Hh, Hpre, W1, W2)
+        ctx.P, ctx.act, ctx.tok = P, act, pos.shape[0]
+        return y
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dy):
+        x, gs, gt, Hh, Hpre, W1, W2 = ctx.saved_tensors
+        dy = dy.contiguous()
+        M, N = dy.shape
+        dHpre = ops.linear_bwd_data(dy, W2, act=ctx.act, aux=Hpre)          # (dy W2) * act'(Hpre)
+        dW2, db2 = ops.linear_bwd_wb(dy, Hh)
+        A0 = ops.patchify3(x, gs, gt, ctx.P)
+        dW1, db1 = ops.linear_bwd_wb(dHpre, A0)
+        del A0
+        dx = None
+        if ctx.needs_input_grad[0]:
+            B, S, _, _, T, C = x.shape
+            dx = ops.unpatchify3(ops.linear_bwd_data(dHpre, W1), B, S, T, C, ctx.P)
+        dpos = ops.group_rowsum(dy, M // ctx.tok, ctx.tok, 1, N) if ctx.needs_input_grad[7] else None
+        return dx, None, None, dW1, db1, dW2, db2, dpos, None, None
+
+
 class TimeAggFn(torch.autograd.Function):
     """TimeAggregator (models/dpot3d.py:143-151) on rows A[M, T*E] (columns (t, i)): y[m, j] = sum_{t,i} A[m, (t,i)] ws[t,i,j]
     with ws = w (time_agg 'mlp') or w * cos(t gamma_i) ('exp_mlp': gamma given)"""
@@ -1355,7 +1393,8 @@ class TimeAggFn(torch.autograd.Function):
 
 
 def _unfold3(t: Tensor, B: int, h: int, P: int, old: int) -> Tensor:
-    """[B*h^3, old*P^3] (rows (b, hx, hy, hz), columns (o, i, j, k)) -> [B*(hP)^3, old] (rows (b, x, y, z)): the scatter of a
+    """(the torch statement of ops.fold3, kept as the yardstick of its tests and timings)
+    [B*h^3, old*P^3] (rows (b, hx, hy, hz), columns (o, i, j, k)) -> [B*(hP)^3, old] (rows (b, x, y, z)): the scatter of a
     k = s = P transposed convolution"""
     return t.view(B, h, h, h, old, P, P, P).permute(0, 1, 5, 2, 6, 3, 7, 4).reshape(B * (h * P) ** 3, old)
 
@@ -1381,8 +1420,10 @@ class Head3DFn(torch.autograd.Function):
         H1pre = torch.empty_like(H1)
         ops.gemm(x, W0, H1, M, N0, E, lda=E, ldb=N0, ldc=N0, bias=b0e.contiguous(), act=act, mode=EPI_ACT, preact=H1pre,
                  ldpre=N0)
-        H1p, H1pre_p = _unfold3(H1, B, h, P, old), _unfold3(H1pre, B, h, P, old)
-        del H1, H1pre
+        H1p = ops.fold3(H1, B, h, P, old)                                   # rows (b, x, y, z)
+        del H1
+        H1pre_p = ops.fold3(H1pre, B, h, P, old)
+        del H1pre
         H2, H2pre = ops.linear_fwd(H1p, W2, b2, act=act, save_pre=True)
         out, _ = ops.linear_fwd(H2, W4, b4)
         ctx.save_for_backward(x, W0, W2, W4, H1p, H1pre_p, H2, H2pre)
@@ -1402,7 +1443,7 @@ class Head3DFn(torch.autograd.Function):
         dW4, db4 = ops.linear_bwd_wb(dout, H2)
         dH1pre_p = ops.linear_bwd_data(dH2pre, W2, act=act, aux=H1pre_p)
         dW2, db2 = ops.linear_bwd_wb(dH2pre, H1p)
-        dH1pre = _fold3(dH1pre_p, B, h, P, old)                             # [M, old*P^3]
+        dH1pre = ops.fold3(dH1pre_p, B, h, P, old, inverse=True)             # [M, old*P^3]
         dW0 = torch.empty(E, N0, dtype=torch.float32, device=dev)
         ops.gemm(x, dH1pre, dW0, E, N0, M, transA=True, lda=E, ldb=N0, ldc=N0, splitk=ops.auto_splitk(E, N0, M, tn=True))
         db0e = ops.colsum(dH1pre, M, N0)

@@ -226,7 +226,8 @@ class RolloutEvaluator:
 @torch.no_grad()
 def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
                  step=None, metrics=None, model_res=None, evaluator=None) -> Tuple[Tensor, Tensor, Tensor]:
-    """evaluate.py:193-213.  Returns (pred [B,X,Y,T_ar,C], sum of the per-step losses, loss of the whole rollout).
+    """evaluate.py:193-213; with a DPOTNet3D and 6-D windows [B,X,Y,Z,T,C] the test loop of finetune3d.py:252-278.
+    Returns (pred [B,X,Y,T_ar,C], sum of the per-step losses, loss of the whole rollout).
     `step(xx) -> im` defaults to the model's forward (a GraphedRollout passes its graph replay).
     metrics: a train.StepMetrics - the test loop's test_l2_step / test_l2_full (train_temporal.py:252-281) are accumulated
     on the device (one launch per rollout, no synchronisation; `metrics.read()` at the end of the loop), and the loss of the
@@ -241,7 +242,15 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
     the same stream, without a synchronisation; the returned values are untouched by it.  None: nothing is enqueued."""
     # weight-only products (packed AFNO weights, folded embed matrices, ...) once per rollout, not once per AR step
     scope = model.weights_scope() if (step is None and hasattr(model, "weights_scope")) else contextlib.nullcontext()
-    step = step or (lambda x: model(x)[0])
+    def forward(x):                      # DPOTNet returns (pred, cls_pred), DPOTNet3D the prediction alone
+        out = model(x)
+        return out if torch.is_tensor(out) else out[0]
+
+    step = step or forward
+    if xx.dim() == 6 and (model_res is not None or evaluator is not None):
+        # the test loop of finetune3d.py:252-278 has neither; the spectral resize and the Evaluator are 2-D kernels
+        raise ValueError(f"rollout_eval: model_res= and evaluator= exist for 2-D windows [B,X,Y,T,C] only, got a 6-D window "
+                         f"{tuple(xx.shape)}")
     T_ar = yy.shape[-2]
     loss_steps = None
     preds = []

@@ -9,7 +9,8 @@ modules below (Conv3d, ConvTranspose3d, GroupNorm, Linear) are parameter contain
 
 The hot path is the block stack: depth x [GroupNorm -> AFNO3D -> GroupNorm -> channel MLP] on the kernels of csrc/dft3.hip, the
 mixer kernels of the 2-D model and the project's GEMMs (functional.block3d).  Patch embedding and the output layer are
-k = s = P convolutions: index rearrangements in torch around the same GEMMs (functional.Mlp2Fn / TimeAggFn / Head3DFn).
+k = s = P convolutions: the index rearrangements of csrc/patch3d.hip (ops.patchify3 / unpatchify3 / fold3) around the same
+GEMMs (functional.PatchEmbed3DFn / TimeAggFn / Head3DFn).
 CUDA (ROCm) tensors only; there is no CPU path.
 """
 from __future__ import annotations
@@ -20,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .functional import AdaINFn, Head3DFn, Mlp2Fn, TimeAggFn, block3d
+from .functional import AdaINFn, Head3DFn, PatchEmbed3DFn, TimeAggFn, block3d
 from .model import ACTIVATIONS, _AFNOParams, _TimeAggParams
 
 TEMPORAL_MODES = 8          # Block builds AFNO3D without temporal_modes (models/dpot3d.py:191): always the default
@@ -48,6 +49,8 @@ class _PatchEmbed3DParams(nn.Module):
 
 
 class DPOTNet3D(nn.Module):
+    cls_output = False          # forward returns the prediction alone (train.rollout: no classification branch)
+
     def __init__(self, img_size=224, patch_size=16, mixing_type='afno', in_channels=1, out_channels=3, in_timesteps=1,
                  out_timesteps=1, n_blocks=4, embed_dim=768, out_layer_dim=32, depth=12, modes=32, mlp_ratio=1.,
                  n_cls=1, normalize=False, act='gelu', time_agg='exp_mlp'):
@@ -143,19 +146,14 @@ class DPOTNet3D(nn.Module):
             s_mu = self.scale_feats_mu(stat)
             s_sigma = self.scale_feats_sigma(stat)
 
-        # four coordinate channels x, y, z, t, then patches: rows ((b, t), hx, hy, hz), columns (c, i, j, k)
-        gs, gt = self._gs, self._gt
-        grid = torch.stack([gs.view(S, 1, 1, 1).expand(S, S, S, T), gs.view(1, S, 1, 1).expand(S, S, S, T),
-                            gs.view(1, 1, S, 1).expand(S, S, S, T), gt.view(1, 1, 1, T).expand(S, S, S, T)], dim=-1)
+        # patches with the four coordinate channels x, y, z, t: rows ((b, t), hx, hy, hz), columns (c, i, j, k) (ops.patchify3)
         Cc = Cin + 4
-        xg = torch.cat([x, grid.unsqueeze(0).expand(B, S, S, S, T, 4)], dim=-1)
         tok = h * h * h
-        A0 = xg.view(B, h, P, h, P, h, P, T, Cc).permute(0, 7, 1, 3, 5, 8, 2, 4, 6).reshape(B * T * tok, Cc * P ** 3)
         pe, ta = self.patch_embed.proj, self.time_agg_layer
         hid = pe[0].weight.shape[0]
         posT = self.pos_embed.view(E, tok).t()                                  # [tok, E]
-        z = Mlp2Fn.apply(A0, pe[0].weight.view(hid, Cc * P ** 3), pe[0].bias, pe[2].weight.view(E, hid), pe[2].bias,
-                         self._act, posT, tok)                                  # conv, act, 1x1 conv, + pos_embed
+        z = PatchEmbed3DFn.apply(x, self._gs, self._gt, pe[0].weight.view(hid, Cc * P ** 3), pe[0].bias,
+                                 pe[2].weight.view(E, hid), pe[2].bias, posT, P, self._act)  # conv, act, 1x1 conv, + pos_embed
         A1 = z.view(B, T, tok, E).permute(0, 2, 1, 3).reshape(B * tok, T * E)   # rows (b, token), columns (t, channel)
         lat = TimeAggFn.apply(A1, ta.w, ta.gamma if self.time_agg == "exp_mlp" else None, self._tt).view(B, tok, E)
         if self.normalize:

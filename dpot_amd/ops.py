@@ -1338,6 +1338,54 @@ def pixel_shuffle(z: Tensor, B: int, h: int, w: int, P: int, Cc: int, inverse: b
     return out
 
 
+def _patch3_dims(what: str, S: int, P: int) -> int:
+    if P < 1 or S < 1 or S % P != 0:
+        raise _lib.DpotHipError(f"{what}: the grid size {S} is not a multiple of the patch size {P}")
+    return S // P
+
+
+def patchify3(x: Tensor, gs: Tensor, gt: Tensor, P: int) -> Tensor:
+    """x[B,S,S,S,T,C] -> the patch matrix A[(b,t,hx,hy,hz), (c,i,j,k)] of DPOTNet3D's k = s = P patch convolution, with the four
+    coordinate channels C..C+3 = gs[x], gs[y], gs[z], gt[t] written from the tables gs[S], gt[T] (csrc/patch3d.hip)"""
+    if x.dim() != 6 or not (x.shape[1] == x.shape[2] == x.shape[3]):
+        raise _lib.DpotHipError(f"patchify3: expected x[B,S,S,S,T,C], got {tuple(x.shape)}")
+    B, S, _, _, T, Cc = x.shape
+    h = _patch3_dims("patchify3", S, P)
+    _req(x, "x"), _req(gs, "gs"), _req(gt, "gt")
+    if gs.numel() != S or gt.numel() != T:
+        raise _lib.DpotHipError(f"patchify3: coordinate tables of {gs.numel()} / {gt.numel()} entries for S = {S}, T = {T}")
+    A = torch.empty(B * T * h ** 3, (Cc + 4) * P ** 3, dtype=torch.float32, device=x.device)
+    check(_lib.load().dpot_patchify3(x.data_ptr(), gs.data_ptr(), gt.data_ptr(), A.data_ptr(), B, S, T, Cc, P, _stream()),
+          "patchify3")
+    return A
+
+
+def unpatchify3(dA: Tensor, B: int, S: int, T: int, Cc: int, P: int) -> Tensor:
+    """adjoint of patchify3 w.r.t. x: dA[B*T*h^3, (Cc+4)*P^3] -> dx[B,S,S,S,T,Cc] (the coordinate columns are dropped)"""
+    h = _patch3_dims("unpatchify3", S, P)
+    _req(dA, "dA")
+    if tuple(dA.shape) != (B * T * h ** 3, (Cc + 4) * P ** 3):
+        raise _lib.DpotHipError(f"unpatchify3: dA {tuple(dA.shape)} is not [{B * T * h ** 3}, {(Cc + 4) * P ** 3}]")
+    dx = torch.empty(B, S, S, S, T, Cc, dtype=torch.float32, device=dA.device)
+    check(_lib.load().dpot_unpatchify3(dA.data_ptr(), dx.data_ptr(), B, S, T, Cc, P, _stream()), "unpatchify3")
+    return dx
+
+
+def fold3(t: Tensor, B: int, h: int, P: int, old: int, inverse: bool = False) -> Tensor:
+    """inverse=False: t[B*h^3, old*P^3] (columns (o,i,j,k)) -> [B*(hP)^3, old] (rows (b,x,y,z)), the scatter of a k = s = P
+    transposed 3-D convolution;  inverse=True: the other way"""
+    if h < 1 or P < 1:
+        raise _lib.DpotHipError(f"fold3: bad grid h = {h}, P = {P}")
+    _req(t, "t")
+    rows, cols = (B * h ** 3, old * P ** 3), (B * (h * P) ** 3, old)
+    want, out = (cols, rows) if inverse else (rows, cols)
+    if tuple(t.shape) != want:
+        raise _lib.DpotHipError(f"fold3: got {tuple(t.shape)}, expected {want}")
+    dst = torch.empty(out, dtype=torch.float32, device=t.device)
+    check(_lib.load().dpot_fold3(t.data_ptr(), dst.data_ptr(), B, h, P, old, int(inverse), _stream()), "fold3")
+    return dst
+
+
 def copy2d_pad(src: Tensor, sR: int, sC: int, dR: int, dC: int, out: Optional[Tensor] = None) -> Tensor:
     dst = _out(out, (dR, dC), src.device)
     check(_lib.load().dpot_copy2d_pad(src.data_ptr(), sR, sC, dst.data_ptr(), dR, dC, _stream()), "copy2d_pad")
@@ -1761,11 +1809,24 @@ def rng_state(device) -> Tensor:
     return _rng_states[key]
 
 
+def noise_dims(xx: Tensor) -> Tuple[int, int, int]:
+    """(B, S, C') of the [B, S, C'] field the noise kernels see - one norm per (b, c') over S - chosen by the window's rank,
+    for the forward and the backward alike:
+      5-D [B,X,Y,T,C]    one norm per (b, c) over X*Y*T     (train_temporal.py:205):  S = X*Y*T, C' = C
+      6-D [B,X,Y,Z,T,C]  one norm per (b, t, c) over X*Y*Z  (finetune3d.py:210):      S = X*Y*Z, C' = T*C
+    (the kernels refuse C' > 1024)"""
+    if xx.dim() not in (5, 6):
+        raise _lib.DpotHipError(f"noise_inject: expected a window [B,X,Y,T,C] or [B,X,Y,Z,T,C], got {tuple(xx.shape)}")
+    B = xx.shape[0]
+    Cc = xx.shape[-1] * (xx.shape[-2] if xx.dim() == 6 else 1)
+    return B, xx.numel() // (B * Cc), Cc
+
+
 def noise_inject(xx: Tensor, eps: Optional[Tensor], noise_scale: float, return_norms: bool = False):
-    """xx + noise_scale * ||xx||_(X,Y,T) * eps;  eps=None: eps ~ N(0,1) is drawn inside the kernel.
-    return_norms: also return the scratch tensor whose first B*C floats are the per-(b,c) norms (for the backward)"""
-    B, Cc = xx.shape[0], xx.shape[-1]
-    S = xx.numel() // (B * Cc)
+    """xx + noise_scale * ||xx|| * eps with the norm of ``noise_dims`` (over X,Y,T per (b,c) for a 5-D window; over X,Y,Z per
+    (b,t,c) for a 6-D one);  eps=None: eps ~ N(0,1) is drawn inside the kernel.
+    return_norms: also return the scratch tensor whose first B*C' floats are the norms (for the backward)"""
+    B, S, Cc = noise_dims(xx)
     out = torch.empty_like(xx)
     lib = _lib.load()
     norms = torch.empty(B * Cc * (1 + lib.dpot_noise_chunks(S, Cc)), dtype=torch.float32, device=xx.device)
@@ -1782,8 +1843,7 @@ def noise_inject_bwd(xx: Tensor, eps: Optional[Tensor], rng_snapshot: Optional[T
                      noise_scale: float) -> Tensor:
     """d/dxx of noise_inject: g + noise_scale * xx / ||xx|| * sum(g * eps); eps given, or re-drawn from the
     generator state the forward used (rng_snapshot = clone of rng_state() taken right after the forward call)"""
-    B, Cc = xx.shape[0], xx.shape[-1]
-    S = xx.numel() // (B * Cc)
+    B, S, Cc = noise_dims(xx)
     lib = _lib.load()
     dx = torch.empty_like(xx)
     part = torch.empty(B * Cc * lib.dpot_noise_chunks(S, Cc), dtype=torch.float32, device=xx.device)

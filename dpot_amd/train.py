@@ -476,11 +476,16 @@ def check_cls_args(opt, cls: Optional[Tensor], cls_weight: float) -> None:
                              "and would leave it frozen; build it with update_tail=True")
 
 
+_NO_CLS = ("{} returns one tensor and no cls_pred (the 3-D fine-tuning model: finetune3d.py has no classification branch), so "
+           "cls_weight = {} has nothing to weigh; pass cls_weight=0")
+
+
 def rollout(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
             noise_scale: float = 0.0, noise: Optional[List[Tensor]] = None, cls: Optional[Tensor] = None,
             cls_weight: float = 0.0, metrics: Optional[StepMetrics] = None) -> Tuple[Tensor, Tensor]:
-    """auto-regressive rollout with summed per-step loss (train_temporal.py:201-219).  Returns (loss, pred); ``loss`` is
-    the relative-L2 rollout loss whatever ``cls_weight`` is - ``rollout_total`` also returns the loss to differentiate."""
+    """auto-regressive rollout with summed per-step loss (train_temporal.py:201-219; with a DPOTNet3D and 6-D windows
+    [B,X,Y,Z,T,C] the loop of finetune3d.py:206-222 with its own noise rule, ops.noise_dims).  Returns (loss, pred); ``loss``
+    is the relative-L2 rollout loss whatever ``cls_weight`` is - ``rollout_total`` also returns the loss to differentiate."""
     return rollout_total(model, xx, yy, msk, T_bundle, noise_scale, noise, cls, cls_weight, metrics)[:2]
 
 
@@ -491,8 +496,12 @@ def rollout_total(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor
     sample ([B] or [B, 1], as data.DeviceBatcher delivers idx_cls).  Returns (loss, pred, total) with
     total = loss + cls_weight * sum over the AR steps of CrossEntropyLoss(reduction='sum')(cls_pred, cls) when
     cls_weight != 0, else total IS loss: the cross-entropy then runs forward-only for ``metrics`` and cls_head receives no
-    gradient.  metrics: a StepMetrics that collects the rollout's scalars (call its ``accumulate`` afterwards)."""
+    gradient.  metrics: a StepMetrics that collects the rollout's scalars (call its ``accumulate`` afterwards).
+    A model whose forward returns ONE tensor (DPOTNet3D) has no classification branch: ``cls`` is ignored, and
+    cls_weight != 0 raises a ValueError."""
     check_cls_args(None, cls, cls_weight)
+    if cls_weight != 0.0 and not getattr(model, "cls_output", True):
+        raise ValueError(_NO_CLS.format(type(model).__name__, cls_weight))
     scope = model.weights_scope() if hasattr(model, "weights_scope") else contextlib.nullcontext()
     with scope:
         return _rollout(model, xx, yy, msk, T_bundle, noise_scale, noise, cls, cls_weight, metrics)
@@ -522,10 +531,16 @@ def _rollout(model, xx, yy, msk, T_bundle, noise_scale, noise, cls=None, cls_wei
             else:
                 xx = _NoiseFn.apply(xx, noise[k] if noise is not None else None, noise_scale)
         try:
-            im, cls_pred = model(xx)
+            out = model(xx)
         finally:
             if tell:
                 model._ar_pos = None                # (never left behind: a later plain forward must not see a stale position)
+        if torch.is_tensor(out):                    # a model without the classification output (DPOTNet3D): labels are ignored
+            if cls_weight != 0.0:
+                raise ValueError(_NO_CLS.format(type(model).__name__, cls_weight))
+            im, cls_pred, want_cls = out, None, False
+        else:
+            im, cls_pred = out
         if metrics is not None:
             B, Cc = im.shape[0], im.shape[-1]
             l = rel_l2_loss(im, y, msk, metrics.stats_slot(k, B, im.numel() // (B * Cc), Cc))

@@ -431,6 +431,17 @@ int dpot_embed_wgrad(const float* x, const float* dhpre, float* workspace, float
 /* z[(b,px,py,i,j), Cc] <-> out[b, px*P+i, py*P+j, Cc]   (ConvTranspose2d k=s=P pixel order) */
 int dpot_pixel_shuffle(const float* z, float* out, int B, int h, int w, int P, int Cc, int inverse,
                        dpot_stream_t stream);
+/* ---- the two ends of DPOTNet3D (csrc/patch3d.hip): exact fp32 rearrangements, one launch each, 64-bit indexing.  Any P >= 1
+ * with P * (P*T*C + 1) floats (fold3: C = old, T = 1) within 64 KiB of LDS; 16-byte accesses when P % 4 == 0 and the bases allow.
+ * patchify3: x[B,S,S,S,T,C] -> A[(b,t,hx,hy,hz), (c,i,j,k)], h = S/P, c in [0,C+4): channels C..C+3 are the coordinates
+ *   gs[hx*P+i], gs[hy*P+j], gs[hz*P+k], gt[t] of get_grid_4d (models/dpot3d.py:338-350), read from the tables gs[S], gt[T].
+ * unpatchify3: the adjoint w.r.t. x, dA -> dx[B,S,S,S,T,C] (coordinate columns ignored; every dx element has one source).
+ * fold3: src[B*h^3, old*P^3] (columns (o,i,j,k)) -> dst[B*(hP)^3, old] (rows (b,x,y,z)), the scatter of a k = s = P transposed
+ *   3-D convolution; inverse = 1: the other way. */
+int dpot_patchify3(const float* x, const float* gs, const float* gt, float* A, int B, int S, int T, int C, int P,
+                   dpot_stream_t stream);
+int dpot_unpatchify3(const float* dA, float* dx, int B, int S, int T, int C, int P, dpot_stream_t stream);
+int dpot_fold3(const float* src, float* dst, int B, int h, int P, int old, int inverse, dpot_stream_t stream);
 /* dst[dR,dC] = src[0:dR,0:dC] zero-filled outside src[sR,sC]  (pad or crop a dense 2-D matrix) */
 int dpot_copy2d_pad(const float* src, int sR, int sC, float* dst, int dR, int dC, dpot_stream_t stream);
 /* dst[C,R] = src[R,C]^T   (batched: nbatch consecutive matrices) */
