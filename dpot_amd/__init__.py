@@ -7,6 +7,7 @@
     from dpot_amd import rollout_eval, GraphedRollout, refill_mask, spectral_resize   # evaluation at any data resolution
     from dpot_amd import RolloutEvaluator              # the PDEBench metric set of the reference's Evaluator, on the device
     from dpot_amd import DPOTNet3D, load_3d_components_from_2d   # 3-D fine-tuning from a pretrained 2-D checkpoint
+    from dpot_amd import DeviceBatcher3D, resize_pad_window3, target_mask3   # the 3-D input pipeline on the device
 
 The compute path is libdpot_hip.so (hand-written HIP kernels behind the C ABI in include/dpot_hip.h).
 """
@@ -17,8 +18,9 @@ from .functional import ClsCEFn, cls_ce_loss  # noqa: F401
 from .train import StepMetrics  # noqa: F401
 from .infer import GraphedRollout, RolloutEvaluator, load_3d_components_from_2d, refill_mask, rollout_eval  # noqa: F401
 from .ops import ResizePlan, spectral_resize, spectral_resize_matrices  # noqa: F401
+from .data import DeviceBatcher3D, resize_pad_window3, target_mask3  # noqa: F401
 
 __version__ = "0.2.9"
 __all__ = ["DPOTNet", "StepMetrics", "ClsCEFn", "cls_ce_loss", "GraphedRollout", "rollout_eval", "refill_mask",
            "spectral_resize", "spectral_resize_matrices", "ResizePlan", "RolloutEvaluator", "DPOTNet3D",
-           "load_3d_components_from_2d"]
+           "load_3d_components_from_2d", "DeviceBatcher3D", "resize_pad_window3", "target_mask3"]

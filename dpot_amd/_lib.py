@@ -94,6 +94,12 @@ class SampleDesc(C.Structure):
                 ("t0", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Sample3Desc(C.Structure):
+    """mirror of struct dpot_sample3_desc"""
+    _fields_ = [("data", c_fp), ("H", C.c_int32), ("W", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("C", C.c_int32),
+                ("t0", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/dpot_hip.h declares
 SIGNATURES = {
     "dpot_version": (c_i, []),
@@ -183,6 +189,7 @@ SIGNATURES = {
     "dpot_window_slide": (c_i, [c_fp] * 3 + [c_i64] + [c_i] * 3 + [c_fp]),
     "dpot_window_slide_bwd": (c_i, [c_fp] * 3 + [c_i64] + [c_i] * 3 + [c_fp]),
     "dpot_resize_pad_window": (c_i, [c_fp, c_i, c_fp, c_fp] + [c_i] * 6 + [c_fp]),
+    "dpot_resize_pad_window3": (c_i, [c_fp, c_i, c_fp, c_fp] + [c_i] * 7 + [c_fp]),
     "dpot_spectral_resize_pad": (c_i, [c_i, c_i]),
     "dpot_spectral_resize": (c_i, [c_fp] * 7 + [c_i] * 6 + [c_fp]),
     "dpot_eval_metrics_pad": (c_i, [c_i, c_i]),

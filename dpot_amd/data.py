@@ -17,6 +17,11 @@ CPU tensors.  Dataset mixing and index sharding are host logic (`MixedIndex`, dp
 Also covered (griddataset.py:159-174): test-mode windows (`train=False`: x = the first t_in frames, y = the following
 t_test frames, the resolution / channel mask of `get_target_mask`), the per-dataset strided `downsample` of the resized
 fields, and `idx_cls` (the dataset index of every sample, int64 [B, 1]).
+
+The 3-D fine-tuning loop (reference: TemporalDataset3D, griddataset.py:454-564, behind the DataLoader of
+finetune3d.py:113-117) is fed the same way from raw [H,W,L,T,C] trajectories: `resize_pad_window3` (csrc/data3d.hip:
+trilinear resize, channel pad, window, sub-sampling in one launch), `target_mask3`, `DeviceBatcher3D`.  The two batchers
+share their slot / event bookkeeping (`_SlotBatcher`); the 3-D one stages only the frames of the window.
 """
 from __future__ import annotations
 
@@ -27,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import SampleDesc, check
+from ._lib import Sample3Desc, SampleDesc, check
 
 Tensor = torch.Tensor
 
@@ -53,6 +58,15 @@ def target_mask(res: int, size_orig: Sequence[int], n_channels: int) -> Tensor:
     return msk
 
 
+def target_mask3(res: int, size_orig: Sequence[int], n_channels: int) -> Tensor:
+    """griddataset.py:503-518: the 3-D evaluation mask [res, res, res, 1, n_channels]
+    (size_orig = [H, W, L, T, C_pred]; a target coarser than the data: k == 0 -> 1)"""
+    msk = torch.zeros(res, res, res, 1, n_channels)
+    kx, ky, kz = (max(res // size_orig[i], 1) for i in range(3))
+    msk[::kx, ::ky, ::kz, :, :size_orig[-1]] = 1
+    return msk
+
+
 class MixedIndex:
     """index arithmetic of MixedTemporalDataset (griddataset.py:50-56,133-141): datasets are concatenated, dataset d
     is repeated data_weights[d] times; global index -> (dataset, sample)"""
@@ -73,24 +87,73 @@ class MixedIndex:
 
 DESC_BYTES = C.sizeof(SampleDesc)          # 32
 DESC_FLOATS = DESC_BYTES // 4
+assert C.sizeof(Sample3Desc) == DESC_BYTES
+
+
+def _check_window(i: int, shape: Sequence[int], t0: int, t_in: int, t_ar: int, n_channels: int) -> None:
+    """what the kernels assume of sample i, shape = (*spatial, T, C): its channels fit and the window lies inside it"""
+    T, Cc = shape[-2], shape[-1]
+    if Cc > n_channels or t0 < 0 or t0 + t_in + t_ar > T:
+        raise ValueError(f"sample {i}: shape {tuple(shape)}, window [{t0}, {t0 + t_in + t_ar}) - needs C <= "
+                         f"{n_channels} and the window inside its {T} frames")
 
 
 def _fill_table(table: np.ndarray, ptrs: Sequence[int], shapes: Sequence[Sequence[int]], starts: Sequence[int],
-                t_in: int, t_ar: int, n_channels: int) -> None:
-    """write the dpot_sample_desc records into `table` (uint8 view of host memory), validating what the kernel assumes"""
-    descs = (SampleDesc * len(ptrs)).from_buffer(table)
-    for i, (ptr, (H, W, T, Cc), t0) in enumerate(zip(ptrs, shapes, starts)):
-        if Cc > n_channels or t0 < 0 or t0 + t_in + t_ar > T:
-            raise ValueError(f"sample {i}: shape {(H, W, T, Cc)}, window [{t0}, {t0 + t_in + t_ar}) - needs C <= "
-                             f"{n_channels} and the window inside its {T} frames")
-        descs[i].data, descs[i].H, descs[i].W, descs[i].T, descs[i].C, descs[i].t0 = ptr, H, W, T, Cc, int(t0)
+                t_in: int, t_ar: int, n_channels: int, desc=SampleDesc) -> None:
+    """write the dpot_sample_desc (desc=Sample3Desc: dpot_sample3_desc) records into `table` (uint8 view of host memory),
+    validating what the kernel assumes"""
+    descs = (desc * len(ptrs)).from_buffer(table)
+    for i, (ptr, shape, t0) in enumerate(zip(ptrs, shapes, starts)):
+        _check_window(i, shape, t0, t_in, t_ar, n_channels)
+        descs[i].data, descs[i].t0 = ptr, int(t0)
+        for (name, _), n in zip(desc._fields_[1:], shape):          # H, W, (L,) T, C in the order of the sample's axes
+            setattr(descs[i], name, n)
 
 
-def _down_shape(res: int, downsample: Tuple[int, int]) -> Tuple[int, int]:
-    dh, dw = int(downsample[0]), int(downsample[1])
-    if dh < 1 or dw < 1:
+def _down_shape(res: int, downsample: Sequence[int]) -> Tuple[int, ...]:
+    down = tuple(int(d) for d in downsample)
+    if any(d < 1 for d in down):
         raise ValueError(f"downsample {downsample}: factors must be >= 1")
-    return (res + dh - 1) // dh, (res + dw - 1) // dw
+    return tuple((res + d - 1) // d for d in down)
+
+
+# spatial axes -> (descriptor, entry point of libdpot_hip, the samples' layout)
+_PIPELINES = {2: (SampleDesc, "dpot_resize_pad_window", "[H,W,T,C]"),
+              3: (Sample3Desc, "dpot_resize_pad_window3", "[H,W,L,T,C]")}
+
+
+def _resize_pad_window(nd: int, samples, starts, res, t_in, t_ar, n_channels, out_xx, out_yy, downsample):
+    """resize_pad_window (nd = 2) and resize_pad_window3 (nd = 3)"""
+    desc, entry, layout = _PIPELINES[nd]
+    what = entry[len("dpot_"):]
+    if len(downsample) != nd:
+        raise ValueError(f"{what}: downsample needs {nd} factors, got {tuple(downsample)}")
+    B = len(samples)
+    dev = samples[0].device
+    out = _down_shape(res, downsample)
+    xx = out_xx if out_xx is not None else torch.empty(B, *out, t_in, n_channels, dtype=torch.float32, device=dev)
+    yy = out_yy if out_yy is not None else (
+        torch.empty(B, *out, t_ar, n_channels, dtype=torch.float32, device=dev) if t_ar > 0 else None)
+    for name, buf, t in (("out_xx", out_xx, t_in), ("out_yy", out_yy, t_ar)):
+        # the kernel writes a dense [B, *ceil(res/d), t, C] block: any other caller-supplied buffer would be garbled or
+        # overrun
+        if buf is not None and not (tuple(buf.shape) == (B, *out, t, n_channels) and buf.is_contiguous()
+                                    and buf.dtype == torch.float32 and buf.device == dev):
+            raise _lib.DpotHipError(f"{what}: {name} must be a contiguous float32 tensor of shape "
+                                    f"{(B, *out, t, n_channels)} on {dev}, got {tuple(buf.shape)} {buf.dtype} "
+                                    f"{buf.device}")
+    for s in samples:
+        if not (s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() and s.dim() == nd + 2):
+            raise _lib.DpotHipError(f"{what}: samples must be contiguous float32 CUDA tensors {layout}")
+    host = np.zeros(B * DESC_BYTES, dtype=np.uint8)
+    _fill_table(host, [s.data_ptr() for s in samples], [tuple(s.shape) for s in samples], starts, t_in, t_ar, n_channels,
+                desc)
+    table = torch.from_numpy(host).to(dev)
+    check(getattr(_lib.load(), entry)(table.data_ptr(), B, xx.data_ptr(), yy.data_ptr() if yy is not None else None,
+                                      res, t_in, t_ar, n_channels, *(int(d) for d in downsample),
+                                      torch.cuda.current_stream().cuda_stream),
+          what)
+    return xx, yy
 
 
 def resize_pad_window(samples: Sequence[Tensor], starts: Sequence[int], res: int, t_in: int, t_ar: int,
@@ -99,43 +162,35 @@ def resize_pad_window(samples: Sequence[Tensor], starts: Sequence[int], res: int
     """samples: CUDA tensors [H,W,T,C] (fp32, contiguous), one per batch entry -> (xx [B,res,res,t_in,Cmax],
     yy [B,res,res,t_ar,Cmax]) through ONE launch of csrc/data.hip.  downsample = (dh, dw): the reference's
     x[::dh, ::dw] on the resized fields (griddataset.py:170-172) - the outputs then have ceil(res/d) points per axis"""
-    B = len(samples)
-    dev = samples[0].device
-    rh, rw = _down_shape(res, downsample)
-    xx = out_xx if out_xx is not None else torch.empty(B, rh, rw, t_in, n_channels, dtype=torch.float32, device=dev)
-    yy = out_yy if out_yy is not None else (
-        torch.empty(B, rh, rw, t_ar, n_channels, dtype=torch.float32, device=dev) if t_ar > 0 else None)
-    for name, buf, t in (("out_xx", out_xx, t_in), ("out_yy", out_yy, t_ar)):
-        # the kernel writes a dense [B, ceil(res/dh), ceil(res/dw), t, C] block: any other caller-supplied buffer would
-        # be garbled or overrun
-        if buf is not None and not (tuple(buf.shape) == (B, rh, rw, t, n_channels) and buf.is_contiguous()
-                                    and buf.dtype == torch.float32 and buf.device == dev):
-            raise _lib.DpotHipError(f"resize_pad_window: {name} must be a contiguous float32 tensor of shape "
-                                    f"{(B, rh, rw, t, n_channels)} on {dev}, got {tuple(buf.shape)} {buf.dtype} "
-                                    f"{buf.device}")
-    for s in samples:
-        if not (s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() and s.dim() == 4):
-            raise _lib.DpotHipError("resize_pad_window: samples must be contiguous float32 CUDA tensors [H,W,T,C]")
-    host = np.zeros(B * DESC_BYTES, dtype=np.uint8)
-    _fill_table(host, [s.data_ptr() for s in samples], [tuple(s.shape) for s in samples], starts, t_in, t_ar, n_channels)
-    table = torch.from_numpy(host).to(dev)
-    check(_lib.load().dpot_resize_pad_window(table.data_ptr(), B, xx.data_ptr(), yy.data_ptr() if yy is not None else None,
-                                             res, t_in, t_ar, n_channels, int(downsample[0]), int(downsample[1]),
-                                             torch.cuda.current_stream().cuda_stream),
-          "resize_pad_window")
-    return xx, yy
+    return _resize_pad_window(2, samples, starts, res, t_in, t_ar, n_channels, out_xx, out_yy, downsample)
 
 
-class DeviceBatcher:
-    """Double-buffered batch producer: raw samples in, device-resident (xx, yy, msk) out, overlapped with the step."""
+def resize_pad_window3(samples: Sequence[Tensor], starts: Sequence[int], res: int, t_in: int, t_ar: int,
+                       n_channels: int, out_xx: Optional[Tensor] = None, out_yy: Optional[Tensor] = None,
+                       downsample: Tuple[int, int, int] = (1, 1, 1)):
+    """samples: CUDA tensors [H,W,L,T,C] (fp32, contiguous), one per batch entry -> (xx [B,res,res,res,t_in,Cmax],
+    yy [B,res,res,res,t_ar,Cmax]; yy is None when t_ar == 0) through ONE launch of csrc/data3d.hip: trilinear resize,
+    channel pad with ones, window [t0, t0 + t_in + t_ar).  downsample = (d0, d1, d2): the reference's
+    x[::d0, ::d1, ::d2] on the resized fields (griddataset.py:557-558) - ceil(res/d) points per axis"""
+    return _resize_pad_window(3, samples, starts, res, t_in, t_ar, n_channels, out_xx, out_yy, downsample)
+
+
+class _SlotBatcher:
+    """What DeviceBatcher and DeviceBatcher3D share, i.e. everything but the layout of a sample: the pinned staging buffers
+    with the descriptor table at their head, the batch slots, and the slot / event / pending bookkeeping of submit, get
+    and release.  A subclass names its number of spatial axes and says which part of a raw sample is staged."""
+    _nd: int
 
     def __init__(self, batch: int, res: int, t_in: int, t_ar: int, n_channels: int, max_raw_floats_per_sample: int,
-                 device="cuda", n_buffers: int = 2, downsample: Tuple[int, int] = (1, 1)):
-        """t_ar: frames of y per sample (training: the rollout length; test mode: t_test of the dataset, with
-        starts = 0 - see `eval_window`).  downsample: one factor pair per batcher (a batch is one tensor)."""
+                 device, n_buffers: int, downsample: Sequence[int]):
+        nd = self._nd
+        self._desc, entry, self._layout = _PIPELINES[nd]
+        self._entry, self._what = entry, entry[len("dpot_"):]
+        if len(downsample) != nd:
+            raise ValueError(f"{type(self).__name__}: downsample needs {nd} factors, got {tuple(downsample)}")
         self.B, self.res, self.t_in, self.t_ar, self.C = batch, res, t_in, t_ar, n_channels
-        self.down = (int(downsample[0]), int(downsample[1]))
-        rh, rw = _down_shape(res, self.down)
+        self.down = tuple(int(d) for d in downsample)
+        out = _down_shape(res, self.down)
         self.dev = torch.device(device)
         self.n = n_buffers
         self.head = batch * DESC_FLOATS                # the descriptor table rides at the head of the staging buffer
@@ -143,11 +198,11 @@ class DeviceBatcher:
         self.stream = torch.cuda.Stream(device=self.dev)
         self.host = [torch.empty(cap, dtype=torch.float32).pin_memory() for _ in range(n_buffers)]
         self.raw = [torch.empty(cap, dtype=torch.float32, device=self.dev) for _ in range(n_buffers)]
-        self.xx = [torch.empty(batch, rh, rw, t_in, n_channels, device=self.dev) for _ in range(n_buffers)]
-        self.yy = [torch.empty(batch, rh, rw, t_ar, n_channels, device=self.dev) for _ in range(n_buffers)]
-        # training mask (griddataset.py:157: ones at the window's resolution, i.e. BEFORE the down-sampling - the reference
-        # does not sub-sample msk; test-mode masks: `target_mask` per dataset)
-        self.msk = torch.ones(batch, res, res, 1, n_channels, device=self.dev)
+        self.xx = [torch.empty(batch, *out, t_in, n_channels, device=self.dev) for _ in range(n_buffers)]
+        self.yy = [torch.empty(batch, *out, t_ar, n_channels, device=self.dev) for _ in range(n_buffers)]
+        # training mask (griddataset.py:157, :548: ones at the window's resolution, i.e. BEFORE the down-sampling - the
+        # reference does not sub-sample msk; test-mode masks: `target_mask` / `target_mask3` per dataset)
+        self.msk = torch.ones(batch, *(res,) * nd, 1, n_channels, device=self.dev)
         self.cls = [torch.zeros(batch, 1, dtype=torch.int64, device=self.dev) for _ in range(n_buffers)]
         self.cls_host = [torch.zeros(batch, 1, dtype=torch.int64).pin_memory() for _ in range(n_buffers)]
         self.ready = [torch.cuda.Event() for _ in range(n_buffers)]       # slot filled (recorded on the copy stream)
@@ -159,34 +214,39 @@ class DeviceBatcher:
         self._last: Optional[int] = None
         self.h2d_bytes = 0
 
+    def _stage(self, a: np.ndarray, t0: int) -> Tuple[np.ndarray, int]:
+        """(the part of raw sample `a` that goes to the device - a view, any strides -, the window start inside it)"""
+        raise NotImplementedError
+
     def submit(self, samples: Sequence, starts: Sequence[int], dataset_ids: Optional[Sequence[int]] = None) -> None:
-        """enqueue one batch: samples = numpy arrays / CPU tensors [H,W,T,C] (or [H,W,T]); returns immediately.
-        dataset_ids: the dataset index of every sample (griddataset.py:174 idx_cls; default zeros)"""
+        """enqueue one batch: samples = numpy arrays / CPU tensors in the batcher's layout (or without the channel axis);
+        returns immediately.  dataset_ids: the dataset index of every sample (griddataset.py:174 idx_cls; default zeros)"""
         assert len(samples) == self.B and len(starts) == self.B
         assert dataset_ids is None or len(dataset_ids) == self.B
+        me = type(self).__name__
         slot = self.k % self.n
         # validate BEFORE anything is overwritten (a bad batch must leave the slot and the counters untouched)
-        arrs, offs, shapes, off = [], [], [], self.head
+        parts, offs, t0s, off = [], [], [], self.head
         for i, (s, t0) in enumerate(zip(samples, starts)):
             a = np.asarray(s, dtype=np.float32) if not torch.is_tensor(s) else s.detach().float().numpy()
-            if a.ndim == 3:
-                a = a[..., None]                       # griddataset.py:145 "augment channel dim"
-            H, W, T, Cc = a.shape
-            if Cc > self.C or t0 < 0 or t0 + self.t_in + self.t_ar > T:
-                raise ValueError(f"sample {i}: shape {(H, W, T, Cc)}, window [{t0}, {t0 + self.t_in + self.t_ar}) - needs "
-                                 f"C <= {self.C} and the window inside its {T} frames")
-            if off + a.size > self.host[slot].numel():
-                raise ValueError("DeviceBatcher: raw samples exceed max_raw_floats_per_sample")
-            arrs.append(a)
+            if a.ndim == self._nd + 1:
+                a = a[..., None]                       # griddataset.py:145, :535 "augment channel dim"
+            if a.ndim != self._nd + 2:
+                raise ValueError(f"sample {i}: shape {a.shape} is not {self._layout}")
+            _check_window(i, a.shape, t0, self.t_in, self.t_ar, self.C)
+            part, t0 = self._stage(a, int(t0))
+            if off + part.size > self.host[slot].numel():
+                raise ValueError(f"{me}: raw samples exceed max_raw_floats_per_sample")
+            parts.append(part)
             offs.append(off)
-            shapes.append(a.shape)
-            off += a.size
+            t0s.append(t0)
+            off += part.size
         # the slot is reused: its pinned staging buffer, raw buffer and xx / yy must be free.  The previous H2D copy +
         # transform of this slot (copy stream) and the step that read it (recorded by release()) are waited for; a slot
         # that was handed out by get() but never release()d has an unknown reader - wait for the whole device then
         if slot in self.pending or slot in self._out:
             if slot in self.pending:
-                raise RuntimeError(f"DeviceBatcher: all {self.n} slots hold batches that were never fetched with get()")
+                raise RuntimeError(f"{me}: all {self.n} slots hold batches that were never fetched with get()")
             torch.cuda.synchronize(self.dev)           # unreleased consumer: conservative, correct
             self._out.discard(slot)
         if self.used[slot]:
@@ -198,21 +258,21 @@ class DeviceBatcher:
         self.used[slot] = True
         host = self.host[slot]
         hnp = host.numpy()
-        for a, o in zip(arrs, offs):
-            hnp[o:o + a.size] = a.reshape(-1)
+        for p, o in zip(parts, offs):
+            hnp[o:o + p.size].reshape(p.shape)[...] = p
         base = self.raw[slot].data_ptr()
-        _fill_table(hnp[:self.head].view(np.uint8), [base + 4 * o for o in offs], shapes, starts, self.t_in, self.t_ar,
-                    self.C)
+        _fill_table(hnp[:self.head].view(np.uint8), [base + 4 * o for o in offs], [p.shape for p in parts], t0s, self.t_in,
+                    self.t_ar, self.C, self._desc)
         self.cls_host[slot].zero_()
         if dataset_ids is not None:
             self.cls_host[slot][:, 0] = torch.as_tensor(list(dataset_ids), dtype=torch.int64)
         with torch.cuda.stream(self.stream):
             self.raw[slot][:off].copy_(host[:off], non_blocking=True)            # ONE H2D copy: table + raw samples
             self.cls[slot].copy_(self.cls_host[slot], non_blocking=True)
-            check(_lib.load().dpot_resize_pad_window(base, self.B, self.xx[slot].data_ptr(), self.yy[slot].data_ptr(),
-                                                     self.res, self.t_in, self.t_ar, self.C, self.down[0], self.down[1],
-                                                     self.stream.cuda_stream),
-                  "resize_pad_window")
+            check(getattr(_lib.load(), self._entry)(base, self.B, self.xx[slot].data_ptr(), self.yy[slot].data_ptr(),
+                                                    self.res, self.t_in, self.t_ar, self.C, *self.down,
+                                                    self.stream.cuda_stream),
+                  self._what)
             self.ready[slot].record(self.stream)
         self.h2d_bytes += (off - self.head) * 4
         self.pending.append(slot)
@@ -241,8 +301,44 @@ class DeviceBatcher:
         """the step reading batch `slot` (default: the latest get()) has been enqueued on the current stream"""
         slot = self._last if slot is None else slot
         if slot is None or slot not in self._out:
-            raise RuntimeError("DeviceBatcher.release: no batch outstanding for this slot")
+            raise RuntimeError(f"{type(self).__name__}.release: no batch outstanding for this slot")
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream())
         self.consumed[slot] = ev
         self._out.discard(slot)
+
+
+class DeviceBatcher(_SlotBatcher):
+    """Double-buffered batch producer: raw samples [H,W,T,C] in, device-resident (xx, yy, msk) out, overlapped with the
+    step."""
+    _nd = 2
+
+    def __init__(self, batch: int, res: int, t_in: int, t_ar: int, n_channels: int, max_raw_floats_per_sample: int,
+                 device="cuda", n_buffers: int = 2, downsample: Tuple[int, int] = (1, 1)):
+        """t_ar: frames of y per sample (training: the rollout length; test mode: t_test of the dataset, with
+        starts = 0 - see `eval_window`).  downsample: one factor pair per batcher (a batch is one tensor)."""
+        super().__init__(batch, res, t_in, t_ar, n_channels, max_raw_floats_per_sample, device, n_buffers, downsample)
+
+    def _stage(self, a, t0):
+        return a, t0                                   # the whole trajectory
+
+
+class DeviceBatcher3D(_SlotBatcher):
+    """DeviceBatcher for raw samples [H,W,L,T,C] (csrc/data3d.hip): (xx [B,r0,r1,r2,t_in,C], yy [B,r0,r1,r2,t_ar,C],
+    msk = ones [B,res,res,res,1,C]).  One difference: only the FRAMES OF THE WINDOW are staged and copied - a
+    [128,128,128,21,5] trajectory sends the 461 MB of its 11 frames, not 880 MB - so the device sees samples with
+    T = t_in + t_ar and t0 = 0, and `max_raw_floats_per_sample` / `h2d_bytes` count the staged floats (`staged_floats`)."""
+    _nd = 3
+
+    def __init__(self, batch: int, res: int, t_in: int, t_ar: int, n_channels: int, max_raw_floats_per_sample: int,
+                 device="cuda", n_buffers: int = 2, downsample: Tuple[int, int, int] = (1, 1, 1)):
+        super().__init__(batch, res, t_in, t_ar, n_channels, max_raw_floats_per_sample, device, n_buffers, downsample)
+
+    def _stage(self, a, t0):
+        return a[..., t0:t0 + self.t_in + self.t_ar, :], 0
+
+
+def staged_floats(shape: Sequence[int], t_in: int, t_ar: int) -> int:
+    """floats DeviceBatcher3D stages for one raw sample of `shape` ([H,W,L,T,C] or [H,W,L,T]): its window's frames"""
+    H, W, L = shape[:3]
+    return H * W * L * (t_in + t_ar) * (shape[4] if len(shape) == 5 else 1)

@@ -800,6 +800,28 @@ typedef struct dpot_sample_desc {
 int dpot_resize_pad_window(const dpot_sample_desc* samples_dev, int nsamples, float* xx, float* yy, int res, int t_in,
                            int t_ar, int n_channels, int down_h, int down_w, dpot_stream_t stream);
 
+/* The 3-D twin (csrc/data3d.hip; utils/griddataset.py:488-501 pad_data and :521-561 __getitem__ of TemporalDataset3D).
+ * One raw 3-D trajectory in device memory: data [H, W, L, T, C] fp32, window start t0 (32 bytes) */
+typedef struct dpot_sample3_desc {
+  const float* data;
+  int32_t H, W, L, T, C;
+  int32_t t0;
+} dpot_sample3_desc;
+/* For every sample b: trilinear resize of the frames t0 .. t0+t_in+t_ar-1 to res^3 (F.interpolate(mode='trilinear'),
+ * align_corners=False semantics, the float source-index rule of the 2-D kernel on three axes), channels C..n_channels-1
+ * filled with ones, then the strided sub-sampling x[::down0, ::down1, ::down2] of the resized field
+ * (griddataset.py:557-558), written as xx[b] = [r0, r1, r2, t_in, n_channels] and yy[b] = [r0, r1, r2, t_ar, n_channels]
+ * with r = ceil(res / down) per axis (yy may be NULL when t_ar == 0).  Samples of one batch may differ in H, W, L, T, C.
+ * `samples_dev` is a DEVICE array of nsamples descriptors; the caller validates it (C <= n_channels,
+ * 0 <= t0, t0 + t_in + t_ar <= T) - a malformed entry is skipped by the kernel.  Every offset is 64-bit (one raw
+ * 128^3 x 21 x 5 sample is 2.2e8 floats, a batch passes 2^31).  1 <= down <= res, nsamples <= 65535,
+ * (t_in + t_ar) * n_channels <= 16384; no alignment is asked of any pointer and no n_channels is special: lanes run
+ * along the flattened (t, c) run of a voxel and on into the next voxel, one float each.  Reads nothing outside the
+ * samples, no atomics, no allocation, legal under stream capture.  Test-mode windows (griddataset.py:549-553) are the
+ * same call with t0 = 0 and t_ar = min(t_test, T - t_in). */
+int dpot_resize_pad_window3(const dpot_sample3_desc* samples_dev, int nsamples, float* xx, float* yy, int res, int t_in,
+                            int t_ar, int n_channels, int down0, int down1, int down2, dpot_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fourier ("spectral") resize of channels-last fields (csrc/resize.hip): the operator of the reference's
  * utils/utilities.py:277-305 as dense fp32 products, one launch.
