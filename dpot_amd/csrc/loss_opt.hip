@@ -749,6 +749,10 @@ extern "C" int dpot_lamb_stage(float* hyper, int64_t* step, double lr, double be
   return check_launch("lamb_stage_kernel");
 }
 
+// chan_sumsq_part_kernel gives every channel a lane of its 256-thread block (chan_layout(C, 256): TS = 256 / CP row lanes);
+// above 256 channels TS would be 0 - a row loop that never advances - so the three entry points refuse such a field
+constexpr int NOISE_MAX_C = 256;
+
 extern "C" int dpot_noise_chunks(int S, int C) {
   long long n = ((long long)S * C + 8191) / 8192;
   if (n > 64) n = 64;
@@ -778,7 +782,8 @@ static int noise_launch(const float* xx, const float* eps, float* out, float* no
 extern "C" int dpot_noise_inject_bwd(const float* xx, const float* eps, const uint64_t* rng_state, const float* g,
                                      const float* norms, float* dx, float* part, float noise_scale, int B, int S, int C,
                                      dpot_stream_t stream) {
-  DPOT_REQUIRE(xx && g && norms && dx && part && B > 0 && S > 0 && C > 0 && C <= 1024, "noise_inject_bwd: bad argument");
+  DPOT_REQUIRE(xx && g && norms && dx && part && B > 0 && S > 0 && C > 0, "noise_inject_bwd: bad argument");
+  DPOT_REQUIRE(C <= NOISE_MAX_C, "noise_inject_bwd: %d channels exceed the limit of %d", C, NOISE_MAX_C);
   DPOT_REQUIRE((eps != nullptr) != (rng_state != nullptr), "noise_inject_bwd: exactly one of eps / rng_state");
   DPOT_REQUIRE(B <= 65535, "noise_inject_bwd: batch too large");
   DPOT_REQUIRE(rng_state == nullptr || ((long long)S * C) % 4 == 0, "noise_inject_bwd: rng path needs S*C %% 4 == 0");
@@ -812,14 +817,16 @@ extern "C" int dpot_window_slide_bwd(const float* dout, float* dxx, float* dim, 
 
 extern "C" int dpot_noise_inject(const float* xx, const float* eps, float* out, float* norms, float noise_scale,
                                  int B, int S, int C, dpot_stream_t stream) {
-  DPOT_REQUIRE(xx && eps && out && norms && B > 0 && S > 0 && C > 0 && C <= 1024, "noise_inject: bad argument");
+  DPOT_REQUIRE(xx && eps && out && norms && B > 0 && S > 0 && C > 0, "noise_inject: bad argument");
+  DPOT_REQUIRE(C <= NOISE_MAX_C, "noise_inject: %d channels exceed the limit of %d", C, NOISE_MAX_C);
   DPOT_REQUIRE(B <= 65535, "noise_inject: batch too large");
   return noise_launch(xx, eps, out, norms, nullptr, noise_scale, B, S, C, stream);
 }
 
 extern "C" int dpot_noise_inject_rng(const float* xx, float* out, float* norms, uint64_t* rng_state, float noise_scale,
                                      int B, int S, int C, dpot_stream_t stream) {
-  DPOT_REQUIRE(xx && out && norms && rng_state && B > 0 && S > 0 && C > 0 && C <= 1024, "noise_inject_rng: bad argument");
+  DPOT_REQUIRE(xx && out && norms && rng_state && B > 0 && S > 0 && C > 0, "noise_inject_rng: bad argument");
+  DPOT_REQUIRE(C <= NOISE_MAX_C, "noise_inject_rng: %d channels exceed the limit of %d", C, NOISE_MAX_C);
   DPOT_REQUIRE(B <= 65535, "noise_inject_rng: batch too large");
   DPOT_REQUIRE(((long long)S * C) % 4 == 0 && aligned16(xx) && aligned16(out),
                "noise_inject_rng: needs S*C %% 4 == 0 and 16-byte aligned fields");

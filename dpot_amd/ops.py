@@ -1814,7 +1814,7 @@ def noise_dims(xx: Tensor) -> Tuple[int, int, int]:
     for the forward and the backward alike:
       5-D [B,X,Y,T,C]    one norm per (b, c) over X*Y*T     (train_temporal.py:205):  S = X*Y*T, C' = C
       6-D [B,X,Y,Z,T,C]  one norm per (b, t, c) over X*Y*Z  (finetune3d.py:210):      S = X*Y*Z, C' = T*C
-    (the kernels refuse C' > 1024)"""
+    (the kernels refuse C' > 256: the channel sum gives every channel a lane of a 256-thread block)"""
     if xx.dim() not in (5, 6):
         raise _lib.DpotHipError(f"noise_inject: expected a window [B,X,Y,T,C] or [B,X,Y,Z,T,C], got {tuple(xx.shape)}")
     B = xx.shape[0]

@@ -600,7 +600,8 @@ int dpot_metrics_accum(dpot_metrics* acc, const float* l2_step, const float* l2_
                        int64_t opt_steps, dpot_stream_t stream);
 
 /* xx_out = xx + noise_scale * ||xx||_2(over X,Y,T per (b,c)) * eps   (train_temporal.py:205)
- * xx, eps: [B, S, C]; norms: B*C*(1 + dpot_noise_chunks(S, C)) floats - [B, C] norms followed by the chunk partials */
+ * xx, eps: [B, S, C], C <= 256 (the forward, its generator variant and the backward return DPOT_EINVAL above that);
+ * norms: B*C*(1 + dpot_noise_chunks(S, C)) floats - [B, C] norms followed by the chunk partials */
 int dpot_noise_chunks(int S, int C);
 int dpot_noise_inject(const float* xx, const float* eps, float* out, float* norms, float noise_scale, int B,
                       int S, int C, dpot_stream_t stream);
