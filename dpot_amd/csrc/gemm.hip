@@ -437,6 +437,10 @@ extern "C" int dpot_gemm_f32(const dpot_gemm_desc* d, dpot_stream_t stream) {
   DPOT_REQUIRE(d->ldb >= (d->transB ? d->K : d->N), "gemm: ldb=%d too small", d->ldb);
   DPOT_REQUIRE(d->ldc >= d->N, "gemm: ldc=%d too small", d->ldc);
   DPOT_REQUIRE(d->epi_mode != DPOT_EPI_DACT || d->aux != nullptr, "gemm: DACT epilogue needs aux");
+  // a leading dimension left at 0 (the field's default) would fold every row of the operand onto row 0
+  DPOT_REQUIRE(d->aux == nullptr || d->ldaux >= d->N, "gemm: ldaux=%d too small (aux is set, N=%d)", d->ldaux, d->N);
+  DPOT_REQUIRE(d->preact == nullptr || d->ldpre >= d->N, "gemm: ldpre=%d too small (preact is set, N=%d)", d->ldpre, d->N);
+  DPOT_REQUIRE(d->res == nullptr || d->ldres >= d->N, "gemm: ldres=%d too small (res is set, N=%d)", d->ldres, d->N);
   DPOT_REQUIRE(d->epi_mode != DPOT_EPI_AFNO_WGRAD ||
                    (d->splitk > 1 && d->M == d->N && d->M % 2 == 0 && !d->bias && !d->res && !d->preact &&
                     !d->accumulate && (d->colsum_of == 0 || d->colsum_of == 2)),

@@ -143,10 +143,12 @@ enum { DPOT_GEMM_F32 = 0, DPOT_GEMM_BF16X6 = 1, DPOT_GEMM_AUTO = 2, DPOT_GEMM_BF
 int dpot_gemm_f32(const dpot_gemm_desc* d, dpot_stream_t stream);
 /* bytes of workspace dpot_gemm_f32 needs for this descriptor (0 when splitk <= 1) */
 int64_t dpot_gemm_workspace_bytes(const dpot_gemm_desc* d);
-/* weight gradients (transA = 1, transB = 0, native fp32, M % 128 == N % 128 == 0, K % 16 == 0, split-K) run on the
- * dedicated kernel of csrc/gemm_tn.hip; this is the split count it wants for a shape (0: shape not eligible - use
- * dpot_gemm_auto_splitk2).  Any splitk > 1 is accepted, the result does not depend on which kernel ran beyond fp32
- * summation order. */
+/* weight gradients run on the dedicated kernel of csrc/gemm_tn.hip when the descriptor is eligible: transA = 1,
+ * transB = 0, native fp32, batch = 1, splitk > 1 with a workspace, M % 128 == N % 128 == 0, K % 32 == 0 (whole slabs of
+ * 32 tokens), A, B and the workspace 16-byte aligned, lda % 4 == ldb % 4 == 0 (strideA, strideB % 4 == 0), splitk <= K / 32
+ * and no split empty: ceil(K / 32 / splitk) * (splitk - 1) < K / 32.  Every other descriptor runs on the generic kernel.
+ * This is the split count the dedicated kernel wants for a shape (0: shape not eligible - use dpot_gemm_auto_splitk2).
+ * Any splitk > 1 is accepted, the result does not depend on which kernel ran beyond fp32 summation order. */
 int dpot_gemm_tn_splitk(int M, int N, int K, int batch);
 /* Both weight gradients of an AFNO block's complex MLP (models/dpot.py:72-94) in one launch + one fixed-order reduce
  * (csrc/gemm_tn.hip): per channel block k  dWbig1[k] = S[:,k]^T dO1pre[:,k], dWbig2[k] = O1[:,k]^T dO2[:,k], un-packed
