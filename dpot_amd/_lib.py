@@ -111,6 +111,8 @@ SIGNATURES = {
     "dpot_gemm_auto_splitk2": (c_i, [c_i, c_i, c_i, c_i, c_i]),
     "dpot_rfft2": (c_i, [c_fp, c_fp] + [c_i] * 8 + [c_fp]),
     "dpot_rfft2_norm_supported": (c_i, [c_i, c_i, c_i]),
+    "dpot_dft2_kernel_kind": (c_i, [c_i] * 9),
+    "dpot_dft2_kernel_kinds": (c_i, [c_i, C.POINTER(c_i), c_i]),
     "dpot_rfft2_norm": (c_i, [c_fp] * 5 + [c_i, c_fp] + [c_i] * 8 + [c_fp]),
     "dpot_irfft2_norm": (c_i, [c_fp] * 6 + [c_i, c_fp] + [c_i] * 8 + [c_fp]),
     "dpot_irfft2": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 8 + [c_fp]),

@@ -172,6 +172,25 @@ static int pick_cc(int E, long long floats_per_channel, int tw_floats) {
   return 0;
 }
 
+// channel chunk of the generic kernels: what one channel keeps in LDS, 0 when not even one channel fits
+static int dft2_generic_cc(int h, int w, int E, int mx, int my, int inverse) {
+  const int tw = ((2 * w + 2 * h + 3) & ~3);
+  const long long per_channel = inverse ? (long long)mx * my * 2 + (long long)h * my * 2 : (long long)h * w + (long long)h * my * 2;
+  return pick_cc(E, per_channel, tw);
+}
+
+// THE kernel selection of dpot_rfft2 / dpot_irfft2 (norm = 1: their GroupNorm-on-load forms): H * 1000 + CC for a register
+// FFT (the table of dft_fast.h), 0 for the generic direct sums, -1 where the call is refused.  The launchers below and
+// dpot_dft2_kernel_kind both call it.  Of the kept modes only my enters the choice of a kernel; mx decides nothing but
+// whether the generic inverse still fits LDS.
+static int dft2_select(int B, int h, int w, int E, int nb, int mx, int my, int inverse, int norm) {
+  if (norm && !dpot_rfft2_norm_supported(h, w, E)) return -1;
+  const int kind = dft2_fast_kind(B, h, w, E, nb, my, inverse, norm);
+  if (kind) return kind;
+  if (norm) return -1;
+  return dft2_generic_cc(h, w, E, mx, my, inverse) ? 0 : -1;
+}
+
 // AFNO weight packing -------------------------------------------------------------------------------
 __device__ __forceinline__ void afno_pack_one(const float* __restrict__ w, const float* __restrict__ b,
                                               float* __restrict__ wbig, float* __restrict__ bbig, int nb, int bs,
@@ -248,27 +267,42 @@ static int check_dft_args(const char* who, int B, int h, int w, int E, int nb, i
   return DPOT_OK;
 }
 
+static bool dft_args_ok(int B, int h, int w, int E, int nb, int mx, int my) {
+  return B > 0 && h > 0 && w > 0 && E > 0 && nb > 0 && E % nb == 0 && mx >= 1 && mx <= h && my >= 1 && my <= w / 2 + 1 &&
+         B <= 65535;
+}
+
+extern "C" int dpot_dft2_kernel_kind(int B, int h, int w, int E, int nb, int mx, int my, int inverse, int norm) {
+  if (!dft_args_ok(B, h, w, E, nb, mx, my)) return -1;
+  return dft2_select(B, h, w, E, nb, mx, my, inverse, norm);
+}
+
+extern "C" int dpot_dft2_kernel_kinds(int inverse, int* out, int cap) {
+  if (!out) cap = 0;
+  const int n = dft2_fast_kinds(inverse, out, cap);
+  if (n < cap) out[n] = 0;            // the generic pair exists in both directions
+  return n + 1;
+}
+
 extern "C" int dpot_rfft2(const float* x, float* spec, int B, int h, int w, int E, int nb, int mx, int my,
                           int col_weights, dpot_stream_t stream) {
   int rc = check_dft_args("rfft2", B, h, w, E, nb, mx, my);
   if (rc) return rc;
   DPOT_REQUIRE(x && spec, "rfft2: null pointer");
-  {
-    int frc = 0;
-    if (try_rfft2_fast(x, spec, B, h, w, E, nb, mx, my, col_weights, (float)(1.0 / sqrt((double)h * (double)w)),
-                       as_stream(stream), &frc))
-      return frc;
-  }
-  const int tw = ((2 * w + 2 * h + 3) & ~3);
-  const int CC = pick_cc(E, (long long)h * w + (long long)h * my * 2, tw);
-  if (CC == 0) {
+  const float scale = (float)(1.0 / sqrt((double)h * (double)w));
+  const int kind = dft2_select(B, h, w, E, nb, mx, my, 0, 0);
+  if (kind > 0)
+    return launch_dft2_fast<0>(kind, Dft2Call{x, nullptr, spec, B, E, nb, mx, my, col_weights, scale, as_stream(stream),
+                                              DftNorm{nullptr, nullptr, nullptr, nullptr, 0}});
+  if (kind < 0) {
     set_error("rfft2: latent grid %dx%d does not fit LDS", h, w);
     return DPOT_EUNSUP;
   }
+  const int tw = ((2 * w + 2 * h + 3) & ~3);
+  const int CC = dft2_generic_cc(h, w, E, mx, my, 0);
   const size_t lds = sizeof(float) * (tw + (size_t)CC * ((size_t)h * w + (size_t)h * my * 2));
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rfft2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                       (int)lds);
-  const float scale = (float)(1.0 / sqrt((double)h * (double)w));
   hipLaunchKernelGGL(rfft2_kernel, dim3(E / CC, B), dim3(256), lds, as_stream(stream), x, spec, h, w, E, nb, mx, my,
                      CC, col_weights, scale);
   return check_launch("rfft2_kernel");
@@ -290,10 +324,11 @@ extern "C" int dpot_rfft2_norm(const float* x, const float* mean, const float* r
   if (rc) return rc;
   DPOT_REQUIRE(x && spec && mean && rstd && gamma && beta && G > 0 && E % G == 0, "rfft2_norm: bad argument");
   DPOT_REQUIRE(dpot_rfft2_norm_supported(h, w, E), "rfft2_norm: latent grid %dx%d has no register-FFT path", h, w);
-  int frc = 0;
-  if (try_rfft2_fast(x, spec, B, h, w, E, nb, mx, my, col_weights, (float)(1.0 / sqrt((double)h * (double)w)),
-                     as_stream(stream), &frc, DftNorm{mean, rstd, gamma, beta, G}))
-    return frc;
+  const int kind = dft2_select(B, h, w, E, nb, mx, my, 0, 1);
+  if (kind > 0)
+    return launch_dft2_fast<0>(kind, Dft2Call{x, nullptr, spec, B, E, nb, mx, my, col_weights,
+                                              (float)(1.0 / sqrt((double)h * (double)w)), as_stream(stream),
+                                              DftNorm{mean, rstd, gamma, beta, G}});
   set_error("rfft2_norm: no register-FFT kernel for this shape");
   return DPOT_EUNSUP;
 }
@@ -303,22 +338,20 @@ extern "C" int dpot_irfft2(const float* spec, const float* res, float* y, int B,
   int rc = check_dft_args("irfft2", B, h, w, E, nb, mx, my);
   if (rc) return rc;
   DPOT_REQUIRE(spec && y, "irfft2: null pointer");
-  {
-    int frc = 0;
-    if (try_irfft2_fast(spec, res, y, B, h, w, E, nb, mx, my, col_weights,
-                        (float)(1.0 / sqrt((double)h * (double)w)), as_stream(stream), &frc))
-      return frc;
-  }
-  const int tw = ((2 * w + 2 * h + 3) & ~3);
-  const int CC = pick_cc(E, (long long)mx * my * 2 + (long long)h * my * 2, tw);
-  if (CC == 0) {
+  const float scale = (float)(1.0 / sqrt((double)h * (double)w));
+  const int kind = dft2_select(B, h, w, E, nb, mx, my, 1, 0);
+  if (kind > 0)
+    return launch_dft2_fast<1>(kind, Dft2Call{spec, res, y, B, E, nb, mx, my, col_weights, scale, as_stream(stream),
+                                              DftNorm{nullptr, nullptr, nullptr, nullptr, 0}});
+  if (kind < 0) {
     set_error("irfft2: latent grid %dx%d does not fit LDS", h, w);
     return DPOT_EUNSUP;
   }
+  const int tw = ((2 * w + 2 * h + 3) & ~3);
+  const int CC = dft2_generic_cc(h, w, E, mx, my, 1);
   const size_t lds = sizeof(float) * (tw + (size_t)CC * ((size_t)mx * my * 2 + (size_t)h * my * 2));
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(irfft2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                       (int)lds);
-  const float scale = (float)(1.0 / sqrt((double)h * (double)w));
   hipLaunchKernelGGL(irfft2_kernel, dim3(E / CC, B), dim3(256), lds, as_stream(stream), spec, res, y, h, w, E, nb,
                      mx, my, CC, col_weights, scale);
   return check_launch("irfft2_kernel");
@@ -370,10 +403,11 @@ extern "C" int dpot_irfft2_norm(const float* spec, const float* res, const float
   if (rc) return rc;
   DPOT_REQUIRE(spec && res && y && mean && rstd && gamma && beta && G > 0 && E % G == 0, "irfft2_norm: bad argument");
   DPOT_REQUIRE(dpot_rfft2_norm_supported(h, w, E), "irfft2_norm: latent grid %dx%d has no register-FFT path", h, w);
-  int frc = 0;
-  if (try_irfft2_fast(spec, res, y, B, h, w, E, nb, mx, my, col_weights, (float)(1.0 / sqrt((double)h * (double)w)),
-                      as_stream(stream), &frc, DftNorm{mean, rstd, gamma, beta, G}))
-    return frc;
+  const int kind = dft2_select(B, h, w, E, nb, mx, my, 1, 1);
+  if (kind > 0)
+    return launch_dft2_fast<1>(kind, Dft2Call{spec, res, y, B, E, nb, mx, my, col_weights,
+                                              (float)(1.0 / sqrt((double)h * (double)w)), as_stream(stream),
+                                              DftNorm{mean, rstd, gamma, beta, G}});
   set_error("irfft2_norm: no register-FFT kernel for this shape");
   return DPOT_EUNSUP;
 }

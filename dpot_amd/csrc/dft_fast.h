@@ -585,80 +585,104 @@ static int launch_irfft2_128(const float* spec, const float* res, float* y, int 
   return check_launch("irfft2_128_kernel");
 }
 
-// returns 1 if a fast kernel was launched (rc in *rc), 0 if the shape has no fast path
-static inline int try_rfft2_fast(const float* x, float* spec, int B, int h, int w, int E, int nb, int mx, int my,
-                                 int colw, float scale, hipStream_t s, int* rc,
-                                 const DftNorm nrm = DftNorm{nullptr, nullptr, nullptr, nullptr, 0}) {
-  constexpr int forced = 0;      // (rounds 3-5: DPOT_DFT_CC forced a channel-chunk width for the sweeps in profiles/r05_dft_cc_L.txt)
-  if (h == 16 && w == 16) {
-    if (forced == 16 && E % 16 == 0) { *rc = launch_rfft2_fast<16, 16, 16>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    // 64-channel slabs only when that still gives every CU >= 2 workgroups (latency hiding); else 32-channel slabs
-    if (forced != 32 && E % 64 == 0 && ((long long)B * (E / 64) >= 512 || forced == 64)) { *rc = launch_rfft2_fast<16, 16, 64>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (E % 32 == 0) { *rc = launch_rfft2_fast<16, 16, 32>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 8 && w == 8) {
-    if (E % 64 == 0 && (long long)B * (E / 64) >= 512) { *rc = launch_rfft2_fast<8, 8, 64>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (E % 32 == 0) { *rc = launch_rfft2_fast<8, 8, 32>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 64 && w == 64) {
-    // 64-point lines in registers (128 values per line item): 8-channel chunks, 132 KiB of LDS for the half-complex plane
-    if (E % 8 == 0) { *rc = launch_rfft2_fast<64, 64, 8>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 32 && w == 32) {
-    // 32-channel chunks (full 128-byte lines per token, 139 KiB of LDS: one workgroup per CU) when that still gives
-    // >= 128 workgroups: 18.0 against 22.7 us at DPOT-L B = 4 (the inverse is FASTER with 16: 29.8 against 42.5 us)
-    // 12-channel chunks: 512 balanced workgroups at DPOT-L B = 4 (see the inverse below) - 15.7 us (32: 18.1, 16: 22.7)
-    // round 5, DPOT-L at batch 16: with >= 2 rounds of 32-channel workgroups the full lines win again (step 90.40 -> 90.22,
-    // 90.63 -> 90.11 ms, profiles/r05_dft_cc_L.txt; 16-channel chunks: +1.0 ms)
-    if (forced != 16 && forced != 12 && E % 32 == 0 && (long long)B * (E / 32) >= 512) { *rc = launch_rfft2_fast<32, 32, 32>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (forced != 16 && forced != 32 && E % 12 == 0 && (E / nb) % 12 == 0 && (long long)B * (E / 12) >= 256) { *rc = launch_rfft2_fast<32, 32, 12>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (forced != 16 && E % 32 == 0 && (long long)B * (E / 32) >= 128) { *rc = launch_rfft2_fast<32, 32, 32>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (E % 16 == 0) { *rc = launch_rfft2_fast<32, 32, 16>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 24 && w == 24) {
-    // round 5: 3 * 2^k lines (192^2 / 384^2 / 768^2 fields at patch 8) - a radix-3 stage in front of three 2^k-point register FFTs
-    if (E % 32 == 0) { *rc = launch_rfft2_fast<24, 24, 32>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (E % 8 == 0) { *rc = launch_rfft2_fast<24, 24, 8>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 48 && w == 48) {
-    if (E % 16 == 0) { *rc = launch_rfft2_fast<48, 48, 16>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (E % 4 == 0) { *rc = launch_rfft2_fast<48, 48, 4>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 96 && w == 96) {
-    if (E % 4 == 0) { *rc = launch_rfft2_fast<96, 96, 4>(x, spec, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 128 && w == 128 && !nrm.mean) {
-    // 1024^2 fields at patch 8: two 64-point register FFTs per line; the kept ky rows in LDS ([my][128][2][CC])
-    if (E % 4 == 0 && my <= 36) { *rc = launch_rfft2_128<4>(x, spec, B, E, nb, mx, my, colw, scale, s); return 1; }
-    if (E % 2 == 0) { *rc = launch_rfft2_128<2>(x, spec, B, E, nb, mx, my, colw, scale, s); return 1; }
-  }
+// ---------------------------------------------------------------------------------------------------------------------
+// Kernel selection in ONE place: the launchers (dpot_rfft2 / dpot_irfft2 and their _norm forms), dpot_dft2_kernel_kind and
+// dpot_dft2_kernel_kinds all read this table.  A row is R(dirs, H, CC, condition): a register-FFT kernel for the H x H grid
+// with CC-channel chunks, compiled for the forward (dirs & 1) and / or the inverse (dirs & 2) transform, chosen by the first
+// row of its grid whose condition holds; its kind is H * 1000 + CC.  No row: the generic direct-sum kernels (kind 0).
+// Conditions see B, E, nb, my, norm and wg(cc) = B * (E / cc), the number of workgroups with cc-channel chunks.
+//   16 / 8:  64-channel slabs only when that still gives every CU >= 2 workgroups (latency hiding); else 32-channel slabs
+//   64:      64-point lines in registers (128 values per line item): 8-channel chunks, 132 KiB of LDS for the half-complex plane
+//   32, forward: 32-channel chunks (full 128-byte lines per token, 139 KiB of LDS: one workgroup per CU) when that still gives
+//            >= 128 workgroups: 18.0 against 22.7 us at DPOT-L B = 4; 12-channel chunks: 512 balanced workgroups at DPOT-L
+//            B = 4 - 15.7 us (32: 18.1, 16: 22.7); round 5, DPOT-L at batch 16: with >= 2 rounds of 32-channel workgroups the
+//            full lines win again (step 90.40 -> 90.22, 90.63 -> 90.11 ms, profiles/r05_dft_cc_L.txt; 16-channel chunks: +1.0 ms)
+//   32, inverse: 12-channel chunks when the blocks allow it: 512 workgroups = 2 per CU at DPOT-L B = 4 (E = 1536) instead of
+//            the 384 of 16-channel chunks (1.5 per CU: half the CUs run two in a row) - 20.4 against 29.8 us; it is FASTER
+//            with 16 than with 32 channels (29.8 against 42.5 us; one workgroup per CU: +4 ms on the DPOT-L step at batch 16,
+//            profiles/r05_dft_cc_L.txt), so the inverse has no 32-channel kernel
+//   24 / 48 / 96: round 5, 3 * 2^k lines (192^2 / 384^2 / 768^2 fields at patch 8) - a radix-3 stage in front of three
+//            2^k-point register FFTs
+//   128:     1024^2 fields at patch 8: two 64-point register FFTs per line; the kept ky rows in LDS ([my][128][2][CC]); these
+//            kernels have no GroupNorm-on-load form
+// ---------------------------------------------------------------------------------------------------------------------
+#define DPOT_DFT2_RULES(R)                                                      \
+  R(3, 16, 64, E % 64 == 0 && wg(64) >= 512)                                    \
+  R(3, 16, 32, E % 32 == 0)                                                     \
+  R(3, 8, 64, E % 64 == 0 && wg(64) >= 512)                                     \
+  R(3, 8, 32, E % 32 == 0)                                                      \
+  R(3, 64, 8, E % 8 == 0)                                                       \
+  R(1, 32, 32, E % 32 == 0 && wg(32) >= 512)                                    \
+  R(3, 32, 12, E % 12 == 0 && (E / nb) % 12 == 0 && wg(12) >= 256)              \
+  R(1, 32, 32, E % 32 == 0 && wg(32) >= 128)                                    \
+  R(3, 32, 16, E % 16 == 0)                                                     \
+  R(3, 24, 32, E % 32 == 0)                                                     \
+  R(3, 24, 8, E % 8 == 0)                                                       \
+  R(3, 48, 16, E % 16 == 0)                                                     \
+  R(3, 48, 4, E % 4 == 0)                                                       \
+  R(3, 96, 4, E % 4 == 0)                                                       \
+  R(3, 128, 4, !norm && E % 4 == 0 && my <= 36)                                 \
+  R(3, 128, 2, !norm && E % 2 == 0)
+
+// kind of the register-FFT kernel for this call, 0: none (the generic kernels' shape)
+static inline int dft2_fast_kind(int B, int h, int w, int E, int nb, int my, int inverse, int norm) {
+  if (h != w) return 0;
+  const int dir = inverse ? 2 : 1;
+  const auto wg = [&](int cc) { return (long long)B * (E / cc); };
+#define DPOT_DFT2_PICK(dirs, H, CC, cond) \
+  if (((dirs) & dir) && h == (H) && (cond)) return (H) * 1000 + (CC);
+  DPOT_DFT2_RULES(DPOT_DFT2_PICK)
+#undef DPOT_DFT2_PICK
   return 0;
 }
-static inline int try_irfft2_fast(const float* spec, const float* res, float* y, int B, int h, int w, int E, int nb,
-                                  int mx, int my, int colw, float scale, hipStream_t s, int* rc,
-                                  const DftNorm nrm = DftNorm{nullptr, nullptr, nullptr, nullptr, 0}) {
-  constexpr int forced = 0;      // (rounds 3-5: DPOT_DFT_CC forced a channel-chunk width for the sweeps in profiles/r05_dft_cc_L.txt)
-  if (h == 16 && w == 16) {
-    if (forced == 16 && E % 16 == 0) { *rc = launch_irfft2_fast<16, 16, 16>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (forced != 32 && E % 64 == 0 && ((long long)B * (E / 64) >= 512 || forced == 64)) { *rc = launch_irfft2_fast<16, 16, 64>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (E % 32 == 0) { *rc = launch_irfft2_fast<16, 16, 32>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 8 && w == 8) {
-    if (E % 64 == 0 && (long long)B * (E / 64) >= 512) { *rc = launch_irfft2_fast<8, 8, 64>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (E % 32 == 0) { *rc = launch_irfft2_fast<8, 8, 32>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 64 && w == 64) {
-    if (E % 8 == 0) { *rc = launch_irfft2_fast<64, 64, 8>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 32 && w == 32) {
-    // 12-channel chunks when the blocks allow it: 512 workgroups = 2 per CU at DPOT-L B = 4 (E = 1536) instead of the
-    // 384 of 16-channel chunks (1.5 per CU: half the CUs run two in a row) - 20.4 against 29.8 us
-    // (32-channel chunks for the inverse, one workgroup per CU: +4 ms on the DPOT-L step at batch 16, profiles/r05_dft_cc_L.txt)
-    if (forced != 16 && E % 12 == 0 && (E / nb) % 12 == 0 && (long long)B * (E / 12) >= 256) { *rc = launch_irfft2_fast<32, 32, 12>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (E % 16 == 0) { *rc = launch_irfft2_fast<32, 32, 16>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 24 && w == 24) {
-    if (E % 32 == 0) { *rc = launch_irfft2_fast<24, 24, 32>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (E % 8 == 0) { *rc = launch_irfft2_fast<24, 24, 8>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 48 && w == 48) {
-    if (E % 16 == 0) { *rc = launch_irfft2_fast<48, 48, 16>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-    if (E % 4 == 0) { *rc = launch_irfft2_fast<48, 48, 4>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 96 && w == 96) {
-    if (E % 4 == 0) { *rc = launch_irfft2_fast<96, 96, 4>(spec, res, y, B, E, nb, mx, my, colw, scale, s, nrm); return 1; }
-  } else if (h == 128 && w == 128 && !nrm.mean) {
-    if (E % 4 == 0 && my <= 36) { *rc = launch_irfft2_128<4>(spec, res, y, B, E, nb, mx, my, colw, scale, s); return 1; }
-    if (E % 2 == 0) { *rc = launch_irfft2_128<2>(spec, res, y, B, E, nb, mx, my, colw, scale, s); return 1; }
+// every register-FFT kind compiled for a direction, in table order, each once; returns the count (out may be shorter)
+static inline int dft2_fast_kinds(int inverse, int* out, int cap) {
+  const int dir = inverse ? 2 : 1;
+  int all[64], n = 0;
+#define DPOT_DFT2_LIST(dirs, H, CC, cond)                 \
+  if ((dirs) & dir) {                                     \
+    const int k = (H) * 1000 + (CC);                      \
+    int seen = 0;                                         \
+    for (int i = 0; i < n; ++i) seen |= all[i] == k;      \
+    if (!seen && n < 64) all[n++] = k;                    \
   }
-  return 0;
+  DPOT_DFT2_RULES(DPOT_DFT2_LIST)
+#undef DPOT_DFT2_LIST
+  for (int i = 0; i < n && i < cap; ++i) out[i] = all[i];
+  return n;
+}
+
+// the operands of one transform: forward in = x, out = spec; inverse in = spec (+ res), out = y
+struct Dft2Call {
+  const float* in;
+  const float* res;
+  float* out;
+  int B, E, nb, mx, my, colw;
+  float scale;
+  hipStream_t s;
+  DftNorm nrm;
+};
+template <int INV, int H, int CC>
+static int launch_dft2_kind(const Dft2Call& a) {
+  if constexpr (H == 128) {
+    if constexpr (INV) return launch_irfft2_128<CC>(a.in, a.res, a.out, a.B, a.E, a.nb, a.mx, a.my, a.colw, a.scale, a.s);
+    else return launch_rfft2_128<CC>(a.in, a.out, a.B, a.E, a.nb, a.mx, a.my, a.colw, a.scale, a.s);
+  } else {
+    if constexpr (INV) return launch_irfft2_fast<H, H, CC>(a.in, a.res, a.out, a.B, a.E, a.nb, a.mx, a.my, a.colw, a.scale, a.s, a.nrm);
+    else return launch_rfft2_fast<H, H, CC>(a.in, a.out, a.B, a.E, a.nb, a.mx, a.my, a.colw, a.scale, a.s, a.nrm);
+  }
+}
+// launches the register-FFT kernel of `kind` (a value dft2_fast_kind returned for this direction)
+template <int INV>
+static int launch_dft2_fast(int kind, const Dft2Call& a) {
+#define DPOT_DFT2_LAUNCH(dirs, H, CC, cond)                                    \
+  if constexpr ((((dirs) >> INV) & 1) != 0) {                                   \
+    if (kind == (H) * 1000 + (CC)) return launch_dft2_kind<INV, H, CC>(a);      \
+  }
+  DPOT_DFT2_RULES(DPOT_DFT2_LAUNCH)
+#undef DPOT_DFT2_LAUNCH
+  set_error("dft2: kind %d is not compiled for the %s transform", kind, INV ? "inverse" : "forward");
+  return DPOT_EUNSUP;
 }
 #endif  // DPOT_DFT_NO_KERNELS
 

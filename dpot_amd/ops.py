@@ -581,6 +581,22 @@ def rfft2_norm_supported(h: int, w: int, E: int) -> bool:
     return bool(_lib.load().dpot_rfft2_norm_supported(h, w, E))
 
 
+def dft2_kernel_kind(B: int, h: int, w: int, E: int, nb: int, mx: int, my: int, inverse: bool = False,
+                     norm: bool = False) -> int:
+    """the kernel rfft2 / irfft2 (inverse) run for this call, norm: their GroupNorm-on-load forms - from the library's own
+    selection (dpot_dft2_kernel_kind): H * 1000 + CC for a register FFT with CC-channel chunks, 0 for the generic direct-sum
+    kernel, -1 where the call is refused"""
+    return _lib.load().dpot_dft2_kernel_kind(B, h, w, E, nb, mx, my, int(inverse), int(norm))
+
+
+def dft2_kernel_kinds(inverse: bool = False) -> Tuple[int, ...]:
+    """every kind dft2_kernel_kind can return >= 0 for this direction: the kernels that are compiled"""
+    buf = (C.c_int * 64)()
+    n = _lib.load().dpot_dft2_kernel_kinds(int(inverse), buf, 64)
+    assert n <= 64
+    return tuple(buf[:n])
+
+
 def rfft2(x: Tensor, h: int, w: int, nb: int, mx: int, my: int, col_weights: int = 0, norm=None) -> Tensor:
     """x[B,h*w,E] -> spec[B*mx*my, 2E] (planar per channel block).
     norm = (mean [B,G], rstd [B,G], gamma [E], beta [E]): the transform of GroupNorm(x) with those statistics, applied on

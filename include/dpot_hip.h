@@ -277,6 +277,13 @@ int dpot_rfft2(const float* x, float* spec, int B, int h, int w, int E, int nb, 
                int col_weights, dpot_stream_t stream);
 int dpot_irfft2(const float* spec, const float* res, float* y, int B, int h, int w, int E, int nb, int mx,
                 int my, int col_weights, dpot_stream_t stream);
+/* The kernel the four entry points of this section run for a call (inverse = 1: dpot_irfft2, norm = 1: the _norm forms),
+ * from the library's own selection - the launchers read the same table: H * 1000 + CC for the register-FFT kernel of the
+ * H x H grid with CC-channel chunks (16064, 32012, 128004, ...), 0 for the generic direct-sum kernel, -1 where the call is
+ * refused (the generic slab does not fit LDS, norm = 1 on a grid without a GroupNorm-on-load kernel, bad arguments).
+ * dpot_dft2_kernel_kinds: every kind compiled for a direction (the generic 0 last) into out[0..cap), returns their number. */
+int dpot_dft2_kernel_kind(int B, int h, int w, int E, int nb, int mx, int my, int inverse, int norm);
+int dpot_dft2_kernel_kinds(int inverse, int* out, int cap);
 /* rfft2(GroupNorm(x)) with the statistics given (mean / rstd [B, G] from dpot_groupnorm_fwd with y == NULL): norm1 of
  * Block.forward (models/dpot.py:167-168) folded into the load of the transform, GroupNorm1(x) is never written.  Register-FFT
  * grids only (8, 16, 32, 64 square): dpot_rfft2_norm_supported. */
