@@ -199,7 +199,13 @@ SIGNATURES = {
     "dpot_eval_metrics_acc_elems": (c_i64, [c_i] * 4),
     "dpot_eval_metrics_stats": (c_i, [c_fp] * 9 + [c_i] * 4 + [c_fp]),
     "dpot_eval_metrics_finalize": (c_i, [c_fp] * 3 + [c_i] * 5 + [c_fp]),
-    "dpot_panel_pack_weights": (c_i, [c_fp, c_i, c_i, c_fp]),
+    "dpot_eval3_pad": (c_i, [c_i, c_i]),
+    "dpot_eval3_max_size": (c_i, [c_i]),
+    "dpot_eval3_acc_elems": (c_i64, [c_i] * 5),
+    "dpot_eval3_work_elems": (c_i64, [c_i] * 6),
+    "dpot_eval3_stats": (c_i, [c_fp] * 12 + [c_i] * 5 + [c_fp]),
+    "dpot_eval3_finalize": (c_i, [c_fp] * 3 + [c_i] * 6 + [c_fp]),
+    "dpot_panel_pack_weights":(c_i, [c_fp, c_i, c_i, c_fp]),
     "dpot_layout_jobs": (c_i, [c_fp, c_i, c_i64, c_fp]),
     "dpot_bf16_packed_elems": (c_i64, [c_i, c_i, c_i]),
     "dpot_bf16_pack_rows": (c_i, [c_fp, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp]),

@@ -49,7 +49,8 @@ int tune(const char* key, int dflt) {
  * 267: dpot_dft3_supported, dpot_rfft3, dpot_irfft3 (csrc/dft3.hip): the transforms of the 3-D model's AFNO3D
  * 268: dpot_wgrad_flush_async, dpot_wgrad_wait, dpot_wgrad_lane_* (csrc/gemm_tn.hip): the batched weight gradients on a
  * library-owned stream beside the caller's
- * 269: dpot_patchify3, dpot_unpatchify3, dpot_fold3 (csrc/patch3d.hip): the index rearrangements at the two ends of DPOTNet3D */
-extern "C" int dpot_version(void) { return 269; }
+ * 269: dpot_patchify3, dpot_unpatchify3, dpot_fold3 (csrc/patch3d.hip): the index rearrangements at the two ends of DPOTNet3D
+ * 270: dpot_eval3_stats, dpot_eval3_finalize and their queries (csrc/evalmetrics3d.hip): the evaluation metrics of 3-D rollouts */
+extern "C" int dpot_version(void) { return 270; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

@@ -16,6 +16,7 @@
 * ``RolloutEvaluator`` - the reference's second evaluation tool, utils/criterion.py:189-239 ``Evaluator(temporal=True,
   griddata=True, component='all')``: per-channel and per-step normalised errors, the boundary error and the error spectrum
   in three wavenumber bands, accumulated on the device (csrc/evalmetrics.hip); ``evaluator=`` hands every rollout to it.
+  3-D rollouts [B, X, Y, Z, T, C] take the same keys, column c being ``Evaluator(..., component=c)`` (csrc/evalmetrics3d.hip).
 """
 from __future__ import annotations
 
@@ -157,7 +158,15 @@ class RolloutEvaluator:
     A channel whose target is identically zero divides by a zero norm: inf or NaN, as IEEE arithmetic and the reference give;
     nothing is counted specially.  There is no mask, no normalizer and no single-component mode.  All batches between two
     ``reset()`` share X, Y, T, C (T <= T_max, C == n_channels); the batch size may change.  X <= 1024, Y <= 304 (the LDS
-    intermediate of a workgroup).  ``update`` is capturable in a hipGraph once a shape has been seen."""
+    intermediate of a workgroup).  ``update`` is capturable in a hipGraph once a shape has been seen.
+
+    3-D fields: ``update`` also takes a pair [B, X, Y, Z, T, C] (csrc/evalmetrics3d.hip) and dispatches on the rank.  The
+    reference's Evaluator cannot run ``component='all'`` on such a field; column c of every key is its
+    ``Evaluator(temporal=True, griddata=True, component=c)(pred[..., c], target)``, in the shapes above: the ratios over all of
+    X*Y*Z*T and, per step, over X*Y*Z; ``bdmse`` is e^2 summed over the six faces x = 0, X-1, y = 0, Y-1, z = 0, Z-1 (an edge
+    counted twice, a corner three times) over 2 XY + 2 YZ + 2 ZX; ``fmse_*`` is |DFT3(e)|^2 over the positive octant summed
+    over the shells floor(sqrt(i^2 + j^2 + k^2)) < K = min(X//2, Y//2, Z//2), per shell sqrt(mean over the samples) / (X Y Z).
+    X, Y, Z <= 512 each.  The batches between two ``reset()`` share the rank as well as the shape."""
 
     def __init__(self, device, n_channels: int, T_max: int, ilow: int = 4, ihigh: int = 12):
         if n_channels < 1 or T_max < 1:
@@ -169,21 +178,22 @@ class RolloutEvaluator:
             raise _lib.DpotHipError(f"RolloutEvaluator must live on the MI355X (got device {self.device}): dpot_amd has no "
                                     "CPU path")
         self.C, self.T_max, self.ilow, self.ihigh = int(n_channels), int(T_max), int(ilow), int(ihigh)
-        self.shape: Optional[Tuple[int, int, int, int]] = None         # (X, Y, T, C) of the batches since reset()
+        self.shape: Optional[Tuple[int, ...]] = None                   # (X, Y[, Z], T, C) of the batches since reset()
         self.acc: Optional[Tensor] = None
-        self._accs: Dict[Tuple[int, int, int, int], Tensor] = {}        # one accumulator per shape ever seen: no re-allocation
+        self._accs: Dict[Tuple[int, ...], Tensor] = {}                  # one accumulator per shape ever seen: no re-allocation
 
     def update(self, pred: Tensor, target: Tensor) -> None:
-        """fold one batch in: pred, target [B, X, Y, T, C] fp32 contiguous on the GPU.  No synchronisation."""
-        if pred.dim() != 5 or pred.shape != target.shape:
-            raise _lib.DpotHipError(f"RolloutEvaluator.update: pred and target must be [B, X, Y, T, C] of one shape, got "
-                                    f"{tuple(pred.shape)} and {tuple(target.shape)}")
+        """fold one batch in: pred, target [B, X, Y, T, C] or [B, X, Y, Z, T, C] fp32 contiguous on the GPU.  No
+        synchronisation."""
+        if pred.dim() not in (5, 6) or pred.shape != target.shape:
+            raise _lib.DpotHipError(f"RolloutEvaluator.update: pred and target must be [B, X, Y, T, C] or [B, X, Y, Z, T, C] "
+                                    f"of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
         shape = tuple(int(s) for s in pred.shape[1:])
-        if shape[3] != self.C or shape[2] > self.T_max:
+        if shape[-1] != self.C or shape[-2] > self.T_max:
             raise _lib.DpotHipError(f"RolloutEvaluator was built for {self.C} channels and T <= {self.T_max}, got "
                                     f"{tuple(pred.shape)}")
         if self.shape is not None and shape != self.shape:
-            raise _lib.DpotHipError(f"RolloutEvaluator: the batches between two reset() must share X, Y, T, C: "
+            raise _lib.DpotHipError(f"RolloutEvaluator: the batches between two reset() must share X, Y, T, C (and the rank): "
                                     f"{self.shape} so far, now {shape}")
         if not (pred.is_cuda and target.is_cuda):
             raise _lib.DpotHipError(f"RolloutEvaluator.update: pred and target must live on the MI355X (got {pred.device}, "
@@ -194,10 +204,13 @@ class RolloutEvaluator:
                 if torch.cuda.is_current_stream_capturing():
                     raise _lib.DpotHipError("RolloutEvaluator: the accumulator of a shape is allocated when it is first seen - "
                                             "run one update (and reset) before capturing")
-                X, Y, T, Cc = shape
-                acc = self._accs[shape] = ops.eval_acc_alloc(X, Y, T, Cc, self.device)
+                alloc = ops.eval_acc_alloc if len(shape) == 4 else ops.eval3_acc_alloc
+                acc = self._accs[shape] = alloc(*shape, self.device)
             self.acc = acc
-        ops.eval_metrics_update(pred, target, self.acc)
+        if len(shape) == 4:
+            ops.eval_metrics_update(pred, target, self.acc)
+        else:
+            ops.eval3_metrics_update(pred, target, self.acc)
         self.shape = shape
 
     def reset(self) -> None:
@@ -219,8 +232,8 @@ class RolloutEvaluator:
             if dist.is_available() and dist.is_initialized():
                 dist.all_reduce(vals, op=dist.ReduceOp.SUM, group=pg)
         vals = vals.cpu().numpy()
-        X, Y, T, Cc = self.shape
-        return ops.eval_finish(vals, int(round(vals[0])), X, Y, T, Cc, self.ilow, self.ihigh)
+        finish = ops.eval_finish if len(self.shape) == 4 else ops.eval3_finish
+        return finish(vals, int(round(vals[0])), *self.shape, self.ilow, self.ihigh)
 
 
 @torch.no_grad()
@@ -239,7 +252,9 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
     the window slide stay at the data resolution.  As in the reference the two resizes also run when model_res equals the
     data resolution (every frequency is kept then: the identity up to rounding).  None: no resize is enqueued.
     evaluator: a RolloutEvaluator - `evaluator.update(pred, yy)` runs on the assembled prediction at the DATA resolution, on
-    the same stream, without a synchronisation; the returned values are untouched by it.  None: nothing is enqueued."""
+    the same stream, without a synchronisation; the returned values are untouched by it.  None: nothing is enqueued.
+    6-D windows take `evaluator=` as well - a RolloutEvaluator, anything else is a ValueError before the rollout starts;
+    `model_res=` does not exist for them (there is no 3-D spectral resize)."""
     # weight-only products (packed AFNO weights, folded embed matrices, ...) once per rollout, not once per AR step
     scope = model.weights_scope() if (step is None and hasattr(model, "weights_scope")) else contextlib.nullcontext()
     def forward(x):                      # DPOTNet returns (pred, cls_pred), DPOTNet3D the prediction alone
@@ -247,10 +262,15 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
         return out if torch.is_tensor(out) else out[0]
 
     step = step or forward
-    if xx.dim() == 6 and (model_res is not None or evaluator is not None):
-        # the test loop of finetune3d.py:252-278 has neither; the spectral resize and the Evaluator are 2-D kernels
-        raise ValueError(f"rollout_eval: model_res= and evaluator= exist for 2-D windows [B,X,Y,T,C] only, got a 6-D window "
+    if xx.dim() == 6 and model_res is not None:
+        # the test loop of finetune3d.py:252-278 has no resize; the spectral resize is a 2-D kernel
+        raise ValueError(f"rollout_eval: model_res= exists for 2-D windows [B,X,Y,T,C] only, got a 6-D window "
                          f"{tuple(xx.shape)}")
+    if xx.dim() == 6 and evaluator is not None and not isinstance(evaluator, RolloutEvaluator):
+        # a 6-D prediction goes to RolloutEvaluator's 3-D kernels; any other object with an update() was written for
+        # [B,X,Y,T,C], and failing before the rollout beats failing (or mis-reading the rank) after it
+        raise ValueError(f"rollout_eval: a 6-D window {tuple(xx.shape)} needs a RolloutEvaluator as evaluator=; "
+                         f"a {type(evaluator).__name__} is taken for 2-D windows [B,X,Y,T,C] only")
     T_ar = yy.shape[-2]
     loss_steps = None
     preds = []
@@ -288,7 +308,8 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
 
 
 class GraphedRollout:
-    """One hipGraph of the forward step for a fixed input shape, replayed for every AR step."""
+    """One hipGraph of the forward step for a fixed input shape, replayed for every AR step.  The model's forward returns
+    (pred, cls_pred) as DPOTNet does, or the prediction alone as DPOTNet3D does (`cls` is then None)."""
 
     def __init__(self, model: nn.Module, example_xx: Tensor):
         self.model = model
@@ -305,7 +326,8 @@ class GraphedRollout:
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
-                self.im, self.cls = model(self.x)
+                out = model(self.x)
+        self.im, self.cls = (out, None) if torch.is_tensor(out) else (out[0], out[1])
         model.train(was_training)
 
     def step(self, xx: Tensor) -> Tensor:
@@ -316,11 +338,12 @@ class GraphedRollout:
     def __call__(self, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1, metrics=None, model_res=None,
                  evaluator=None):
         """model_res: the graph's own resolution - xx, yy, msk may then live at any data resolution; the two resizes of an
-        AR step run outside the captured graph, on the same stream (rollout_eval).  evaluator: as in rollout_eval"""
+        AR step run outside the captured graph, on the same stream (rollout_eval).  evaluator: as in rollout_eval.  A graph
+        captured for 6-D windows [B, X, Y, Z, T, C] takes metrics= and evaluator=, not model_res="""
         want = tuple(self.x.shape)
         if model_res is not None:
             if xx.dim() != 5:
-                raise ValueError(f"GraphedRollout: input must be [B, X, Y, T, C], got {tuple(xx.shape)}")
+                raise ValueError(f"GraphedRollout: model_res= needs an input [B, X, Y, T, C], got {tuple(xx.shape)}")
             if _size2(model_res) != want[1:3]:
                 raise ValueError(f"GraphedRollout captured at resolution {want[1:3]}, model_res is {_size2(model_res)}")
             want = want[:1] + tuple(xx.shape[1:3]) + want[3:]

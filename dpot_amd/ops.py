@@ -2239,3 +2239,192 @@ def eval_metrics_update(pred: Tensor, target: Tensor, acc: Tensor) -> None:
                                       specp.data_ptr(), B, nx, ny, T * C, _stream()), "eval_metrics_stats")
     check(lib.dpot_eval_metrics_finalize(statp.data_ptr(), specp.data_ptr(), acc.data_ptr(), B, nx, ny, T, C, _stream()),
           "eval_metrics_finalize")
+
+
+# ------------------------------------------------------------------------------------------------------
+# The same metric set for 3-D rollouts [B, X, Y, Z, T, C] (csrc/evalmetrics3d.hip): column c of every key is the reference's
+# Evaluator(temporal=True, griddata=True, component=c).  eval_dft_tables serves all three axes.
+# ------------------------------------------------------------------------------------------------------
+def eval3_shell_table(nx: int, ny: int, nz: int):
+    """int32 [nx // 2, ny // 2, nz // 2]: the shell floor(sqrt(i^2 + j^2 + k^2)) of wavenumber (i, j, k) of the positive
+    octant, or -1 where that shell is >= K = min(nx // 2, ny // 2, nz // 2) and the reference drops the wavenumber.  Integer
+    arithmetic, as eval_shell_table."""
+    import numpy as np
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"eval3_shell_table: sizes must be >= 2, got {nx} x {ny} x {nz}")
+    i = np.arange(nx // 2, dtype=np.int64)[:, None, None]
+    j = np.arange(ny // 2, dtype=np.int64)[None, :, None]
+    k = np.arange(nz // 2, dtype=np.int64)[None, None, :]
+    v = i * i + j * j + k * k
+    s = np.sqrt(v.astype(np.float64)).astype(np.int64)
+    s -= (s * s > v)
+    s += ((s + 1) * (s + 1) <= v)
+    assert ((s * s <= v) & ((s + 1) * (s + 1) > v)).all()
+    K = min(nx // 2, ny // 2, nz // 2)
+    return np.where(s < K, s, -1).astype(np.int32)
+
+
+def eval3_shell_ranges(nx: int, ny: int, nz: int):
+    """int32 [nz // 2, nx // 2, K + 1]: entry [k, i, s] = number of j in [0, ny // 2) whose shell in row (k, i) is below s.
+    The shell grows with j, so the members of shell s in row (k, i) are the j range [k, i, s] .. [k, i, s + 1]; what lies at
+    or beyond [k, i, K] is dropped.  This is the form of eval3_shell_table the kernel walks."""
+    import numpy as np
+    sh = eval3_shell_table(nx, ny, nz).astype(np.int64)
+    K = min(nx // 2, ny // 2, nz // 2)
+    sh = np.where(sh < 0, K, sh)                                   # dropped: beyond every kept shell
+    out = np.empty((nz // 2, nx // 2, K + 1), dtype=np.int32)
+    for s in range(K + 1):
+        out[:, :, s] = (sh < s).sum(axis=1).T
+    return out
+
+
+def eval3_acc_layout(nx: int, ny: int, nz: int, T: int, C: int):
+    """(offsets, total) of the accumulator in 8-byte words - eval_acc_layout with K = min(nx // 2, ny // 2, nz // 2)"""
+    K = min(nx // 2, ny // 2, nz // 2)
+    off = {"count": 0, "c": 2, "tc": 2 + 3 * C, "spec": 2 + 3 * C + 4 * T * C}
+    return off, 2 + 3 * C + 4 * T * C + T * C * K
+
+
+def eval3_finish(acc, samples: int, nx: int, ny: int, nz: int, T: int, C: int, ilow: int = 4, ihigh: int = 12):
+    """the dict of RolloutEvaluator.read() for 3-D fields from the accumulated sums (eval_finish with one more axis: the root
+    of the mean shell sums over nx ny nz; `bdmse` [C, T] is the error on the six faces)"""
+    import numpy as np
+    import warnings
+    acc = np.asarray(acc, dtype=np.float64)
+    off, total = eval3_acc_layout(nx, ny, nz, T, C)
+    if acc.shape != (total,):
+        raise ValueError(f"eval3_finish: the accumulator of {nx}x{ny}x{nz}, T={T}, C={C} has {total} words, got {acc.shape}")
+    K = min(nx // 2, ny // 2, nz // 2)
+    n = float(samples) if samples else float("nan")
+    c = acc[off["c"]:off["tc"]].reshape(3, C) / n
+    tc = acc[off["tc"]:off["spec"]].reshape(4, T, C) / n
+    shells = np.sqrt(acc[off["spec"]:].reshape(T, C, K) / n) / float(nx * ny * nz)
+    out = {"nmae": c[0:1], "nmse": c[1:2], "nmxe": c[2:3], "nmae_t": tc[0:1], "nmse_t": tc[1:2], "nmxe_t": tc[2:3],
+           "bdmse": tc[3].T}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)            # the mean of an empty band IS NaN
+        for key, band in (("fmse_low", shells[..., :ilow]), ("fmse_mid", shells[..., ilow:ihigh]),
+                          ("fmse_high", shells[..., ihigh:])):
+            out[key] = band.mean(axis=-1) if band.shape[-1] else np.full((T, C), np.nan)
+    out = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
+    out["samples"] = int(samples)
+    return out
+
+
+class Eval3Plan:
+    """The tables of dpot_eval3_stats for one field size, built in float64, rounded to fp32, zero-padded to the kernel's tile
+    multiples and kept in device memory.  `host_tables` is the host part alone."""
+
+    @staticmethod
+    def pads(nx: int, ny: int, nz: int):
+        """(nxp, nyp, nzp, hxp, hyp, hzp): the contraction extents and the wavenumber extents n // 2, each rounded up to 16 -
+        the values dpot_eval3_pad returns (checked when a plan is built)"""
+        r = lambda n: (n + 15) // 16 * 16
+        return r(nx), r(ny), r(nz), r(nx // 2), r(ny // 2), r(nz // 2)
+
+    @staticmethod
+    def host_tables(nx: int, ny: int, nz: int):
+        """dict of numpy arrays: cxT, sxT fp32 [nxp, hxp], cy, sy fp32 [nyp, hyp], czT, szT fp32 [nzp, hzp], jlo int32
+        [nz // 2, nx // 2, K + 1]"""
+        import numpy as np
+        nxp, nyp, nzp, hxp, hyp, hzp = Eval3Plan.pads(nx, ny, nz)
+
+        def padded(a, shape):
+            outp = np.zeros(shape, dtype=np.float32)
+            outp[:a.shape[0], :a.shape[1]] = a.astype(np.float32)
+            return outp
+
+        cx, sx = eval_dft_tables(nx)
+        cy, sy = eval_dft_tables(ny)
+        cz, sz = eval_dft_tables(nz)
+        return {"cxT": padded(cx.T, (nxp, hxp)), "sxT": padded(sx.T, (nxp, hxp)), "cy": padded(cy.T, (nyp, hyp)),
+                "sy": padded(sy.T, (nyp, hyp)), "czT": padded(cz.T, (nzp, hzp)), "szT": padded(sz.T, (nzp, hzp)),
+                "jlo": np.ascontiguousarray(eval3_shell_ranges(nx, ny, nz))}
+
+    def __init__(self, nx: int, ny: int, nz: int, device):
+        lib = _lib.load()
+        self.sizes = (nx, ny, nz)
+        limits = tuple(lib.dpot_eval3_max_size(a) for a in range(3))
+        if nx > limits[0] or ny > limits[1] or nz > limits[2]:
+            raise _lib.DpotHipError(f"eval3_metrics: a {nx} x {ny} x {nz} field is beyond the supported size (nx <= "
+                                    f"{limits[0]}; ny <= {limits[1]}: the LDS intermediate of a workgroup; nz <= {limits[2]})")
+        want = tuple(lib.dpot_eval3_pad(n, h) for h in (0, 1) for n in self.sizes)
+        if want != self.pads(nx, ny, nz):
+            raise _lib.DpotHipError(f"Eval3Plan: the library pads {self.sizes} to {want}, this module to "
+                                    f"{self.pads(nx, ny, nz)}")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DpotHipError(f"Eval3Plan {self.sizes}: the tables are uploaded when a field size is first used - call "
+                                    "ops.eval3_plan(...) (or one update) before capturing")
+        self.dev = {}
+        for name, a in self.host_tables(nx, ny, nz).items():
+            t = torch.empty(a.shape, dtype=torch.int32 if name == "jlo" else torch.float32, device=device)
+            t.copy_(torch.from_numpy(a))
+            self.dev[name] = t
+        self.work = {}
+
+    def workspace(self, B: int, TC: int, device):
+        """(statp, specp, G) of a batch size: allocated when it is first seen (not under capture), then reused"""
+        w = self.work.get((B, TC))
+        if w is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.DpotHipError(f"Eval3Plan {self.sizes}: the workspace of B={B}, T*C={TC} is allocated when that "
+                                        "shape is first used - run one update before capturing")
+            n = [_lib.load().dpot_eval3_work_elems(which, B, *self.sizes, TC) for which in range(3)]
+            if min(n) < 1:
+                raise _lib.DpotHipError(f"Eval3Plan {self.sizes}: the library sizes no workspace for B={B}, T*C={TC}")
+            w = self.work[(B, TC)] = (torch.empty(n[0], dtype=torch.float64, device=device),
+                                      torch.empty(n[1], dtype=torch.float32, device=device),
+                                      torch.empty(n[2], dtype=torch.float32, device=device))
+        return w
+
+
+_eval3_plans = {}
+
+
+def eval3_plan(nx: int, ny: int, nz: int, device) -> Eval3Plan:
+    """the cached Eval3Plan of (n_x, n_y, n_z, device)"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(nx), int(ny), int(nz), device)
+    plan = _eval3_plans.get(key)
+    if plan is None:
+        plan = _eval3_plans[key] = Eval3Plan(*key)
+    return plan
+
+
+def eval3_acc_alloc(nx: int, ny: int, nz: int, T: int, C: int, device) -> Tensor:
+    """a zeroed accumulator for eval3_metrics_update (int64 words; word 0 the sample count, the rest doubles)"""
+    n = eval3_acc_layout(nx, ny, nz, T, C)[1]
+    if n != _lib.load().dpot_eval3_acc_elems(nx, ny, nz, T, C):
+        raise _lib.DpotHipError(f"eval3_acc_alloc: the library lays the accumulator of {nx}x{ny}x{nz}, T={T}, C={C} out "
+                                "differently")
+    return torch.zeros(n, dtype=torch.int64, device=device)
+
+
+def eval3_metrics_update(pred: Tensor, target: Tensor, acc: Tensor) -> None:
+    """acc += the Evaluator sums of this batch: pred, target [B, X, Y, Z, T, C] fp32 contiguous on the GPU, acc from
+    eval3_acc_alloc for the same (X, Y, Z, T, C).  Three launches on the current stream, no synchronisation; capturable once
+    the field size and the batch size have been seen (their tables and workspace are cached)."""
+    _req(pred, "eval3_metrics: pred")
+    _req(target, "eval3_metrics: target")
+    if pred.dim() != 6 or pred.shape != target.shape or pred.device != target.device:
+        raise _lib.DpotHipError(f"eval3_metrics: pred and target must be [B, X, Y, Z, T, C] of one shape on one device, got "
+                                f"{tuple(pred.shape)} on {pred.device} and {tuple(target.shape)} on {target.device}")
+    B, nx, ny, nz, T, C = pred.shape
+    if min(B, T, C) < 1 or min(nx, ny, nz) < 2:
+        raise _lib.DpotHipError(f"eval3_metrics: cannot evaluate {tuple(pred.shape)}: every spatial size must be >= 2 and no "
+                                "dimension empty")
+    if (not acc.is_cuda or acc.device != pred.device or acc.dtype != torch.int64 or not acc.is_contiguous()
+            or acc.numel() != eval3_acc_layout(nx, ny, nz, T, C)[1]):
+        raise _lib.DpotHipError(f"eval3_metrics: acc must be the {eval3_acc_layout(nx, ny, nz, T, C)[1]} int64 words of "
+                                f"eval3_acc_alloc({nx}, {ny}, {nz}, {T}, {C}) on {pred.device}")
+    plan = eval3_plan(nx, ny, nz, pred.device)
+    statp, specp, G = plan.workspace(B, T * C, pred.device)
+    d, lib = plan.dev, _lib.load()
+    check(lib.dpot_eval3_stats(pred.data_ptr(), target.data_ptr(), d["cxT"].data_ptr(), d["sxT"].data_ptr(),
+                               d["cy"].data_ptr(), d["sy"].data_ptr(), d["czT"].data_ptr(), d["szT"].data_ptr(),
+                               d["jlo"].data_ptr(), statp.data_ptr(), specp.data_ptr(), G.data_ptr(), B, nx, ny, nz, T * C,
+                               _stream()), "eval3_stats")
+    check(lib.dpot_eval3_finalize(statp.data_ptr(), specp.data_ptr(), acc.data_ptr(), B, nx, ny, nz, T, C, _stream()),
+          "eval3_finalize")

@@ -878,6 +878,43 @@ int dpot_eval_metrics_stats(const float* pred, const float* target, const float*
 int dpot_eval_metrics_finalize(const double* statp, const float* specp, double* acc, int B, int nx, int ny, int T, int C,
                                dpot_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Rollout evaluation metrics of 3-D fields (csrc/evalmetrics3d.hip): per channel c the reference's Evaluator(temporal=True,
+ * griddata=True, component=c) (utils/criterion.py:189-239, the 3-D branch of compute_fourier_error :295-340) for pred,
+ * target [B, nx, ny, nz, T, C], accumulated over batches on the device.  Three launches per batch:
+ *   dpot_eval3_stats     (two launches) e = pred - target is formed in fp32 before the transform.  The z pass contracts z for
+ *     the wavenumbers 0 <= k < nz/2 into the half spectrum G [B][TC][nz/2][cos|sin][nx ny] (fp32 workspace) and takes the
+ *     pointwise statistics on the way; the xy pass transforms every complex plane of G over the positive quadrant
+ *     0 <= i < nx/2, 0 <= j < ny/2 through LDS and sums |DFT3(e)|^2 over the shells floor(sqrt(i^2 + j^2 + k^2)) < K =
+ *     min(nx/2, ny/2, nz/2).  All three passes are dense fp32 MFMA products.
+ *       statp [B][TC][parts][8] doubles {sum|e|, sum|t|, sum e^2, sum t^2, max|e|, max|t|, sum of e^2 over the six faces
+ *             x = 0, nx-1; y = 0, ny-1; z = 0, nz-1 (an edge twice, a corner three times), unused};
+ *       specp [B][TC][nz/2][ns][K] floats, ns = pad(nx, 1) / 16;  G as above.  dpot_eval3_work_elems(which = 0 | 1 | 2, ...)
+ *       gives the element counts of statp | specp | G (0 for sizes that are not supported).
+ *       cxT, sxT [nxp][hxp], czT, szT [nzp][hzp]: cos / sin(2 pi i x / n), row x;  cy, sy [nyp][hyp]: row y; all ZERO-padded,
+ *       n?p = pad(n, 0), h?p = pad(n, 1), pad = dpot_eval3_pad (half = 0: n rounded up to 16; half = 1: n / 2 rounded up to 16).
+ *       jlo [nz/2][nx/2][K + 1] int32: jlo[k][i][s] = number of j in [0, ny/2) with floor(sqrt(i^2 + j^2 + k^2)) < s (row
+ *       (k, i) of shell s is the j range jlo[k][i][s] .. jlo[k][i][s+1]).
+ *   dpot_eval3_finalize  acc += this batch.  acc: dpot_eval3_acc_elems(nx, ny, nz, T, C) 8-byte words, zeroed by the caller,
+ *     the layout of dpot_eval_metrics_finalize: [0] int64 number of samples, [1] reserved, then doubles, each a sum over the
+ *     samples: nmae | nmse | nmxe [3][C] (ratios over all of X*Y*Z*T), nmae_t | nmse_t | nmxe_t | bd [4][T][C] (ratios over
+ *     X*Y*Z; bd = sqrt(face sum / (2 nx ny + 2 ny nz + 2 nz nx))), shell sums [T][C][K].  A zero target norm divides as IEEE
+ *     does (inf / NaN), as the reference.
+ * Sizes: nx, ny, nz >= 2, any parity; n <= dpot_eval3_max_size(axis) on axis 0, 1, 2 (512 each; on axis 1 that is the LDS
+ * intermediate of a workgroup, checked on the host) - beyond: DPOT_EUNSUP, nothing is launched.  B * TC <= 65535.  Any
+ * TC >= 1 (16-byte loads when TC % 4 == 0 and both fields are 16-byte aligned).  Reads nothing outside the tensors; every
+ * element of statp (but the unused slot), specp and G that a later launch reads is written; fixed reduction order, no
+ * atomics, no allocation, legal under stream capture. */
+int dpot_eval3_pad(int n, int half);
+int dpot_eval3_max_size(int axis);
+int64_t dpot_eval3_acc_elems(int nx, int ny, int nz, int T, int C);
+int64_t dpot_eval3_work_elems(int which, int B, int nx, int ny, int nz, int TC);
+int dpot_eval3_stats(const float* pred, const float* target, const float* cxT, const float* sxT, const float* cy,
+                     const float* sy, const float* czT, const float* szT, const int32_t* jlo, double* statp, float* specp,
+                     float* G, int B, int nx, int ny, int nz, int TC, dpot_stream_t stream);
+int dpot_eval3_finalize(const double* statp, const float* specp, double* acc, int B, int nx, int ny, int nz, int T, int C,
+                        dpot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
