@@ -233,17 +233,23 @@ SIGNATURES = {
     "dpot_tn_split_range": (c_i, [c_i] * 3 + [C.POINTER(c_i)] * 2),
     "dpot_mlp_wgrad_batch_splitk": (c_i, [c_i] * 4),
     "dpot_mlp_wgrad_batch_ws_elems": (c_i64, [c_i] * 4),
-    "dpot_mlp_wgrad_batch": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i] * 4 + [c_fp, c_i, c_fp]),
+    "dpot_tn_chain_count": (c_i, [c_i] * 2),
+    "dpot_tn_chain_nodes": (c_i, [c_i] * 3 + [C.POINTER(c_i)] * 2),
+    "dpot_mlp_wgrad_batch_chain": (c_i, [c_i] * 4),
+    "dpot_afno_wgrad_batch_chain": (c_i, [c_i] * 4),
+    "dpot_mlp_wgrad_chain_ws_elems": (c_i64, [c_i] * 4),
+    "dpot_afno_wgrad_chain_ws_elems": (c_i64, [c_i] * 5),
+    "dpot_mlp_wgrad_batch": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i] * 4 + [c_fp, c_i, c_i, c_fp]),
     "dpot_afno_wgrad_batch_plan": (c_i, [c_i] * 4 + [C.POINTER(c_i)] * 2),
     "dpot_afno_wgrad_batch_ws_elems": (c_i64, [c_i] * 4),
-    "dpot_afno_wgrad_batch": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i] * 5 + [c_fp] + [c_i] * 3 + [c_fp]),
-    "dpot_wgrad_batch_finalize": (c_i, [C.POINTER(WgradBlock)] + [c_i] * 11 + [c_fp]),
+    "dpot_afno_wgrad_batch": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i] * 5 + [c_fp] + [c_i] * 4 + [c_fp]),
+    "dpot_wgrad_batch_finalize": (c_i, [C.POINTER(WgradBlock)] + [c_i] * 13 + [c_fp]),
     "dpot_wgrad_lane_init": (c_i, []),
     "dpot_wgrad_lane_ready": (c_i, []),
     "dpot_wgrad_lane_pending": (c_i, []),
     "dpot_wgrad_lane_shutdown": (c_i, []),
     "dpot_wgrad_flush_async": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i] * 4 + [c_fp, c_i] + [C.POINTER(C.c_void_p)] * 4
-                               + [c_i] * 4 + [c_fp] + [c_i] * 3 + [C.POINTER(WgradBlock)] + [c_i] * 3 + [c_fp]),
+                               + [c_i] * 4 + [c_fp] + [c_i] * 3 + [C.POINTER(WgradBlock)] + [c_i] * 5 + [c_fp]),
     "dpot_wgrad_wait": (c_i, [c_fp]),
     "dpot_bf16_pack_both_supported": (c_i, [c_i, c_i]),
     "dpot_bf16_pack_both": (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),

@@ -50,7 +50,10 @@ int tune(const char* key, int dflt) {
  * 268: dpot_wgrad_flush_async, dpot_wgrad_wait, dpot_wgrad_lane_* (csrc/gemm_tn.hip): the batched weight gradients on a
  * library-owned stream beside the caller's
  * 269: dpot_patchify3, dpot_unpatchify3, dpot_fold3 (csrc/patch3d.hip): the index rearrangements at the two ends of DPOTNet3D
- * 270: dpot_eval3_stats, dpot_eval3_finalize and their queries (csrc/evalmetrics3d.hip): the evaluation metrics of 3-D rollouts */
-extern "C" int dpot_version(void) { return 270; }
+ * 270: dpot_eval3_stats, dpot_eval3_finalize and their queries (csrc/evalmetrics3d.hip): the evaluation metrics of 3-D rollouts
+ * 271: mlp_chain / afno_chain on dpot_mlp_wgrad_batch, dpot_afno_wgrad_batch, dpot_wgrad_batch_finalize, dpot_wgrad_flush_async;
+ * dpot_tn_chain_count, dpot_tn_chain_nodes, dpot_*_wgrad_batch_chain, dpot_*_wgrad_chain_ws_elems (csrc/gemm_tn.hip): chained
+ * token ranges in the batched weight gradients */
+extern "C" int dpot_version(void) { return 271; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

@@ -67,8 +67,35 @@ struct TnArgs {
   // token range, tile): one operand set per XCD at DPOT-Tiny (its operands cross into that L2 once), workgroups that share a
   // token range next to each other
   int raster, nwg;
+  // chained launches (gemm_tn_chain_kernel): a workgroup owns a NODE of tn_sum_nodes' tree - 1, 2 or 4 consecutive token ranges
+  // (tn_chain_node) - and stores ONE partial for it; nodes / nodes12 = tn_chain_count(splits / splits12, chain) replace splits /
+  // splits12 in the grid and in the workspace layout, the ranges themselves stay those of slabs_per_split / slabs_per_split12
+  int nodes, nodes12;
   TnSet sets[TN_MAXSETS];
 };
+
+// The nodes of a chain c in {1, 2, 4} over `splits` token ranges: complete subtrees of the tree tn_sum_nodes evaluates - per
+// full group of eight ranges 8 / c nodes of c ranges, the ranges behind the last full group in pairs, a last odd one alone
+__host__ __device__ inline int tn_chain_count(int splits, int chain) {
+  if (chain <= 1) return splits;
+  return (splits >> 3) * (8 / chain) + ((splits & 7) + 1) / 2;
+}
+// workspace slots of a three-product launch: its tiles P1 / P2 have tn_chain_count(splits12) nodes, the sum product
+// tn_chain_count(splits).  At chain 4 the count is NOT monotone in the ranges (quads exist only inside full groups of eight:
+// 6 ranges are three pairs, 8 ranges two quads), so splits12 <= splits does not make the first the smaller: the layout -
+// slot stride, the column sums behind the last slot - goes by the larger of the two
+__host__ __device__ inline int tn_chain_slots(int splits12, int splits, int chain) {
+  const int a = tn_chain_count(splits12, chain), b = tn_chain_count(splits, chain);
+  return a > b ? a : b;
+}
+__host__ __device__ inline void tn_chain_node(int splits, int chain, int i, int* first, int* n) {
+  if (chain <= 1) { *first = i; *n = 1; return; }
+  const int full = (splits >> 3) * (8 / chain);        // nodes inside the full groups of eight
+  if (i < full) { *first = i * chain; *n = chain; return; }
+  const int f = 8 * (splits >> 3) + 2 * (i - full);
+  *first = f;
+  *n = splits - f < 2 ? splits - f : 2;
+}
 
 constexpr int TN_TOK = 32;                 // tokens per slab
 constexpr int TN_W = 128;                  // tile width (both operands)
@@ -86,26 +113,35 @@ __device__ __forceinline__ void tn_glds16(const float* g, float* l) {
                                    (__attribute__((address_space(3))) void*)l, 16, 0, 0);
 }
 
-__global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
+// CHAIN = 1: a workgroup owns one token range.  CHAIN = 2 / 4 (the batched launches): it owns a node of up to CHAIN consecutive
+// ranges (tn_chain_node).  The loader waves stream the node's slabs as one run; the compute waves accumulate every range from
+// 0.0f exactly as its own workgroup would, and at a range boundary fold `acc` into a hold tile in the association of
+// tn_sum_nodes' tree: (r0 + r1) for a pair, (r0 + r1) + (r2 + r3) for a quad - plain fp32 adds, the roundings the finalising
+// launch performs on the partials of CHAIN = 1.  A quad would need three live tiles (acc, r2, r0 + r1: 146 + 128 VGPRs, over
+// the 256 two waves on a SIMD can have): its first pair sum is parked in the node's own workspace slot - each lane reads back
+// what it stored itself - and added when r2 + r3 is complete.  zs is the node index then, the workspace is [node][batch]...
+template <int CHAIN>
+__device__ __forceinline__ void tn_body(const TnArgs& p) {
   __shared__ __attribute__((aligned(16))) float lds[TN_RING * TN_SLABF];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
   const int ntiles = p.tiles1 * p.tiles2;
+  const int ns = CHAIN == 1 ? p.splits : p.nodes, ns12 = CHAIN == 1 ? p.splits12 : p.nodes12;   // slots per tile
   int tile, zbg, zs;                                    // zbg: problem index over the whole launch
   if (p.raster) {
     const int bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3;
     const int q = p.nwg >> 3, r = p.nwg & 7;
     const int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
     if (p.gauss) {
-      const int W = 2 * p.splits12 + p.splits;
+      const int W = 2 * ns12 + ns;
       zbg = w / W;
       const int rr = w - zbg * W;
-      tile = rr < p.splits12 ? 0 : rr < 2 * p.splits12 ? 1 : 2;
-      zs = rr - (tile == 2 ? 2 * p.splits12 : tile * p.splits12);
+      tile = rr < ns12 ? 0 : rr < 2 * ns12 ? 1 : 2;
+      zs = rr - (tile == 2 ? 2 * ns12 : tile * ns12);
     } else {
-      const int per = ntiles * p.splits;
+      const int per = ntiles * ns;
       zbg = w / per;
       const int rr = w - zbg * per;
       zs = rr / ntiles;
@@ -115,18 +151,18 @@ __global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
     // three-product form: a ONE-dimensional grid of exactly the workgroups that have work - per problem splits12 token ranges of
     // P1, splits12 of P2, `splits` of the sum-product tile (the hardware deals consecutive workgroups to the 8 XCDs in turn: a grid
     // with idle members leaves some XCD with more than its 32 workgroups and the launch with a second round)
-    const int W = 2 * p.splits12 + p.splits;
+    const int W = 2 * ns12 + ns;
     const int lin = blockIdx.x;
     zbg = lin / W;
     const int r = lin - zbg * W;
-    tile = r < p.splits12 ? 0 : r < 2 * p.splits12 ? 1 : 2;
-    zs = r - (tile == 2 ? 2 * p.splits12 : tile * p.splits12);
+    tile = r < ns12 ? 0 : r < 2 * ns12 ? 1 : 2;
+    zs = r - (tile == 2 ? 2 * ns12 : tile * ns12);
   } else {
     const int bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3;
     const int q = ntiles >> 3, r = ntiles & 7;
     tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    zbg = blockIdx.z / p.splits;
-    zs = blockIdx.z - zbg * p.splits;
+    zbg = blockIdx.z / ns;
+    zs = blockIdx.z - zbg * ns;
   }
   const int set = zbg / p.nper, zq = zbg - set * p.nper;
   const int grp = zbg / p.batch, zb = zbg - grp * p.batch;
@@ -136,14 +172,17 @@ __global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
   if (p.gauss) t1 = t2 = (tile == 1 ? 1 : 0);
   const int nslab_all = p.T / TN_TOK;
   const int sps = p.gauss && !g3 ? p.slabs_per_split12 : p.slabs_per_split;
-  int slab0 = zs * sps;
+  int r0 = zs, nr = 1;                                  // the node's first range and its ranges
+  if constexpr (CHAIN > 1) tn_chain_node(p.gauss && !g3 ? p.splits12 : p.splits, CHAIN, zs, &r0, &nr);
+  int slab0 = r0 * sps;
   int nslab = nslab_all - slab0;
-  nslab = nslab < sps ? nslab : sps;
+  nslab = nslab < nr * sps ? nslab : nr * sps;
   if (nslab < 0) nslab = 0;
   if (g3) {                                             // 16-token slabs: twice as many over the same token range
     slab0 *= 2;
     nslab *= 2;
   }
+  const int rslab = g3 ? 2 * sps : sps;                 // slabs of this workgroup per ORIGINAL token range
 
   auto bar = [&]() __attribute__((always_inline)) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -212,6 +251,60 @@ __global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
   const int offB = TN_TOK * TN_W + kq * TN_W + wn * 64 + 4 * i16;
   constexpr int NQ = TN_TOK / 4;                        // 4-token MFMA steps per slab
 
+  // where this lane's part of the partial tile goes: element (n1 = 4*(4*kq + r) + ea, n2 = 4*i16 + eb) of the wave's 64 x 64
+  // block (three-product form: [split][batch][3 tiles][128][128])
+  float* const ws = p.gauss ? wsg + (((long long)zs * p.batch + zb) * 3 + tile) * (TN_W * TN_W)
+                            : wsg + ((long long)zs * p.batch + zb) * p.N1 * p.N2;
+  const int ldw = p.gauss ? TN_W : p.N2;
+  const int n1b = (p.gauss ? 0 : t1 * TN_W) + wm * 64, n2b = (p.gauss ? 0 : t2 * TN_W) + wn * 64 + 4 * i16;
+  // lanes with equal i16 hold the column sums over the tokens = kq (mod 4): fixed-order butterfly over kq
+  auto cs_butterfly = [&]() __attribute__((always_inline)) {
+    auto over_kq = [](float v) __attribute__((always_inline)) {
+      v += __shfl_xor(v, 16);
+      v += __shfl_xor(v, 32);
+      return v;
+    };
+    cs = tn_f32x4{over_kq(cs.x), over_kq(cs.y), over_kq(cs.z), over_kq(cs.w)};
+  };
+  // chained ranges: `fold` ends the original range k < 3 of the node when more slabs follow.  k = 0, 2: the range opens a pair,
+  // its tile moves to `hold`; k = 1: the pair (r0 + r1) of a quad is complete and is parked in the node's slot
+  tn_f32x4 hold[4][4];
+#pragma unroll
+  for (int ea = 0; ea < 4; ++ea)
+#pragma unroll
+    for (int eb = 0; eb < 4; ++eb) hold[ea][eb] = tn_f32x4{0.f, 0.f, 0.f, 0.f};
+  tn_f32x4 csh = {0.f, 0.f, 0.f, 0.f}, csp = csh;
+  int k = 0, left = rslab;
+  auto fold = [&]() __attribute__((always_inline)) {
+    if (cs_a || cs_b) cs_butterfly();
+    const bool quad_pair = CHAIN > 2 && k == 1;
+    csp = quad_pair ? csh + cs : csp;                   // (selects, not conditional stores)
+    csh = quad_pair ? csh : cs;
+    if (quad_pair) {
+#pragma unroll
+      for (int ea = 0; ea < 4; ++ea)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int n1 = n1b + 4 * (4 * kq + r) + ea;
+          *reinterpret_cast<float4*>(ws + (long long)n1 * ldw + n2b) =
+              make_float4(hold[ea][0][r] + acc[ea][0][r], hold[ea][1][r] + acc[ea][1][r], hold[ea][2][r] + acc[ea][2][r],
+                          hold[ea][3][r] + acc[ea][3][r]);
+        }
+    } else {
+#pragma unroll
+      for (int ea = 0; ea < 4; ++ea)
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) hold[ea][eb] = acc[ea][eb];
+    }
+#pragma unroll
+    for (int ea = 0; ea < 4; ++ea)
+#pragma unroll
+      for (int eb = 0; eb < 4; ++eb) acc[ea][eb] = tn_f32x4{0.f, 0.f, 0.f, 0.f};
+    cs = tn_f32x4{0.f, 0.f, 0.f, 0.f};
+    ++k;
+    left = rslab;
+  };
+
   bar();                                                // P
   if (g3) {
     // sum-product tile: slab image A [16 tok][256] | B [16 tok][256]; per 4-token step four fragment reads (Ar, Ai, Br, Bi),
@@ -246,6 +339,9 @@ __global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
             acc[ea][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ea], b[eb], acc[ea][eb], 0, 0, 0);
       }
       ring = rn;
+      if constexpr (CHAIN > 1) {
+        if (--left == 0 && g + 1 < nslab) fold();
+      }
     }
   } else {
   tn_f32x4 fa = {0.f, 0.f, 0.f, 0.f}, fb = fa;
@@ -277,41 +373,58 @@ __global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) {
           acc[ea][eb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ea], b[eb], acc[ea][eb], 0, 0, 0);
     }
     ring = rn;
+    if constexpr (CHAIN > 1) {
+      if (--left == 0 && g + 1 < nslab) fold();
+    }
   }
   }
 
-  // partial tile: element (n1 = 4*(4*kq + r) + ea, n2 = 4*i16 + eb) of the wave's 64 x 64 block
-  // (three-product form: [split][batch][3 tiles][128][128])
-  float* ws = p.gauss ? wsg + (((long long)zs * p.batch + zb) * 3 + tile) * (TN_W * TN_W)
-                      : wsg + ((long long)zs * p.batch + zb) * p.N1 * p.N2;
-  const int ldw = p.gauss ? TN_W : p.N2;
-  const int n1b = (p.gauss ? 0 : t1 * TN_W) + wm * 64, n2b = (p.gauss ? 0 : t2 * TN_W) + wn * 64 + 4 * i16;
+  // the node's last range is in acc, k ranges were folded before it: k odd - it closes a pair with `hold`; k >= 2 - the parked
+  // first pair of the quad comes back, (r0 + r1) + (r2 + r3)
+  if constexpr (CHAIN > 1) {
+    if (k & 1) {
+#pragma unroll
+      for (int ea = 0; ea < 4; ++ea)
+#pragma unroll
+        for (int eb = 0; eb < 4; ++eb) acc[ea][eb] = hold[ea][eb] + acc[ea][eb];
+    }
+  }
 #pragma unroll
   for (int ea = 0; ea < 4; ++ea)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int n1 = n1b + 4 * (4 * kq + r) + ea;
-      *reinterpret_cast<float4*>(ws + (long long)n1 * ldw + n2b) =
-          make_float4(acc[ea][0][r], acc[ea][1][r], acc[ea][2][r], acc[ea][3][r]);
+      float4* const dst = reinterpret_cast<float4*>(ws + (long long)n1 * ldw + n2b);
+      float4 o = make_float4(acc[ea][0][r], acc[ea][1][r], acc[ea][2][r], acc[ea][3][r]);
+      if constexpr (CHAIN > 2) {
+        if (k >= 2) {
+          const float4 pk = *dst;
+          o = make_float4(pk.x + o.x, pk.y + o.y, pk.z + o.z, pk.w + o.w);
+        }
+      }
+      *dst = o;
     }
   if (cs_a || cs_b) {
-    // lanes with equal i16 hold the sums over the tokens = kq (mod 4): fixed-order butterfly over kq
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float v = cs[e];
-      v += __shfl_xor(v, 16);
-      v += __shfl_xor(v, 32);
-      cs[e] = v;
+    cs_butterfly();
+    if constexpr (CHAIN > 1) {
+      if (k & 1) cs = csh + cs;
+      if (k >= 2) cs = csp + cs;
     }
     if (kq == 0) {
       const int L = p.csL ? p.csL : (cs_a ? p.N1 : p.N2);
       const int g0 = cs_a ? t1 * TN_W + wm * 64 : t2 * TN_W + wn * 64;
       const long long prod = p.gauss ? 3ll * TN_W * TN_W : (long long)p.N1 * p.N2;
-      float* wc = wsg + (long long)p.splits * p.batch * prod + ((long long)zs * p.batch + zb) * L + g0 + 4 * i16;
+      const int nslot = ns12 > ns ? ns12 : ns;          // = splits unchained (splits12 <= splits); tn_chain_slots chained
+      float* wc = wsg + (long long)nslot * p.batch * prod + ((long long)zs * p.batch + zb) * L + g0 + 4 * i16;
       *reinterpret_cast<float4*>(wc) = make_float4(cs[0], cs[1], cs[2], cs[3]);
     }
   }
 }
+
+__global__ __launch_bounds__(384) void gemm_tn_kernel(const TnArgs p) { tn_body<1>(p); }
+// the chained forms (dpot_mlp_wgrad_batch / dpot_afno_wgrad_batch at a chain of 2 or 4)
+template <int CHAIN>
+__global__ __launch_bounds__(384) void gemm_tn_chain_kernel(const TnArgs p) { tn_body<CHAIN>(p); }
 
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -713,9 +826,37 @@ namespace dpot {
 // sum_s w[s * stride], s < splits: always the same association ((0+1)+(2+3))+((4+5)+(6+7)) per group of eight, groups in
 // order - deterministic - with eight independent loads in flight (a dependent chain of `splits` L2 round trips made the
 // reduce kernels latency bound: 16 MB in 12 us)
-__device__ __forceinline__ float tn_sum_splits(const float* __restrict__ w, long long stride, int splits) {
+//
+// chain = 2 / 4: the workspace holds one partial per NODE (tn_chain_node: the kernel has already formed the pairs / quads of
+// this very tree, with the same fp32 adds), slot j = node j; what is left of the tree is evaluated here - every rounding is the
+// one chain = 1 performs
+__device__ __forceinline__ float tn_sum_nodes(const float* __restrict__ w, long long stride, int splits, int chain) {
   float v = 0.f;
   int s = 0;
+  if (chain > 1) {
+    int j = 0;
+    if (chain == 2) {
+      for (; s + 8 <= splits; s += 8, j += 4) {
+        const float a0 = w[(long long)(j + 0) * stride], a1 = w[(long long)(j + 1) * stride];
+        const float a2 = w[(long long)(j + 2) * stride], a3 = w[(long long)(j + 3) * stride];
+        v += (a0 + a1) + (a2 + a3);
+      }
+    } else {
+      for (; s + 8 <= splits; s += 8, j += 2) {
+        const float a0 = w[(long long)(j + 0) * stride], a1 = w[(long long)(j + 1) * stride];
+        v += a0 + a1;
+      }
+    }
+    // the tail's pairs and a last odd range: at most four slots, loaded before the first add (independent loads in flight)
+    const int nt = (splits - s + 1) >> 1;
+    const float t0 = nt > 0 ? w[(long long)(j + 0) * stride] : 0.f, t1 = nt > 1 ? w[(long long)(j + 1) * stride] : 0.f;
+    const float t2 = nt > 2 ? w[(long long)(j + 2) * stride] : 0.f, t3 = nt > 3 ? w[(long long)(j + 3) * stride] : 0.f;
+    if (nt > 0) v += t0;
+    if (nt > 1) v += t1;
+    if (nt > 2) v += t2;
+    if (nt > 3) v += t3;
+    return v;
+  }
   for (; s + 8 <= splits; s += 8) {
     const float a0 = w[(long long)(s + 0) * stride], a1 = w[(long long)(s + 1) * stride];
     const float a2 = w[(long long)(s + 2) * stride], a3 = w[(long long)(s + 3) * stride];
@@ -735,7 +876,8 @@ __device__ __forceinline__ float tn_sum_splits(const float* __restrict__ w, long
 // blockIdx.x / gridDim.x, block_finalize_kernel a slice of its grid)
 __device__ __forceinline__ void afno_wgrad2_reduce_body(int bid, int nblk, const float* __restrict__ ws, int splits, int nb,
                                                         int bs, float* __restrict__ dw1, float* __restrict__ db1,
-                                                        float* __restrict__ dw2, float* __restrict__ db2, int gauss) {
+                                                        float* __restrict__ dw2, float* __restrict__ db2, int gauss,
+                                                        int chain) {
   const int n2 = 2 * bs;
   const long long MN = gauss ? 3ll * bs * bs : (long long)n2 * n2, total = MN * 2 * nb;
   const long long nw = (long long)nb * bs * bs;
@@ -748,24 +890,24 @@ __device__ __forceinline__ void afno_wgrad2_reduce_body(int bid, int nblk, const
     if (gauss) {     // P1 = Ar^T Br, P2 = Ai^T Bi, P3 = (Ar + Ai)^T (Bi - Br): dWr = P1 + P2, dWi = P3 + P1 - P2
       // (gauss = the number of token ranges of P1 / P2 and of the column sums, TnArgs::splits12 - <= splits)
       const long long e = (long long)i * bs + o, t = (long long)bs * bs;
-      const float p1 = tn_sum_splits(base + e, total, gauss);
-      const float p2 = tn_sum_splits(base + t + e, total, gauss);
-      const float p3 = tn_sum_splits(base + 2 * t + e, total, splits);
+      const float p1 = tn_sum_nodes(base + e, total, gauss, chain);
+      const float p2 = tn_sum_nodes(base + t + e, total, gauss, chain);
+      const float p3 = tn_sum_nodes(base + 2 * t + e, total, splits, chain);
       dw[q] = p1 + p2;
       dw[nw + q] = p3 + p1 - p2;
       continue;
     }
-    const float rr = tn_sum_splits(base + (long long)i * n2 + o, total, splits);
-    const float ii = tn_sum_splits(base + (long long)(bs + i) * n2 + bs + o, total, splits);
-    const float ri = tn_sum_splits(base + (long long)i * n2 + bs + o, total, splits);
-    const float ir = tn_sum_splits(base + (long long)(bs + i) * n2 + o, total, splits);
+    const float rr = tn_sum_nodes(base + (long long)i * n2 + o, total, splits, chain);
+    const float ii = tn_sum_nodes(base + (long long)(bs + i) * n2 + bs + o, total, splits, chain);
+    const float ri = tn_sum_nodes(base + (long long)i * n2 + bs + o, total, splits, chain);
+    const float ir = tn_sum_nodes(base + (long long)(bs + i) * n2 + o, total, splits, chain);
     dw[q] = rr + ii;
     dw[nw + q] = ri - ir;
   }
-  const float* wc = ws + (long long)splits * total;
+  const float* wc = ws + (long long)tn_chain_slots(gauss ? gauss : splits, splits, chain) * total;
   const long long nc = (long long)2 * nb * n2;
   for (long long idx = bid * 256ll + threadIdx.x; idx < nc; idx += (long long)nblk * 256) {
-    const float v = tn_sum_splits(wc + idx, nc, gauss ? gauss : splits);
+    const float v = tn_sum_nodes(wc + idx, nc, gauss ? gauss : splits, chain);
     const int layer = idx >= (long long)nb * n2;
     const long long q = idx - (long long)layer * nb * n2;
     const int c = (int)(q % bs), part = (int)((q / bs) & 1), k = (int)(q / n2);
@@ -775,7 +917,7 @@ __device__ __forceinline__ void afno_wgrad2_reduce_body(int bid, int nblk, const
 __global__ __launch_bounds__(256) void afno_wgrad2_reduce_kernel(const float* __restrict__ ws, int splits, int nb, int bs,
                                                                  float* __restrict__ dw1, float* __restrict__ db1,
                                                                  float* __restrict__ dw2, float* __restrict__ db2, int gauss) {
-  afno_wgrad2_reduce_body(blockIdx.x, gridDim.x, ws, splits, nb, bs, dw1, db1, dw2, db2, gauss);
+  afno_wgrad2_reduce_body(blockIdx.x, gridDim.x, ws, splits, nb, bs, dw1, db1, dw2, db2, gauss, 1);
 }
 
 // three-product form of the AFNO weight gradient (TnArgs::gauss): 128 channels per block, and 96 (DPOT-Large): gemm_tn96g_kernel;
@@ -888,7 +1030,7 @@ extern "C" int dpot_afno_wgrad2(const float* S, const float* dO1pre, const float
 namespace dpot {
 __device__ __forceinline__ void mlp_wgrad2_reduce_body(int bid, int nblk, const float* __restrict__ ws, int splits, int E,
                                                        int mh, float* __restrict__ dW2, float* __restrict__ dW1,
-                                                       float* __restrict__ db2, float* __restrict__ db1) {
+                                                       float* __restrict__ db2, float* __restrict__ db1, int chain) {
   __shared__ float tile[32][33];
   const long long MN = (long long)E * mh, total = 2 * MN;
   const int L = E > mh ? E : mh;
@@ -901,7 +1043,7 @@ __device__ __forceinline__ void mlp_wgrad2_reduce_body(int bid, int nblk, const 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int r = r0 + ty + 8 * q;
-      const float v = tn_sum_splits(ws + (long long)prob * MN + (long long)r * mh + c0 + tx, total, splits);
+      const float v = tn_sum_nodes(ws + (long long)prob * MN + (long long)r * mh + c0 + tx, total, splits, chain);
       if (prob == 0) dW2[(long long)r * mh + c0 + tx] = v;
       else tile[ty + 8 * q][tx] = v;
     }
@@ -915,16 +1057,16 @@ __device__ __forceinline__ void mlp_wgrad2_reduce_body(int bid, int nblk, const 
       __syncthreads();
     }
   }
-  const float* wc = ws + (long long)splits * total;
+  const float* wc = ws + (long long)tn_chain_count(splits, chain) * total;
   for (int idx = bid * 256 + threadIdx.x; idx < E + mh; idx += nblk * 256) {
     const int prob = idx >= E, g = idx - prob * E;
-    (prob ? db1 : db2)[g] = tn_sum_splits(wc + (long long)prob * L + g, 2ll * L, splits);
+    (prob ? db1 : db2)[g] = tn_sum_nodes(wc + (long long)prob * L + g, 2ll * L, splits, chain);
   }
 }
 __global__ __launch_bounds__(256) void mlp_wgrad2_reduce_kernel(const float* __restrict__ ws, int splits, int E, int mh,
                                                                 float* __restrict__ dW2, float* __restrict__ dW1,
                                                                 float* __restrict__ db2, float* __restrict__ db1) {
-  mlp_wgrad2_reduce_body(blockIdx.x, gridDim.x, ws, splits, E, mh, dW2, dW1, db2, db1);
+  mlp_wgrad2_reduce_body(blockIdx.x, gridDim.x, ws, splits, E, mh, dW2, dW1, db2, db1, 1);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1007,9 +1149,9 @@ __device__ __forceinline__ void gn_param_grad_body(int bx, const float* __restri
 __global__ __launch_bounds__(256) void block_finalize_kernel(const FinalizeArgs a) {
   const int b = blockIdx.x;
   if (b < a.nA) {
-    afno_wgrad2_reduce_body(b, a.nA, a.a_ws, a.a_splits, a.a_nb, a.a_bs, a.a_dw1, a.a_db1, a.a_dw2, a.a_db2, a.a_gauss);
+    afno_wgrad2_reduce_body(b, a.nA, a.a_ws, a.a_splits, a.a_nb, a.a_bs, a.a_dw1, a.a_db1, a.a_dw2, a.a_db2, a.a_gauss, 1);
   } else if (b < a.nA + a.nM) {
-    mlp_wgrad2_reduce_body(b - a.nA, a.nM, a.m_ws, a.m_splits, a.m_E, a.m_mh, a.m_dW2, a.m_dW1, a.m_db2, a.m_db1);
+    mlp_wgrad2_reduce_body(b - a.nA, a.nM, a.m_ws, a.m_splits, a.m_E, a.m_mh, a.m_dW2, a.m_dW1, a.m_db2, a.m_db1, 1);
   } else if (b < a.nA + a.nM + a.nG) {
     const int g = b - a.nA - a.nM, per = (a.g_E + 63) / 64;
     const int job = g / per;
@@ -1164,8 +1306,8 @@ static int afno_batch_splits(int nslab, int nb, int bs, int per, int* s12_out) {
 
 struct WgradFinalizeArgs {
   dpot_wgrad_block blk[WB_MAXBLK];                    // 128 bytes each
-  int a_splits, a_nb, a_bs, a_gauss, nA;              // slice A of every block: afno_wgrad2_reduce_body
-  int m_splits, m_E, m_mh, nM;                        // slice M: mlp_wgrad2_reduce_body
+  int a_splits, a_nb, a_bs, a_gauss, a_chain, nA;             // slice A of every block: afno_wgrad2_reduce_body
+  int m_splits, m_E, m_mh, m_chain, nM;                       // slice M: mlp_wgrad2_reduce_body
   int g_jobs, g_B, g_E, nG;                           // slice G: gn_param_grad_body
 };
 // grid = blocks x (nA + nM + nG) workgroups, block-major: the slices of block_finalize_kernel, once per DPOT block
@@ -1174,9 +1316,9 @@ __global__ __launch_bounds__(256) void wgrad_batch_finalize_kernel(const WgradFi
   const int k = blockIdx.x / per, b = blockIdx.x - k * per;
   const dpot_wgrad_block& w = a.blk[k];
   if (b < a.nA) {
-    afno_wgrad2_reduce_body(b, a.nA, w.afno_ws, a.a_splits, a.a_nb, a.a_bs, w.dw1, w.db1, w.dw2, w.db2, a.a_gauss);
+    afno_wgrad2_reduce_body(b, a.nA, w.afno_ws, a.a_splits, a.a_nb, a.a_bs, w.dw1, w.db1, w.dw2, w.db2, a.a_gauss, a.a_chain);
   } else if (b < a.nA + a.nM) {
-    mlp_wgrad2_reduce_body(b - a.nA, a.nM, w.mlp_ws, a.m_splits, a.m_E, a.m_mh, w.dW2, w.dW1, w.dfb2, w.dfb1);
+    mlp_wgrad2_reduce_body(b - a.nA, a.nM, w.mlp_ws, a.m_splits, a.m_E, a.m_mh, w.dW2, w.dW1, w.dfb2, w.dfb1, a.m_chain);
   } else {
     const int g = b - a.nA - a.nM, pj = (a.g_E + 63) / 64;
     const int job = g / pj;
@@ -1216,9 +1358,66 @@ extern "C" int64_t dpot_mlp_wgrad_batch_ws_elems(int E, int mh, int splitk, int 
   return (int64_t)n * dpot_mlp_wgrad2_ws_elems(E, mh, splitk);
 }
 
+// ---- chained token ranges ----------------------------------------------------------------------------------------------------
+// At the per-block split factors the batched launches run several rounds of short workgroups and move ~130 MB of partials per
+// DPOT-Tiny step through HBM, only for the finalising launch to add them again in tn_sum_nodes' tree.  A chain c in {2, 4} lets
+// ONE workgroup walk the ranges of a node of that tree and add them in registers in the tree's association: the same bits, 1/c
+// of the partials and workgroups.  Node j of a tile takes slot j of the workspace (tn_chain_count slots instead of `splits`).
+static bool tn_chain_ok(int chain) { return chain == 1 || chain == 2 || chain == 4; }
+
+extern "C" int dpot_tn_chain_count(int splits, int chain) {
+  if (splits < 1 || !tn_chain_ok(chain)) return 0;
+  return tn_chain_count(splits, chain);
+}
+
+extern "C" int dpot_tn_chain_nodes(int splits, int chain, int i, int* first_range, int* nranges) {
+  DPOT_REQUIRE(splits >= 1 && tn_chain_ok(chain) && first_range && nranges && i >= 0 && i < tn_chain_count(splits, chain),
+               "tn_chain_nodes: bad arguments");
+  tn_chain_node(splits, chain, i, first_range, nranges);
+  return DPOT_OK;
+}
+
+// the largest chain that still leaves one full round of 256 workgroups: the fastest for the launch ALONE.  The model does not
+// chain by default - beside the embed backward every chain setting costs the step 20 - 40 us (profiles/wgrad_chain_ab.txt)
+extern "C" int dpot_mlp_wgrad_batch_chain(int E, int mh, int splitk, int n) {
+  if (n < 1 || splitk < 1 || E <= 0 || mh <= 0 || E % TN_W || mh % TN_W) return 1;
+  const long long tiles = 2ll * wb_per_launch(n) * (E / TN_W) * (mh / TN_W);
+  for (int c = 4; c > 1; c >>= 1)
+    if (tiles * tn_chain_count(splitk, c) >= 256) return c;
+  return 1;
+}
+// (three-product form; `per_launch` blocks per launch.)  Capped at TN_AFNO_CHAIN_MAX: measured at DPOT-Tiny, 2 - 512 equal
+// workgroups - 158 us, as unchained; 4 - 320 workgroups of 4, 4, 2 (, 2) ranges - 201 us (profiles/wgrad_chain_ab.txt)
+constexpr int TN_AFNO_CHAIN_MAX = 2;
+extern "C" int dpot_afno_wgrad_batch_chain(int nb, int per_launch, int splits12, int splitk) {
+  if (nb < 1 || per_launch < 1 || splits12 < 1 || splitk < splits12) return 1;
+  const long long P = 2ll * per_launch * nb;
+  for (int c = TN_AFNO_CHAIN_MAX; c > 1; c >>= 1)
+    if (P * (2 * tn_chain_count(splits12, c) + tn_chain_count(splitk, c)) >= 256) return c;
+  return 1;
+}
+
+extern "C" int64_t dpot_mlp_wgrad_chain_ws_elems(int E, int mh, int splitk, int mlp_chain) {
+  return dpot_mlp_wgrad2_ws_elems(E, mh, tn_chain_ok(mlp_chain) ? tn_chain_count(splitk, mlp_chain) : splitk);
+}
+// (splits12 <= 0: splitk.)  Slots by tn_chain_slots: the larger node count of the P1 / P2 tiles and the sum-product tile
+extern "C" int64_t dpot_afno_wgrad_chain_ws_elems(int nb, int bs, int splits12, int splitk, int afno_chain) {
+  if (splits12 <= 0 || splits12 > splitk) splits12 = splitk;
+  return dpot_afno_wgrad2_ws_elems(nb, bs, tn_chain_ok(afno_chain) ? tn_chain_slots(splits12, splitk, afno_chain) : splitk);
+}
+
+namespace dpot {
+static void tn_launch_chain(int chain, unsigned nwg, hipStream_t s, const TnArgs& p) {
+  if (chain == 4) hipLaunchKernelGGL(gemm_tn_chain_kernel<4>, dim3(nwg), dim3(384), 0, s, p);
+  else if (chain == 2) hipLaunchKernelGGL(gemm_tn_chain_kernel<2>, dim3(nwg), dim3(384), 0, s, p);
+  else hipLaunchKernelGGL(gemm_tn_kernel, dim3(nwg), dim3(384), 0, s, p);
+}
+}  // namespace dpot
+
 extern "C" int dpot_mlp_wgrad_batch(const float* const* do2, const float* const* Hh, const float* const* xn2,
                                     const float* const* dHpre, int n, int T, int E, int mh, float* workspace, int splitk,
-                                    dpot_stream_t stream) {
+                                    int mlp_chain, dpot_stream_t stream) {
+  DPOT_REQUIRE(tn_chain_ok(mlp_chain), "mlp_wgrad_batch: chain %d (1, 2 or 4)", mlp_chain);
   DPOT_REQUIRE(do2 && Hh && xn2 && dHpre && workspace && n >= 1, "mlp_wgrad_batch: null pointer");
   DPOT_REQUIRE(mlp_batch_shape_ok(T, E, mh), "mlp_wgrad_batch: needs E, mh %% 128 == 0, T %% 32 == 0");
   const int nslab = T / TN_TOK;
@@ -1226,7 +1425,7 @@ extern "C" int dpot_mlp_wgrad_batch(const float* const* do2, const float* const*
                "mlp_wgrad_batch: split factor %d leaves an empty token range (%d slabs)", splitk, nslab);
   DPOT_REQUIRE(aligned16(workspace), "mlp_wgrad_batch: workspace must be 16-byte aligned");
   const int per = wb_per_launch(n);
-  const long long wsb = dpot_mlp_wgrad2_ws_elems(E, mh, splitk);
+  const long long wsb = dpot_mlp_wgrad_chain_ws_elems(E, mh, splitk, mlp_chain);
   hipStream_t s = as_stream(stream);
   for (int b0 = 0; b0 < n; b0 += per) {
     const int nb_l = n - b0 < per ? n - b0 : per;
@@ -1248,10 +1447,11 @@ extern "C" int dpot_mlp_wgrad_batch(const float* const* do2, const float* const*
     p.ws_group = wsb;
     p.csL = E > mh ? E : mh;
     p.gauss = 0; p.splits12 = p.splits; p.slabs_per_split12 = p.slabs_per_split;
-    const long long nwg = 2ll * nb_l * p.tiles1 * p.tiles2 * splitk;
+    p.nodes = p.nodes12 = tn_chain_count(splitk, mlp_chain);
+    const long long nwg = 2ll * nb_l * p.tiles1 * p.tiles2 * p.nodes;
     DPOT_REQUIRE(nwg <= 0x7fffffff, "mlp_wgrad_batch: grid too large");
     p.raster = 1; p.nwg = (int)nwg;
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)nwg), dim3(384), 0, s, p);
+    tn_launch_chain(mlp_chain, (unsigned)nwg, s, p);
     int rc = check_launch("gemm_tn_kernel");
     if (rc) return rc;
   }
@@ -1286,8 +1486,9 @@ extern "C" int64_t dpot_afno_wgrad_batch_ws_elems(int nb, int bs, int splitk, in
 
 extern "C" int dpot_afno_wgrad_batch(const float* const* S, const float* const* dO1pre, const float* const* O1,
                                      const float* const* dO2, int n, int ld, int Mm, int nb, int bs, float* workspace,
-                                     int per_launch, int splits12, int splitk, dpot_stream_t stream) {
+                                     int per_launch, int splits12, int splitk, int afno_chain, dpot_stream_t stream) {
   DPOT_REQUIRE(S && dO1pre && O1 && dO2 && workspace && n >= 1, "afno_wgrad_batch: null pointer");
+  DPOT_REQUIRE(tn_chain_ok(afno_chain), "afno_wgrad_batch: chain %d (1, 2 or 4)", afno_chain);
   const int N = 2 * bs;
   DPOT_REQUIRE(nb > 0 && bs == TN_W && tn_gauss(bs) && Mm > 0 && Mm % TN_TOK == 0 && ld >= nb * N && ld % 4 == 0,
                "afno_wgrad_batch: needs the three-product form (bs == 128, DPOT_TUNE wgrad_gauss != 0), Mm %% 32 == 0");
@@ -1297,7 +1498,7 @@ extern "C" int dpot_afno_wgrad_batch(const float* const* S, const float* const* 
                    tn_no_empty(nslab, splits12) == splits12,
                "afno_wgrad_batch: split factors (%d, %d) leave an empty token range (%d slabs)", splits12, splitk, nslab);
   DPOT_REQUIRE(aligned16(workspace), "afno_wgrad_batch: workspace must be 16-byte aligned");
-  const long long wsb = dpot_afno_wgrad2_ws_elems(nb, bs, splitk);
+  const long long wsb = dpot_afno_wgrad_chain_ws_elems(nb, bs, splits12, splitk, afno_chain);
   hipStream_t s = as_stream(stream);
   for (int b0 = 0; b0 < n; b0 += per_launch) {
     const int nb_l = n - b0 < per_launch ? n - b0 : per_launch;
@@ -1320,10 +1521,12 @@ extern "C" int dpot_afno_wgrad_batch(const float* const* S, const float* const* 
     p.slabs_per_split12 = (nslab + splits12 - 1) / splits12;
     p.ws = workspace + (long long)b0 * wsb;
     p.ws_group = wsb;
-    const long long nwg = 2ll * nb_l * nb * (2 * splits12 + splitk);
+    p.nodes = tn_chain_count(splitk, afno_chain);
+    p.nodes12 = tn_chain_count(splits12, afno_chain);
+    const long long nwg = 2ll * nb_l * nb * (2 * p.nodes12 + p.nodes);
     DPOT_REQUIRE(nwg <= 0x7fffffff, "afno_wgrad_batch: grid too large");
     p.raster = 1; p.nwg = (int)nwg;
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3((unsigned)nwg), dim3(384), 0, s, p);
+    tn_launch_chain(afno_chain, (unsigned)nwg, s, p);
     int rc = check_launch("gemm_tn_kernel");
     if (rc) return rc;
   }
@@ -1331,20 +1534,22 @@ extern "C" int dpot_afno_wgrad_batch(const float* const* S, const float* const* 
 }
 
 extern "C" int dpot_wgrad_batch_finalize(const dpot_wgrad_block* blocks, int n, int afno_splits12, int afno_splitk, int nb,
-                                         int bs, int mlp_splitk, int E, int mh, int gn_jobs, int B, int Egn,
-                                         dpot_stream_t stream) {
+                                         int bs, int mlp_splitk, int E, int mh, int gn_jobs, int B, int Egn, int mlp_chain,
+                                         int afno_chain, dpot_stream_t stream) {
   DPOT_REQUIRE(blocks && n >= 1, "wgrad_batch_finalize: no blocks");
+  DPOT_REQUIRE(tn_chain_ok(mlp_chain) && tn_chain_ok(afno_chain), "wgrad_batch_finalize: chains (%d, %d) must be 1, 2 or 4",
+               mlp_chain, afno_chain);
   DPOT_REQUIRE(gn_jobs >= 0 && gn_jobs <= 2, "wgrad_batch_finalize: at most two GroupNorm jobs per block");
   WgradFinalizeArgs a{};
   if (afno_splitk > 0) {
     DPOT_REQUIRE(nb > 0 && bs == TN_W && afno_splits12 >= 1 && afno_splits12 <= afno_splitk, "wgrad_batch_finalize: bad AFNO slice");
-    a.a_splits = afno_splitk; a.a_nb = nb; a.a_bs = bs; a.a_gauss = afno_splits12;
+    a.a_splits = afno_splitk; a.a_nb = nb; a.a_bs = bs; a.a_gauss = afno_splits12; a.a_chain = afno_chain;
     long long blocksA = (2ll * nb * bs * bs + 255) / 256;
     a.nA = (int)(blocksA > 4096 ? 4096 : blocksA);
   }
   if (mlp_splitk > 0) {
     DPOT_REQUIRE(E > 0 && mh > 0 && E % 32 == 0 && mh % 32 == 0, "wgrad_batch_finalize: bad channel-MLP slice");
-    a.m_splits = mlp_splitk; a.m_E = E; a.m_mh = mh;
+    a.m_splits = mlp_splitk; a.m_E = E; a.m_mh = mh; a.m_chain = mlp_chain;
     const long long blocksM = 2ll * (E / 32) * (mh / 32);
     a.nM = (int)(blocksM > 2048 ? 2048 : blocksM);
   }
@@ -1466,7 +1671,7 @@ extern "C" int dpot_wgrad_flush_async(const float* const* do2, const float* cons
                                       const float* const* S, const float* const* dO1pre, const float* const* O1,
                                       const float* const* dO2, int ld, int Mm, int nb, int bs, float* afno_ws, int per_launch,
                                       int afno_splits12, int afno_splitk, const dpot_wgrad_block* blocks, int gn_jobs, int B,
-                                      int Egn, dpot_stream_t stream) {
+                                      int Egn, int mlp_chain, int afno_chain, dpot_stream_t stream) {
   std::lock_guard<std::mutex> lock(g_lane_mutex);
   hipStream_t caller = as_stream(stream);
   const bool capturing = stream_capturing(caller);
@@ -1487,9 +1692,15 @@ extern "C" int dpot_wgrad_flush_async(const float* const* do2, const float* cons
     if (rc) return rc;
   }
   dpot_stream_t run = L ? (dpot_stream_t)L->stream : stream;
-  int rc = dpot_mlp_wgrad_batch(do2, Hh, xn2, dHpre, n, T, E, mh, mlp_ws, mlp_splitk, run);
-  if (!rc) rc = dpot_afno_wgrad_batch(S, dO1pre, O1, dO2, n, ld, Mm, nb, bs, afno_ws, per_launch, afno_splits12, afno_splitk, run);
-  if (!rc) rc = dpot_wgrad_batch_finalize(blocks, n, afno_splits12, afno_splitk, nb, bs, mlp_splitk, E, mh, gn_jobs, B, Egn, run);
+  // The AFNO launch goes FIRST.  The embed backward beside the lane opens with its two MFMA-bound fold GEMMs (768 and 528
+  // workgroups) and goes on with short latency-bound launches.  Beside the channel-MLP launch the first fold GEMM took 124 us
+  // (38 us alone) - and 334 us beside a chained, one-round MLP launch, whose 256 workgroups hold every CU for 300 us; beside
+  // the AFNO launch (shorter workgroups, a third of them the VALU-heavy sum-product tiles) the fold GEMMs get through, and the
+  // long MLP launch then runs beside the short launches.  Independent workspaces: no result depends on the order.  DPOT-Tiny
+  // step 2.9275 -> 2.8859 ms against the parent commit (profiles/wgrad_chain_ab.txt, section 4)
+  int rc = dpot_afno_wgrad_batch(S, dO1pre, O1, dO2, n, ld, Mm, nb, bs, afno_ws, per_launch, afno_splits12, afno_splitk, afno_chain, run);
+  if (!rc) rc = dpot_mlp_wgrad_batch(do2, Hh, xn2, dHpre, n, T, E, mh, mlp_ws, mlp_splitk, mlp_chain, run);
+  if (!rc) rc = dpot_wgrad_batch_finalize(blocks, n, afno_splits12, afno_splitk, nb, bs, mlp_splitk, E, mh, gn_jobs, B, Egn, mlp_chain, afno_chain, run);
   if (L) {   // also after a failed launch: the lane has been forked and must be joined again
     const int rc2 = lane_hip(hipEventRecord(L->done, L->stream), "hipEventRecord(done)");
     if (rc2) return rc ? rc : rc2;

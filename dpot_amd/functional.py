@@ -100,7 +100,12 @@ class WgradBatch:
     By default the batched launches cut the tokens exactly as the per-block launches do (several rounds of workgroups in one
     launch): every partial and every sum is the same, the gradients are bit-identical to the per-block schedule's.
     DPOT_TUNE fused_small=3 selects the one-round rules instead (fewer, longer token ranges: less partial traffic, another
-    summation order).
+    summation order).  The default batch can CHAIN its token ranges (`chains`, `ops.wgrad_chain_scope`): a workgroup walks 2 or 4
+    consecutive ranges, restarts its accumulators at every range boundary and adds the ranges' tiles in registers in the
+    association of the finalising launch's summation tree - the one-round rules' traffic and launch shape, every rounding still
+    the per-block schedule's.  The default is NO chain: alone the three launches gain 27 us at DPOT-Tiny (490 -> 463 us), but
+    beside the embed backward the long one-round workgroups keep its launches off the CUs and the step LOSES 20 - 40 us at
+    every chain setting (profiles/wgrad_chain_ab.txt).
 
     The flush is the last thing block 0's backward does; the embed backward that follows is a chain of small launches that reads
     none of its results.  By default (DPOT_TUNE fused_small=4, `ops.wgrad_lane_scope`) the three launch sets therefore go to the
@@ -111,6 +116,7 @@ class WgradBatch:
         self.expected = self.delivered = 0
         self.jobs = []
         self.lane = ops.wgrad_lane_enabled()     # read in the forward: the flush runs on the autograd engine's thread
+        self.chain = ops.wgrad_chain_override()
 
     def register(self) -> None:
         self.expected += 1
@@ -147,6 +153,16 @@ class WgradBatch:
         return ops.mlp_wgrad2_splitk(M, E, mh, mp), min(n, ops.wgrad_batch_max_blocks()), s12, sk
 
     @staticmethod
+    def chains(splits, override=None):
+        """(mlp_chain, afno_chain) of the batch the 4-tuple `splits` describes: (1, 1) - no chain, the measured optimum of the step - or
+        the `override` of `ops.wgrad_chain_scope` for the default batch (the largest chains that leave a full round of
+        workgroups are `ops.mlp_wgrad_batch_chain` / `ops.afno_wgrad_batch_chain`); always (1, 1) under the one-round rules,
+        whose ranges are already one round long"""
+        if ops.wgrad_batch_one_round() or not all(splits) or override is None:
+            return 1, 1
+        return override
+
+    @staticmethod
     def _lane_ok(g) -> bool:
         """The flush may run beside the rest of the backward (ops.wgrad_flush_async) when nobody looks at its gradients before
         the backward ends - no gradient-ready callbacks (a data-parallel reducer, hooks) - and every sink is the ONLY outstanding
@@ -167,6 +183,7 @@ class WgradBatch:
         M, E, mh, mp, adims, _ = g[0].key
         dev = g[0].mlp[0].device
         skm, per, s12, sk = WgradBatch.splits(len(g), M, E, mh, mp, *adims)
+        cm, ca = WgradBatch.chains((skm, per, s12, sk), self.chain)
         lane = self.lane and self._lane_ok(g)
         if not lane:
             ops.wgrad_lane_join()        # nothing pending in a backward of one schedule; a mixed one adds on this stream below
@@ -178,11 +195,11 @@ class WgradBatch:
         aouts = [outs(j, _AFNO_PARAMS, ((2, nb, bs, bs), (2, nb, bs)) * 2) for j in g]
         gn = [[(part,) + outs(j, names, ((E,), (E,))) for part, names in zip(j.gn, _GN_PARAMS)] for j in g]
         if lane:
-            ops.wgrad_flush_async(mops, skm, mouts, aops, nb, bs, per, s12, sk, aouts, gn)
+            ops.wgrad_flush_async(mops, skm, mouts, aops, nb, bs, per, s12, sk, aouts, gn, cm, ca)
         else:
-            mws = ops.mlp_wgrad_batch(*mops, skm)
-            aws = ops.afno_wgrad_batch(*aops, nb, bs, per, s12, sk)
-            ops.wgrad_batch_finalize((aws, s12, sk, nb, bs, aouts), (mws, skm, E, mh, mouts), gn)
+            mws = ops.mlp_wgrad_batch(*mops, skm, cm)
+            aws = ops.afno_wgrad_batch(*aops, nb, bs, per, s12, sk, ca)
+            ops.wgrad_batch_finalize((aws, s12, sk, nb, bs, aouts), (mws, skm, E, mh, mouts), gn, cm, ca)
         for i, j in enumerate(g):
             dW2, db2, dW1, db1 = mouts[i]
             (_, dg1, db1n), (_, dg2, db2n) = gn[i]

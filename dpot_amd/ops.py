@@ -854,6 +854,54 @@ def wgrad_lane_scope(on: Optional[bool]):
         _tls.wgrad_lane = prev
 
 
+@contextlib.contextmanager
+def wgrad_chain_scope(chains):
+    """the chains (mlp_chain, afno_chain) - each 1, 2 or 4 - that the default batch of the forward passes run on this thread
+    inside gives its two launches (functional.WgradBatch reads it when DPOTNet creates it), or None = the default, no chain.
+    For tests and A/B runs in one process; the results do not depend on it."""
+    if chains is not None:
+        chains = (int(chains[0]), int(chains[1]))
+        if not all(c in (1, 2, 4) for c in chains):
+            raise ValueError(f"wgrad_chain_scope: chains {chains} must be 1, 2 or 4")
+    prev = getattr(_tls, "wgrad_chain", None)
+    _tls.wgrad_chain = chains
+    try:
+        yield
+    finally:
+        _tls.wgrad_chain = prev
+
+
+def wgrad_chain_override():
+    """(mlp_chain, afno_chain) of the enclosing `wgrad_chain_scope`, or None"""
+    return getattr(_tls, "wgrad_chain", None)
+
+
+def tn_chain_count(splits: int, chain: int) -> int:
+    """workspace slots (nodes) of `splits` token ranges chained by `chain`; 0: bad arguments"""
+    return _lib.load().dpot_tn_chain_count(splits, chain)
+
+
+def tn_chain_nodes(splits: int, chain: int):
+    """[(first range, ranges)] of every node, in dispatch order (csrc/gemm_tn.hip tn_chain_node)"""
+    lib, out = _lib.load(), []
+    f, c = C.c_int(0), C.c_int(0)
+    for i in range(lib.dpot_tn_chain_count(splits, chain)):
+        check(lib.dpot_tn_chain_nodes(splits, chain, i, C.byref(f), C.byref(c)), "tn_chain_nodes")
+        out.append((f.value, c.value))
+    return out
+
+
+def mlp_wgrad_batch_chain(E: int, mh: int, splitk: int, n: int) -> int:
+    """the largest chain of `mlp_wgrad_batch` over n blocks that leaves a full round of 256 workgroups (fastest for the launch
+    alone; not the model's default, see functional.WgradBatch)"""
+    return _lib.load().dpot_mlp_wgrad_batch_chain(E, mh, splitk, n)
+
+
+def afno_wgrad_batch_chain(nb: int, per_launch: int, splits12: int, splitk: int) -> int:
+    """the same for `afno_wgrad_batch` at `per_launch` blocks per launch, at most 2 (4 leaves unequal workgroups: slower)"""
+    return _lib.load().dpot_afno_wgrad_batch_chain(nb, per_launch, splits12, splitk)
+
+
 def wgrad_lane_enabled() -> bool:
     v = getattr(_tls, "wgrad_lane", None)
     return tune("fused_small") == 4 if v is None else bool(v)
@@ -915,16 +963,18 @@ def mlp_wgrad_batch_splitk(T: int, E: int, mh: int, n: int, precision: Optional[
     return _lib.load().dpot_mlp_wgrad_batch_splitk(T, E, mh, n) if prec == GEMM_F32 else 0
 
 
-def mlp_wgrad_batch(do2, Hh, xn2, dHpre, splitk: int) -> Tensor:
+def mlp_wgrad_batch(do2, Hh, xn2, dHpre, splitk: int, chain: int = 1) -> Tensor:
     """partials of both channel-MLP weight gradients of len(do2) blocks (lists of per-block operands, as `mlp_wgrad2`):
-    returns the workspace [n, elems] - row i in the layout `mlp_wgrad2(defer=True)` leaves, for `wgrad_batch_finalize`"""
-    n, T, E, mh, ws = _mlp_wgrad_batch_ws(do2, Hh, xn2, dHpre, splitk)
+    returns the workspace [n, elems] - row i in the layout `mlp_wgrad2(defer=True)` leaves, for `wgrad_batch_finalize`.
+    chain 2 / 4: a workgroup walks up to that many consecutive token ranges and stores one partial per node of the
+    finalising launch's summation tree (same bits; give `wgrad_batch_finalize` the same chain)"""
+    n, T, E, mh, ws = _mlp_wgrad_batch_ws(do2, Hh, xn2, dHpre, splitk, chain)
     check(_lib.load().dpot_mlp_wgrad_batch(_ptr_array(do2), _ptr_array(Hh), _ptr_array(xn2), _ptr_array(dHpre), n, T, E, mh,
-                                           ws.data_ptr(), splitk, _stream()), "mlp_wgrad_batch")
+                                           ws.data_ptr(), splitk, chain, _stream()), "mlp_wgrad_batch")
     return ws
 
 
-def _mlp_wgrad_batch_ws(do2, Hh, xn2, dHpre, splitk: int):
+def _mlp_wgrad_batch_ws(do2, Hh, xn2, dHpre, splitk: int, chain: int = 1):
     """(n, T, E, mh, workspace [n, elems]) of `mlp_wgrad_batch` after its operand checks"""
     n = len(do2)
     T, E = do2[0].shape
@@ -932,7 +982,8 @@ def _mlp_wgrad_batch_ws(do2, Hh, xn2, dHpre, splitk: int):
     for a, b, c, d in zip(do2, Hh, xn2, dHpre):
         assert a.shape == (T, E) and c.shape == (T, E) and b.shape == (T, mh) and d.shape == (T, mh)
         assert a.is_contiguous() and b.is_contiguous() and c.is_contiguous() and d.is_contiguous()
-    ws = torch.empty(n, _lib.load().dpot_mlp_wgrad2_ws_elems(E, mh, splitk), dtype=torch.float32, device=do2[0].device)
+    ws = torch.empty(n, _lib.load().dpot_mlp_wgrad_chain_ws_elems(E, mh, splitk, chain), dtype=torch.float32,
+                     device=do2[0].device)
     return n, T, E, mh, ws
 
 
@@ -946,36 +997,40 @@ def afno_wgrad_batch_plan(Mm: int, nb: int, bs: int, n: int) -> Tuple[int, int, 
     return per, s12.value, s.value
 
 
-def afno_wgrad_batch(S, dO1pre, O1, dO2, nb: int, bs: int, per_launch: int, splits12: int, splitk: int) -> Tensor:
+def afno_wgrad_batch(S, dO1pre, O1, dO2, nb: int, bs: int, per_launch: int, splits12: int, splitk: int,
+                     chain: int = 1) -> Tensor:
     """partials of both AFNO weight gradients of len(S) blocks (lists of per-block operands, as `afno_wgrad2`), `per_launch`
-    blocks per launch: returns the workspace [n, elems], row i in the layout of `afno_wgrad2(defer=True)`"""
-    n, Mm, ld, ws = _afno_wgrad_batch_ws(S, dO1pre, O1, dO2, nb, bs, splitk)
+    blocks per launch: returns the workspace [n, elems], row i in the layout of `afno_wgrad2(defer=True)`; chain: as
+    `mlp_wgrad_batch`"""
+    n, Mm, ld, ws = _afno_wgrad_batch_ws(S, dO1pre, O1, dO2, nb, bs, splitk, chain, splits12)
     check(_lib.load().dpot_afno_wgrad_batch(_ptr_array(S), _ptr_array(dO1pre), _ptr_array(O1), _ptr_array(dO2), n, ld, Mm, nb,
-                                            bs, ws.data_ptr(), per_launch, splits12, splitk, _stream()), "afno_wgrad_batch")
+                                            bs, ws.data_ptr(), per_launch, splits12, splitk, chain, _stream()), "afno_wgrad_batch")
     return ws
 
 
-def _afno_wgrad_batch_ws(S, dO1pre, O1, dO2, nb: int, bs: int, splitk: int):
+def _afno_wgrad_batch_ws(S, dO1pre, O1, dO2, nb: int, bs: int, splitk: int, chain: int = 1, splits12: int = 0):
     """(n, Mm, ld, workspace [n, elems]) of `afno_wgrad_batch` after its operand checks"""
     n = len(S)
     Mm, ld = S[0].shape
     for ts in (S, dO1pre, O1, dO2):
         for t in ts:
             assert t.shape == (Mm, ld) and t.is_contiguous()
-    ws = torch.empty(n, _lib.load().dpot_afno_wgrad2_ws_elems(nb, bs, splitk), dtype=torch.float32, device=S[0].device)
+    ws = torch.empty(n, _lib.load().dpot_afno_wgrad_chain_ws_elems(nb, bs, splits12, splitk, chain), dtype=torch.float32,
+                     device=S[0].device)
     return n, Mm, ld, ws
 
 
-def wgrad_batch_finalize(afno, mlp, gn):
-    """ONE launch that finalises n blocks (csrc/gemm_tn.hip wgrad_batch_finalize_kernel).
+def wgrad_batch_finalize(afno, mlp, gn, mlp_chain: int = 1, afno_chain: int = 1):
+    """ONE launch that finalises n blocks (csrc/gemm_tn.hip wgrad_batch_finalize_kernel); mlp_chain / afno_chain: the chains
+    the workspaces were written with.
     afno: None | (ws [n, .], splits12, splitk, nb, bs, [(dw1, db1, dw2, db2)] * n);
     mlp:  None | (ws [n, .], splitk, E, mh, [(dW2, db2, dW1, db1)] * n);
     gn:   [[(part [2, B, E], dgamma, dbeta)] * jobs] * n  (jobs <= 2, outputs allocated by the caller)"""
     blocks, n, jobs, B, Eg = _wgrad_block_table(afno, mlp, gn)
     a = afno if afno is not None else (None, 0, 0, 0, 0)
     m = mlp if mlp is not None else (None, 0, 0, 0)
-    check(_lib.load().dpot_wgrad_batch_finalize(blocks, n, a[1], a[2], a[3], a[4], m[1], m[2], m[3], jobs, B, Eg, _stream()),
-          "wgrad_batch_finalize")
+    check(_lib.load().dpot_wgrad_batch_finalize(blocks, n, a[1], a[2], a[3], a[4], m[1], m[2], m[3], jobs, B, Eg, mlp_chain,
+                                                afno_chain, _stream()), "wgrad_batch_finalize")
 
 
 def _wgrad_block_table(afno, mlp, gn):
@@ -999,20 +1054,21 @@ def _wgrad_block_table(afno, mlp, gn):
 
 
 def wgrad_flush_async(mlp_ops, skm: int, mouts, afno_ops, nb: int, bs: int, per_launch: int, splits12: int, splitk: int,
-                      aouts, gn) -> None:
+                      aouts, gn, mlp_chain: int = 1, afno_chain: int = 1) -> None:
     """`mlp_wgrad_batch`, `afno_wgrad_batch` and `wgrad_batch_finalize` of one group of blocks on the library's lane, behind
     the current stream (csrc/gemm_tn.hip dpot_wgrad_flush_async).  mlp_ops / afno_ops: the four operand lists of the two
     launches; mouts, aouts, gn: the outputs per block as `wgrad_batch_finalize` takes them.  Everything the launches touch
     stays referenced until `wgrad_lane_join` has ordered the stream behind the lane."""
-    n, T, E, mh, mws = _mlp_wgrad_batch_ws(*mlp_ops, skm)
-    _, Mm, ld, aws = _afno_wgrad_batch_ws(*afno_ops, nb, bs, splitk)
+    n, T, E, mh, mws = _mlp_wgrad_batch_ws(*mlp_ops, skm, mlp_chain)
+    _, Mm, ld, aws = _afno_wgrad_batch_ws(*afno_ops, nb, bs, splitk, afno_chain, splits12)
     blocks, _, jobs, B, Eg = _wgrad_block_table((aws, splits12, splitk, nb, bs, aouts), (mws, skm, E, mh, mouts), gn)
     stream = _stream()
     with _lane_lock:
         _lane_held.append((stream, (mlp_ops, afno_ops, aws, mws, mouts, aouts, gn)))
     check(_lib.load().dpot_wgrad_flush_async(*[_ptr_array(t) for t in mlp_ops], n, T, E, mh, mws.data_ptr(), skm,
                                              *[_ptr_array(t) for t in afno_ops], ld, Mm, nb, bs, aws.data_ptr(), per_launch,
-                                             splits12, splitk, blocks, jobs, B, Eg, stream), "wgrad_flush_async")
+                                             splits12, splitk, blocks, jobs, B, Eg, mlp_chain, afno_chain, stream),
+          "wgrad_flush_async")
 
 
 def afno_mlp2_supported(nb: int, bs: int) -> bool:

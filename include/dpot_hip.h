@@ -195,7 +195,20 @@ int dpot_block_finalize(const float* afno_ws, int afno_splitk, int nb, int bs, f
  * dpot_afno_wgrad_batch_plan: blocks per launch and the split factors (splits12 token ranges for the products P1 / P2, splits
  * for the sum product) such that sets * nb * (2 * splits12 + splits) <= 256 with splits12 : splits = 5 : 6 unless the tokens
  * limit the split; 0: not covered (bs != 128 or DPOT_TUNE wgrad_gauss=0) - use the per-block entries.
- * dpot_tn_split_range: the tokens [first_tok, first_tok + ntok) of range i when T tokens are cut into `splits` ranges. */
+ * dpot_tn_split_range: the tokens [first_tok, first_tok + ntok) of range i when T tokens are cut into `splits` ranges.
+ * CHAINED token ranges (mlp_chain / afno_chain = 2 or 4; 1: none): one workgroup walks a NODE of 1 .. chain consecutive ranges -
+ * a complete subtree of the fixed tree the finalising launch adds the partials in (per full group of eight ranges pairs or
+ * quads, behind it pairs and a last odd range) - restarts its accumulators at every range boundary, adds the ranges' tiles in
+ * registers in the tree's association and stores ONE partial per node (AFNO: slots = the larger node count of splits12 and splits - at chain 4
+ * fewer ranges can mean more nodes).  Every rounding is the one chain = 1 performs: the same
+ * bits, 1 / chain of the partials and workgroups.  The workspace is laid out by nodes (dpot_*_wgrad_chain_ws_elems per block).
+ * dpot_tn_chain_count: nodes of `splits` ranges (0: bad arguments).  dpot_tn_chain_nodes: node i = ranges [first_range,
+ * first_range + nranges), in the order the kernel dispatches them (long nodes first).  dpot_mlp_wgrad_batch_chain /
+ * dpot_afno_wgrad_batch_chain: the largest chain that leaves a launch a full round of 256 workgroups (AFNO: at most 2 - chain 4
+ * cuts (10, 12) ranges into unequal nodes, 201 against 158 us).  A launch and the finalising launch that reads its workspace
+ * must be given the same chain.  Measured at DPOT-Tiny, batch 32: alone the three launches take 490 us unchained, 463 us at
+ * chains (4, 2); beside the embed backward on the lane every chain setting makes the STEP slower (the one-round workgroups hold
+ * the CUs the embed backward's launches wait for), so the model passes chain 1 (profiles/wgrad_chain_ab.txt). */
 typedef struct dpot_wgrad_block {
   const float* afno_ws; float *dw1, *db1, *dw2, *db2;     /* as dpot_afno_wgrad2 */
   const float* mlp_ws; float *dW2, *dfb2, *dW1, *dfb1;    /* as dpot_mlp_wgrad2 */
@@ -205,24 +218,32 @@ int dpot_wgrad_batch_max_blocks(void);
 int dpot_tn_split_range(int T, int splits, int i, int* first_tok, int* ntok);
 int dpot_mlp_wgrad_batch_splitk(int T, int E, int mh, int n);
 int64_t dpot_mlp_wgrad_batch_ws_elems(int E, int mh, int splitk, int n);
+int dpot_tn_chain_count(int splits, int chain);
+int dpot_tn_chain_nodes(int splits, int chain, int i, int* first_range, int* nranges);
+int dpot_mlp_wgrad_batch_chain(int E, int mh, int splitk, int n);
+int dpot_afno_wgrad_batch_chain(int nb, int per_launch, int splits12, int splitk);
+int64_t dpot_mlp_wgrad_chain_ws_elems(int E, int mh, int splitk, int mlp_chain);
+int64_t dpot_afno_wgrad_chain_ws_elems(int nb, int bs, int splits12, int splitk, int afno_chain);
 int dpot_mlp_wgrad_batch(const float* const* do2, const float* const* Hh, const float* const* xn2, const float* const* dHpre,
-                         int n, int T, int E, int mh, float* workspace, int splitk, dpot_stream_t stream);
+                         int n, int T, int E, int mh, float* workspace, int splitk, int mlp_chain, dpot_stream_t stream);
 int dpot_afno_wgrad_batch_plan(int Mm, int nb, int bs, int n, int* splits12, int* splits);
 int64_t dpot_afno_wgrad_batch_ws_elems(int nb, int bs, int splitk, int n);
 int dpot_afno_wgrad_batch(const float* const* S, const float* const* dO1pre, const float* const* O1, const float* const* dO2,
                           int n, int ld, int Mm, int nb, int bs, float* workspace, int per_launch, int splits12, int splitk,
-                          dpot_stream_t stream);
+                          int afno_chain, dpot_stream_t stream);
 /* ONE finalising launch for n blocks: per block the slices of dpot_block_finalize (AFNO partials when afno_splitk > 0,
- * channel-MLP partials when mlp_splitk > 0, gn_jobs <= 2 GroupNorm parameter gradients), the same reduction bodies. */
+ * channel-MLP partials when mlp_splitk > 0, gn_jobs <= 2 GroupNorm parameter gradients), the same reduction bodies.
+ * mlp_chain / afno_chain: the chains the workspaces were written with (what is left of the tree is added here). */
 int dpot_wgrad_batch_finalize(const dpot_wgrad_block* blocks, int n, int afno_splits12, int afno_splitk, int nb, int bs,
-                              int mlp_splitk, int E, int mh, int gn_jobs, int B, int Egn, dpot_stream_t stream);
+                              int mlp_splitk, int E, int mh, int gn_jobs, int B, int Egn, int mlp_chain, int afno_chain,
+                              dpot_stream_t stream);
 /* The weight-gradient LANE: the three launch sets above on a library-owned stream beside the caller's (csrc/gemm_tn.hip).
  * Nothing reads a weight gradient before the optimiser, so the caller's stream can go on with the embed backward meanwhile.
  * One lane per device - a non-blocking stream at the default priority (any other measured slower under graph replay) and two events
  * without timing - created by dpot_wgrad_lane_init() or the first flush, never while the caller's stream is capturing (that
  * flush runs on the caller's stream).  This is the library's only state; it is guarded by a mutex.
  * dpot_wgrad_flush_async: the arguments of dpot_mlp_wgrad_batch, dpot_afno_wgrad_batch and dpot_wgrad_batch_finalize (n, the
- *   split factors, nb, bs, E, mh once).  Records the fork event on `stream`, makes the lane wait for it, issues the three
+ *   split factors, the chains, nb, bs, E, mh once; the AFNO launch first, see csrc/gemm_tn.hip).  Records the fork event on `stream`, makes the lane wait for it, issues the three
  *   launch sets on the lane through those entry points, records the done event on the lane and counts one pending flush.
  *   Inside a stream capture the lane becomes a parallel branch of the capture; dpot_wgrad_wait joins it back.
  *   The caller keeps every buffer the launches read or write alive, and unused by others, until it has called dpot_wgrad_wait.
@@ -237,7 +258,8 @@ int dpot_wgrad_flush_async(const float* const* do2, const float* const* Hh, cons
                            int n, int T, int E, int mh, float* mlp_ws, int mlp_splitk, const float* const* S,
                            const float* const* dO1pre, const float* const* O1, const float* const* dO2, int ld, int Mm, int nb,
                            int bs, float* afno_ws, int per_launch, int afno_splits12, int afno_splitk,
-                           const dpot_wgrad_block* blocks, int gn_jobs, int B, int Egn, dpot_stream_t stream);
+                           const dpot_wgrad_block* blocks, int gn_jobs, int B, int Egn, int mlp_chain, int afno_chain,
+                           dpot_stream_t stream);
 int dpot_wgrad_wait(dpot_stream_t stream);
 /* Small weight-only layout jobs (zero-padded copies, small transposes, bias broadcasts, "+ bias") in ONE launch from a DEVICE
  * table: dst[i0][i1][i2] (contiguous d0 x d1 x d2) = (inside v0 x v1 x v2 ? src[i0 s0 + i1 s1 + i2 s2] : 0) + (add ? add[i2] : 0).
