@@ -21,27 +21,23 @@
 //               order.  The spectrum never reaches HBM; what does is [b][plane][stripe][K] shell partials and
 //               [b][plane][stripe][8] statistics partials.
 // eval_finalize_kernel: one thread per accumulator entry adds the stripes and the samples in order (double) and folds the
-//   per-sample ratios into the accumulator.
+//   per-sample ratios into the accumulator (the arithmetic of an entry: evalmetrics_common.h, shared with evalmetrics3d.hip,
+//   as are the pointwise statistics and their reduction).
 // Nothing outside the tensors is read: loads past nx, ny or TC are predicated to 0.0f, which adds nothing to any statistic.
-#include "common.h"
-
-#include <math.h>
+#include "evalmetrics_common.h"
 
 namespace dpot {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int EV_IS = 16;                  // wavenumbers i per workgroup (one 16-row MFMA tile each for cos and sin)
-constexpr int EV_PC = 4;                   // planes per workgroup
+constexpr int EV_PC = EVAL_PC;             // planes per workgroup
 constexpr int EV_ROWS = 2 * EV_IS * EV_PC; // rows (P|Q, i, pc) of the LDS intermediate
-constexpr int EV_NW = 4;                   // waves
+constexpr int EV_NW = EVAL_NW;             // waves
 constexpr int EV_CT = 3;                   // j tiles a wave can hold in registers: ny/2 <= 16 * EV_NW * EV_CT
 constexpr int EV_LDS_MAX = 160 * 1024;
 constexpr int EV_TAIL = EV_NW * EV_PC * 8 * 8;                     // bytes behind the intermediate: the waves' statistics
 constexpr int EV_LD_MAX = (EV_LDS_MAX - EV_TAIL) / 4 / EV_ROWS;    // LDS row length nyp + 4 a workgroup can hold
 constexpr int EV_NY_MAX = (EV_LD_MAX - 4) / 16 * 16;               // 304
 constexpr int EV_NX_MAX = 1024;
-constexpr int EV_NSTAT = 7;                // sum|e| sum|t| sum e^2 sum t^2 max|e| max|t| boundary; slot 7 of a record unused
 
 struct EvalArgs {
   const float* pred;
@@ -59,10 +55,6 @@ struct EvalArgs {
 struct EvalChunk {      // the operands of 16 k (= x) values of pass 1, per lane
   f32x4 p[4], t[4];
   float ac[4], as[4];
-};
-
-struct EvalStats {
-  float ae[EV_PC], at[EV_PC], se[EV_PC], st[EV_PC], me[EV_PC], mt[EV_PC], bd[EV_PC];
 };
 
 template <bool VEC>
@@ -124,18 +116,7 @@ __device__ __forceinline__ void eval_pass1_tile(const EvalArgs& a, const float* 
       if (STATS) {
         const int x = k0 + 4 * s + lg;
         const float w = wy + (x == 0 ? 1.f : 0.f) + (x == a.nx - 1 ? 1.f : 0.f);   // out-of-range points hold e = 0
-#pragma unroll
-        for (int pc = 0; pc < EV_PC; ++pc) {
-          const float ev = e[pc], tv = cur.t[s][pc];
-          const float e2 = ev * ev;
-          st.ae[pc] += __builtin_fabsf(ev);
-          st.at[pc] += __builtin_fabsf(tv);
-          st.se[pc] += e2;
-          st.st[pc] = fmaf(tv, tv, st.st[pc]);
-          st.me[pc] = __builtin_elementwise_maximum(st.me[pc], __builtin_fabsf(ev));   // NaN-propagating
-          st.mt[pc] = __builtin_elementwise_maximum(st.mt[pc], __builtin_fabsf(tv));
-          st.bd[pc] = fmaf(w, e2, st.bd[pc]);
-        }
+        eval_stats_point(st, e, cur.t[s], w);
       }
     }
     cur = nxt;
@@ -166,45 +147,16 @@ __global__ __launch_bounds__(64 * EV_NW, VEC ? 2 : 1) void eval_stats_kernel(con
 
   // ---- pass 1: contract x, count the points --------------------------------------------------------------------------
   EvalStats st;
-#pragma unroll
-  for (int pc = 0; pc < EV_PC; ++pc) st.ae[pc] = st.at[pc] = st.se[pc] = st.st[pc] = st.me[pc] = st.mt[pc] = st.bd[pc] = 0.f;
+  eval_stats_zero(st);
   for (int yt = wave; yt < a.nyp / 16; yt += EV_NW) {
     if ((yt / EV_NW + yt % EV_NW) % ns == stripe)                  // one owner per tile, spread over the waves
       eval_pass1_tile<VEC, true>(a, pr, tg, ev_lds, LD, yt, i0, p0, npc, lr, lg, st);
     else
       eval_pass1_tile<VEC, false>(a, pr, tg, ev_lds, LD, yt, i0, p0, npc, lr, lg, st);
   }
-#pragma unroll
-  for (int pc = 0; pc < EV_PC; ++pc) {
-    const double v0 = wave_sum_d((double)st.ae[pc]), v1 = wave_sum_d((double)st.at[pc]);
-    const double v2 = wave_sum_d((double)st.se[pc]), v3 = wave_sum_d((double)st.st[pc]);
-    const double v6 = wave_sum_d((double)st.bd[pc]);
-    float me = st.me[pc], mt = st.mt[pc];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      me = __builtin_elementwise_maximum(me, __shfl_xor(me, off, 64));
-      mt = __builtin_elementwise_maximum(mt, __shfl_xor(mt, off, 64));
-    }
-    if (lane == 0) {
-      double* w = wstat + (wave * EV_PC + pc) * 8;
-      w[0] = v0, w[1] = v1, w[2] = v2, w[3] = v3, w[4] = (double)me, w[5] = (double)mt, w[6] = v6;
-    }
-  }
+  eval_stats_wave_reduce(st, wstat, wave, lane);
   __syncthreads();
-  if ((int)threadIdx.x < EV_PC * EV_NSTAT) {
-    const int pc = threadIdx.x / EV_NSTAT, k = threadIdx.x % EV_NSTAT;
-    if (pc < npc) {
-      double v = wstat[pc * 8 + k];
-      for (int w = 1; w < EV_NW; ++w) {                            // the waves in order
-        const double o = wstat[(w * EV_PC + pc) * 8 + k];
-        if (k == 4 || k == 5)
-          v = (o > v || o != o) ? o : v;
-        else
-          v += o;
-      }
-      a.statp[(((size_t)b * a.TC + p0 + pc) * ns + stripe) * 8 + k] = v;
-    }
-  }
+  eval_stats_store(wstat, a.statp, (size_t)b * a.TC + p0, npc, ns, stripe);
 
   // ---- pass 2: contract y, |E|^2 in registers --------------------------------------------------------------------------
   f32x4 spec[EV_CT][4];
@@ -273,100 +225,43 @@ __global__ __launch_bounds__(64 * EV_NW, VEC ? 2 : 1) void eval_stats_kernel(con
 }
 
 // ---- finalize ------------------------------------------------------------------------------------------------------
-// acc (doubles): [0] = number of samples (int64 bits), [1] reserved, then nmae|nmse|nmxe [3][C], then
-// nmae_t|nmse_t|nmxe_t|bd [4][T][C], then the shell sums [T][C][K]; every entry a sum over the samples seen.
-__device__ __forceinline__ void eval_plane_stats(const double* __restrict__ statp, int b, int p, int TC, int ns, double* v) {
-  const double* r = statp + ((size_t)b * TC + p) * ns * 8;
+// one THREAD per accumulator entry (eval_finalize_entry) walks the stripes in order
+struct EvalGather {
+  const double* __restrict__ statp;      // [B][TC][ns][8]
+  const float* __restrict__ specp;       // [B][TC][ns][K]
+  int TC, ns, K;
+  __device__ __forceinline__ bool writes() const { return true; }
+  __device__ __forceinline__ void plane_stats(int b, int p, double* v) const {
+    const double* r = statp + ((size_t)b * TC + p) * ns * 8;
 #pragma unroll
-  for (int k = 0; k < EV_NSTAT; ++k) v[k] = r[k];
-  for (int s = 1; s < ns; ++s) {                                   // the stripes in order
-    r += 8;
-    v[0] += r[0], v[1] += r[1], v[2] += r[2], v[3] += r[3], v[6] += r[6];
-    v[4] = (r[4] > v[4] || r[4] != r[4]) ? r[4] : v[4];
-    v[5] = (r[5] > v[5] || r[5] != r[5]) ? r[5] : v[5];
+    for (int k = 0; k < EVAL_NSTAT; ++k) v[k] = r[k];
+    for (int s = 1; s < ns; ++s) eval_stats_fold(v, r += 8);
   }
-}
+  __device__ __forceinline__ double shell_sum(double sum, int b, int p, int s) const {
+    const float* r = specp + ((size_t)b * TC + p) * ns * K + s;
+    for (int q = 0; q < ns; ++q) sum += (double)r[(size_t)q * K];
+    return sum;
+  }
+};
 
 __global__ __launch_bounds__(256) void eval_finalize_kernel(const double* __restrict__ statp, const float* __restrict__ specp,
-                                                            double* __restrict__ acc, int B, int nx, int ny, int T, int C,
-                                                            int ns, int K) {
-  const int TC = T * C;
-  const long long n_items = (long long)C + TC + (long long)TC * K + 1;
-  const long long idx = blockIdx.x * 256ll + threadIdx.x;
-  if (idx >= n_items) return;
-  double* out = acc + 2;
-  if (idx == n_items - 1) {                                        // the sample count
-    long long* cnt = reinterpret_cast<long long*>(acc);
-    cnt[0] += B;
-    return;
-  }
-  if (idx < C) {                                                   // whole-rollout ratios of channel c
-    const int c = (int)idx;
-    double mae = 0.0, mse = 0.0, mxe = 0.0;
-    for (int b = 0; b < B; ++b) {
-      double tot[EV_NSTAT] = {0, 0, 0, 0, 0, 0, 0};
-      for (int t = 0; t < T; ++t) {
-        double v[EV_NSTAT];
-        eval_plane_stats(statp, b, t * C + c, TC, ns, v);
-        tot[0] += v[0], tot[1] += v[1], tot[2] += v[2], tot[3] += v[3];
-        tot[4] = (v[4] > tot[4] || v[4] != v[4]) ? v[4] : tot[4];
-        tot[5] = (v[5] > tot[5] || v[5] != v[5]) ? v[5] : tot[5];
-      }
-      mae += tot[0] / tot[1];
-      mse += sqrt(tot[2] / tot[3]);
-      mxe += tot[4] / tot[5];
-    }
-    out[c] += mae;
-    out[C + c] += mse;
-    out[2 * C + c] += mxe;
-    return;
-  }
-  if (idx < C + TC) {                                              // per-step ratios and the boundary error of plane p
-    const int p = (int)(idx - C);
-    double mae = 0.0, mse = 0.0, mxe = 0.0, bd = 0.0;
-    for (int b = 0; b < B; ++b) {
-      double v[EV_NSTAT];
-      eval_plane_stats(statp, b, p, TC, ns, v);
-      mae += v[0] / v[1];
-      mse += sqrt(v[2] / v[3]);
-      mxe += v[4] / v[5];
-      bd += sqrt(v[6] / (double)(2 * nx + 2 * ny));
-    }
-    double* o = out + 3 * C;
-    o[p] += mae;
-    o[TC + p] += mse;
-    o[2 * TC + p] += mxe;
-    o[3 * TC + p] += bd;
-    return;
-  }
-  {                                                                // shell s of plane p
-    const long long e = idx - C - TC;
-    const int p = (int)(e / K), s = (int)(e % K);
-    double sum = 0.0;
-    for (int b = 0; b < B; ++b) {
-      const float* r = specp + ((size_t)b * TC + p) * ns * K + s;
-      for (int q = 0; q < ns; ++q) sum += (double)r[(size_t)q * K];
-    }
-    out[3 * C + 4 * TC + e] += sum;
-  }
+                                                            double* __restrict__ acc, int B, double faces, int T, int C, int ns,
+                                                            int K) {
+  const EvalGather g = {statp, specp, T * C, ns, K};
+  eval_finalize_entry(g, blockIdx.x * 256ll + threadIdx.x, acc, B, faces, T, C, K);
 }
 
 }  // namespace dpot
 
 using namespace dpot;
 
-extern "C" int dpot_eval_metrics_pad(int n, int half) {
-  if (n <= 0) return 0;
-  const int m = half ? n / 2 : n;
-  return m <= 0 ? 0 : (m + 15) / 16 * 16;
-}
+extern "C" int dpot_eval_metrics_pad(int n, int half) { return eval_pad(n, half); }
 
 extern "C" int dpot_eval_metrics_max_size(int axis) { return axis == 0 ? EV_NX_MAX : EV_NY_MAX; }
 
 extern "C" int64_t dpot_eval_metrics_acc_elems(int nx, int ny, int T, int C) {
   if (nx < 2 || ny < 2 || T < 1 || C < 1) return 0;
-  const int64_t K = nx / 2 < ny / 2 ? nx / 2 : ny / 2, TC = (int64_t)T * C;
-  return 2 + 3 * (int64_t)C + 4 * TC + TC * K;
+  return eval_acc_elems(nx / 2 < ny / 2 ? nx / 2 : ny / 2, T, C);
 }
 
 extern "C" int dpot_eval_metrics_stats(const float* pred, const float* target, const float* cxT, const float* sxT,
@@ -385,8 +280,8 @@ extern "C" int dpot_eval_metrics_stats(const float* pred, const float* target, c
   a.pred = pred, a.target = target, a.cxT = cxT, a.sxT = sxT, a.cy = cy, a.sy = sy, a.jlo = jlo;
   a.statp = statp, a.specp = specp;
   a.nx = nx, a.ny = ny, a.TC = TC, a.hx = nx / 2, a.hy = ny / 2, a.K = a.hx < a.hy ? a.hx : a.hy;
-  a.nxp = dpot_eval_metrics_pad(nx, 0), a.nyp = dpot_eval_metrics_pad(ny, 0);
-  a.hxp = dpot_eval_metrics_pad(nx, 1), a.hyp = dpot_eval_metrics_pad(ny, 1);
+  a.nxp = eval_pad(nx, 0), a.nyp = eval_pad(ny, 0);
+  a.hxp = eval_pad(nx, 1), a.hyp = eval_pad(ny, 1);
   static_assert(EV_NY_MAX / 2 <= 16 * EV_NW * EV_CT, "a wave cannot hold its j tiles");
   static_assert(EV_PC * EV_IS * (EV_NY_MAX / 2 + 16 + 1) <= EV_ROWS * (EV_NY_MAX + 4), "|E|^2 must fit over P and Q");
   const size_t lds = sizeof(float) * (size_t)EV_ROWS * (a.nyp + 4) + EV_TAIL;
@@ -415,9 +310,9 @@ extern "C" int dpot_eval_metrics_finalize(const double* statp, const float* spec
               EV_NY_MAX);
     return DPOT_EUNSUP;
   }
-  const int ns = dpot_eval_metrics_pad(nx, 1) / EV_IS, K = nx / 2 < ny / 2 ? nx / 2 : ny / 2;
-  const int64_t items = (int64_t)C + (int64_t)T * C * (1 + K) + 1;          // eval_finalize_kernel's n_items
-  hipLaunchKernelGGL(eval_finalize_kernel, dim3((unsigned)cdiv64(items, 256)), dim3(256), 0, as_stream(stream), statp, specp,
-                     acc, B, nx, ny, T, C, ns, K);
+  const int ns = eval_pad(nx, 1) / EV_IS, K = nx / 2 < ny / 2 ? nx / 2 : ny / 2;
+  const double edges = 2.0 * nx + 2.0 * ny;                        // corners twice, as the reference adds rows and columns
+  hipLaunchKernelGGL(eval_finalize_kernel, dim3((unsigned)cdiv64(eval_finalize_items(K, T, C), 256)), dim3(256), 0,
+                     as_stream(stream), statp, specp, acc, B, edges, T, C, ns, K);
   return check_launch("eval_finalize_kernel");
 }

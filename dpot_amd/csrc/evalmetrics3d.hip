@@ -25,21 +25,18 @@
 //               shell s in row (k, i) (host table jlo[k][i][s] .. jlo[k][i][s+1], integer arithmetic) in ascending j: a fixed
 //               order.  The full spectrum never reaches HBM; what does is [B][TC][nz/2][stripes][K] shell partials.
 // eval3_finalize_kernel: one wave per accumulator entry adds the partials (lane-strided, then a butterfly: a fixed order) and
-//   the samples in order (double) and folds the per-sample ratios into the accumulator.
+//   the samples in order (double) and folds the per-sample ratios into the accumulator (the arithmetic of an entry:
+//   evalmetrics_common.h, shared with evalmetrics.hip, as are the pointwise statistics and their reduction).
 // Bytes per update: pred and target are read once from HBM (stripes beyond nz = 128 re-read through L2), G is written once and
 // read once per i stripe (nx / 32 of them, neighbours in the grid); everything else is tables and partials.
 // Nothing outside the tensors is read: loads past a row, past nz or past TC are predicated to 0.0f, which adds nothing to
 // any statistic, and G is read only where eval3_z_kernel wrote it.
-#include "common.h"
-
-#include <math.h>
+#include "evalmetrics_common.h"
 
 namespace dpot {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int E3_PC = 4;                   // planes (t, c) per workgroup of the z pass
-constexpr int E3_NW = 4;                   // waves
+constexpr int E3_PC = EVAL_PC;             // planes (t, c) per workgroup of the z pass
+constexpr int E3_NW = EVAL_NW;             // waves
 constexpr int E3_NKT = 4;                  // 16-wavenumber k tiles a wave of the z pass can hold
 constexpr int E3_TPW = 1;                  // row tiles per wave of the z pass (4: 64 workgroups at [1, 128^3, 1, 4] - measured slower)
 constexpr int E3_TPG = E3_NW * E3_TPW;     // row tiles per workgroup
@@ -51,7 +48,6 @@ constexpr int E3_LDS_MAX = 160 * 1024;
 constexpr int E3_NY_MAX = 512;             // (E3_NY_MAX + 4) * E3_ROWS floats = 129 KiB of LDS
 constexpr int E3_NX_MAX = 512;
 constexpr int E3_NZ_MAX = 512;
-constexpr int E3_NSTAT = 7;                // sum|e| sum|t| sum e^2 sum t^2 max|e| max|t| faces; slot 7 of a record unused
 
 struct Eval3ZArgs {
   const float* pred;
@@ -64,15 +60,11 @@ struct Eval3ZArgs {
   int tpw;              // row tiles per wave = E3_TPW, as a run-time value: see eval3_z_kernel
 };
 
-struct Eval3Stats {
-  float ae[E3_PC], at[E3_PC], se[E3_PC], st[E3_PC], me[E3_PC], mt[E3_PC], bd[E3_PC];
-};
-
 // one tile of 16 rows r: its NKT k tiles of Gc and Gs into G; STATS: this tile's points are counted here
 template <bool VEC, int NKT, bool STATS>
 __device__ __forceinline__ void eval3_z_tile(const Eval3ZArgs& a, const float* __restrict__ pr, const float* __restrict__ tg,
                                              float* __restrict__ Gb, int rt, int kt0, int p0, int npc, int lr, int lg,
-                                             Eval3Stats& st) {
+                                             EvalStats& st) {
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const int r = rt * 16 + lr;
   const bool rok = r < a.R;
@@ -120,18 +112,7 @@ __device__ __forceinline__ void eval3_z_tile(const Eval3ZArgs& a, const float* _
         }
       if (STATS) {
         const float w = wxy + (z == 0 ? 1.f : 0.f) + (z == a.nz - 1 ? 1.f : 0.f);   // out-of-range points hold e = 0
-#pragma unroll
-        for (int pc = 0; pc < E3_PC; ++pc) {
-          const float ev = e[pc], tv = t[pc];
-          const float e2 = ev * ev;
-          st.ae[pc] += __builtin_fabsf(ev);
-          st.at[pc] += __builtin_fabsf(tv);
-          st.se[pc] += e2;
-          st.st[pc] = fmaf(tv, tv, st.st[pc]);
-          st.me[pc] = __builtin_elementwise_maximum(st.me[pc], __builtin_fabsf(ev));   // NaN-propagating
-          st.mt[pc] = __builtin_elementwise_maximum(st.mt[pc], __builtin_fabsf(tv));
-          st.bd[pc] = fmaf(w, e2, st.bd[pc]);
-        }
+        eval_stats_point(st, e, t, w);
       }
     }
   }
@@ -170,7 +151,9 @@ __global__ __launch_bounds__(64 * E3_NW) void eval3_z_kernel(const Eval3ZArgs a)
   float* __restrict__ Gb = a.G + (size_t)b * a.TC * a.hz * 2 * a.R;
   const int npc = a.TC - p0 < E3_PC ? a.TC - p0 : E3_PC;
 
-  Eval3Stats st;
+  // zeroed here and not by eval_stats_zero: through the helper (or `= {}`) the one-tile kernels are allocated 128 / 135 VGPRs
+  // instead of 142 / 146 and change occupancy; every other shared helper leaves this kernel's registers as they were
+  EvalStats st;
 #pragma unroll
   for (int pc = 0; pc < E3_PC; ++pc) st.ae[pc] = st.at[pc] = st.se[pc] = st.st[pc] = st.me[pc] = st.mt[pc] = st.bd[pc] = 0.f;
   // a.tpw is a run-time value so that this stays a loop around ONE copy of each tile body: with the constant 1 the compiler
@@ -184,38 +167,9 @@ __global__ __launch_bounds__(64 * E3_NW) void eval3_z_kernel(const Eval3ZArgs a)
     else
       eval3_z_tile<VEC, NKT, false>(a, pr, tg, Gb, rt, stripe * NKT, p0, npc, lr, lg, st);
   }
-#pragma unroll
-  for (int pc = 0; pc < E3_PC; ++pc) {
-    const double v0 = wave_sum_d((double)st.ae[pc]), v1 = wave_sum_d((double)st.at[pc]);
-    const double v2 = wave_sum_d((double)st.se[pc]), v3 = wave_sum_d((double)st.st[pc]);
-    const double v6 = wave_sum_d((double)st.bd[pc]);
-    float me = st.me[pc], mt = st.mt[pc];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      me = __builtin_elementwise_maximum(me, __shfl_xor(me, off, 64));
-      mt = __builtin_elementwise_maximum(mt, __shfl_xor(mt, off, 64));
-    }
-    if (lane == 0) {
-      double* w = wstat + (wave * E3_PC + pc) * 8;
-      w[0] = v0, w[1] = v1, w[2] = v2, w[3] = v3, w[4] = (double)me, w[5] = (double)mt, w[6] = v6;
-    }
-  }
+  eval_stats_wave_reduce(st, wstat, wave, lane);
   __syncthreads();
-  if ((int)threadIdx.x < E3_PC * E3_NSTAT) {
-    const int pc = threadIdx.x / E3_NSTAT, k = threadIdx.x % E3_NSTAT;
-    if (pc < npc) {
-      double v = wstat[pc * 8 + k];
-      for (int w = 1; w < E3_NW; ++w) {                            // the waves in order
-        const double o = wstat[(w * E3_PC + pc) * 8 + k];
-        if (k == 4 || k == 5)
-          v = (o > v || o != o) ? o : v;
-        else
-          v += o;
-      }
-      const int parts = a.nchunks * a.nstripes, part = chunk * a.nstripes + stripe;
-      a.statp[(((size_t)b * a.TC + p0 + pc) * parts + part) * 8 + k] = v;
-    }
-  }
+  eval_stats_store(wstat, a.statp, (size_t)b * a.TC + p0, npc, a.nchunks * a.nstripes, chunk * a.nstripes + stripe);
 }
 
 // ---- the two remaining axes and the shell sums ---------------------------------------------------------------------------
@@ -356,121 +310,52 @@ __global__ __launch_bounds__(64 * E3_NW) void eval3_xy_kernel(const Eval3XYArgs 
 }
 
 // ---- finalize ------------------------------------------------------------------------------------------------------
-// acc (doubles): [0] = number of samples (int64 bits), [1] reserved, then nmae|nmse|nmxe [3][C], then
-// nmae_t|nmse_t|nmxe_t|bd [4][T][C], then the shell sums [T][C][K]; every entry a sum over the samples seen.
-// One WAVE per accumulator entry: lane l takes the partials l, l + 64, ... in order and a butterfly combines the lanes - a
-// fixed order for a shape, and a + b = b + a keeps the lanes identical.  (One thread per entry, as evalmetrics.hip has it,
-// walks nz/2 x stripes shell partials and row-tiles / 4 statistics partials one after the other: measured 84 - 183 us.)
-__device__ __forceinline__ double eval3_wave_max(double v) {      // NaN-propagating
+// One WAVE per accumulator entry (eval_finalize_entry): lane l takes the partials l, l + 64, ... in order and a butterfly
+// combines the lanes - a fixed order for a shape, and a + b = b + a keeps the lanes identical.  (One thread per entry, as
+// evalmetrics.hip has it, walks nz/2 x stripes shell partials and row-tiles / 4 statistics partials one after the other:
+// measured 84 - 183 us.)
+struct Eval3Gather {
+  const double* __restrict__ statp;      // [B][TC][parts][8]
+  const float* __restrict__ specp;       // [B][TC][nq = (k, i stripe)][K]
+  int TC, parts, nq, K, lane;
+  __device__ __forceinline__ bool writes() const { return lane == 0; }
+  __device__ __forceinline__ void plane_stats(int b, int p, double* v) const {
+    const double* r = statp + ((size_t)b * TC + p) * parts * 8;
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_xor(v, off, 64);
-    v = (o > v || o != o) ? o : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ void eval3_plane_stats(const double* __restrict__ statp, int b, int p, int TC, int parts, int lane,
-                                                  double* v) {
-  const double* r = statp + ((size_t)b * TC + p) * parts * 8;
+    for (int k = 0; k < EVAL_NSTAT; ++k) v[k] = 0.0;               // sums of magnitudes and maxima of magnitudes: 0 is neutral
+    for (int s = lane; s < parts; s += 64) eval_stats_fold(v, r + (size_t)s * 8);
+    v[0] = wave_sum_d(v[0]), v[1] = wave_sum_d(v[1]), v[2] = wave_sum_d(v[2]), v[3] = wave_sum_d(v[3]), v[6] = wave_sum_d(v[6]);
 #pragma unroll
-  for (int k = 0; k < E3_NSTAT; ++k) v[k] = 0.0;                   // sums of magnitudes and maxima of magnitudes: 0 is neutral
-  for (int s = lane; s < parts; s += 64) {
-    const double* q = r + (size_t)s * 8;
-    v[0] += q[0], v[1] += q[1], v[2] += q[2], v[3] += q[3], v[6] += q[6];
-    v[4] = (q[4] > v[4] || q[4] != q[4]) ? q[4] : v[4];
-    v[5] = (q[5] > v[5] || q[5] != q[5]) ? q[5] : v[5];
+    for (int off = 32; off > 0; off >>= 1) {
+      v[4] = eval_max_nan(v[4], __shfl_xor(v[4], off, 64));
+      v[5] = eval_max_nan(v[5], __shfl_xor(v[5], off, 64));
+    }
   }
-  v[0] = wave_sum_d(v[0]), v[1] = wave_sum_d(v[1]), v[2] = wave_sum_d(v[2]), v[3] = wave_sum_d(v[3]), v[6] = wave_sum_d(v[6]);
-  v[4] = eval3_wave_max(v[4]), v[5] = eval3_wave_max(v[5]);
-}
+  __device__ __forceinline__ double shell_sum(double sum, int b, int p, int s) const {
+    const float* r = specp + ((size_t)b * TC + p) * nq * K + s;
+    double part = 0.0;
+    for (int q = lane; q < nq; q += 64) part += (double)r[(size_t)q * K];
+    return sum + wave_sum_d(part);
+  }
+};
 
 __global__ __launch_bounds__(256) void eval3_finalize_kernel(const double* __restrict__ statp, const float* __restrict__ specp,
                                                              double* __restrict__ acc, int B, double faces, int T, int C,
                                                              int parts, int nq, int K) {
-  const int TC = T * C, lane = threadIdx.x & 63;
-  const long long n_items = (long long)C + TC + (long long)TC * K + 1;
-  const long long idx = blockIdx.x * 4ll + (threadIdx.x >> 6);     // wave-uniform
-  if (idx >= n_items) return;
-  double* out = acc + 2;
-  if (idx == n_items - 1) {                                        // the sample count
-    long long* cnt = reinterpret_cast<long long*>(acc);
-    if (lane == 0) cnt[0] += B;
-    return;
-  }
-  if (idx < C) {                                                   // whole-rollout ratios of channel c
-    const int c = (int)idx;
-    double mae = 0.0, mse = 0.0, mxe = 0.0;
-    for (int b = 0; b < B; ++b) {
-      double tot[E3_NSTAT] = {0, 0, 0, 0, 0, 0, 0};
-      for (int t = 0; t < T; ++t) {
-        double v[E3_NSTAT];
-        eval3_plane_stats(statp, b, t * C + c, TC, parts, lane, v);
-        tot[0] += v[0], tot[1] += v[1], tot[2] += v[2], tot[3] += v[3];
-        tot[4] = (v[4] > tot[4] || v[4] != v[4]) ? v[4] : tot[4];
-        tot[5] = (v[5] > tot[5] || v[5] != v[5]) ? v[5] : tot[5];
-      }
-      mae += tot[0] / tot[1];
-      mse += sqrt(tot[2] / tot[3]);
-      mxe += tot[4] / tot[5];
-    }
-    if (lane == 0) {
-      out[c] += mae;
-      out[C + c] += mse;
-      out[2 * C + c] += mxe;
-    }
-    return;
-  }
-  if (idx < C + TC) {                                              // per-step ratios and the face error of plane p
-    const int p = (int)(idx - C);
-    double mae = 0.0, mse = 0.0, mxe = 0.0, bd = 0.0;
-    for (int b = 0; b < B; ++b) {
-      double v[E3_NSTAT];
-      eval3_plane_stats(statp, b, p, TC, parts, lane, v);
-      mae += v[0] / v[1];
-      mse += sqrt(v[2] / v[3]);
-      mxe += v[4] / v[5];
-      bd += sqrt(v[6] / faces);
-    }
-    if (lane == 0) {
-      double* o = out + 3 * C;
-      o[p] += mae;
-      o[TC + p] += mse;
-      o[2 * TC + p] += mxe;
-      o[3 * TC + p] += bd;
-    }
-    return;
-  }
-  {                                                                // shell s of plane p
-    const long long e = idx - C - TC;
-    const int p = (int)(e / K), s = (int)(e % K);
-    double sum = 0.0;
-    for (int b = 0; b < B; ++b) {
-      const float* r = specp + ((size_t)b * TC + p) * nq * K + s;
-      double part = 0.0;
-      for (int q = lane; q < nq; q += 64) part += (double)r[(size_t)q * K];      // (k, i stripe)
-      sum += wave_sum_d(part);
-    }
-    if (lane == 0) out[3 * C + 4 * TC + e] += sum;
-  }
+  const Eval3Gather g = {statp, specp, T * C, parts, nq, K, (int)(threadIdx.x & 63)};
+  eval_finalize_entry(g, blockIdx.x * 4ll + (threadIdx.x >> 6), acc, B, faces, T, C, K);   // the entry is wave-uniform
 }
 
 struct Eval3Geom {
   int hx, hy, hz, K, nxp, nyp, nzp, hxp, hyp, hzp, ns, nkt, nstripes, ntiles, nchunks, parts;
 };
 
-static int eval3_pad(int n, int half) {
-  if (n <= 0) return 0;
-  const int m = half ? n / 2 : n;
-  return m <= 0 ? 0 : (m + 15) / 16 * 16;
-}
-
 static Eval3Geom eval3_geom(int nx, int ny, int nz) {
   Eval3Geom g;
   g.hx = nx / 2, g.hy = ny / 2, g.hz = nz / 2;
   g.K = g.hx < g.hy ? (g.hx < g.hz ? g.hx : g.hz) : (g.hy < g.hz ? g.hy : g.hz);
-  g.nxp = eval3_pad(nx, 0), g.nyp = eval3_pad(ny, 0), g.nzp = eval3_pad(nz, 0);
-  g.hxp = eval3_pad(nx, 1), g.hyp = eval3_pad(ny, 1), g.hzp = eval3_pad(nz, 1);
+  g.nxp = eval_pad(nx, 0), g.nyp = eval_pad(ny, 0), g.nzp = eval_pad(nz, 0);
+  g.hxp = eval_pad(nx, 1), g.hyp = eval_pad(ny, 1), g.hzp = eval_pad(nz, 1);
   g.ns = g.hxp / E3_IS;
   const int ktiles = g.hzp / 16;
   g.nkt = ktiles >= 3 ? E3_NKT : ktiles;                           // 1, 2 or 4 k tiles per workgroup of the z pass
@@ -504,14 +389,13 @@ static void eval3_launch_z(const Eval3ZArgs& a, int nkt, dim3 grid, hipStream_t 
 
 using namespace dpot;
 
-extern "C" int dpot_eval3_pad(int n, int half) { return eval3_pad(n, half); }
+extern "C" int dpot_eval3_pad(int n, int half) { return eval_pad(n, half); }
 
 extern "C" int dpot_eval3_max_size(int axis) { return axis == 0 ? E3_NX_MAX : axis == 1 ? E3_NY_MAX : E3_NZ_MAX; }
 
 extern "C" int64_t dpot_eval3_acc_elems(int nx, int ny, int nz, int T, int C) {
   if (nx < 2 || ny < 2 || nz < 2 || T < 1 || C < 1) return 0;
-  const int64_t K = eval3_geom(nx, ny, nz).K, TC = (int64_t)T * C;
-  return 2 + 3 * (int64_t)C + 4 * TC + TC * K;
+  return eval_acc_elems(eval3_geom(nx, ny, nz).K, T, C);
 }
 
 extern "C" int64_t dpot_eval3_work_elems(int which, int B, int nx, int ny, int nz, int TC) {
@@ -574,8 +458,7 @@ extern "C" int dpot_eval3_finalize(const double* statp, const float* specp, doub
   if (!eval3_size_ok("eval3_finalize", nx, ny, nz)) return DPOT_EUNSUP;
   const Eval3Geom g = eval3_geom(nx, ny, nz);
   const double faces = 2.0 * nx * ny + 2.0 * ny * nz + 2.0 * nz * nx;
-  const int64_t items = (int64_t)C + (int64_t)T * C * (1 + g.K) + 1;          // eval3_finalize_kernel's n_items
-  hipLaunchKernelGGL(eval3_finalize_kernel, dim3((unsigned)cdiv64(items, 4)), dim3(256), 0, as_stream(stream), statp, specp,
-                     acc, B, faces, T, C, g.parts, g.hz * g.ns, g.K);
+  hipLaunchKernelGGL(eval3_finalize_kernel, dim3((unsigned)cdiv64(eval_finalize_items(g.K, T, C), 4)), dim3(256), 0,
+                     as_stream(stream), statp, specp, acc, B, faces, T, C, g.parts, g.hz * g.ns, g.K);
   return check_launch("eval3_finalize_kernel");
 }

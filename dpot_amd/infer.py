@@ -160,7 +160,7 @@ class RolloutEvaluator:
     ``reset()`` share X, Y, T, C (T <= T_max, C == n_channels); the batch size may change.  X <= 1024, Y <= 304 (the LDS
     intermediate of a workgroup).  ``update`` is capturable in a hipGraph once a shape has been seen.
 
-    3-D fields: ``update`` also takes a pair [B, X, Y, Z, T, C] (csrc/evalmetrics3d.hip) and dispatches on the rank.  The
+    3-D fields: ``update`` also takes a pair [B, X, Y, Z, T, C] (csrc/evalmetrics3d.hip); ops takes the rank from the shape.  The
     reference's Evaluator cannot run ``component='all'`` on such a field; column c of every key is its
     ``Evaluator(temporal=True, griddata=True, component=c)(pred[..., c], target)``, in the shapes above: the ratios over all of
     X*Y*Z*T and, per step, over X*Y*Z; ``bdmse`` is e^2 summed over the six faces x = 0, X-1, y = 0, Y-1, z = 0, Z-1 (an edge
@@ -204,13 +204,9 @@ class RolloutEvaluator:
                 if torch.cuda.is_current_stream_capturing():
                     raise _lib.DpotHipError("RolloutEvaluator: the accumulator of a shape is allocated when it is first seen - "
                                             "run one update (and reset) before capturing")
-                alloc = ops.eval_acc_alloc if len(shape) == 4 else ops.eval3_acc_alloc
-                acc = self._accs[shape] = alloc(*shape, self.device)
+                acc = self._accs[shape] = ops.eval_acc_alloc(*shape, self.device)
             self.acc = acc
-        if len(shape) == 4:
-            ops.eval_metrics_update(pred, target, self.acc)
-        else:
-            ops.eval3_metrics_update(pred, target, self.acc)
+        ops.eval_metrics_update(pred, target, self.acc)
         self.shape = shape
 
     def reset(self) -> None:
@@ -232,8 +228,7 @@ class RolloutEvaluator:
             if dist.is_available() and dist.is_initialized():
                 dist.all_reduce(vals, op=dist.ReduceOp.SUM, group=pg)
         vals = vals.cpu().numpy()
-        finish = ops.eval_finish if len(self.shape) == 4 else ops.eval3_finish
-        return finish(vals, int(round(vals[0])), *self.shape, self.ilow, self.ihigh)
+        return ops.eval_finish(vals, int(round(vals[0])), *self.shape, self.ilow, self.ihigh)
 
 
 @torch.no_grad()

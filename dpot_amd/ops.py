@@ -11,7 +11,7 @@ import contextlib
 import functools
 import threading
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -2103,9 +2103,54 @@ def spectral_resize(x: Tensor, out_size, out: Optional[Tensor] = None) -> Tensor
 
 # ------------------------------------------------------------------------------------------------------
 # Rollout evaluation metrics: the reference's Evaluator (utils/criterion.py:189-239, compute_fourier_error :246-360) on the
-# device (csrc/evalmetrics.hip).  The host tables are pure numpy: the CPU tests check them without a GPU.
+# device, for 2-D rollouts [B, X, Y, T, C] (csrc/evalmetrics.hip) and 3-D ones [B, X, Y, Z, T, C] (csrc/evalmetrics3d.hip) through
+# one host path.  The host tables are pure numpy: the CPU tests check them without a GPU.
 # ------------------------------------------------------------------------------------------------------
 EVAL_KEYS = ("nmae", "nmse", "nmxe", "nmae_t", "nmse_t", "nmxe_t", "bdmse", "fmse_low", "fmse_mid", "fmse_high")
+
+
+def _eval_work_plane(lib, B, nx, ny, TC):
+    """one record of 8 doubles and K shell partials per (b, plane, stripe of 16 wavenumbers i)"""
+    n = B * TC * (lib.dpot_eval_metrics_pad(nx, 1) // 16)
+    return n * 8, n * min(nx // 2, ny // 2)
+
+
+def _eval_work_field(lib, B, nx, ny, nz, TC):
+    """the library's own figures: statistics partials, shell partials and the half spectrum G between the z and the xy pass"""
+    return tuple(lib.dpot_eval3_work_elems(which, B, nx, ny, nz, TC) for which in range(3))
+
+
+class _EvalRank(NamedTuple):
+    """What differs between planes [B, X, Y, T, C] (csrc/evalmetrics.hip) and fields [B, X, Y, Z, T, C]
+    (csrc/evalmetrics3d.hip: column c of every key is the reference's Evaluator(temporal=True, griddata=True, component=c));
+    everything below this record serves both and takes the rank from the number of spatial sizes."""
+    noun: str            # what one (b, t, c) slice is called in messages
+    axes: tuple          # table name suffix per axis (cos "c" + suffix, sin "s" + suffix): the stats entry point takes them in
+                         # this order, then jlo, then the workspace
+    limits: str          # the size limits of max_size(axis), as the message words them
+    pad: str             # C entry points
+    max_size: str
+    acc_elems: str
+    stats: str
+    finalize: str
+    work: object         # (lib, B, *sizes, TC) -> elements of statp (doubles) and of each fp32 buffer behind it
+
+
+_EVAL_RANKS = {
+    2: _EvalRank("plane", ("xT", "y"), "nx <= {}, ny <= {}: the LDS intermediate of a workgroup", "dpot_eval_metrics_pad",
+                 "dpot_eval_metrics_max_size", "dpot_eval_metrics_acc_elems", "dpot_eval_metrics_stats",
+                 "dpot_eval_metrics_finalize", _eval_work_plane),
+    3: _EvalRank("field", ("xT", "y", "zT"), "nx <= {}; ny <= {}: the LDS intermediate of a workgroup; nz <= {}",
+                 "dpot_eval3_pad", "dpot_eval3_max_size", "dpot_eval3_acc_elems", "dpot_eval3_stats", "dpot_eval3_finalize",
+                 _eval_work_field),
+}
+
+
+def _eval_rank(what: str, sizes) -> _EvalRank:
+    rank = _EVAL_RANKS.get(len(sizes))
+    if rank is None:
+        raise ValueError(f"{what}: need the 2 or 3 spatial sizes of a plane or a field, got {tuple(sizes)}")
+    return rank
 
 
 def eval_dft_tables(n: int):
@@ -2119,60 +2164,65 @@ def eval_dft_tables(n: int):
     return np.cos(ang), np.sin(ang)
 
 
-def eval_shell_table(nx: int, ny: int):
-    """int32 [nx // 2, ny // 2]: the shell floor(sqrt(i^2 + j^2)) of wavenumber (i, j) of the positive quadrant, or -1 where
-    that shell is >= K = min(nx // 2, ny // 2) and the reference drops the wavenumber.  Integer arithmetic: the float square
-    root is only a first guess that two integer comparisons correct."""
+def eval_shell_table(*sizes: int):
+    """int32 [nx // 2, ny // 2] or [nx // 2, ny // 2, nz // 2]: the shell floor(sqrt(i^2 + j^2 (+ k^2))) of a wavenumber of the
+    positive quadrant (octant), or -1 where that shell is >= K = min(n // 2 for n in sizes) and the reference drops the
+    wavenumber.  Integer arithmetic: the float square root is only a first guess that two integer comparisons correct."""
     import numpy as np
-    if nx < 2 or ny < 2:
-        raise ValueError(f"eval_shell_table: sizes must be >= 2, got {nx} x {ny}")
-    i = np.arange(nx // 2, dtype=np.int64)[:, None]
-    j = np.arange(ny // 2, dtype=np.int64)[None, :]
-    v = i * i + j * j
+    _eval_rank("eval_shell_table", sizes)
+    if min(sizes) < 2:
+        raise ValueError(f"eval_shell_table: sizes must be >= 2, got {' x '.join(map(str, sizes))}")
+    v = sum(g.astype(np.int64) ** 2 for g in np.ogrid[tuple(slice(n // 2) for n in sizes)])
     s = np.sqrt(v.astype(np.float64)).astype(np.int64)
     s -= (s * s > v)
     s += ((s + 1) * (s + 1) <= v)
     assert ((s * s <= v) & ((s + 1) * (s + 1) > v)).all()
-    K = min(nx // 2, ny // 2)
-    return np.where(s < K, s, -1).astype(np.int32)
+    return np.where(s < min(n // 2 for n in sizes), s, -1).astype(np.int32)
 
 
-def eval_shell_ranges(nx: int, ny: int):
-    """int32 [nx // 2, K + 1]: entry [i, s] = number of j in [0, ny // 2) whose shell in row i is below s.  The shell grows
-    with j, so the members of shell s in row i are the j range [i, s] .. [i, s + 1]; what lies at or beyond [i, K] is
-    dropped.  This is the form of eval_shell_table the kernel walks."""
+def eval_shell_ranges(*sizes: int):
+    """int32 [nx // 2, K + 1] or [nz // 2, nx // 2, K + 1]: entry [(k,) i, s] = number of j in [0, ny // 2) whose shell in row
+    (k,) i is below s.  The shell grows with j, so the members of shell s in a row are the j range [.., s] .. [.., s + 1]; what
+    lies at or beyond [.., K] is dropped.  This is the form of eval_shell_table the kernels walk."""
     import numpy as np
-    sh = eval_shell_table(nx, ny).astype(np.int64)
-    K = min(nx // 2, ny // 2)
+    sh = eval_shell_table(*sizes).astype(np.int64)
+    K = min(n // 2 for n in sizes)
     sh = np.where(sh < 0, K, sh)                                   # dropped: beyond every kept shell
-    return (sh[:, :, None] < np.arange(K + 1)[None, None, :]).sum(axis=1).astype(np.int32)
+    below = np.stack([(sh < s).sum(axis=1) for s in range(K + 1)], axis=-1)          # [i, (k,) s]
+    return np.ascontiguousarray(np.moveaxis(below, 0, -2), dtype=np.int32)
 
 
-def eval_acc_layout(nx: int, ny: int, T: int, C: int):
-    """(offsets, total) of the accumulator in 8-byte words: 'count' (int64), then doubles - 'c' [3, C] = nmae | nmse | nmxe,
-    'tc' [4, T, C] = nmae_t | nmse_t | nmxe_t | boundary, 'spec' [T, C, K] - every entry a sum over the samples"""
-    K = min(nx // 2, ny // 2)
+def eval_acc_layout(*dims: int):
+    """(offsets, total) of the accumulator of dims = (X, Y[, Z], T, C) in 8-byte words: 'count' (int64), then doubles - 'c'
+    [3, C] = nmae | nmse | nmxe, 'tc' [4, T, C] = nmae_t | nmse_t | nmxe_t | boundary, 'spec' [T, C, K] - every entry a sum
+    over the samples"""
+    *sizes, T, C = dims
+    _eval_rank("eval_acc_layout", sizes)
     off = {"count": 0, "c": 2, "tc": 2 + 3 * C, "spec": 2 + 3 * C + 4 * T * C}
-    return off, 2 + 3 * C + 4 * T * C + T * C * K
+    return off, off["spec"] + T * C * min(n // 2 for n in sizes)
 
 
-def eval_finish(acc, samples: int, nx: int, ny: int, T: int, C: int, ilow: int = 4, ihigh: int = 12):
+def eval_finish(acc, samples: int, *dims: int, ilow: int = 4, ihigh: int = 12):
     """the dict of RolloutEvaluator.read() from the accumulated sums (`acc`: float64 array of eval_acc_layout's words, the
-    count word ignored; `samples`: the count): the means over the samples, the root of the mean shell sums over nx ny, and
-    the three band means (an empty band is NaN, as torch.mean of an empty slice in the reference).  float32 arrays with
-    the reference's shapes: nmae.. [1, C], nmae_t.. [1, T, C], fmse_* [T, C], bdmse [C, T] (the reference returns the
-    boundary error untransposed)."""
+    count word ignored; `samples`: the count; dims = (X, Y[, Z], T, C), or (X, Y[, Z], T, C, ilow, ihigh) with both band
+    limits behind them - 4 or 5 numbers without, 6 or 7 with, so the count tells): the means over the samples, the root of the mean
+    shell sums over the product of the spatial sizes, and the three band means (an empty band is NaN, as torch.mean of an
+    empty slice in the reference).  float32 arrays with the reference's shapes: nmae.. [1, C], nmae_t.. [1, T, C], fmse_*
+    [T, C], bdmse [C, T] (the reference returns the boundary error - of a field: on the six faces - untransposed)."""
     import numpy as np
     import warnings
+    if len(dims) in (6, 7):
+        *dims, ilow, ihigh = dims
+    *sizes, T, C = dims
     acc = np.asarray(acc, dtype=np.float64)
-    off, total = eval_acc_layout(nx, ny, T, C)
+    off, total = eval_acc_layout(*dims)
     if acc.shape != (total,):
-        raise ValueError(f"eval_finish: the accumulator of {nx}x{ny}, T={T}, C={C} has {total} words, got {acc.shape}")
-    K = min(nx // 2, ny // 2)
+        raise ValueError(f"eval_finish: the accumulator of {'x'.join(map(str, sizes))}, T={T}, C={C} has {total} words, got "
+                         f"{acc.shape}")
     n = float(samples) if samples else float("nan")
     c = acc[off["c"]:off["tc"]].reshape(3, C) / n
     tc = acc[off["tc"]:off["spec"]].reshape(4, T, C) / n
-    shells = np.sqrt(acc[off["spec"]:].reshape(T, C, K) / n) / float(nx * ny)
+    shells = np.sqrt(acc[off["spec"]:].reshape(T, C, -1) / n) / float(np.prod(sizes, dtype=np.int64))
     out = {"nmae": c[0:1], "nmse": c[1:2], "nmxe": c[2:3], "nmae_t": tc[0:1], "nmse_t": tc[1:2], "nmxe_t": tc[2:3],
            "bdmse": tc[3].T}
     with warnings.catch_warnings():
@@ -2186,301 +2236,119 @@ def eval_finish(acc, samples: int, nx: int, ny: int, T: int, C: int, ilow: int =
 
 
 class EvalPlan:
-    """The tables of dpot_eval_metrics_stats for one plane size, built in float64, rounded to fp32, zero-padded to the kernel's
-    tile multiples and kept in device memory.  `host_tables` is the host part alone."""
+    """The tables of dpot_eval_metrics_stats / dpot_eval3_stats for one plane or field size, built in float64, rounded to
+    fp32, zero-padded to the kernels' tile multiples and kept in device memory.  `host_tables` is the host part alone."""
 
     @staticmethod
-    def pads(nx: int, ny: int):
-        """(nxp, nyp, hxp, hyp): the contraction extents and the wavenumber extents nx // 2, ny // 2, each rounded up to 16 -
-        the values dpot_eval_metrics_pad returns (checked when a plan is built)"""
+    def pads(*sizes: int):
+        """(nxp, nyp[, nzp], hxp, hyp[, hzp]): the contraction extents and the wavenumber extents n // 2, each rounded up to
+        16 - the values the library's pad entry point returns (checked when a plan is built)"""
         r = lambda n: (n + 15) // 16 * 16
-        return r(nx), r(ny), r(nx // 2), r(ny // 2)
+        return tuple(r(n) for n in sizes) + tuple(r(n // 2) for n in sizes)
 
     @staticmethod
-    def host_tables(nx: int, ny: int):
-        """dict of numpy arrays: cxT, sxT fp32 [nxp, hxp], cy, sy fp32 [nyp, hyp], jlo int32 [nx // 2, K + 1]"""
+    def host_tables(*sizes: int):
+        """dict of numpy arrays: cxT, sxT fp32 [nxp, hxp], cy, sy fp32 [nyp, hyp], for a field czT, szT fp32 [nzp, hzp], and
+        jlo int32 = eval_shell_ranges"""
         import numpy as np
-        nxp, nyp, hxp, hyp = EvalPlan.pads(nx, ny)
+        rank, pads, out = _eval_rank("EvalPlan", sizes), EvalPlan.pads(*sizes), {}
+        for a, (axis, n) in enumerate(zip(rank.axes, sizes)):
+            for name, tab in zip("cs", eval_dft_tables(n)):
+                t = out[name + axis] = np.zeros((pads[a], pads[len(sizes) + a]), dtype=np.float32)
+                t[:n, :n // 2] = tab.T.astype(np.float32)
+        out["jlo"] = eval_shell_ranges(*sizes)
+        return out
 
-        def padded(a, shape):
-            outp = np.zeros(shape, dtype=np.float32)
-            outp[:a.shape[0], :a.shape[1]] = a.astype(np.float32)
-            return outp
-
-        cx, sx = eval_dft_tables(nx)
-        cy, sy = eval_dft_tables(ny)
-        return {"cxT": padded(cx.T, (nxp, hxp)), "sxT": padded(sx.T, (nxp, hxp)), "cy": padded(cy.T, (nyp, hyp)),
-                "sy": padded(sy.T, (nyp, hyp)), "jlo": np.ascontiguousarray(eval_shell_ranges(nx, ny))}
-
-    def __init__(self, nx: int, ny: int, device):
+    def __init__(self, *sizes_device):
+        *sizes, device = sizes_device
+        sizes = tuple(sizes)
         lib = _lib.load()
-        self.sizes = (nx, ny)
-        if nx > lib.dpot_eval_metrics_max_size(0) or ny > lib.dpot_eval_metrics_max_size(1):
-            raise _lib.DpotHipError(f"eval_metrics: a {nx} x {ny} plane is beyond the supported size (nx <= "
-                                    f"{lib.dpot_eval_metrics_max_size(0)}, ny <= {lib.dpot_eval_metrics_max_size(1)}: the LDS "
-                                    "intermediate of a workgroup)")
-        want = (lib.dpot_eval_metrics_pad(nx, 0), lib.dpot_eval_metrics_pad(ny, 0), lib.dpot_eval_metrics_pad(nx, 1),
-                lib.dpot_eval_metrics_pad(ny, 1))
-        if want != self.pads(nx, ny):
-            raise _lib.DpotHipError(f"EvalPlan: the library pads {self.sizes} to {want}, this module to {self.pads(nx, ny)}")
+        self.sizes, self.rank = sizes, _eval_rank("EvalPlan", sizes)
+        limits = [getattr(lib, self.rank.max_size)(a) for a in range(len(sizes))]
+        if any(n > m for n, m in zip(sizes, limits)):
+            raise _lib.DpotHipError(f"eval_metrics: a {' x '.join(map(str, sizes))} {self.rank.noun} is beyond the supported "
+                                    f"size ({self.rank.limits.format(*limits)})")
+        want = tuple(getattr(lib, self.rank.pad)(n, h) for h in (0, 1) for n in sizes)
+        if want != self.pads(*sizes):
+            raise _lib.DpotHipError(f"EvalPlan: the library pads {sizes} to {want}, this module to {self.pads(*sizes)}")
         if torch.cuda.is_current_stream_capturing():
-            raise _lib.DpotHipError(f"EvalPlan {self.sizes}: the tables are uploaded when a plane size is first used - call "
-                                    "ops.eval_plan(...) (or one update) before capturing")
-        self.n_stripes = want[2] // 16
-        self.K = min(nx // 2, ny // 2)
+            raise _lib.DpotHipError(f"EvalPlan {sizes}: the tables are uploaded when a {self.rank.noun} size is first used - "
+                                    "call ops.eval_plan(...) (or one update) before capturing")
         self.dev = {}
-        for name, a in self.host_tables(nx, ny).items():
+        for name, a in self.host_tables(*sizes).items():
             t = torch.empty(a.shape, dtype=torch.int32 if name == "jlo" else torch.float32, device=device)
             t.copy_(torch.from_numpy(a))
             self.dev[name] = t
         self.work = {}
 
     def workspace(self, B: int, TC: int, device):
-        """(statp, specp) of a batch size: allocated when it is first seen (not under capture), then reused"""
+        """the buffers of a batch size between the two launches - statp (doubles), then the fp32 ones, in the order the
+        stats entry point takes them: allocated when the size is first seen (not under capture), then reused"""
         w = self.work.get((B, TC))
         if w is None:
             if torch.cuda.is_current_stream_capturing():
                 raise _lib.DpotHipError(f"EvalPlan {self.sizes}: the workspace of B={B}, T*C={TC} is allocated when that shape "
                                         "is first used - run one update before capturing")
-            w = self.work[(B, TC)] = (torch.empty(B * TC * self.n_stripes * 8, dtype=torch.float64, device=device),
-                                      torch.empty(B * TC * self.n_stripes * self.K, dtype=torch.float32, device=device))
+            n = self.rank.work(_lib.load(), B, *self.sizes, TC)
+            if min(n) < 1:
+                raise _lib.DpotHipError(f"EvalPlan {self.sizes}: the library sizes no workspace for B={B}, T*C={TC}")
+            w = self.work[(B, TC)] = tuple(torch.empty(m, dtype=torch.float32 if i else torch.float64, device=device)
+                                           for i, m in enumerate(n))
         return w
 
 
 _eval_plans = {}
 
 
-def eval_plan(nx: int, ny: int, device) -> EvalPlan:
-    """the cached EvalPlan of (n_x, n_y, device)"""
+def eval_plan(*sizes_device) -> EvalPlan:
+    """the cached EvalPlan of (n_x, n_y[, n_z], device)"""
+    *sizes, device = sizes_device
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    key = (int(nx), int(ny), device)
+    key = tuple(int(n) for n in sizes) + (device,)
     plan = _eval_plans.get(key)
     if plan is None:
         plan = _eval_plans[key] = EvalPlan(*key)
     return plan
 
 
-def eval_acc_alloc(nx: int, ny: int, T: int, C: int, device) -> Tensor:
-    """a zeroed accumulator for eval_metrics_update (int64 words; word 0 the sample count, the rest doubles)"""
-    n = eval_acc_layout(nx, ny, T, C)[1]
-    if n != _lib.load().dpot_eval_metrics_acc_elems(nx, ny, T, C):
-        raise _lib.DpotHipError(f"eval_acc_alloc: the library lays the accumulator of {nx}x{ny}, T={T}, C={C} out differently")
+def eval_acc_alloc(*dims_device) -> Tensor:
+    """a zeroed accumulator of (X, Y[, Z], T, C, device) for eval_metrics_update (int64 words; word 0 the sample count, the
+    rest doubles)"""
+    *dims, device = dims_device
+    n = eval_acc_layout(*dims)[1]
+    if n != getattr(_lib.load(), _eval_rank("eval_acc_alloc", dims[:-2]).acc_elems)(*dims):
+        raise _lib.DpotHipError(f"eval_acc_alloc: the library lays the accumulator of {'x'.join(map(str, dims[:-2]))}, "
+                                f"T={dims[-2]}, C={dims[-1]} out differently")
     return torch.zeros(n, dtype=torch.int64, device=device)
 
 
 def eval_metrics_update(pred: Tensor, target: Tensor, acc: Tensor) -> None:
-    """acc += the Evaluator sums of this batch: pred, target [B, X, Y, T, C] fp32 contiguous on the GPU, acc from
-    eval_acc_alloc for the same (X, Y, T, C).  Two launches on the current stream, no synchronisation; capturable once the
-    plane size and the batch size have been seen (their tables and workspace are cached)."""
+    """acc += the Evaluator sums of this batch: pred, target [B, X, Y, T, C] or [B, X, Y, Z, T, C] fp32 contiguous on the
+    GPU, acc from eval_acc_alloc for the same (X, Y[, Z], T, C).  Two launches (a field: three) on the current stream, no
+    synchronisation; capturable once the spatial size and the batch size have been seen (their tables and workspace are
+    cached)."""
     _req(pred, "eval_metrics: pred")
     _req(target, "eval_metrics: target")
-    if pred.dim() != 5 or pred.shape != target.shape or pred.device != target.device:
-        raise _lib.DpotHipError(f"eval_metrics: pred and target must be [B, X, Y, T, C] of one shape on one device, got "
-                                f"{tuple(pred.shape)} on {pred.device} and {tuple(target.shape)} on {target.device}")
-    B, nx, ny, T, C = pred.shape
-    if min(B, T, C) < 1 or min(nx, ny) < 2:
+    rank = _EVAL_RANKS.get(pred.dim() - 3)
+    if rank is None or pred.shape != target.shape or pred.device != target.device:
+        raise _lib.DpotHipError(f"eval_metrics: pred and target must be [B, X, Y, T, C] or [B, X, Y, Z, T, C] of one shape on "
+                                f"one device, got {tuple(pred.shape)} on {pred.device} and {tuple(target.shape)} on "
+                                f"{target.device}")
+    B, *dims = pred.shape
+    *sizes, T, C = dims
+    if min(B, T, C) < 1 or min(sizes) < 2:
         raise _lib.DpotHipError(f"eval_metrics: cannot evaluate {tuple(pred.shape)}: every spatial size must be >= 2 and no "
                                 "dimension empty")
+    words = eval_acc_layout(*dims)[1]
     if (not acc.is_cuda or acc.device != pred.device or acc.dtype != torch.int64 or not acc.is_contiguous()
-            or acc.numel() != eval_acc_layout(nx, ny, T, C)[1]):
-        raise _lib.DpotHipError(f"eval_metrics: acc must be the {eval_acc_layout(nx, ny, T, C)[1]} int64 words of "
-                                f"eval_acc_alloc({nx}, {ny}, {T}, {C}) on {pred.device}")
-    plan = eval_plan(nx, ny, pred.device)
-    statp, specp = plan.workspace(B, T * C, pred.device)
-    d, lib = plan.dev, _lib.load()
-    check(lib.dpot_eval_metrics_stats(pred.data_ptr(), target.data_ptr(), d["cxT"].data_ptr(), d["sxT"].data_ptr(),
-                                      d["cy"].data_ptr(), d["sy"].data_ptr(), d["jlo"].data_ptr(), statp.data_ptr(),
-                                      specp.data_ptr(), B, nx, ny, T * C, _stream()), "eval_metrics_stats")
-    check(lib.dpot_eval_metrics_finalize(statp.data_ptr(), specp.data_ptr(), acc.data_ptr(), B, nx, ny, T, C, _stream()),
-          "eval_metrics_finalize")
-
-
-# ------------------------------------------------------------------------------------------------------
-# The same metric set for 3-D rollouts [B, X, Y, Z, T, C] (csrc/evalmetrics3d.hip): column c of every key is the reference's
-# Evaluator(temporal=True, griddata=True, component=c).  eval_dft_tables serves all three axes.
-# ------------------------------------------------------------------------------------------------------
-def eval3_shell_table(nx: int, ny: int, nz: int):
-    """int32 [nx // 2, ny // 2, nz // 2]: the shell floor(sqrt(i^2 + j^2 + k^2)) of wavenumber (i, j, k) of the positive
-    octant, or -1 where that shell is >= K = min(nx // 2, ny // 2, nz // 2) and the reference drops the wavenumber.  Integer
-    arithmetic, as eval_shell_table."""
-    import numpy as np
-    if min(nx, ny, nz) < 2:
-        raise ValueError(f"eval3_shell_table: sizes must be >= 2, got {nx} x {ny} x {nz}")
-    i = np.arange(nx // 2, dtype=np.int64)[:, None, None]
-    j = np.arange(ny // 2, dtype=np.int64)[None, :, None]
-    k = np.arange(nz // 2, dtype=np.int64)[None, None, :]
-    v = i * i + j * j + k * k
-    s = np.sqrt(v.astype(np.float64)).astype(np.int64)
-    s -= (s * s > v)
-    s += ((s + 1) * (s + 1) <= v)
-    assert ((s * s <= v) & ((s + 1) * (s + 1) > v)).all()
-    K = min(nx // 2, ny // 2, nz // 2)
-    return np.where(s < K, s, -1).astype(np.int32)
-
-
-def eval3_shell_ranges(nx: int, ny: int, nz: int):
-    """int32 [nz // 2, nx // 2, K + 1]: entry [k, i, s] = number of j in [0, ny // 2) whose shell in row (k, i) is below s.
-    The shell grows with j, so the members of shell s in row (k, i) are the j range [k, i, s] .. [k, i, s + 1]; what lies at
-    or beyond [k, i, K] is dropped.  This is the form of eval3_shell_table the kernel walks."""
-    import numpy as np
-    sh = eval3_shell_table(nx, ny, nz).astype(np.int64)
-    K = min(nx // 2, ny // 2, nz // 2)
-    sh = np.where(sh < 0, K, sh)                                   # dropped: beyond every kept shell
-    out = np.empty((nz // 2, nx // 2, K + 1), dtype=np.int32)
-    for s in range(K + 1):
-        out[:, :, s] = (sh < s).sum(axis=1).T
-    return out
-
-
-def eval3_acc_layout(nx: int, ny: int, nz: int, T: int, C: int):
-    """(offsets, total) of the accumulator in 8-byte words - eval_acc_layout with K = min(nx // 2, ny // 2, nz // 2)"""
-    K = min(nx // 2, ny // 2, nz // 2)
-    off = {"count": 0, "c": 2, "tc": 2 + 3 * C, "spec": 2 + 3 * C + 4 * T * C}
-    return off, 2 + 3 * C + 4 * T * C + T * C * K
-
-
-def eval3_finish(acc, samples: int, nx: int, ny: int, nz: int, T: int, C: int, ilow: int = 4, ihigh: int = 12):
-    """the dict of RolloutEvaluator.read() for 3-D fields from the accumulated sums (eval_finish with one more axis: the root
-    of the mean shell sums over nx ny nz; `bdmse` [C, T] is the error on the six faces)"""
-    import numpy as np
-    import warnings
-    acc = np.asarray(acc, dtype=np.float64)
-    off, total = eval3_acc_layout(nx, ny, nz, T, C)
-    if acc.shape != (total,):
-        raise ValueError(f"eval3_finish: the accumulator of {nx}x{ny}x{nz}, T={T}, C={C} has {total} words, got {acc.shape}")
-    K = min(nx // 2, ny // 2, nz // 2)
-    n = float(samples) if samples else float("nan")
-    c = acc[off["c"]:off["tc"]].reshape(3, C) / n
-    tc = acc[off["tc"]:off["spec"]].reshape(4, T, C) / n
-    shells = np.sqrt(acc[off["spec"]:].reshape(T, C, K) / n) / float(nx * ny * nz)
-    out = {"nmae": c[0:1], "nmse": c[1:2], "nmxe": c[2:3], "nmae_t": tc[0:1], "nmse_t": tc[1:2], "nmxe_t": tc[2:3],
-           "bdmse": tc[3].T}
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", RuntimeWarning)            # the mean of an empty band IS NaN
-        for key, band in (("fmse_low", shells[..., :ilow]), ("fmse_mid", shells[..., ilow:ihigh]),
-                          ("fmse_high", shells[..., ihigh:])):
-            out[key] = band.mean(axis=-1) if band.shape[-1] else np.full((T, C), np.nan)
-    out = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
-    out["samples"] = int(samples)
-    return out
-
-
-class Eval3Plan:
-    """The tables of dpot_eval3_stats for one field size, built in float64, rounded to fp32, zero-padded to the kernel's tile
-    multiples and kept in device memory.  `host_tables` is the host part alone."""
-
-    @staticmethod
-    def pads(nx: int, ny: int, nz: int):
-        """(nxp, nyp, nzp, hxp, hyp, hzp): the contraction extents and the wavenumber extents n // 2, each rounded up to 16 -
-        the values dpot_eval3_pad returns (checked when a plan is built)"""
-        r = lambda n: (n + 15) // 16 * 16
-        return r(nx), r(ny), r(nz), r(nx // 2), r(ny // 2), r(nz // 2)
-
-    @staticmethod
-    def host_tables(nx: int, ny: int, nz: int):
-        """dict of numpy arrays: cxT, sxT fp32 [nxp, hxp], cy, sy fp32 [nyp, hyp], czT, szT fp32 [nzp, hzp], jlo int32
-        [nz // 2, nx // 2, K + 1]"""
-        import numpy as np
-        nxp, nyp, nzp, hxp, hyp, hzp = Eval3Plan.pads(nx, ny, nz)
-
-        def padded(a, shape):
-            outp = np.zeros(shape, dtype=np.float32)
-            outp[:a.shape[0], :a.shape[1]] = a.astype(np.float32)
-            return outp
-
-        cx, sx = eval_dft_tables(nx)
-        cy, sy = eval_dft_tables(ny)
-        cz, sz = eval_dft_tables(nz)
-        return {"cxT": padded(cx.T, (nxp, hxp)), "sxT": padded(sx.T, (nxp, hxp)), "cy": padded(cy.T, (nyp, hyp)),
-                "sy": padded(sy.T, (nyp, hyp)), "czT": padded(cz.T, (nzp, hzp)), "szT": padded(sz.T, (nzp, hzp)),
-                "jlo": np.ascontiguousarray(eval3_shell_ranges(nx, ny, nz))}
-
-    def __init__(self, nx: int, ny: int, nz: int, device):
-        lib = _lib.load()
-        self.sizes = (nx, ny, nz)
-        limits = tuple(lib.dpot_eval3_max_size(a) for a in range(3))
-        if nx > limits[0] or ny > limits[1] or nz > limits[2]:
-            raise _lib.DpotHipError(f"eval3_metrics: a {nx} x {ny} x {nz} field is beyond the supported size (nx <= "
-                                    f"{limits[0]}; ny <= {limits[1]}: the LDS intermediate of a workgroup; nz <= {limits[2]})")
-        want = tuple(lib.dpot_eval3_pad(n, h) for h in (0, 1) for n in self.sizes)
-        if want != self.pads(nx, ny, nz):
-            raise _lib.DpotHipError(f"Eval3Plan: the library pads {self.sizes} to {want}, this module to "
-                                    f"{self.pads(nx, ny, nz)}")
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.DpotHipError(f"Eval3Plan {self.sizes}: the tables are uploaded when a field size is first used - call "
-                                    "ops.eval3_plan(...) (or one update) before capturing")
-        self.dev = {}
-        for name, a in self.host_tables(nx, ny, nz).items():
-            t = torch.empty(a.shape, dtype=torch.int32 if name == "jlo" else torch.float32, device=device)
-            t.copy_(torch.from_numpy(a))
-            self.dev[name] = t
-        self.work = {}
-
-    def workspace(self, B: int, TC: int, device):
-        """(statp, specp, G) of a batch size: allocated when it is first seen (not under capture), then reused"""
-        w = self.work.get((B, TC))
-        if w is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise _lib.DpotHipError(f"Eval3Plan {self.sizes}: the workspace of B={B}, T*C={TC} is allocated when that "
-                                        "shape is first used - run one update before capturing")
-            n = [_lib.load().dpot_eval3_work_elems(which, B, *self.sizes, TC) for which in range(3)]
-            if min(n) < 1:
-                raise _lib.DpotHipError(f"Eval3Plan {self.sizes}: the library sizes no workspace for B={B}, T*C={TC}")
-            w = self.work[(B, TC)] = (torch.empty(n[0], dtype=torch.float64, device=device),
-                                      torch.empty(n[1], dtype=torch.float32, device=device),
-                                      torch.empty(n[2], dtype=torch.float32, device=device))
-        return w
-
-
-_eval3_plans = {}
-
-
-def eval3_plan(nx: int, ny: int, nz: int, device) -> Eval3Plan:
-    """the cached Eval3Plan of (n_x, n_y, n_z, device)"""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (int(nx), int(ny), int(nz), device)
-    plan = _eval3_plans.get(key)
-    if plan is None:
-        plan = _eval3_plans[key] = Eval3Plan(*key)
-    return plan
-
-
-def eval3_acc_alloc(nx: int, ny: int, nz: int, T: int, C: int, device) -> Tensor:
-    """a zeroed accumulator for eval3_metrics_update (int64 words; word 0 the sample count, the rest doubles)"""
-    n = eval3_acc_layout(nx, ny, nz, T, C)[1]
-    if n != _lib.load().dpot_eval3_acc_elems(nx, ny, nz, T, C):
-        raise _lib.DpotHipError(f"eval3_acc_alloc: the library lays the accumulator of {nx}x{ny}x{nz}, T={T}, C={C} out "
-                                "differently")
-    return torch.zeros(n, dtype=torch.int64, device=device)
-
-
-def eval3_metrics_update(pred: Tensor, target: Tensor, acc: Tensor) -> None:
-    """acc += the Evaluator sums of this batch: pred, target [B, X, Y, Z, T, C] fp32 contiguous on the GPU, acc from
-    eval3_acc_alloc for the same (X, Y, Z, T, C).  Three launches on the current stream, no synchronisation; capturable once
-    the field size and the batch size have been seen (their tables and workspace are cached)."""
-    _req(pred, "eval3_metrics: pred")
-    _req(target, "eval3_metrics: target")
-    if pred.dim() != 6 or pred.shape != target.shape or pred.device != target.device:
-        raise _lib.DpotHipError(f"eval3_metrics: pred and target must be [B, X, Y, Z, T, C] of one shape on one device, got "
-                                f"{tuple(pred.shape)} on {pred.device} and {tuple(target.shape)} on {target.device}")
-    B, nx, ny, nz, T, C = pred.shape
-    if min(B, T, C) < 1 or min(nx, ny, nz) < 2:
-        raise _lib.DpotHipError(f"eval3_metrics: cannot evaluate {tuple(pred.shape)}: every spatial size must be >= 2 and no "
-                                "dimension empty")
-    if (not acc.is_cuda or acc.device != pred.device or acc.dtype != torch.int64 or not acc.is_contiguous()
-            or acc.numel() != eval3_acc_layout(nx, ny, nz, T, C)[1]):
-        raise _lib.DpotHipError(f"eval3_metrics: acc must be the {eval3_acc_layout(nx, ny, nz, T, C)[1]} int64 words of "
-                                f"eval3_acc_alloc({nx}, {ny}, {nz}, {T}, {C}) on {pred.device}")
-    plan = eval3_plan(nx, ny, nz, pred.device)
-    statp, specp, G = plan.workspace(B, T * C, pred.device)
-    d, lib = plan.dev, _lib.load()
-    check(lib.dpot_eval3_stats(pred.data_ptr(), target.data_ptr(), d["cxT"].data_ptr(), d["sxT"].data_ptr(),
-                               d["cy"].data_ptr(), d["sy"].data_ptr(), d["czT"].data_ptr(), d["szT"].data_ptr(),
-                               d["jlo"].data_ptr(), statp.data_ptr(), specp.data_ptr(), G.data_ptr(), B, nx, ny, nz, T * C,
-                               _stream()), "eval3_stats")
-    check(lib.dpot_eval3_finalize(statp.data_ptr(), specp.data_ptr(), acc.data_ptr(), B, nx, ny, nz, T, C, _stream()),
-          "eval3_finalize")
+            or acc.numel() != words):
+        raise _lib.DpotHipError(f"eval_metrics: acc must be the {words} int64 words of eval_acc_alloc"
+                                f"({', '.join(map(str, dims))}) on {pred.device}")
+    plan = eval_plan(*sizes, pred.device)
+    work = [w.data_ptr() for w in plan.workspace(B, T * C, pred.device)]
+    lib = _lib.load()
+    check(getattr(lib, rank.stats)(pred.data_ptr(), target.data_ptr(), *(t.data_ptr() for t in plan.dev.values()), *work, B,
+                                   *sizes, T * C, _stream()), rank.stats[5:])
+    check(getattr(lib, rank.finalize)(work[0], work[1], acc.data_ptr(), B, *sizes, T, C, _stream()), rank.finalize[5:])

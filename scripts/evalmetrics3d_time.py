@@ -40,7 +40,7 @@ class Yardstick:
         sizes, (T, C) = shape[1:-2], shape[-2:]
         self.sp = tuple(range(1, 1 + len(sizes)))
         self.K = min(n // 2 for n in sizes)
-        sh = (ops.eval3_shell_table(*sizes) if len(sizes) == 3 else ops.eval_shell_table(*sizes)).astype(np.int64)
+        sh = ops.eval_shell_table(*sizes).astype(np.int64)
         self.idx = torch.from_numpy(np.where(sh < 0, self.K, sh).reshape(-1)).to(device)      # dropped -> a spare shell
         self.faces = float(2 * sum(sizes)) if len(sizes) == 2 else float(
             2 * (sizes[0] * sizes[1] + sizes[1] * sizes[2] + sizes[2] * sizes[0]))
@@ -125,7 +125,7 @@ def main():
         ev.update(pred, target)
         ys.update(pred, target)
         got = ev.read()
-        want = (ops.eval3_finish if three else ops.eval_finish)(ys.acc_vector(), ys.count, *shape[1:])
+        want = ops.eval_finish(ys.acc_vector(), ys.count, *shape[1:])
         dev_max = max(float(np.nanmax(np.abs(got[k] - want[k]) / np.abs(want[k]))) for k in ops.EVAL_KEYS
                       if np.isfinite(want[k]).any())
         for _ in range(3):

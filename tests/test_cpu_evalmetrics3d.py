@@ -94,7 +94,7 @@ def test_shell_table_is_the_integer_square_root(sizes):
     nx, ny, nz = sizes
     hx, hy, hz = nx // 2, ny // 2, nz // 2
     K = min(hx, hy, hz)
-    tab = ops.eval3_shell_table(nx, ny, nz)
+    tab = ops.eval_shell_table(nx, ny, nz)
     assert tab.shape == (hx, hy, hz) and tab.dtype == np.int32
     dropped = 0
     for i in range(hx):
@@ -105,7 +105,7 @@ def test_shell_table_is_the_integer_square_root(sizes):
                 dropped += s >= K
     assert (tab == -1).sum() == dropped > 0                        # the far corner of the octant lies beyond shell K - 1
     # the range form the kernel walks describes the same table: row (k, i), shell s = the j range [k, i, s] .. [k, i, s + 1]
-    rng = ops.eval3_shell_ranges(nx, ny, nz)
+    rng = ops.eval_shell_ranges(nx, ny, nz)
     assert rng.shape == (hz, hx, K + 1) and rng.dtype == np.int32
     rebuilt = np.full_like(tab, -1)
     for k in range(hz):
@@ -115,7 +115,7 @@ def test_shell_table_is_the_integer_square_root(sizes):
                 rebuilt[i, rng[k, i, s]:rng[k, i, s + 1], k] = s
     assert np.array_equal(rebuilt, tab)
     with pytest.raises(ValueError):
-        ops.eval3_shell_table(nx, 1, nz)
+        ops.eval_shell_table(nx, 1, nz)
 
 
 @pytest.mark.parametrize("sizes", [(6, 5, 7), (8, 8, 8), (10, 12, 9), (20, 33, 26), (16, 40, 12)])
@@ -136,10 +136,10 @@ def test_dft_tables_along_three_axes_reproduce_fftn_on_the_positive_octant(sizes
     scale = np.abs(want).max()
     assert np.abs(re - want.real).max() <= 1e-12 * scale and np.abs(im - want.imag).max() <= 1e-12 * scale
     # what the kernels receive: fp32, transposed where they want them K-major, zero in the padding
-    pads = ops.Eval3Plan.pads(nx, ny, nz)
+    pads = ops.EvalPlan.pads(nx, ny, nz)
     assert all(v % 16 == 0 for v in pads) and pads[0] >= nx and pads[4] >= hy and pads[5] - hz < 16
     nxp, nyp, nzp, hxp, hyp, hzp = pads
-    h = ops.Eval3Plan.host_tables(nx, ny, nz)
+    h = ops.EvalPlan.host_tables(nx, ny, nz)
     for key, full, used, src in (("cxT", (nxp, hxp), (nx, hx), cx.T), ("sxT", (nxp, hxp), (nx, hx), sx.T),
                                  ("cy", (nyp, hyp), (ny, hy), cy.T), ("sy", (nyp, hyp), (ny, hy), sy.T),
                                  ("czT", (nzp, hzp), (nz, hz), cz.T), ("szT", (nzp, hzp), (nz, hz), sz.T)):
@@ -149,13 +149,13 @@ def test_dft_tables_along_three_axes_reproduce_fftn_on_the_positive_octant(sizes
         pad[:used[0], :used[1]] = False
         assert not a[pad].any(), f"{key}: non-zero padding"
         assert np.array_equal(a[:used[0], :used[1]], src.astype(np.float32)), key
-    assert np.array_equal(h["jlo"], ops.eval3_shell_ranges(nx, ny, nz)) and h["jlo"].flags["C_CONTIGUOUS"]
+    assert np.array_equal(h["jlo"], ops.eval_shell_ranges(nx, ny, nz)) and h["jlo"].flags["C_CONTIGUOUS"]
 
 
 def acc_vector(sums, nx, ny, nz, T, C):
-    """tests/eval3d_ref.batch_sums laid out as the device accumulator (ops.eval3_acc_layout)"""
+    """tests/eval3d_ref.batch_sums laid out as the device accumulator (ops.eval_acc_layout)"""
     from dpot_amd import ops
-    off, total = ops.eval3_acc_layout(nx, ny, nz, T, C)
+    off, total = ops.eval_acc_layout(nx, ny, nz, T, C)
     acc = np.zeros(total)
     acc[off["c"]:off["tc"]] = sums["c"].reshape(-1)
     acc[off["tc"]:off["spec"]] = sums["tc"].reshape(-1)
@@ -165,7 +165,7 @@ def acc_vector(sums, nx, ny, nz, T, C):
 
 @pytest.mark.parametrize("name", ["two_batches", "o6x5x7_t3c2", "r10x12x9_t2c3"])
 def test_read_arithmetic_and_batch_additivity(name):
-    """the numpy model of read() (ops.eval3_finish) on sums added over two batches equals eval_ref and the reference on the
+    """the numpy model of read() (ops.eval_finish) on sums added over two batches equals eval_ref and the reference on the
     concatenation; shapes and dtypes are the 2-D evaluator's"""
     from dpot_amd import ops
     fx = load(FIXTURE)
@@ -175,7 +175,7 @@ def test_read_arithmetic_and_batch_additivity(name):
     cut = 1 if B < 3 else 2
     s = E.add_sums(E.batch_sums(p[:cut], t[:cut]), E.batch_sums(p[cut:], t[cut:]))
     assert s["count"] == B
-    got = ops.eval3_finish(acc_vector(s, nx, ny, nz, T, C), B, nx, ny, nz, T, C, ilow, ihigh)
+    got = ops.eval_finish(acc_vector(s, nx, ny, nz, T, C), B, nx, ny, nz, T, C, ilow, ihigh)
     ref = E.eval_ref(p, t, ilow, ihigh)
     assert got["samples"] == B and set(got) == set(E.KEYS) | {"samples"} and set(ops.EVAL_KEYS) == set(E.KEYS)
     for key in E.KEYS:
@@ -186,8 +186,8 @@ def test_read_arithmetic_and_batch_additivity(name):
         assert (np.abs(got[key][fin] - want[fin]) <= 2.0 ** -23 * np.abs(want[fin])).all(), key     # one fp32 rounding
         assert (np.abs(got[key][fin] - ref[key][fin]) <= 2.0 ** -23 * np.abs(ref[key][fin])).all(), key
     with pytest.raises(ValueError):
-        ops.eval3_finish(np.zeros(3), 1, nx, ny, nz, T, C)
-    none = ops.eval3_finish(np.zeros(ops.eval3_acc_layout(nx, ny, nz, T, C)[1]), 0, nx, ny, nz, T, C, ilow, ihigh)
+        ops.eval_finish(np.zeros(3), 1, nx, ny, nz, T, C)
+    none = ops.eval_finish(np.zeros(ops.eval_acc_layout(nx, ny, nz, T, C)[1]), 0, nx, ny, nz, T, C, ilow, ihigh)
     assert none["samples"] == 0 and np.isnan(none["nmae"]).all()
 
 
@@ -210,12 +210,12 @@ def test_cpu_tensors_and_bad_arguments_raise():
         ev.read()                                                  # nothing to read
     acc = torch.zeros(4, dtype=torch.int64)
     with pytest.raises(_lib.DpotHipError, match="MI355X"):
-        ops.eval3_metrics_update(z, z, acc)
+        ops.eval_metrics_update(z, z, acc)
     for bad in (z.double(), z.transpose(1, 2)):
         with pytest.raises(_lib.DpotHipError):
-            ops.eval3_metrics_update(bad, bad, acc)
+            ops.eval_metrics_update(bad, bad, acc)
     with pytest.raises(ValueError):
-        ops.eval3_shell_ranges(1, 8, 8)
+        ops.eval_shell_ranges(1, 8, 8)
 
 
 def test_rollout_eval_takes_an_evaluator_but_no_model_res_for_6d_windows():
@@ -249,7 +249,7 @@ def test_abi_has_the_eval3_entry_points():
     limits = [lib.dpot_eval3_max_size(a) for a in range(3)]
     assert min(limits) >= 128                                      # 128^3: the raw resolution of the reference's 3-D data
     for shape in ((128, 128, 128, 1, 4), (6, 5, 7, 3, 2), (16, 300, 9, 1, 1)):
-        assert lib.dpot_eval3_acc_elems(*shape) == ops.eval3_acc_layout(*shape)[1]
+        assert lib.dpot_eval3_acc_elems(*shape) == ops.eval_acc_layout(*shape)[1]
     assert lib.dpot_eval3_acc_elems(8, 1, 8, 1, 1) == 0
     # the workspace of a batch: statistics partials, shell partials [B, TC, nz/2, stripes of 16 i, K], the half spectrum
     assert lib.dpot_eval3_work_elems(0, 2, 20, 33, 26, 3) % (2 * 3 * 8) == 0 and lib.dpot_eval3_work_elems(0, 2, 20, 33, 26, 3) > 0
@@ -267,3 +267,57 @@ def test_abi_has_the_eval3_entry_points():
         assert rc == -2 and b"beyond the supported size" in lib.dpot_last_error()
         assert f"{sizes[0]}x{sizes[1]}x{sizes[2]}".encode() in lib.dpot_last_error()
         assert lib.dpot_eval3_finalize(fake, fake, fake, 1, *sizes, 1, 1, None) == -2
+
+
+# ---- one host path for both ranks: what a plane and a field must agree on --------------------------------------------
+RANK_SIZES = [(6, 5, 7), (9, 11, 10), (16, 16, 16), (17, 40, 12), (12, 10, 8), (33, 16, 48)]
+
+
+@pytest.mark.parametrize("sizes", RANK_SIZES)
+def test_shell_tables_of_both_ranks_agree_on_the_plane_k_equals_0(sizes):
+    """k = 0 adds nothing to i^2 + j^2: the field's rows of k = 0 are the plane's, cut at the field's smaller K"""
+    from dpot_amd import ops
+    nx, ny, nz = sizes
+    K3 = min(nx // 2, ny // 2, nz // 2)
+    assert np.array_equal(ops.eval_shell_ranges(nx, ny, nz)[0], ops.eval_shell_ranges(nx, ny)[:, :K3 + 1])
+    plane = ops.eval_shell_table(nx, ny)
+    assert np.array_equal(ops.eval_shell_table(nx, ny, nz)[:, :, 0], np.where(plane >= K3, -1, plane))
+    for bad in ((nx,), (nx, ny, nz, 4)):
+        with pytest.raises(ValueError):
+            ops.eval_shell_table(*bad)
+
+
+@pytest.mark.parametrize("TC", [(1, 1), (3, 2), (10, 4)])
+@pytest.mark.parametrize("sizes", RANK_SIZES)
+def test_accumulator_layout_of_both_ranks_and_of_the_library(sizes, TC):
+    from dpot_amd import _lib, ops
+    lib = _lib.load()
+    (nx, ny, nz), (T, C) = sizes, TC
+    K2, K3 = min(nx // 2, ny // 2), min(nx // 2, ny // 2, nz // 2)
+    (off2, total2), (off3, total3) = ops.eval_acc_layout(nx, ny, T, C), ops.eval_acc_layout(nx, ny, nz, T, C)
+    assert off2 == off3 and total2 - total3 == T * C * (K2 - K3)
+    assert lib.dpot_eval_metrics_acc_elems(nx, ny, T, C) == total2
+    assert lib.dpot_eval3_acc_elems(nx, ny, nz, T, C) == total3
+
+
+@pytest.mark.parametrize("sizes", [(6, 5, 8), (9, 11, 16), (16, 16, 16)])
+def test_finish_of_both_ranks_differs_by_the_spectrum_divisor_alone(sizes):
+    """the same words read as the accumulator of a field and of its plane (nx, ny), whose K is the field's (nz // 2 is not the
+    smallest): fmse_* of the plane is nz times the field's, every other key is equal.  nz is a power of two, so the factor
+    is exact in every rounding on the way (a / (nx ny nz) = (a / (nx ny)) / nz bit for bit, the band mean and the float32
+    rounding commute with it)."""
+    from dpot_amd import ops
+    nx, ny, nz = sizes
+    T, C, B = 3, 2, 5
+    assert min(nx // 2, ny // 2) <= nz // 2 and nz & (nz - 1) == 0
+    total = ops.eval_acc_layout(nx, ny, nz, T, C)[1]
+    assert total == ops.eval_acc_layout(nx, ny, T, C)[1]
+    acc = np.random.RandomState(nx * 100 + nz).uniform(0.5, 40.0, total)
+    for ilow, ihigh in ((1, 2), (2, 5), (4, 12)):
+        field = ops.eval_finish(acc, B, nx, ny, nz, T, C, ilow, ihigh)
+        plane = ops.eval_finish(acc, B, nx, ny, T, C, ilow, ihigh)
+        assert set(field) == set(plane) == set(ops.EVAL_KEYS) | {"samples"} and field["samples"] == plane["samples"] == B
+        for key in ops.EVAL_KEYS:
+            want = field[key] * np.float32(nz) if key.startswith("fmse_") else field[key]
+            assert plane[key].dtype == np.float32 and np.array_equal(plane[key], want, equal_nan=True), (key, ilow, ihigh)
+        assert np.isfinite(field["fmse_low"]).all() and (field["fmse_low"] > 0).all()

@@ -1,4 +1,4 @@
-"""GPU tests of the 3-D evaluation metrics (csrc/evalmetrics3d.hip, ops.eval3_metrics_update, dpot_amd.RolloutEvaluator on
+"""GPU tests of the 3-D evaluation metrics (csrc/evalmetrics3d.hip, ops.eval_metrics_update, dpot_amd.RolloutEvaluator on
 [B, X, Y, Z, T, C] and the `evaluator=` argument of the 3-D rollouts): the fixture the reference wrote per component
 (g20_evalmetrics3d, its float64 results), the float64 restatement (tests/eval3d_ref.py), determinism, guards, accumulation
 over batches, graph replay, and the eager and graphed rollouts of a DPOTNet3D.  The op tests run on the guarded, poisoned
@@ -144,7 +144,7 @@ def test_largest_supported_size_and_one_beyond(axis, guarded):
     big = torch.zeros(1, *sizes, 1, 1, device="cuda")
     with pytest.raises(_lib.DpotHipError, match=f"{sizes[0]} x {sizes[1]} x {sizes[2]}"):
         RolloutEvaluator("cuda", n_channels=1, T_max=1).update(big, big)
-    d = ops.eval3_plan(16, 16, 16, "cuda").dev
+    d = ops.eval_plan(16, 16, 16, "cuda").dev
     statp = guard.full_nan((64,), dtype=torch.float64)
     specp, G = guard.full_nan((64,)), guard.full_nan((64,))
     rc = lib.dpot_eval3_stats(big.data_ptr(), big.data_ptr(), d["cxT"].data_ptr(), d["sxT"].data_ptr(), d["cy"].data_ptr(),
@@ -165,17 +165,17 @@ def test_update_is_deterministic_and_stays_inside_its_buffers(cube, TC, guarded)
     nx, ny, nz = cube
     p, t = fields((2, nx, ny, nz, 1, TC), 5, near=True)
     pd, td = guard.wrap(torch.from_numpy(p), "cuda"), guard.wrap(torch.from_numpy(t), "cuda")
-    a1, a2 = ops.eval3_acc_alloc(nx, ny, nz, 1, TC, "cuda"), ops.eval3_acc_alloc(nx, ny, nz, 1, TC, "cuda")
-    ops.eval3_metrics_update(pd, td, a1)
-    ops.eval3_metrics_update(pd, td, a2)
+    a1, a2 = ops.eval_acc_alloc(nx, ny, nz, 1, TC, "cuda"), ops.eval_acc_alloc(nx, ny, nz, 1, TC, "cuda")
+    ops.eval_metrics_update(pd, td, a1)
+    ops.eval_metrics_update(pd, td, a2)
     torch.cuda.synchronize()
     assert torch.equal(a1, a2) and int(a1[0]) == 2
-    ops.eval3_metrics_update(pd, td, a1)
-    ops.eval3_metrics_update(pd, td, a2)
+    ops.eval_metrics_update(pd, td, a1)
+    ops.eval_metrics_update(pd, td, a2)
     torch.cuda.synchronize()
     assert torch.equal(a1, a2) and int(a1[0]) == 4
     ilow, ihigh = bands_for(nx, ny, nz)
-    got = ops.eval3_finish(np.concatenate([[4.0], a1[1:].view(torch.float64).cpu().numpy()]), 4, nx, ny, nz, 1, TC, ilow, ihigh)
+    got = ops.eval_finish(np.concatenate([[4.0], a1[1:].view(torch.float64).cpu().numpy()]), 4, nx, ny, nz, 1, TC, ilow, ihigh)
     compare(got, E.eval_ref(np.concatenate([p, p]), np.concatenate([t, t]), ilow, ihigh), f"accumulator {cube} TC={TC}")
     guard.check()
 
@@ -314,3 +314,44 @@ def test_rollouts_of_a_3d_model_with_an_evaluator(B):
         twice = ev.read()
         assert twice["samples"] == 2 * B
         compare(twice, want, f"3-D rollout evaluator B={B}, two equal rollouts")     # means over equal samples
+
+
+def test_one_evaluator_across_ranks(guarded):
+    """planes, a field and the planes again through ONE evaluator: the plan and accumulator caches both ranks now share
+    keep them apart (every read equals a fresh evaluator's on the same pair, the third the first), and a change of rank
+    without reset() is refused"""
+    import eval_ref as E2
+    from dpot_amd import RolloutEvaluator, _lib
+    from resize_ref import hash_field
+
+    def pair(shape, salt):
+        p, t = fields(shape, salt, near=True) if len(shape) == 6 else E2.hashed_pair(shape, salt, hash_field)
+        return guard.wrap(torch.from_numpy(p), "cuda"), guard.wrap(torch.from_numpy(t), "cuda")
+
+    def fresh(p, t):
+        one = RolloutEvaluator("cuda", n_channels=2, T_max=3)
+        one.update(p, t)
+        return one.read()
+
+    def same(a, b, what):
+        assert a["samples"] == b["samples"] == 2, what
+        for key in E.KEYS:
+            assert np.array_equal(a[key], b[key], equal_nan=True), f"{what} {key}"
+
+    plane, field = pair((2, 9, 11, 3, 2), 31), pair((2, 9, 11, 10, 3, 2), 32)
+    ev = RolloutEvaluator("cuda", n_channels=2, T_max=3)
+    ev.update(*plane)
+    first = ev.read()
+    same(first, fresh(*plane), "planes")
+    with pytest.raises(_lib.DpotHipError):                         # a 6-D update without the reset() in between
+        ev.update(*field)
+    ev.reset()
+    ev.update(*field)
+    same(ev.read(), fresh(*field), "field")
+    ev.reset()
+    ev.update(*plane)
+    third = ev.read()
+    same(third, fresh(*plane), "planes again")
+    same(third, first, "third against first")
+    assert np.isfinite(first["nmse"]).all() and not np.array_equal(first["nmse"], fresh(*field)["nmse"])
+    guard.check()
