@@ -1195,6 +1195,20 @@ extern "C" int dpot_gemm_bf16p_kernel_kind(int M, int N, int K, int splitk, int 
   const int kind = pl.use_bd ? (pl.cpw == 2 ? 3 : 2) : 0;
   return kind + (pl.colt == 6 ? 8 : 0);
 }
+// the whole launch plan of dpot_gemm_bf16p, host only (tests pin every cell of the selection with it): out[0..7] = kind (as
+// dpot_gemm_bf16p_kernel_kind), tilesM, tilesN (after the 192 switch), splits, slabs_per_split, super_r, super_c, grid.x.
+// Returns 8, or -1 for what the launch refuses by shape (unsupported M / N / K, planes, more splits than slabs) or n < 8
+extern "C" int dpot_gemm_bf16p_plan(int M, int N, int K, int splitk, int planes, int packed_outputs, int* out, int n) {
+  if (!out || n < 8 || !dpot_gemm_bf16p_supported(M, N, K) || (planes != 1 && planes != 3)) return -1;
+  const int nslab = planes == 3 ? K >> 4 : K >> 5;
+  if ((splitk > 1 ? splitk : 1) > nslab || splitk > 65535) return -1;
+  const Bf16pPlan pl = bf16p_plan(M, N, K, splitk, planes, packed_outputs != 0);
+  out[0] = dpot_gemm_bf16p_kernel_kind(M, N, K, splitk, planes, packed_outputs);
+  out[1] = pl.tilesM; out[2] = pl.tilesN; out[3] = pl.splits; out[4] = pl.slabs_per_split;
+  out[5] = pl.super_r; out[6] = pl.super_c;
+  out[7] = (int)pl.grid;
+  return 8;
+}
 
 extern "C" int dpot_gemm_bf16p(const void* Apacked, const void* Wpacked, const float* bias, const float* aux, int ldaux,
                                const float* res, int ldres, float* pre, int ldpre, float* C, int ldc, int M, int N, int K,
@@ -1307,6 +1321,62 @@ static bool pair_use_bd(long long grid, int splits, int sps) {
   return bd && (grid * splits >= 512 || sps >= 128);
 }
 
+// kernel selection of dpot_gemm_bf16p_pair in ONE place, as bf16p_plan is for the single launch: the launch and
+// dpot_gemm_bf16p_pair_plan read the same plan.  `splits` is the validated split count (>= 1, no empty split)
+struct Bf16pPairPlan {
+  int tilesM[2], tilesN[2], row_major[2], splits, slabs_per_split, colt, cpw;
+  bool use_bd;
+  unsigned grid;
+};
+static Bf16pPairPlan bf16p_pair_plan(int M0, int N0, int M1, int N1, int K, int splits) {
+  Bf16pPairPlan pl;
+  const int Ms[2] = {M0, M1}, Ns[2] = {N0, N1};
+  for (int i = 0; i < 2; ++i) {
+    pl.tilesM[i] = (Ms[i] + 32 * PB_ROWT - 1) / (32 * PB_ROWT);
+    pl.tilesN[i] = Ns[i] / (32 * PB_COLT);
+  }
+  const int nslab = K >> 5;
+  pl.splits = splits;
+  pl.slabs_per_split = (nslab + splits - 1) / splits;
+  // 128 x 192 tiles when they need fewer workgroup-rounds' worth of time: DPOT-L's weight gradients are 1536 x 6144 and
+  // 6144 x 1536 - 288 + 288 tiles of 128 x 256 = 2.25 rounds of 256 CUs, i.e. THREE rounds; 384 + 384 tiles of 128 x 192 are
+  // exactly three rounds of tiles three quarters the size (a 192-wide tile costs ~0.83 of a 256-wide one: 20 instead of
+  // 24 KiB of operands per slab, and the loop is bound by those)
+  static const int allow192 = tune("bf16p_shape", 1);
+  pl.colt = PB_COLT;
+  if (allow192 && splits == 1 && N0 % 192 == 0 && N1 % 192 == 0) {
+    const long long t8 = (long long)pl.tilesM[0] * pl.tilesN[0] + (long long)pl.tilesM[1] * pl.tilesN[1];
+    const long long t6 = (long long)pl.tilesM[0] * (N0 / 192) + (long long)pl.tilesM[1] * (N1 / 192);
+    const double c8 = (double)((t8 + 255) / 256), c6 = 0.83 * (double)((t6 + 255) / 256);
+    if (c6 < 0.97 * c8) pl.colt = 6;
+  }
+  if (pl.colt == 6) {
+    pl.tilesN[0] = N0 / 192;
+    pl.tilesN[1] = N1 / 192;
+  }
+  pl.grid = (unsigned)(pl.tilesM[0] * pl.tilesN[0] + pl.tilesM[1] * pl.tilesN[1]);
+  pl.use_bd = pair_use_bd(pl.grid, splits, pl.slabs_per_split);
+  for (int i = 0; i < 2; ++i)
+    pl.row_major[i] = pl.use_bd ? bf16p_row_major(pl.tilesM[i], pl.tilesN[i], PB_ROWT, pl.colt) : 0;
+  pl.cpw = pl.colt == 6 ? 1 : bd_cpw((long long)pl.grid * splits);
+  return pl;
+}
+// the launch plan of dpot_gemm_bf16p_pair, host only: out[0..5] = kind (0 = LDS-DMA, 2 = B-direct with eight waves, 3 =
+// B-direct with four waves; + 8 on 128 x 192 tiles), splits, slabs_per_split, row_major of problem 0, of problem 1, grid.x.
+// Returns 6, or -1 for what the launch refuses by shape (unsupported shapes, more splits than slabs, an empty split) or n < 6
+extern "C" int dpot_gemm_bf16p_pair_plan(int M0, int N0, int M1, int N1, int K, int splitk, int* out, int n) {
+  if (!out || n < 6 || !dpot_gemm_bf16p_supported(M0, N0, K) || !dpot_gemm_bf16p_supported(M1, N1, K)) return -1;
+  const int nslab = K >> 5, splits = splitk > 1 ? splitk : 1;
+  if (splits > nslab || splits > 65535) return -1;
+  const int sps = (nslab + splits - 1) / splits;
+  if ((nslab + sps - 1) / sps != splits) return -1;
+  const Bf16pPairPlan pl = bf16p_pair_plan(M0, N0, M1, N1, K, splits);
+  out[0] = (pl.use_bd ? (pl.cpw == 2 ? 3 : 2) : 0) + (pl.colt == 6 ? 8 : 0);
+  out[1] = pl.splits; out[2] = pl.slabs_per_split; out[3] = pl.row_major[0]; out[4] = pl.row_major[1];
+  out[5] = (int)pl.grid;
+  return 6;
+}
+
 extern "C" int dpot_gemm_bf16p_pair(const void* A0, const void* W0, float* C0, int ldc0, int M0, int N0, const void* A1,
                                     const void* W1, float* C1, int ldc1, int M1, int N1, int K, int splitk,
                                     float* workspace, dpot_stream_t stream) {
@@ -1323,6 +1393,7 @@ extern "C" int dpot_gemm_bf16p_pair(const void* A0, const void* W0, float* C0, i
   DPOT_REQUIRE(splits <= nslab && splits <= 65535, "gemm_bf16p_pair: too many splits");
   const int sps = (nslab + splits - 1) / splits;
   DPOT_REQUIRE((nslab + sps - 1) / sps == splits, "gemm_bf16p_pair: splitk would leave an empty split (use dpot_gemm_bf16p_pair_splitk)");
+  const Bf16pPairPlan pl = bf16p_pair_plan(M0, N0, M1, N1, K, splits);
   Bf16pPair pp;
   const void* As[2] = {A0, A1};
   const void* Ws[2] = {W0, W1};
@@ -1334,8 +1405,8 @@ extern "C" int dpot_gemm_bf16p_pair(const void* A0, const void* W0, float* C0, i
     p.A = reinterpret_cast<const unsigned short*>(As[i]);
     p.W = reinterpret_cast<const unsigned short*>(Ws[i]);
     p.M = Ms[i]; p.N = Ns[i]; p.K = K;
-    p.tilesM = (Ms[i] + 32 * PB_ROWT - 1) / (32 * PB_ROWT);
-    p.tilesN = Ns[i] / (32 * PB_COLT);
+    p.tilesM = pl.tilesM[i];
+    p.tilesN = pl.tilesN[i];
     EpiArgs& e = p.e;
     e.C = Cs[i]; e.ldc = lds_[i]; e.sC = 0;
     e.bias = nullptr; e.sBias = 0;
@@ -1344,34 +1415,16 @@ extern "C" int dpot_gemm_bf16p_pair(const void* A0, const void* W0, float* C0, i
     e.res = nullptr; e.ldres = 0; e.res_div = 0; e.res_mod = 0; e.sRes = 0;
     e.act = 0; e.mode = DPOT_EPI_LINEAR; e.accumulate = 0;
     e.M = Ms[i]; e.N = Ns[i];
-    p.splits = splits;
-    p.slabs_per_split = sps;
+    p.splits = pl.splits;
+    p.slabs_per_split = pl.slabs_per_split;
     p.ws = wss[i];
     p.out_rows = nullptr; p.out_trans = nullptr; p.cs_part = nullptr;
-    p.dact_out = nullptr; p.dact_in = nullptr; p.super_r = 0; p.super_c = 0;
+    p.dact_out = nullptr; p.dact_in = nullptr; p.super_r = 0; p.super_c = pl.row_major[i];
   }
-  // 128 x 192 tiles when they need fewer workgroup-rounds' worth of time: DPOT-L's weight gradients are 1536 x 6144 and
-  // 6144 x 1536 - 288 + 288 tiles of 128 x 256 = 2.25 rounds of 256 CUs, i.e. THREE rounds; 384 + 384 tiles of 128 x 192 are
-  // exactly three rounds of tiles three quarters the size (a 192-wide tile costs ~0.83 of a 256-wide one: 20 instead of
-  // 24 KiB of operands per slab, and the loop is bound by those)
-  static const int allow192 = tune("bf16p_shape", 1);
-  int colt = PB_COLT;
-  if (allow192 && splits == 1 && N0 % 192 == 0 && N1 % 192 == 0) {
-    const long long t8 = (long long)pp.a[0].tilesM * pp.a[0].tilesN + (long long)pp.a[1].tilesM * pp.a[1].tilesN;
-    const long long t6 = (long long)pp.a[0].tilesM * (N0 / 192) + (long long)pp.a[1].tilesM * (N1 / 192);
-    const double c8 = (double)((t8 + 255) / 256), c6 = 0.83 * (double)((t6 + 255) / 256);
-    if (c6 < 0.97 * c8) colt = 6;
-  }
-  if (colt == 6) {
-    pp.a[0].tilesN = N0 / 192;
-    pp.a[1].tilesN = N1 / 192;
-  }
-  pp.n0 = pp.a[0].tilesM * pp.a[0].tilesN;
-  const unsigned grid = (unsigned)(pp.n0 + pp.a[1].tilesM * pp.a[1].tilesN);
-  const bool use_bd = pair_use_bd(grid, splits, sps);
-  if (use_bd) {
-    for (int i = 0; i < 2; ++i) pp.a[i].super_c = bf16p_row_major(pp.a[i].tilesM, pp.a[i].tilesN, PB_ROWT, colt);
-    const int cpw = colt == 6 ? 1 : bd_cpw((long long)grid * splits);
+  pp.n0 = pl.tilesM[0] * pl.tilesN[0];
+  const int colt = pl.colt, cpw = pl.cpw;
+  const unsigned grid = pl.grid;
+  if (pl.use_bd) {
 #define BD_LAUNCH(CT, CW, LA) hipLaunchKernelGGL((gemm_bf16p_bd_pair_kernel<CT, CW, LA>), dim3(grid, splits), dim3(64 * CT / CW), 0, as_stream(stream), pp)
     if (colt == 6) BD_LAUNCH(6, 1, 3);
     else if (cpw == 2) BD_LAUNCH(8, 2, 3);

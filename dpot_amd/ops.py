@@ -459,6 +459,43 @@ def gemm_bf16p_kernel_name(M: int, N: int, K: int, splitk: int = 1, planes: int 
     return BF16P_KERNEL_KINDS.get(k & 7, f"kind {k}") + (" on 128 x 192 tiles" if k >= 8 else "")
 
 
+class Bf16pPlan(NamedTuple):
+    """launch plan of dpot_gemm_bf16p (include/dpot_hip.h, dpot_gemm_bf16p_plan)"""
+    kind: int              # 0 LDS-DMA, 2 B-direct eight waves, 3 B-direct four waves, 4 bf16x6; + 8 on 128 x 192 tiles
+    tilesM: int
+    tilesN: int            # of 192 columns when kind >= 8
+    splits: int
+    slabs_per_split: int
+    super_r: int           # > 0: super-blocks of super_r x super_c tiles, grid padded to rounds of 256 workgroups
+    super_c: int           # with super_r == 0: 1 = row-major XCD-contiguous order, 0 = column-major
+    grid: int
+
+
+class Bf16pPairPlan(NamedTuple):
+    """launch plan of dpot_gemm_bf16p_pair (dpot_gemm_bf16p_pair_plan)"""
+    kind: int              # 0, 2 or 3 as above; + 8 on 128 x 192 tiles
+    splits: int
+    slabs_per_split: int
+    row_major0: int
+    row_major1: int
+    grid: int
+
+
+def gemm_bf16p_plan(M: int, N: int, K: int, splitk: int = 1, planes: int = 1,
+                    packed_outputs: bool = False) -> Optional[Bf16pPlan]:
+    """the plan dpot_gemm_bf16p launches with, from the library's own selection (host only); None: the launch refuses"""
+    buf = (C.c_int * 8)()
+    n = _lib.load().dpot_gemm_bf16p_plan(M, N, K, splitk, planes, int(packed_outputs), buf, 8)
+    return Bf16pPlan(*buf[:8]) if n == 8 else None
+
+
+def gemm_bf16p_pair_plan(M0: int, N0: int, M1: int, N1: int, K: int, splitk: int = 1) -> Optional[Bf16pPairPlan]:
+    """the plan dpot_gemm_bf16p_pair launches with for an explicit splitk (host only); None: the launch refuses"""
+    buf = (C.c_int * 6)()
+    n = _lib.load().dpot_gemm_bf16p_pair_plan(M0, N0, M1, N1, K, splitk, buf, 6)
+    return Bf16pPairPlan(*buf[:6]) if n == 6 else None
+
+
 def gemm_bf16p_pair(A0: Tensor, W0: Tensor, M0: int, N0: int, A1: Tensor, W1: Tensor, M1: int, N1: int, K: int,
                     out0: Optional[Tensor] = None, out1: Optional[Tensor] = None,
                     splitk: Optional[int] = None) -> Tuple[Tensor, Tensor]:

@@ -785,6 +785,13 @@ int dpot_gemm_bf16p_supported(int M, int N, int K);
  * (8 compute + 4 loader waves), 1 = two-workgroup kernel, 2 = B-direct with eight 128 x 32 waves, 3 = B-direct with four
  * 128 x 64 waves (two workgroups per CU), 4 = bf16x6; + 8 when it runs on 128 x 192 tiles; -1: unsupported shape */
 int dpot_gemm_bf16p_kernel_kind(int M, int N, int K, int splitk, int planes, int packed_outputs);
+/* the whole launch plan of dpot_gemm_bf16p, from the selection the launch itself reads (host only, no GPU needed):
+ * out[0..7] = kind (as above), tilesM, tilesN (of 192 columns when kind >= 8), splits (empty splits removed),
+ * slabs_per_split (32-k slabs; 16-k for planes == 3), super_r, super_c, grid.x.  Tile order: super_r > 0 - super-blocks of
+ * super_r x super_c tiles, grid.x padded to whole rounds of 256 workgroups (the padding ones return at once); super_r == 0 -
+ * XCD-contiguous, row-major when super_c == 1 (B-direct kernels only), else column-major.  Returns 8; -1: the launch
+ * refuses the shape (unsupported M / N / K, planes, more splits than slabs) or n < 8 */
+int dpot_gemm_bf16p_plan(int M, int N, int K, int splitk, int planes, int packed_outputs, int* out, int n);
 int dpot_gemm_bf16p(const void* Apacked, const void* Wpacked, const float* bias, const float* aux, int ldaux,
                     const float* res, int ldres, float* pre, int ldpre, float* C, int ldc, int M, int N, int K, int act,
                     int epi_mode, int planes, int splitk, float* workspace, void* out_rows, void* out_trans,
@@ -796,6 +803,11 @@ int dpot_gemm_bf16p_pair_wanted(int M0, int N0, int M1, int N1, int K);
 /* common split-K factor of the pair launch: 0 = do not pair, 1 = no split, s > 1 = s splits (workspace of
  * s * (M0*N0 + M1*N1) floats; the partial sums are reduced in a fixed order by two further launches) */
 int dpot_gemm_bf16p_pair_splitk(int M0, int N0, int M1, int N1, int K);
+/* the launch plan of dpot_gemm_bf16p_pair for an explicit splitk (host only): out[0..5] = kind (0 = LDS-DMA, 2 = B-direct
+ * with eight waves, 3 = B-direct with four waves; + 8 on 128 x 192 tiles), splits, slabs_per_split, row-major tile order of
+ * problem 0, of problem 1, grid.x (the tiles of both problems).  Returns 6; -1: the launch refuses (unsupported shapes,
+ * more splits than slabs, a splitk that leaves an empty split) or n < 6 */
+int dpot_gemm_bf16p_pair_plan(int M0, int N0, int M1, int N1, int K, int splitk, int* out, int n);
 int dpot_gemm_bf16p_pair(const void* A0, const void* W0, float* C0, int ldc0, int M0, int N0, const void* A1,
                          const void* W1, float* C1, int ldc1, int M1, int N1, int K, int splitk, float* workspace,
                          dpot_stream_t stream);

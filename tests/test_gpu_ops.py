@@ -612,9 +612,9 @@ def test_gemm_panel_static_weight(ops, M, N, K):
 
 
 @pytest.mark.parametrize("M,N,K", [(8192, 1024, 1024), (300, 256, 64), (4096, 512, 2048), (129, 768, 96), (1, 256, 32),
-                                   (65500, 256, 64), (16400, 1024, 96),
+                                   (65500, 256, 64), (16400, 1024, 96),              # >= 512 tiles: the two-workgroup kernel, ragged M
                                    # one row less / more than the 32-row rounding of the packs (dpot_bf16_packed_elems)
-                                   (31, 256, 32), (33, 256, 256), (63, 512, 256)])   # >= 512 tiles: the two-workgroup kernel, ragged M
+                                   (31, 256, 32), (33, 256, 256), (63, 512, 256)])
 def test_gemm_bf16_panel(ops, M, N, K):
     """bf16 panel GEMM (csrc/gemm_bf16p.hip): packed bf16 operands, fp32 accumulation.  Checked against an fp64 product of
     the bf16-ROUNDED operands (exactly what the kernel multiplies: error there is fp32 accumulation only) and, loosely,
