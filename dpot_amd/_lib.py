@@ -253,6 +253,12 @@ SIGNATURES = {
     "dpot_wgrad_flush_async": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i] * 4 + [c_fp, c_i] + [C.POINTER(C.c_void_p)] * 4
                                + [c_i] * 4 + [c_fp] + [c_i] * 3 + [C.POINTER(WgradBlock)] + [c_i] * 5 + [c_fp]),
     "dpot_wgrad_wait": (c_i, [c_fp]),
+    "dpot_lane_init": (c_i, [c_i]),
+    "dpot_lane_ready": (c_i, [c_i]),
+    "dpot_lane_pending": (c_i, [c_i]),
+    "dpot_lane_shutdown": (c_i, [c_i]),
+    "dpot_lane_fork": (c_i, [c_i, c_fp, C.POINTER(C.c_void_p)]),
+    "dpot_lane_join": (c_i, [c_i, c_fp]),
     "dpot_bf16_pack_both_supported": (c_i, [c_i, c_i]),
     "dpot_bf16_pack_both": (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp]),
     "dpot_bf16_pack_both_norm": (c_i, [c_fp, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_fp]),

@@ -53,7 +53,9 @@ int tune(const char* key, int dflt) {
  * 270: dpot_eval3_stats, dpot_eval3_finalize and their queries (csrc/evalmetrics3d.hip): the evaluation metrics of 3-D rollouts
  * 271: mlp_chain / afno_chain on dpot_mlp_wgrad_batch, dpot_afno_wgrad_batch, dpot_wgrad_batch_finalize, dpot_wgrad_flush_async;
  * dpot_tn_chain_count, dpot_tn_chain_nodes, dpot_*_wgrad_batch_chain, dpot_*_wgrad_chain_ws_elems (csrc/gemm_tn.hip): chained
- * token ranges in the batched weight gradients */
-extern "C" int dpot_version(void) { return 271; }
+ * token ranges in the batched weight gradients
+ * 272: dpot_lane_init, dpot_lane_ready, dpot_lane_pending, dpot_lane_shutdown, dpot_lane_fork, dpot_lane_join (csrc/gemm_tn.hip):
+ * a table of library-owned lanes; the weight-gradient lane is lane 0, the side lane of the step's small chains lane 1 */
+extern "C" int dpot_version(void) { return 272; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

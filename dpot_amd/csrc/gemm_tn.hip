@@ -1577,34 +1577,42 @@ extern "C" int dpot_wgrad_batch_finalize(const dpot_wgrad_block* blocks, int n, 
   return DPOT_OK;
 }
 
-// ---- the weight-gradient lane ------------------------------------------------------------------------------------------------
-// The batched weight gradients above are ~500 us of MFMA work that nothing reads before the optimiser, while the embed backward
-// that follows them on the caller's stream is a chain of small latency-bound launches.  The lane is ONE library-owned stream per
-// device (non-blocking, default priority) plus a fork and a done event: dpot_wgrad_flush_async issues the three launch sets on
-// it behind the caller's stream, dpot_wgrad_wait joins it back.  Inside a stream capture the event record / wait pair pulls the
-// lane into the capture as a parallel branch; the lane is never CREATED there (a first use under capture runs on the caller's
-// stream).  The only state the library keeps; every access is under the mutex.
+// ---- the library's lanes ---------------------------------------------------------------------------------------------------
+// Lane 0, the weight-gradient lane: the batched weight gradients above are ~500 us of MFMA work that nothing reads before the
+// optimiser, while the embed backward that follows them on the caller's stream is a chain of small latency-bound launches.
+// Lane 1, the side lane: short chains of latency-bound launches whose neighbours on the step's stream are independent of them
+// and bound by another resource (the weight-only prologue beside the HBM-bound embed forward, the classification head beside
+// the de-embed GEMM, the first conv's gradients beside the weight-only chain of the embed backward).
+// A lane is ONE library-owned stream per device (non-blocking, default priority) plus a fork and a done event.
+// dpot_lane_fork orders the lane behind the caller's stream and hands out its handle, dpot_lane_join orders the caller behind
+// the lane; dpot_wgrad_flush_async / dpot_wgrad_wait are the same pair around the three launch sets, on lane 0.  Inside a
+// stream capture the event record / wait pair pulls the lane into the capture as a parallel branch; a lane is never CREATED
+// there (a first use under capture runs on the caller's stream).  The only state the library keeps; every access is under the
+// mutex.
 namespace dpot {
 constexpr int LANE_MAXDEV = 64;
-struct WgradLane {
+constexpr int LANE_COUNT = 2;       // the step's stream plus these: never more than three streams live at once
+struct Lane {
   hipStream_t stream;
   hipEvent_t fork, done;
-  int pending;          // flushes since the last wait
-  bool ready, captured; // captured: the last done event was recorded inside a stream capture
+  int pending;          // forks since the last join
+  int flushes;          // of them weight-gradient flushes (dpot_wgrad_lane_pending)
+  bool ready, captured; // captured: the last fork was made inside a stream capture
 };
-static WgradLane g_lane[LANE_MAXDEV];
+static Lane g_lane[LANE_COUNT][LANE_MAXDEV];
 static std::mutex g_lane_mutex;
 
 static int lane_hip(hipError_t e, const char* what) {
   if (e == hipSuccess) return DPOT_OK;
   (void)hipGetLastError();
-  set_error("wgrad lane: %s: %s", what, hipGetErrorString(e));
+  set_error("lane: %s: %s", what, hipGetErrorString(e));
   return DPOT_EHIP;
 }
-static WgradLane* lane_of_current_device() {
+static Lane* lane_of_current_device(int lane = 0) {
   int dev = -1;
+  if (lane < 0 || lane >= LANE_COUNT) return nullptr;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= LANE_MAXDEV) { (void)hipGetLastError(); return nullptr; }
-  return &g_lane[dev];
+  return &g_lane[lane][dev];
 }
 static bool stream_capturing(hipStream_t s) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
@@ -1615,10 +1623,10 @@ static bool stream_capturing(hipStream_t s) {
 // the lowest or at the highest priority of the device's range the replay of the captured step takes twice as long (6.3 ms
 // against 2.93 ms; in the kernel trace the lane's first launch starts ~200 us after the fork and the step's own launches fall
 // behind as well - cause inside the runtime's graph replay, not looked into), so there is no priority to choose.
-static int lane_create(WgradLane* L) {
+static int lane_create(Lane* L) {
   if (L->ready) return DPOT_OK;
   int rc;
-  WgradLane n{};
+  Lane n{};
   rc = lane_hip(hipStreamCreateWithPriority(&n.stream, hipStreamNonBlocking, 0), "hipStreamCreateWithPriority");
   if (rc) return rc;
   rc = lane_hip(hipEventCreateWithFlags(&n.fork, hipEventDisableTiming), "hipEventCreateWithFlags");
@@ -1631,40 +1639,109 @@ static int lane_create(WgradLane* L) {
   *L = n;
   return DPOT_OK;
 }
-}  // namespace dpot
-
-extern "C" int dpot_wgrad_lane_init(void) {
-  std::lock_guard<std::mutex> lock(g_lane_mutex);
-  WgradLane* L = lane_of_current_device();
-  DPOT_REQUIRE(L, "wgrad lane: no current device");
-  return lane_create(L);
+// (mutex held)  Order L behind `caller`; *forked = false when L does not exist and may not be created (a first use inside a
+// stream capture): the work then belongs on the caller's own stream and nothing is counted.
+static int lane_fork_locked(Lane* L, hipStream_t caller, bool* forked) {
+  *forked = false;
+  const bool capturing = stream_capturing(caller);
+  if (!L->ready) {
+    if (capturing) return DPOT_OK;
+    int rc = lane_create(L);
+    if (rc) return rc;
+  }
+  int rc = lane_hip(hipEventRecord(L->fork, caller), "hipEventRecord(fork)");
+  if (rc) return rc;
+  rc = lane_hip(hipStreamWaitEvent(L->stream, L->fork, 0), "hipStreamWaitEvent(fork)");
+  if (rc) return rc;
+  L->pending += 1;
+  L->captured = capturing;
+  *forked = true;
+  return DPOT_OK;
 }
-
-extern "C" int dpot_wgrad_lane_ready(void) {
-  std::lock_guard<std::mutex> lock(g_lane_mutex);
-  WgradLane* L = lane_of_current_device();
-  return L && L->ready ? 1 : 0;
+// (mutex held)  Order `caller` behind everything L has been given; clears the counts.  Nothing when nothing is pending.
+static int lane_join_locked(Lane* L, hipStream_t caller) {
+  if (!L || !L->ready || L->pending == 0) return DPOT_OK;
+  const bool capturing = stream_capturing(caller);
+  if (L->captured && !capturing) {   // the capture the fork belonged to has ended or was abandoned: nothing left to order
+    L->pending = L->flushes = 0;
+    return DPOT_OK;
+  }
+  DPOT_REQUIRE(L->captured == capturing, "lane: a fork outside a capture cannot be joined inside one");
+  int rc = lane_hip(hipEventRecord(L->done, L->stream), "hipEventRecord(done)");
+  if (rc) return rc;
+  rc = lane_hip(hipStreamWaitEvent(caller, L->done, 0), "hipStreamWaitEvent(done)");
+  if (rc) return rc;
+  L->pending = L->flushes = 0;
+  return DPOT_OK;
 }
-
-extern "C" int dpot_wgrad_lane_pending(void) {
-  std::lock_guard<std::mutex> lock(g_lane_mutex);
-  WgradLane* L = lane_of_current_device();
-  return L ? L->pending : 0;
-}
-
-extern "C" int dpot_wgrad_lane_shutdown(void) {
-  std::lock_guard<std::mutex> lock(g_lane_mutex);
-  WgradLane* L = lane_of_current_device();
+static int lane_shutdown_locked(Lane* L) {
   if (!L || !L->ready) return DPOT_OK;
-  DPOT_REQUIRE(L->pending == 0, "wgrad lane: shutdown with %d flushes not waited for", L->pending);
+  DPOT_REQUIRE(L->pending == 0, "lane: shutdown with %d forks not joined", L->pending);
   int rc = lane_hip(hipStreamSynchronize(L->stream), "hipStreamSynchronize");
   if (rc) return rc;
   (void)hipEventDestroy(L->fork);
   (void)hipEventDestroy(L->done);
   (void)hipStreamDestroy(L->stream);
-  *L = WgradLane{};
+  *L = Lane{};
   return DPOT_OK;
 }
+}  // namespace dpot
+
+extern "C" int dpot_lane_init(int lane) {
+  std::lock_guard<std::mutex> lock(g_lane_mutex);
+  DPOT_REQUIRE(lane >= 0 && lane < LANE_COUNT, "lane: no lane %d", lane);
+  Lane* L = lane_of_current_device(lane);
+  DPOT_REQUIRE(L, "lane: no current device");
+  return lane_create(L);
+}
+
+extern "C" int dpot_lane_ready(int lane) {
+  std::lock_guard<std::mutex> lock(g_lane_mutex);
+  Lane* L = lane_of_current_device(lane);
+  return L && L->ready ? 1 : 0;
+}
+
+extern "C" int dpot_lane_pending(int lane) {
+  std::lock_guard<std::mutex> lock(g_lane_mutex);
+  Lane* L = lane_of_current_device(lane);
+  return L ? L->pending : 0;
+}
+
+extern "C" int dpot_lane_shutdown(int lane) {
+  std::lock_guard<std::mutex> lock(g_lane_mutex);
+  DPOT_REQUIRE(lane >= 0 && lane < LANE_COUNT, "lane: no lane %d", lane);
+  return lane_shutdown_locked(lane_of_current_device(lane));
+}
+
+extern "C" int dpot_lane_fork(int lane, dpot_stream_t caller, dpot_stream_t* lane_stream) {
+  std::lock_guard<std::mutex> lock(g_lane_mutex);
+  DPOT_REQUIRE(lane >= 0 && lane < LANE_COUNT, "lane: no lane %d", lane);
+  DPOT_REQUIRE(lane_stream, "lane: fork without a place for the stream handle");
+  *lane_stream = caller;
+  Lane* L = lane_of_current_device(lane);
+  DPOT_REQUIRE(L, "lane: no current device");
+  bool forked = false;
+  int rc = lane_fork_locked(L, as_stream(caller), &forked);
+  if (!rc && forked) *lane_stream = (dpot_stream_t)L->stream;
+  return rc;
+}
+
+extern "C" int dpot_lane_join(int lane, dpot_stream_t caller) {
+  std::lock_guard<std::mutex> lock(g_lane_mutex);
+  DPOT_REQUIRE(lane >= 0 && lane < LANE_COUNT, "lane: no lane %d", lane);
+  return lane_join_locked(lane_of_current_device(lane), as_stream(caller));
+}
+
+extern "C" int dpot_wgrad_lane_init(void) { return dpot_lane_init(0); }
+extern "C" int dpot_wgrad_lane_ready(void) { return dpot_lane_ready(0); }
+
+extern "C" int dpot_wgrad_lane_pending(void) {
+  std::lock_guard<std::mutex> lock(g_lane_mutex);
+  Lane* L = lane_of_current_device(0);
+  return L ? L->flushes : 0;
+}
+
+extern "C" int dpot_wgrad_lane_shutdown(void) { return dpot_lane_shutdown(0); }
 
 extern "C" int dpot_wgrad_flush_async(const float* const* do2, const float* const* Hh, const float* const* xn2,
                                       const float* const* dHpre, int n, int T, int E, int mh, float* mlp_ws, int mlp_splitk,
@@ -1673,24 +1750,15 @@ extern "C" int dpot_wgrad_flush_async(const float* const* do2, const float* cons
                                       int afno_splits12, int afno_splitk, const dpot_wgrad_block* blocks, int gn_jobs, int B,
                                       int Egn, int mlp_chain, int afno_chain, dpot_stream_t stream) {
   std::lock_guard<std::mutex> lock(g_lane_mutex);
-  hipStream_t caller = as_stream(stream);
-  const bool capturing = stream_capturing(caller);
-  WgradLane* L = lane_of_current_device();
+  Lane* L = lane_of_current_device(0);
   DPOT_REQUIRE(L, "wgrad lane: no current device");
-  if (!L->ready) {
-    if (capturing) {
-      L = nullptr;      // never created under capture: everything on the caller's stream
-    } else {
-      int rc = lane_create(L);
-      if (rc) return rc;
-    }
-  }
-  if (L) {
-    int rc = lane_hip(hipEventRecord(L->fork, caller), "hipEventRecord(fork)");
-    if (rc) return rc;
-    rc = lane_hip(hipStreamWaitEvent(L->stream, L->fork, 0), "hipStreamWaitEvent(fork)");
+  bool forked = false;
+  {
+    int rc = lane_fork_locked(L, as_stream(stream), &forked);
     if (rc) return rc;
   }
+  if (!forked) L = nullptr;      // never created under capture: everything on the caller's stream
+  else L->flushes += 1;          // also when a launch below fails: the lane has been forked and must be joined again
   dpot_stream_t run = L ? (dpot_stream_t)L->stream : stream;
   // The AFNO launch goes FIRST.  The embed backward beside the lane opens with its two MFMA-bound fold GEMMs (768 and 528
   // workgroups) and goes on with short latency-bound launches.  Beside the channel-MLP launch the first fold GEMM took 124 us
@@ -1701,27 +1769,7 @@ extern "C" int dpot_wgrad_flush_async(const float* const* do2, const float* cons
   int rc = dpot_afno_wgrad_batch(S, dO1pre, O1, dO2, n, ld, Mm, nb, bs, afno_ws, per_launch, afno_splits12, afno_splitk, afno_chain, run);
   if (!rc) rc = dpot_mlp_wgrad_batch(do2, Hh, xn2, dHpre, n, T, E, mh, mlp_ws, mlp_splitk, mlp_chain, run);
   if (!rc) rc = dpot_wgrad_batch_finalize(blocks, n, afno_splits12, afno_splitk, nb, bs, mlp_splitk, E, mh, gn_jobs, B, Egn, mlp_chain, afno_chain, run);
-  if (L) {   // also after a failed launch: the lane has been forked and must be joined again
-    const int rc2 = lane_hip(hipEventRecord(L->done, L->stream), "hipEventRecord(done)");
-    if (rc2) return rc ? rc : rc2;
-    L->pending += 1;
-    L->captured = capturing;
-  }
   return rc;
 }
 
-extern "C" int dpot_wgrad_wait(dpot_stream_t stream) {
-  std::lock_guard<std::mutex> lock(g_lane_mutex);
-  WgradLane* L = lane_of_current_device();
-  if (!L || !L->ready || L->pending == 0) return DPOT_OK;
-  const bool capturing = stream_capturing(as_stream(stream));
-  if (L->captured && !capturing) {   // the capture the flush belonged to has ended or was abandoned: nothing left to order
-    L->pending = 0;
-    return DPOT_OK;
-  }
-  DPOT_REQUIRE(L->captured == capturing, "wgrad lane: a flush outside a capture cannot be waited for inside one");
-  int rc = lane_hip(hipStreamWaitEvent(as_stream(stream), L->done, 0), "hipStreamWaitEvent(done)");
-  if (rc) return rc;
-  L->pending = 0;
-  return DPOT_OK;
-}
+extern "C" int dpot_wgrad_wait(dpot_stream_t stream) { return dpot_lane_join(0, stream); }

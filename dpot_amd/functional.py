@@ -108,7 +108,7 @@ class WgradBatch:
     every chain setting (profiles/wgrad_chain_ab.txt).
 
     The flush is the last thing block 0's backward does; the embed backward that follows is a chain of small launches that reads
-    none of its results.  By default (DPOT_TUNE fused_small=4, `ops.wgrad_lane_scope`) the three launch sets therefore go to the
+    none of its results.  By default (DPOT_TUNE fused_small=4 or 5, `ops.wgrad_lane_scope`) the three launch sets therefore go to the
     library's weight-gradient lane, a stream of its own that is forked from this one and joined back when the backward ends
     (`_lane_ok`, ops.wgrad_flush_async).  Same launches, same results."""
 
@@ -251,11 +251,25 @@ def embed_layout_jobs(pos, w0, b0, w2, b2):
             (pos, b2, (1, tok, E), (1, tok, E), (0, 1, tok))]                  # pos^T [tok, E] + conv bias
 
 
-def embed_derived(pos, w0, b0, w2, b2, taw, tagamma, tt, T: int, grid=None, layouts=None):
+def embed_implicit_tables(w0, w0p, b0p, grid):
+    """(wfrag, bt) of the implicit-GEMM patch embedding (csrc/embed.hip): data-channel weights in fragment order, and the
+    unit-grid channels folded into a bias table  bt[(tok,t), n] = b0[n] + sum_{c>=C,i,j} grid[(tok,t),(c,i,j)] w0[n,c,i,j].
+    With the layout pieces, all of the weight-only products that `embed_fwd` reads."""
+    hidp, K0 = w0p.shape
+    kg = grid.shape[1]
+    wfrag = ops.embed_pack_w0(w0)
+    bt = torch.empty(grid.shape[0], hidp, dtype=torch.float32, device=grid.device)
+    ops.gemm(grid, w0p[:, K0 - kg:], bt, grid.shape[0], hidp, kg, transB=True, lda=kg, ldb=K0, ldc=hidp, bias=b0p)
+    return wfrag, bt
+
+
+def embed_derived(pos, w0, b0, w2, b2, taw, tagamma, tt, T: int, grid=None, layouts=None, implicit_tables: bool = True):
     """weight-only products of the embed stage (they depend on no activation, so a T_ar-step rollout computes them
     once per optimiser step, see DPOTNet.weights_scope): padded conv weights, pos+bias, the cos-scaled aggregation
     weights and the folded [1x1 conv -> TimeAggregator] matrices V / c described in EmbedFn.forward.  layouts: the four
-    tensors of `embed_layout_jobs`, already refreshed (DPOTNet: one launch for all layout pieces of the model)"""
+    tensors of `embed_layout_jobs`, already refreshed (DPOTNet: one launch for all layout pieces of the model).
+    implicit_tables=False leaves wfrag and bt None: the caller adds `embed_implicit_tables` (packs.ModelPacks.derive runs the rest
+    on the side lane)"""
     hid, E = w0.shape[0], w2.shape[0]
     K0 = w0[0].numel()
     hidp = _pad4(hid)
@@ -277,13 +291,8 @@ def embed_derived(pos, w0, b0, w2, b2, taw, tagamma, tt, T: int, grid=None, layo
     cc = torch.empty(tok, E, dtype=torch.float32, device=dev)
     ops.gemm(posb, wsum, cc, tok, E, E, lda=E, ldb=E, ldc=E)
     wfrag = bt = None
-    if grid is not None:
-        # implicit-GEMM patch embedding (csrc/embed.hip): data-channel weights in fragment order, and the unit-grid
-        # channels folded into a bias table  bt[(tok,t), n] = b0[n] + sum_{c>=C,i,j} grid[(tok,t),(c,i,j)] w0[n,c,i,j]
-        kg = grid.shape[1]
-        wfrag = ops.embed_pack_w0(w0)
-        bt = torch.empty(grid.shape[0], hidp, dtype=torch.float32, device=dev)
-        ops.gemm(grid, w0p[:, K0 - kg:], bt, grid.shape[0], hidp, kg, transB=True, lda=kg, ldb=K0, ldc=hidp, bias=b0p)
+    if grid is not None and implicit_tables:
+        wfrag, bt = embed_implicit_tables(w0, w0p, b0p, grid)
     return w0p, b0p, w2p, posb, ws, V, wsum, cc, wfrag, bt, grid
 
 
@@ -312,6 +321,7 @@ class EmbedFn(torch.autograd.Function):
             Hh, Hpre = ops.embed_fwd(x, wfrag, bt, hidp, act)
         else:
             Hh, Hpre = ops.linear_fwd(A0, w0p, b0p, act=act, save_pre=True)    # [M0, hidp]
+        ops.side_lane_join()             # V and cc of `derived` (packs.ModelPacks.derive: side-lane site `weights`)
         # Everything after the activation is LINEAR (1x1 conv hid->E, + pos_embed, TimeAggregator), and the hidden
         # width is only hid = out_channels*P+3 (35).  Instead of materialising z[M0, E] (168 MB at B=32) and
         # contracting it with ws[T*E, E] (K = 5120), the 1x1 conv is folded INTO the aggregation weights every step:
@@ -327,6 +337,7 @@ class EmbedFn(torch.autograd.Function):
         ctx.dims = (B, X, Y, T, Cc, P, h, w, hid, hidp, E, K0, act)
         ctx.sinks = _sinks(ctx, (pos, w0, b0, w2, b2, taw, tagamma), 1)
         ctx.weights_epoch = _epoch_of(ctx.sinks)
+        ctx.side = ops.side_lane_enabled("patch")        # read in the forward: the backward runs on the autograd engine's thread
         return Yl.view(B, tok, E)
 
     @staticmethod
@@ -344,56 +355,68 @@ class EmbedFn(torch.autograd.Function):
         dHpre = torch.empty(M0, hidp, dtype=torch.float32, device=dev)         # viewed [M, T*hidp]
         ops.gemm(dY, V, dHpre, M, T * hidp, E, transB=True, lda=E, ldb=E, ldc=T * hidp, act=act, mode=EPI_DACT,
                  aux=Hpre, ldaux=T * hidp)
-        dV = torch.empty(T * hidp, E, dtype=torch.float32, device=dev)
-        ops.gemm(Hh, dY, dV, T * hidp, E, M, transA=True, lda=T * hidp, ldb=E, ldc=E,
-                 splitk=ops.auto_splitk(T * hidp, E, M, tn=True))
-        dc = ops.group_rowsum(dY, B, tok, 1, E)                                # [tok, E]
-        # c = posb wsum  ->  dwsum = posb^T dc, dposb = dc wsum^T
-        dwsum = torch.empty(E, E, dtype=torch.float32, device=dev)
-        ops.gemm(posb, dc, dwsum, E, E, tok, transA=True, lda=E, ldb=E, ldc=E, splitk=ops.auto_splitk(E, E, tok, tn=True))
-        dposb = torch.empty(tok, E, dtype=torch.float32, device=dev)
-        ops.gemm(dc, wsum, dposb, tok, E, E, transB=True, lda=E, ldb=E, ldc=E)
-        dpos = s_pos.done(ops.transpose2d(dposb, 1, tok, E, out=s_pos.out()).view(1, E, h, w))
-        db2 = s_b2.done(ops.colsum(dposb, tok, E, out=s_b2.out()))
-        # V_t = w2^T ws_t  ->  dw2 = sum_t ws_t dV_t^T,  dws_t = w2 dV_t (+ dwsum for every t)
-        dw2_t = torch.empty(T, E, hidp, dtype=torch.float32, device=dev)
-        ops.gemm(ws, dV, dw2_t, E, hidp, E, transB=True, lda=E, ldb=E, ldc=hidp, batch=T, strideA=E * E,
-                 strideB=hidp * E, strideC=E * hidp)
-        dw2p = ops.colsum(dw2_t, T, E * hidp).view(E, hidp)
-        dw2 = s_w2.done(ops.copy2d_pad(dw2p, E, hidp, E, hid, out=s_w2.out()).view(E, hid, 1, 1))
-        dws = s_taw.out() if tagamma is None else None
-        dws = ops._out(dws, (T, E, E), dev)
-        ops.gemm(w2p, dV, dws, E, E, hidp, lda=hidp, ldb=E, ldc=E, batch=T, strideA=0, strideB=hidp * E,
-                 strideC=E * E, res=dwsum, ldres=E, strideRes=0)
-        if tagamma is not None:
-            dtaw, dgamma = ops.timeagg_scale_w_bwd(dws, taw, tagamma, tt, out_dw=s_taw.out(),
-                                                   out_dgamma=s_gamma.out())
-            dtaw, dgamma = s_taw.done(dtaw), s_gamma.done(dgamma)
-        else:
-            dtaw, dgamma = s_taw.done(dws), None
-        # first (PxP / stride P) conv
-        if ctx.implicit:
-            # data channels: implicit weight-gradient GEMM over x (A0 holds x here); unit-grid channels: the grid matrix
-            # is batch independent -> contract it with the batch-summed dHpre; both land in the gradient slot itself
-            db0 = s_b0.done(ops.colsum(dHpre, M0, hid, ld=hidp, out=s_b0.out()))
-            dw0 = ops._out(s_w0.out(), (hid, K0), dev)
-            ops.embed_wgrad(A0, dHpre, dw0, hid)
-            dHs = ops.group_rowsum(dHpre, B, tok * T, 1, hidp)                 # [tok*T, hidp]
-            kg = grid.shape[1]
-            ops.gemm(dHs, grid, dw0[:, K0 - kg:], hid, kg, tok * T, transA=True, lda=hidp, ldb=kg, ldc=K0)
-            dw0 = s_w0.done(dw0.view(hid, Cc + 3, P, P))
-        elif hid == hidp:
-            dw0p, db0 = ops.linear_bwd_wb(dHpre, A0, None, s_b0.out())          # [hidp, K0] (padded: 16-byte loads)
-            db0 = s_b0.done(db0)
-        else:
-            db0 = s_b0.done(ops.colsum(dHpre, M0, hid, ld=hidp, out=s_b0.out()))
-            dw0p = ops.linear_bwd_weight(dHpre, A0)
-        if not ctx.implicit:
-            dw0 = s_w0.done(ops.copy2d_pad(dw0p, hidp, K0, hid, K0, out=s_w0.out()).view(hid, Cc + 3, P, P))
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dA0 = ops.linear_bwd_data(dHpre, w0p)                              # [M0, K0]
-            dx = ops.unpatchify(dA0, B, X, Y, T, Cc, P)
+        def first_conv():
+            """(dw0, db0) of the first (PxP / stride P) conv, before their sinks: they need only dHpre"""
+            if ctx.implicit:
+                # data channels: implicit weight-gradient GEMM over x (A0 holds x here); unit-grid channels: the grid matrix
+                # is batch independent -> contract it with the batch-summed dHpre; both land in the gradient slot itself
+                db0 = ops.colsum(dHpre, M0, hid, ld=hidp, out=s_b0.out())
+                dw0 = ops._out(s_w0.out(), (hid, K0), dev)
+                ops.embed_wgrad(A0, dHpre, dw0, hid)
+                dHs = ops._scratch(ops.group_rowsum(dHpre, B, tok * T, 1, hidp))   # [tok*T, hidp]
+                kg = grid.shape[1]
+                ops.gemm(dHs, grid, dw0[:, K0 - kg:], hid, kg, tok * T, transA=True, lda=hidp, ldb=kg, ldc=K0)
+                return dw0.view(hid, Cc + 3, P, P), db0
+            if hid == hidp:
+                dw0p, db0 = ops.linear_bwd_wb(dHpre, A0, None, s_b0.out())      # [hidp, K0] (padded: 16-byte loads)
+            else:
+                db0 = ops.colsum(dHpre, M0, hid, ld=hidp, out=s_b0.out())
+                dw0p = ops.linear_bwd_weight(dHpre, A0)
+            return ops.copy2d_pad(ops._scratch(dw0p), hidp, K0, hid, K0, out=s_w0.out()).view(hid, Cc + 3, P, P), db0
+
+        # Side-lane site `patch` (ops.side_lane): the first conv's gradients are a chain of their own beside the weight-only chain
+        # below; their sinks are told after the join - a gradient-ready callback must never see an unfinished slot
+        try:
+            if ctx.side:
+                with ops.side_lane("patch", on=True, join=False):
+                    dw0, db0 = first_conv()
+            dV = torch.empty(T * hidp, E, dtype=torch.float32, device=dev)
+            ops.gemm(Hh, dY, dV, T * hidp, E, M, transA=True, lda=T * hidp, ldb=E, ldc=E,
+                     splitk=ops.auto_splitk(T * hidp, E, M, tn=True))
+            dc = ops.group_rowsum(dY, B, tok, 1, E)                                # [tok, E]
+            # c = posb wsum  ->  dwsum = posb^T dc, dposb = dc wsum^T
+            dwsum = torch.empty(E, E, dtype=torch.float32, device=dev)
+            ops.gemm(posb, dc, dwsum, E, E, tok, transA=True, lda=E, ldb=E, ldc=E, splitk=ops.auto_splitk(E, E, tok, tn=True))
+            dposb = torch.empty(tok, E, dtype=torch.float32, device=dev)
+            ops.gemm(dc, wsum, dposb, tok, E, E, transB=True, lda=E, ldb=E, ldc=E)
+            dpos = s_pos.done(ops.transpose2d(dposb, 1, tok, E, out=s_pos.out()).view(1, E, h, w))
+            db2 = s_b2.done(ops.colsum(dposb, tok, E, out=s_b2.out()))
+            # V_t = w2^T ws_t  ->  dw2 = sum_t ws_t dV_t^T,  dws_t = w2 dV_t (+ dwsum for every t)
+            dw2_t = torch.empty(T, E, hidp, dtype=torch.float32, device=dev)
+            ops.gemm(ws, dV, dw2_t, E, hidp, E, transB=True, lda=E, ldb=E, ldc=hidp, batch=T, strideA=E * E,
+                     strideB=hidp * E, strideC=E * hidp)
+            dw2p = ops.colsum(dw2_t, T, E * hidp).view(E, hidp)
+            dw2 = s_w2.done(ops.copy2d_pad(dw2p, E, hidp, E, hid, out=s_w2.out()).view(E, hid, 1, 1))
+            dws = s_taw.out() if tagamma is None else None
+            dws = ops._out(dws, (T, E, E), dev)
+            ops.gemm(w2p, dV, dws, E, E, hidp, lda=hidp, ldb=E, ldc=E, batch=T, strideA=0, strideB=hidp * E,
+                     strideC=E * E, res=dwsum, ldres=E, strideRes=0)
+            if tagamma is not None:
+                dtaw, dgamma = ops.timeagg_scale_w_bwd(dws, taw, tagamma, tt, out_dw=s_taw.out(),
+                                                       out_dgamma=s_gamma.out())
+                dtaw, dgamma = s_taw.done(dtaw), s_gamma.done(dgamma)
+            else:
+                dtaw, dgamma = s_taw.done(dws), None
+            if not ctx.side:
+                dw0, db0 = first_conv()
+            dx = None
+            if ctx.needs_input_grad[0]:
+                dA0 = ops.linear_bwd_data(dHpre, w0p)                              # [M0, K0]
+                dx = ops.unpatchify(dA0, B, X, Y, T, Cc, P)
+        finally:
+            ops.side_lane_join()
+        db0 = s_b0.done(db0)
+        dw0 = s_w0.done(dw0)
         return dx, dpos, dw0, db0, dw2, db2, dtaw, dgamma, None, None, None, None, None, None, None
 
 

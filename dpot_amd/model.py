@@ -173,10 +173,13 @@ class DPOTNet(nn.Module):
         pe, ta = self.patch_embed.proj, self.time_agg_layer
         P = self.patch_size
         h = self.latent_size[0]
-        d_emb, pk, d_head, mlp_pk = self.packs.derive(self)
-        lat = EmbedFn.apply(x, self.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, ta.w,
-                            ta.gamma if self.time_agg == "exp_mlp" else None, self._gx, self._gy, self._gt, self._tt,
-                            P, self._act, d_emb)
+        d_emb, pk, d_head, mlp_pk = self.packs.derive(self, defer=True)
+        try:       # EmbedFn.forward joins the side lane that `derive` may have left forked, between its two launches
+            lat = EmbedFn.apply(x, self.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, ta.w,
+                                ta.gamma if self.time_agg == "exp_mlp" else None, self._gx, self._gy, self._gt, self._tt,
+                                P, self._act, d_emb)
+        finally:
+            ops.side_lane_join()
         if self.normalize:
             lat = AdaINFn.apply(lat, s_sigma, s_mu)                     # AdaIN (models/dpot.py:386-387)
         recompute = self.recompute_blocks and torch.is_grad_enabled()

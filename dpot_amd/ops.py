@@ -165,11 +165,13 @@ TUNE_KEYS = {
                        "un-paired weight gradients"),
     "packs": (1, "0 = bf16 packs by separate pack passes only: none from the one-launch AFNO layer, the GroupNorm backward or Adam"),
     "pack_both": (1, "0 = bf16 channel MLP without the pack-both path (one pack pass per operand form, fp32 pre-activation saved)"),
-    "fused_small": (4, "0 = separate small launches: per-block reduce launches, eight layout launches, torch ops for the cls head; "
+    "fused_small": (5, "0 = separate small launches: per-block reduce launches, eight layout launches, torch ops for the cls head; "
                        "2 = as 1, but the blocks' weight gradients and their finalising launch per block instead of batched; "
                        "3 = as 1 with the batched launches cut by the one-round rules (another summation order); "
                        "4 = as 1 with the batched launches on the library's own stream beside the embed backward "
-                       "(dpot_wgrad_flush_async); 1 = the batched launches on the step's stream, one after the other"),
+                       "(dpot_wgrad_flush_async); 5 = as 4 with the step's latency-bound side chains on the library's side lane "
+                       "(ops.side_lane: the weight-only prologue beside the embed forward, the first conv's gradients beside the "
+                       "weight-only chain of the embed backward); 1 = the batched launches on the step's stream, one after the other"),
     "embed_implicit": (1, "0 = explicit patch matrix + GEMM instead of the implicit-GEMM patch embedding"),
     "mixer6": (1, "bf16x6 mixer kernel afno_mlp6 under gemm_precision 'auto' / 'bf16x6': 1 = where it measured faster (96 channels "
                   "per block: DPOT-L), 2 = wherever supported (also 128), 0 = never (the fp32 matrix-core kernels)"),
@@ -204,8 +206,24 @@ def tune(key: str, default: Optional[int] = None) -> int:
     return _parse_tune().get(key, d)
 
 
-def _stream() -> int:
+def _step_stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _stream() -> int:
+    """the stream every launch of this module goes to: torch's current stream, or - inside a `side_lane` block of this thread -
+    the library's side lane"""
+    s = getattr(_tls, "side_stream", None)
+    return _step_stream() if s is None else s
+
+
+def _scratch(t: Tensor) -> Tensor:
+    """a workspace that its op drops when it returns.  On the step's stream the allocator may hand it out again at once (stream
+    order protects it); inside a `side_lane` block it stays referenced until the join has been issued."""
+    if getattr(_tls, "side_stream", None) is not None:
+        with _lane_lock:
+            _side_held.append(t)
+    return t
 
 
 def _req(t: Tensor, name: str = "tensor") -> Tensor:
@@ -272,7 +290,7 @@ def gemm(A: Tensor, B: Tensor, C_: Tensor, M: int, N: int, K: int, *, transA: bo
     ws = None
     if splitk > 1:
         L = M if d.colsum_of == 1 else N if d.colsum_of == 2 else 0
-        ws = torch.empty(splitk * batch * (M * N + L), dtype=torch.float32, device=A.device)
+        ws = _scratch(torch.empty(splitk * batch * (M * N + L), dtype=torch.float32, device=A.device))
         d.splitk, d.workspace = splitk, ws.data_ptr()
     else:
         d.splitk, d.workspace = 1, None
@@ -867,8 +885,8 @@ def block_finalize_enabled() -> bool:
 
 def wgrad_batch_enabled() -> bool:
     """the weight gradients of all blocks in batched launches + one finalising launch (DPOT_TUNE fused_small=2: per block;
-    4, the default: the batched launches on the weight-gradient lane, `wgrad_lane_enabled`)"""
-    return tune("fused_small") in (1, 3, 4)
+    4 and 5, the default: the batched launches on the weight-gradient lane, `wgrad_lane_enabled`)"""
+    return tune("fused_small") in (1, 3, 4, 5)
 
 
 def wgrad_batch_one_round() -> bool:
@@ -882,7 +900,7 @@ def wgrad_batch_one_round() -> bool:
 def wgrad_lane_scope(on: Optional[bool]):
     """whether the forward passes run on this thread inside hand their batched weight gradients to the library's lane
     (functional.WgradBatch reads it when DPOTNet creates it, so the backward may run anywhere later): True / False, or None =
-    DPOT_TUNE fused_small (4, the default: the lane).  For one process that runs both schedules."""
+    DPOT_TUNE fused_small (4 and 5, the default: the lane).  For one process that runs both schedules."""
     prev = getattr(_tls, "wgrad_lane", None)
     _tls.wgrad_lane = on
     try:
@@ -941,7 +959,7 @@ def afno_wgrad_batch_chain(nb: int, per_launch: int, splits12: int, splitk: int)
 
 def wgrad_lane_enabled() -> bool:
     v = getattr(_tls, "wgrad_lane", None)
-    return tune("fused_small") == 4 if v is None else bool(v)
+    return tune("fused_small") in (4, 5) if v is None else bool(v)
 
 
 def wgrad_lane_init() -> None:
@@ -977,6 +995,100 @@ def wgrad_lane_join() -> None:
         del _lane_held[:]
     for stream in dict.fromkeys(st for st, _ in held):
         check(_lib.load().dpot_wgrad_wait(stream), "wgrad_wait")
+
+
+# ---- the side lane (lane 1 of csrc/gemm_tn.hip) ------------------------------------------------------------------------------
+# Short chains of latency-bound launches that run beside independent work of the step's stream:
+#   weights  packs.ModelPacks.derive: everything `embed_fwd` does not read, joined by EmbedFn.forward before the fold GEMM
+#   patch    EmbedFn.backward: the first conv's gradients beside the weight-only chain
+# Same launches, same arguments, same results; DPOT_TUNE fused_small=5 (the default) switches on the sites of SIDE_SITES_DEFAULT.
+# (A third site, the classification head beside the de-embed GEMM, measured 11 us against a spread of 9 us and was taken out
+# again: profiles/side_lane_ab.txt, section 2.)
+SIDE_LANE = 1
+SIDE_SITES = ("weights", "patch")
+SIDE_SITES_DEFAULT = SIDE_SITES
+_side_held = []          # what the lane's queued launches touch and their ops have dropped (`_scratch`)
+_side_forks = 0          # forks not joined yet, as this module counts them (a join with none pending costs no library call)
+
+
+@contextlib.contextmanager
+def side_lane_scope(sites):
+    """the side-lane sites (a subset of SIDE_SITES) of the forward passes run on this thread inside, and of their backward
+    passes wherever those run; None = DPOT_TUNE fused_small.  For the ablation and the tests."""
+    if sites is not None:
+        sites = tuple(sites)
+        if any(s not in SIDE_SITES for s in sites):
+            raise ValueError(f"side_lane_scope: sites {sites} not among {SIDE_SITES}")
+    prev = getattr(_tls, "side_sites", None)
+    _tls.side_sites = sites
+    try:
+        yield
+    finally:
+        _tls.side_sites = prev
+
+
+def side_lane_enabled(site: str) -> bool:
+    v = getattr(_tls, "side_sites", None)
+    if v is None:
+        v = SIDE_SITES_DEFAULT if tune("fused_small") == 5 else ()
+    return site in v
+
+
+def side_lane_ready() -> bool:
+    return bool(_lib.load().dpot_lane_ready(SIDE_LANE))
+
+
+def side_lane_pending() -> int:
+    """forks of the current device's side lane since the last join (tests, assertions)"""
+    return _lib.load().dpot_lane_pending(SIDE_LANE)
+
+
+def side_lane_shutdown() -> None:
+    side_lane_join()
+    check(_lib.load().dpot_lane_shutdown(SIDE_LANE), "lane_shutdown")
+
+
+def side_lane_join() -> None:
+    """order torch's current stream behind the side lane (dpot_lane_join) and release what the lane's launches use.  Nothing
+    when nothing is pending; may be repeated."""
+    global _side_forks
+    with _lane_lock:
+        if _side_forks == 0:
+            return
+    check(_lib.load().dpot_lane_join(SIDE_LANE, _step_stream()), "lane_join")
+    with _lane_lock:
+        _side_forks = 0
+        del _side_held[:]
+
+
+@contextlib.contextmanager
+def side_lane(site: str, on: Optional[bool] = None, join: bool = True):
+    """Fork the side lane behind torch's current stream and send every launch of this module made inside the block, on this
+    thread, to the lane (`_stream`).  torch's current stream stays the step's: allocations belong to it, and NO torch op may
+    run inside the block - allocate what one would, or let the ops of this module allocate, before any further work goes to
+    the step's stream.  on: whether the site takes the lane (None = `side_lane_enabled(site)`); off, or nested in another
+    block, the launches stay where they were going.  join=False leaves the lane forked when the block ends normally - the
+    caller joins (`side_lane_join`) before anything reads the block's results; an exception inside always joins."""
+    global _side_forks
+    if on is None:
+        on = side_lane_enabled(site)
+    if not on or getattr(_tls, "side_stream", None) is not None:
+        yield
+        return
+    step = _step_stream()
+    handle = C.c_void_p()
+    check(_lib.load().dpot_lane_fork(SIDE_LANE, step, C.byref(handle)), "lane_fork")
+    with _lane_lock:
+        _side_forks += 1
+    _tls.side_stream = handle.value or 0
+    ok = False
+    try:
+        yield
+        ok = True
+    finally:
+        _tls.side_stream = None
+        if join or not ok:
+            side_lane_join()
 
 
 def wgrad_batch_max_blocks() -> int:
@@ -1422,7 +1534,7 @@ def embed_wgrad(x: Tensor, dhpre: Tensor, dw0: Tensor, hid: int) -> Tensor:
     """data-channel columns of the patch-conv weight gradient: dw0[hid, K0][:, :4*64] (deterministic two-launch sum)"""
     lib = _lib.load()
     B, X, Y, T, _ = x.shape
-    ws = torch.empty(lib.dpot_embed_wgrad_ws_elems(B, X, Y), dtype=torch.float32, device=x.device)
+    ws = _scratch(torch.empty(lib.dpot_embed_wgrad_ws_elems(B, X, Y), dtype=torch.float32, device=x.device))
     check(lib.dpot_embed_wgrad(x.data_ptr(), dhpre.data_ptr(), ws.data_ptr(), dw0.data_ptr(), dw0.stride(0), hid, B, X,
                                Y, T, dhpre.shape[1], _stream()), "embed_wgrad")
     return dw0
@@ -1510,7 +1622,7 @@ def transpose2d(src: Tensor, nbatch: int, R: int, Cn: int, out: Optional[Tensor]
 def colsum(X: Tensor, M: int, N: int, ld: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
     lib = _lib.load()
     out = _out(out, (N,), X.device)
-    part = torch.empty(lib.dpot_colsum_parts(M), N, dtype=torch.float32, device=X.device)
+    part = _scratch(torch.empty(lib.dpot_colsum_parts(M), N, dtype=torch.float32, device=X.device))
     check(lib.dpot_colsum(X.data_ptr(), M, N, ld or N, out.data_ptr(), part.data_ptr(), _stream()), "colsum")
     return out
 

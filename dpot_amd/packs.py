@@ -12,7 +12,8 @@ from __future__ import annotations
 import contextlib
 
 from . import ops
-from .functional import embed_derived, embed_grid_matrix, embed_layout_jobs, head_derived, head_layout_jobs, mlp_pack_kind
+from .functional import (embed_derived, embed_grid_matrix, embed_implicit_tables, embed_layout_jobs, head_derived,
+                         head_layout_jobs, mlp_pack_kind)
 
 
 def _where(*tensors):
@@ -70,17 +71,23 @@ class ModelPacks:
             self.held = None
             if m.pos_embed.is_cuda:
                 with ops.precision_scope(m.gemm_precision, m.mlp_precision):
-                    self.derive(m)
+                    self.derive(m, defer=True)       # the first pass's EmbedFn.forward joins the side lane
         try:
             yield
         finally:
             self.depth -= 1
             if self.depth == 0:
                 self.held = None
+                ops.side_lane_join()                 # a scope that ran no forward
 
     # -- the derived weights of one forward -------------------------------------------------------------
-    def derive(self, m):
-        """-> (embed products, AFNO items, head products + (de-embed packs,), channel-MLP packs per block | None)"""
+    def derive(self, m, defer: bool = False):
+        """-> (embed products, AFNO items, head products + (de-embed packs,), channel-MLP packs per block | None)
+
+        Side-lane site `weights` (ops.side_lane): only the layout jobs, `embed_pack_w0` and the bias-table GEMM feed `embed_fwd`
+        and go to the caller's stream; the scaled aggregation weights, the V and c products, the AFNO packs, the de-embed
+        transpose and the panel packs are first read by the fold GEMM and go to the lane.  Every table is built before the fork
+        (building one runs torch ops).  defer: return with the lane still forked - the caller's EmbedFn.forward joins."""
         if self.depth > 0 and self.held is not None:
             return self.held
         pe, ta, ol = m.patch_embed.proj, m.time_agg_layer, m.out_layer
@@ -96,27 +103,38 @@ class ModelPacks:
             jobs = je + head_layout_jobs(ol[0].bias, ol[4].weight, ol[4].bias, m.patch_size, ol[0].weight.shape[1])
             lay = self._table("layout", _where(*(j[k] for k in (0, 1) for j in jobs)), lambda: ops.LayoutJobs(jobs)).refresh()
             lay_e, lay_h = lay[:len(je)], lay[len(je):]
-        emb = embed_derived(m.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, ta.w,
-                            ta.gamma if m.time_agg == "exp_mlp" else None, m._tt, m.in_timesteps, grid=grid, layouts=lay_e)
-        # Wbig = [[Wr, Wi], [-Wi, Wr]] of every AFNO layer + its fragment-block-major forms, ONE launch for all layers
-        pk = []
+        afno = None
         if len(m.blocks):
             pairs = [p for blk in m.blocks for p in ((blk.filter.w1, blk.filter.b1), (blk.filter.w2, blk.filter.b2))]
-            pk = self._table("afno", _where(*(t for p in pairs for t in p)), lambda: ops.AfnoPacks(pairs)).refresh()
+            afno = self._table("afno", _where(*(t for p in pairs for t in p)), lambda: ops.AfnoPacks(pairs))
         w0 = ol[0].weight
         wt = self._table("wt", _where(w0), lambda: w0.new_empty(m.embed_dim, m.patch_size ** 2 * w0.shape[1]))
-        head = head_derived(w0, ol[0].bias, ol[4].weight, ol[4].bias, m.patch_size, wt_out=wt, layouts=lay_h)
-        mlp_pk, head_pk = self._panels(m, wt)
+        stale = []
+        mlp_pk, head_pk = self._panels(m, wt, stale)
+        eargs = (m.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, ta.w,
+                 ta.gamma if m.time_agg == "exp_mlp" else None, m._tt, m.in_timesteps)
+        side = lay_e is not None and ops.side_lane_enabled("weights")     # the lane's products read the layout pieces
+        with ops.side_lane("weights", on=side, join=False):
+            emb = embed_derived(*eargs, grid=grid, layouts=lay_e, implicit_tables=not side)
+            # Wbig = [[Wr, Wi], [-Wi, Wr]] of every AFNO layer + its fragment-block-major forms, ONE launch for all layers
+            pk = afno.refresh() if afno is not None else []
+            head = head_derived(w0, ol[0].bias, ol[4].weight, ol[4].bias, m.patch_size, wt_out=wt, layouts=lay_h)
+            for pp in stale:
+                pp.refresh()
+        if side and grid is not None:
+            emb = emb[:8] + embed_implicit_tables(pe[0].weight, emb[0], emb[1], grid) + emb[10:]
+        if not defer:
+            ops.side_lane_join()
         d = (emb, pk, head + (head_pk,), mlp_pk)
         if self.depth > 0:
             self.held = d
         return d
 
-    def _panels(self, m, wt):
+    def _panels(self, m, wt, stale):
         """fragment-block-major copies of the static weights of the panel GEMMs, ONE launch per set: per block W1, W1^T,
         W2, W2^T (channel-MLP forward x W^T and data gradient dy W) - fp32 for csrc/gemm_panel.hip, or bf16 / bf16x6 for
         csrc/gemm_bf16p.hip by the channel-MLP precision - and the de-embed matrix wt [E, P*P*old] both ways (fp32).
-        Returns (per-block MlpPacks | None, (wt fwd, wt bwd) | None)."""
+        Returns (per-block MlpPacks | None, (wt fwd, wt bwd) | None); the sets to refresh are appended to `stale`."""
         E, n_out, nb = m.embed_dim, wt.shape[1], len(m.blocks)
         ws = [b.mlp[i].weight for b in m.blocks for i in (0, 2)]            # [mh, E, 1, 1], [E, mh, 1, 1] per block
         mlp_pk = head_pk = None
@@ -128,7 +146,8 @@ class ModelPacks:
 
         def panel(name, key, jobs, bf16, planes=1):          # key: the set's placement beyond ws + its mode flags
             pp = self._table(name, _where(*ws) + key, lambda: ops.PanelPacks(jobs(), bf16=bf16, planes=planes))
-            self.ensure_fresh(pp)
+            if not self.is_fresh(pp):
+                stale.append(pp)
             return pp
 
         kind = mlp_pack_kind(E, ws[0].shape[0]) if nb else None

@@ -261,6 +261,25 @@ int dpot_wgrad_flush_async(const float* const* do2, const float* const* Hh, cons
                            const dpot_wgrad_block* blocks, int gn_jobs, int B, int Egn, int mlp_chain, int afno_chain,
                            dpot_stream_t stream);
 int dpot_wgrad_wait(dpot_stream_t stream);
+/* The library's LANES: lane 0 is the weight-gradient lane above (the dpot_wgrad_* entry points are its users), lane 1 the SIDE
+ * lane for short latency-bound chains that run beside independent work of the caller's stream (csrc/gemm_tn.hip; DESIGN.md
+ * section 5).  The same rules: one non-blocking stream at the default priority and two events per lane and device, created by
+ * dpot_lane_init or the first fork, never while the caller's stream is capturing; every access under the library's mutex.
+ * dpot_lane_fork: records the fork event on `caller`, makes the lane wait for it, stores the lane's stream handle in
+ *   *lane_stream - launch the side work with it - and counts one pending fork.  A first use inside a stream capture creates
+ *   nothing, counts nothing and stores `caller` itself: the side work then runs serially on the caller's stream.
+ * dpot_lane_join: records the done event on the lane, makes `caller` wait for it and clears the pending count.  With nothing
+ *   pending it does nothing and may be repeated.  Forks made inside a capture that has ended are dropped.
+ *   The caller keeps every buffer the side work touches alive, and unused by others, until it has joined - also when a launch
+ *   of the side work failed.
+ * dpot_lane_pending: forks since the last join (current device; dpot_wgrad_lane_pending counts lane 0's flushes only).
+ * dpot_lane_ready: 1 when the lane exists.  dpot_lane_shutdown: drains and destroys it (nothing may be pending). */
+int dpot_lane_init(int lane);
+int dpot_lane_ready(int lane);
+int dpot_lane_pending(int lane);
+int dpot_lane_shutdown(int lane);
+int dpot_lane_fork(int lane, dpot_stream_t caller, dpot_stream_t* lane_stream);
+int dpot_lane_join(int lane, dpot_stream_t caller);
 /* Small weight-only layout jobs (zero-padded copies, small transposes, bias broadcasts, "+ bias") in ONE launch from a DEVICE
  * table: dst[i0][i1][i2] (contiguous d0 x d1 x d2) = (inside v0 x v1 x v2 ? src[i0 s0 + i1 s1 + i2 s2] : 0) + (add ? add[i2] : 0).
  * The pieces DPOTNet derives from its parameters once per optimiser step (models/dpot.py:198-202 padded for the MFMA
