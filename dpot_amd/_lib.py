@@ -270,6 +270,13 @@ SIGNATURES = {
     "dpot_embed_wgrad": (c_i, [c_fp] * 4 + [c_i] * 7 + [c_fp]),
     "dpot_gemm_panel_supported": (c_i, [c_i, c_i, c_i]),
     "dpot_gemm_panel": (c_i, [c_fp, c_i, c_fp, c_fp, c_fp, c_i, c_fp, c_i, c_fp, c_i, c_fp, c_i] + [c_i] * 5 + [c_fp]),
+    "dpot_aa_max_size": (c_i, [c_i]),
+    "dpot_aa_tab_words": (c_i64, [c_i, c_i]),
+    "dpot_aa_vtab_words": (c_i64, [c_i] * 4),
+    "dpot_aa_lrelu_fwd": (c_i, [c_fp] * 4 + [c_i] * 5 + [c_f, c_fp]),
+    "dpot_aa_lrelu_bwd": (c_i, [c_fp] * 5 + [c_i] * 4 + [c_f, c_fp]),
+    "dpot_aa_up_fwd": (c_i, [c_fp] * 4 + [c_i] * 7 + [c_fp]),
+    "dpot_aa_up_adj": (c_i, [c_fp] * 3 + [c_i] * 6 + [c_fp]),
 }
 
 _lib = None

@@ -55,7 +55,9 @@ int tune(const char* key, int dflt) {
  * dpot_tn_chain_count, dpot_tn_chain_nodes, dpot_*_wgrad_batch_chain, dpot_*_wgrad_chain_ws_elems (csrc/gemm_tn.hip): chained
  * token ranges in the batched weight gradients
  * 272: dpot_lane_init, dpot_lane_ready, dpot_lane_pending, dpot_lane_shutdown, dpot_lane_fork, dpot_lane_join (csrc/gemm_tn.hip):
- * a table of library-owned lanes; the weight-gradient lane is lane 0, the side lane of the step's small chains lane 1 */
-extern "C" int dpot_version(void) { return 272; }
+ * a table of library-owned lanes; the weight-gradient lane is lane 0, the side lane of the step's small chains lane 1
+ * 273: dpot_aa_lrelu_fwd, dpot_aa_lrelu_bwd, dpot_aa_up_fwd, dpot_aa_up_adj and their queries (csrc/aa_act.hip): the anti-aliased
+ * activation of the CDPOT model */
+extern "C" int dpot_version(void) { return 273; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

@@ -6,6 +6,7 @@ kernels directly (no autograd tracing inside a stage, no eager-PyTorch math):
   HeadFn    out_layer (ConvTranspose as GEMM + pixel tail) and cls_head                             models/dpot.py:394-398
   RelL2Fn   masked relative L2 loss                                                                 utils/criterion.py:38-59
   AFNO3DFn, GroupNormFn, Mlp2Fn, TimeAggFn, Head3DFn, block3d   the 3-D model's stages          models/dpot3d.py
+  AALReLUFn, PatchConvFn, LinearFn, ClsHeadFn, TokenMeanFn      the CDPOT model's stages        models/dpot_res.py
 
 Internal activation layout: channels-last tokens [B, h*w, E] (row-major [B*h*w, E]).
 
@@ -1503,3 +1504,125 @@ def block3d(x, n1w, n1b, w1, b1, w2, b2, n2w, n2b, f1w, f1b, f2w, f2b, dims3, nb
     xn2 = GroupNormFn.apply(y1, n2w, n2b, 8)
     out = Mlp2Fn.apply(xn2.view(B * tok, E), f1w.view(mh, E), f1b, f2w.view(E, mh), f2b, act, x.reshape(B * tok, E), 0)
     return out.view(B, tok, E)
+
+
+# ======================================================================================================
+# CDPOT model (models/dpot_res.py): the anti-aliased activation and the plain stages around it
+# ======================================================================================================
+class AALReLUFn(torch.autograd.Function):
+    """ops.aa_lrelu on a channels-last field x[N, h, w, C] with bias [Cb], C % Cb == 0: bilinear up by 2, LeakyReLU,
+    anti-aliased bilinear down by 2, optionally bilinear up to out_size, + bias (the reference's LReLu_torch).  Keeps x and
+    nothing of the up-sampled size: the backward recomputes the up-sampled field inside its kernel."""
+
+    @staticmethod
+    def forward(ctx, x, bias, out_size=None, slope: float = 0.01):
+        x, bias = x.contiguous(), bias.contiguous()
+        ctx.save_for_backward(x)
+        ctx.Cb, ctx.slope = bias.shape[0], float(slope)
+        return ops.aa_lrelu(x, bias, out_size, slope)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        dx, dbias = ops.aa_lrelu_bwd(x, dy.contiguous(), ctx.Cb, ctx.slope)
+        return dx, dbias, None, None
+
+
+class LinearFn(torch.autograd.Function):
+    """y[M, N] = x[M, K] W[N, K]^T + b (+ res): one Linear / 1x1 convolution.  res [R, N] with res_mod = R is added to row m as
+    res[(m // res_div) % R] (a per-token table under rows (b, token, t): res_div = T)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, res=None, res_div: int = 0, res_mod: int = 0):
+        ops.capture_precision(ctx)
+        x, W = x.contiguous(), W.contiguous()
+        res = res.contiguous() if res is not None else None
+        y, _ = ops.linear_fwd(x, W, b, res=res, res_div=res_div, res_mod=res_mod)
+        ctx.save_for_backward(x, W)
+        ctx.res_div, ctx.res_mod, ctx.has_res = max(res_div, 1), res_mod, res is not None
+        return y
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dy):
+        x, W = ctx.saved_tensors
+        dy = dy.contiguous()
+        M, N = dy.shape
+        dW, db = ops.linear_bwd_wb(dy, x)
+        dx = ops.linear_bwd_data(dy, W) if ctx.needs_input_grad[0] else None
+        dres = None
+        if ctx.has_res and ctx.needs_input_grad[3]:
+            dres = dy if not ctx.res_mod else ops.group_rowsum(dy, M // (ctx.res_mod * ctx.res_div), ctx.res_mod, ctx.res_div, N)
+        return dx, dW, db, dres, None, None
+
+
+class ClsHeadFn(torch.autograd.Function):
+    """cls_head on the token mean cm[B, E]: Linear, act, Linear, act, Linear (models/dpot_res.py:467-473)"""
+
+    @staticmethod
+    def forward(ctx, cm, c0w, c0b, c2w, c2b, c4w, c4b, act: int):
+        ops.capture_precision(ctx)
+        cm = cm.contiguous()
+        c1, c1pre = ops.linear_fwd(cm, c0w, c0b, act=act, save_pre=True)
+        c2, c2pre = ops.linear_fwd(c1, c2w, c2b, act=act, save_pre=True)
+        cls, _ = ops.linear_fwd(c2, c4w, c4b)
+        ctx.save_for_backward(cm, c1, c1pre, c2, c2pre, c0w, c2w, c4w)
+        ctx.act = act
+        return cls
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dcls):
+        cm, c1, c1pre, c2, c2pre, c0w, c2w, c4w = ctx.saved_tensors
+        act = ctx.act
+        dcls = dcls.contiguous()
+        dc2pre = ops.linear_bwd_data(dcls, c4w, act=act, aux=c2pre)
+        dc4w, dc4b = ops.linear_bwd_wb(dcls, c2)
+        dc1pre = ops.linear_bwd_data(dc2pre, c2w, act=act, aux=c1pre)
+        dc2w, dc2b = ops.linear_bwd_wb(dc2pre, c1)
+        dcm = ops.linear_bwd_data(dc1pre, c0w) if ctx.needs_input_grad[0] else None
+        dc0w, dc0b = ops.linear_bwd_wb(dc1pre, cm)
+        return dcm, dc0w, dc0b, dc2w, dc2b, dc4w, dc4b, None
+
+
+class PatchConvFn(torch.autograd.Function):
+    """The k = s = P convolution of the 2-D patch embedding WITHOUT an activation, on the raw window x[B, X, Y, T, C]:
+    ops.patchify (the three coordinate channels come from the tables gx, gy, gt) and one GEMM -> rows (b, hx, hy, t), hid
+    columns.  x is kept, not the patch matrix: the backward gathers it again for the weight gradient."""
+
+    @staticmethod
+    def forward(ctx, x, gx, gy, gt, W, b, P: int):
+        ops.capture_precision(ctx)
+        x, W = x.contiguous(), W.contiguous()
+        A0 = ops.patchify(x, gx, gy, gt, P)
+        y, _ = ops.linear_fwd(A0, W, b)
+        ctx.save_for_backward(x, gx, gy, gt, W)
+        ctx.P = P
+        return y
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dy):
+        x, gx, gy, gt, W = ctx.saved_tensors
+        dy = dy.contiguous()
+        A0 = ops.patchify(x, gx, gy, gt, ctx.P)
+        dW, db = ops.linear_bwd_wb(dy, A0)
+        del A0
+        dx = None
+        if ctx.needs_input_grad[0]:
+            B, X, Y, T, C = x.shape
+            dx = ops.unpatchify(ops.linear_bwd_data(dy, W), B, X, Y, T, C, ctx.P)
+        return dx, None, None, None, dW, db, None
+
+
+class TokenMeanFn(torch.autograd.Function):
+    """x[B, tokens, E] -> the mean over the tokens [B, E]"""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.tok = x.shape[1]
+        return ops.token_mean(x.contiguous())
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.token_mean_bwd(dy.contiguous(), ctx.tok)

@@ -2501,3 +2501,210 @@ def eval_metrics_update(pred: Tensor, target: Tensor, acc: Tensor) -> None:
     check(getattr(lib, rank.stats)(pred.data_ptr(), target.data_ptr(), *(t.data_ptr() for t in plan.dev.values()), *work, B,
                                    *sizes, T * C, _stream()), rank.stats[5:])
     check(getattr(lib, rank.finalize)(work[0], work[1], acc.data_ptr(), B, *sizes, T, C, _stream()), rank.finalize[5:])
+
+
+# ------------------------------------------------------------------------------------------------------
+# Anti-aliased activation of the CDPOT model (csrc/aa_act.hip): bilinear up by 2, LeakyReLU, anti-aliased bilinear down by 2,
+# optionally bilinear up to an output size, + a per-channel bias (models/filter_networks.py:481-518).  The resize matrices
+# and tap tables are pure numpy: the CPU tests check them without a GPU.
+# ------------------------------------------------------------------------------------------------------
+def aa_resize_matrix(n: int, m: int):
+    """float64 [m, n]: one axis of F.interpolate(mode='bilinear', antialias=True) from n to m samples.  Output i sits at
+    c = (n/m)(i + 0.5) and weighs the inputs j in [int(c - s + 0.5), int(c + s + 0.5)), clipped to the axis, by the triangle
+    max(0, 1 - |(j - c + 0.5) / s|) of half-width s = max(n/m, 1), normalised to sum 1."""
+    import numpy as np
+    n, m = int(n), int(m)
+    if n < 1 or m < 1:
+        raise ValueError(f"aa_resize_matrix: sizes must be >= 1 (got {n} -> {m})")
+    scale = n / m
+    support = max(scale, 1.0)
+    inv = 1.0 / support
+    A = np.zeros((m, n), dtype=np.float64)
+    for i in range(m):
+        c = scale * (i + 0.5)
+        lo, hi = max(int(c - support + 0.5), 0), min(int(c + support + 0.5), n)
+        j = np.arange(lo, hi, dtype=np.float64)
+        wt = np.maximum(0.0, 1.0 - np.abs((j - c + 0.5) * inv))
+        A[i, lo:hi] = wt / wt.sum()
+    return A
+
+
+def _aa_taps(A, K: int, what: str):
+    """rows of a dense matrix as K taps each: (index int32 [rows, K], weight fp32 [rows, K]); unused taps carry weight 0 and
+    repeat the row's last index (always inside the axis)"""
+    import numpy as np
+    rows = A.shape[0]
+    idx = np.zeros((rows, K), dtype=np.int32)
+    wt = np.zeros((rows, K), dtype=np.float32)
+    for r in range(rows):
+        nz = np.nonzero(A[r])[0]
+        if len(nz) > K:
+            raise ValueError(f"aa tables: {what} row {r} has {len(nz)} taps, the kernels take {K}")
+        idx[r, :len(nz)] = nz
+        idx[r, len(nz):] = nz[-1] if len(nz) else 0
+        wt[r, :len(nz)] = A[r, nz]
+    return idx, wt
+
+
+def _aa_csr(A):
+    """rows of a dense matrix [rows, cols] in CSR form padded to 2 * cols entries: (ptr int32 [rows + 1], index int32, weight fp32)"""
+    import numpy as np
+    rows, cols = A.shape
+    ptr = np.zeros(rows + 1, dtype=np.int32)
+    idx = np.zeros(2 * cols, dtype=np.int32)
+    wt = np.zeros(2 * cols, dtype=np.float32)
+    k = 0
+    for r in range(rows):
+        nz = np.nonzero(A[r])[0]
+        if k + len(nz) > 2 * cols:
+            raise ValueError("aa tables: a bilinear up-sampling row has more than 2 taps")
+        idx[k:k + len(nz)] = nz
+        wt[k:k + len(nz)] = A[r, nz]
+        k += len(nz)
+        ptr[r + 1] = k
+    return ptr, idx, wt
+
+
+def aa_core_tables(h: int, w: int):
+    """int32 words [32 (h + w)] of dpot_aa_lrelu_fwd / _bwd (include/dpot_hip.h): per axis the taps of U (n -> 2n), D (2n -> n),
+    U^T and D^T, weights as fp32 bit patterns"""
+    import numpy as np
+    parts = []
+    for n in (int(h), int(w)):
+        U, D = aa_resize_matrix(n, 2 * n), aa_resize_matrix(2 * n, n)
+        for A, K, what in ((U, 2, "U"), (D, 4, "D"), (U.T, 4, "U^T"), (D.T, 2, "D^T")):
+            idx, wt = _aa_taps(A, K, f"{what} ({n})")
+            parts += [idx.reshape(-1), wt.reshape(-1).view(np.int32)]
+    return np.concatenate(parts)
+
+
+def aa_up_tables(h: int, w: int, H: int, W: int):
+    """int32 words of dpot_aa_up_fwd / _adj: the taps of V (rows h -> H, columns w -> W), then V^T of both in CSR form"""
+    import numpy as np
+    Vh, Vw = aa_resize_matrix(h, H), aa_resize_matrix(w, W)
+    parts = []
+    for V in (Vh, Vw):
+        idx, wt = _aa_taps(V, 2, "V")
+        parts += [idx.reshape(-1), wt.reshape(-1).view(np.int32)]
+    for V in (Vh, Vw):
+        ptr, idx, wt = _aa_csr(V.T)
+        parts += [ptr, idx, wt.view(np.int32)]
+    return np.concatenate(parts)
+
+
+class AAPlan:
+    """The tap tables of the anti-aliased activation for one size tuple (h, w, H, W) - H = W = 0: no output size - built in
+    float64, rounded to fp32 and kept in device memory"""
+
+    def __init__(self, h: int, w: int, H: int, W: int, device):
+        lib = _lib.load()
+        self.sizes = (h, w, H, W)
+        lat, outm = lib.dpot_aa_max_size(0), lib.dpot_aa_max_size(1)
+        if not (1 <= h <= lat and 1 <= w <= lat):
+            raise ValueError(f"aa_lrelu: latent size {h}x{w} is not supported (1 <= h, w <= {lat})")
+        if (H or W) and not (h <= H <= outm and w <= W <= outm):
+            raise ValueError(f"aa_lrelu: output size {H}x{W} is not supported for a {h}x{w} field (per axis: input size <= "
+                             f"output size <= {outm})")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DpotHipError(f"AAPlan {self.sizes}: the tap tables are uploaded when a size tuple is first used - call "
+                                    "ops.aa_plan(...) (or the operator itself) once before capturing")
+        core = aa_core_tables(h, w)
+        if len(core) != lib.dpot_aa_tab_words(h, w):
+            raise _lib.DpotHipError(f"AAPlan: {len(core)} table words, the library expects {lib.dpot_aa_tab_words(h, w)}")
+        self.tab = torch.empty(len(core), dtype=torch.int32, device=device)
+        self.tab.copy_(torch.from_numpy(core))
+        self.vtab = None
+        if H or W:
+            up = aa_up_tables(h, w, H, W)
+            if len(up) != lib.dpot_aa_vtab_words(h, w, H, W):
+                raise _lib.DpotHipError(f"AAPlan: {len(up)} up-sampling table words, the library expects "
+                                        f"{lib.dpot_aa_vtab_words(h, w, H, W)}")
+            self.vtab = torch.empty(len(up), dtype=torch.int32, device=device)
+            self.vtab.copy_(torch.from_numpy(up))
+
+
+_aa_plans = {}
+
+
+def aa_plan(h: int, w: int, H: int, W: int, device) -> AAPlan:
+    """the cached AAPlan of (h, w, H, W, device); H = W = 0 without an output size"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(h), int(w), int(H), int(W), device)
+    plan = _aa_plans.get(key)
+    if plan is None:
+        plan = _aa_plans[key] = AAPlan(*key)
+    return plan
+
+
+def _aa_out_size(out_size, h: int, w: int):
+    if out_size is None:
+        return 0, 0
+    H, W = (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
+    return (0, 0) if (H, W) == (h, w) else (H, W)      # V is the identity at the input size: skipped, as the reference does
+
+
+def _aa_args(x: Tensor, bias: Tensor, what: str):
+    _req(x, f"{what}: x")
+    _req(bias, f"{what}: bias")
+    if x.dim() != 4 or bias.dim() != 1 or x.numel() == 0 or bias.numel() == 0 or x.shape[3] % bias.shape[0] or \
+            bias.device != x.device:
+        raise ValueError(f"{what}: x must be a non-empty [N, h, w, C] and bias [Cb] with C % Cb == 0 on one device, got "
+                         f"{tuple(x.shape)} and {tuple(bias.shape)}")
+    return tuple(x.shape)
+
+
+def aa_lrelu(x: Tensor, bias: Tensor, out_size=None, slope: float = 0.01, out: Optional[Tensor] = None) -> Tensor:
+    """y [N, H, W, C] = V D lrelu(U x U^T) D^T V^T + bias[c % Cb] of a channels-last x [N, h, w, C]: bilinear up by 2,
+    LeakyReLU(slope), anti-aliased bilinear down by 2, bilinear up to out_size = (H, W) / one int (None or the input size:
+    skipped), + bias [Cb] (the reference's LReLu_torch).  One launch, two with an output size (the field at the latent size
+    goes through a scratch tensor; the 2h x 2w field never exists)."""
+    N, h, w, C = _aa_args(x, bias, "aa_lrelu")
+    H, W = _aa_out_size(out_size, h, w)
+    plan = aa_plan(h, w, H, W, x.device)
+    shape = (N, H or h, W or w, C)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _req(out, "aa_lrelu: out")
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise _lib.DpotHipError(f"aa_lrelu: out must be {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
+        if out.data_ptr() == x.data_ptr():
+            raise _lib.DpotHipError("aa_lrelu: out must not alias x")
+    lib = _lib.load()
+    Cb = bias.shape[0]
+    if plan.vtab is None:
+        check(lib.dpot_aa_lrelu_fwd(x.data_ptr(), bias.data_ptr(), out.data_ptr(), plan.tab.data_ptr(), N, h, w, C, Cb,
+                                    float(slope), _stream()), "aa_lrelu_fwd")
+        return out
+    z = _scratch(torch.empty_like(x))
+    check(lib.dpot_aa_lrelu_fwd(x.data_ptr(), None, z.data_ptr(), plan.tab.data_ptr(), N, h, w, C, Cb, float(slope),
+                                _stream()), "aa_lrelu_fwd")
+    check(lib.dpot_aa_up_fwd(z.data_ptr(), bias.data_ptr(), out.data_ptr(), plan.vtab.data_ptr(), N, h, w, H, W, C, Cb,
+                             _stream()), "aa_up_fwd")
+    return out
+
+
+def aa_lrelu_bwd(x: Tensor, dy: Tensor, Cb: int, slope: float = 0.01, out_dbias: Optional[Tensor] = None):
+    """(dx [N, h, w, C], dbias [Cb]) of aa_lrelu for dy [N, H, W, C] (H x W the output size of the forward, or h x w): the
+    up-sampled field is recomputed from x inside the kernel; the kernel's per-sample bias partials are finished by colsum"""
+    _req(x, "aa_lrelu_bwd: x")
+    _req(dy, "aa_lrelu_bwd: dy")
+    if x.dim() != 4 or dy.dim() != 4 or x.numel() == 0 or dy.shape[0] != x.shape[0] or dy.shape[3] != x.shape[3] or \
+            Cb < 1 or x.shape[3] % Cb or dy.device != x.device:
+        raise ValueError(f"aa_lrelu_bwd: x [N, h, w, C] and dy [N, H, W, C] with C % Cb == 0 on one device, got "
+                         f"{tuple(x.shape)}, {tuple(dy.shape)} and Cb = {Cb}")
+    N, h, w, C = x.shape
+    H, W = _aa_out_size((dy.shape[1], dy.shape[2]), h, w)
+    plan = aa_plan(h, w, H, W, x.device)
+    lib = _lib.load()
+    g = dy
+    if plan.vtab is not None:
+        g = _scratch(torch.empty_like(x))
+        check(lib.dpot_aa_up_adj(dy.data_ptr(), g.data_ptr(), plan.vtab.data_ptr(), N, h, w, H, W, C, _stream()), "aa_up_adj")
+    dx = torch.empty_like(x)
+    part = _scratch(torch.empty(N, C, dtype=torch.float32, device=x.device))
+    check(lib.dpot_aa_lrelu_bwd(x.data_ptr(), g.data_ptr(), dx.data_ptr(), part.data_ptr(), plan.tab.data_ptr(), N, h, w, C,
+                                float(slope), _stream()), "aa_lrelu_bwd")
+    return dx, colsum(part, N * (C // Cb), Cb, out=out_dbias)

@@ -968,6 +968,39 @@ int dpot_eval3_stats(const float* pred, const float* target, const float* cxT, c
 int dpot_eval3_finalize(const double* statp, const float* specp, double* acc, int B, int nx, int ny, int nz, int T, int C,
                         dpot_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Anti-aliased activation of the CDPOT model (csrc/aa_act.hip; the reference's LReLu_torch, models/filter_networks.py:481-518)
+ * on channels-last fields:   y[n,:,:,c] = V_h D_h lrelu(U_h x[n,:,:,c] U_w^T) D_w^T V_w^T + bias[c % Cb]
+ * U: bilinear n -> 2n, D: anti-aliased bilinear 2n -> n, V: bilinear (h, w) -> (H, W).  Four launches:
+ *   dpot_aa_lrelu_fwd  out[N,h,w,C] = D lrelu(U x U^T) D^T (+ bias[c % Cb] when bias != NULL: the form without V)
+ *   dpot_aa_up_fwd     y[N,H,W,C]   = V z V^T (+ bias[c % Cb])
+ *   dpot_aa_up_adj     g[N,h,w,C]   = V^T dy V
+ *   dpot_aa_lrelu_bwd  dx[N,h,w,C]  = U^T [ lrelu'(U x U^T) . (D^T g D) ] U   (lrelu' = 1 where the up-sampled value is > 0,
+ *                      the slope elsewhere, also at exactly 0), part[N, C] = sum over the pixels of g: since the rows of V sum
+ *                      to 1 this is the per-sample bias gradient (finish with dpot_colsum over the rows (n, c / Cb))
+ * The 2h x 2w up-sampled field exists in registers only; the backward recomputes it from x.
+ * tab: dpot_aa_tab_words(h, w) = 32 (h + w) 32-bit words on the device, per axis n (h first, then w), index words int32 and
+ * weight words fp32: U taps [2n][2] index | weight, D taps [n][4] index | weight, U^T [n][4] index | weight (the up-sampled
+ * values an input feeds), D^T [2n][2] index | weight; unused taps carry weight 0 and a valid index.
+ * vtab: dpot_aa_vtab_words(h, w, H, W) words: V taps of the rows [H][2] index | weight, of the columns [W][2] index | weight,
+ * then V^T of the rows in CSR form ptr [h+1] | index [2H] | weight [2H] and of the columns ptr [w+1] | index [2W] | weight [2W].
+ * Every index must lie inside its axis (the kernels do not check the tables; dpot_amd/ops.py AAPlan builds them in float64).
+ * Sizes: 1 <= h, w <= dpot_aa_max_size(0) (= 64: the plane of a workgroup lives in LDS), h <= H, w <= W <= dpot_aa_max_size(1)
+ * (= 1024) - beyond: DPOT_EUNSUP, nothing is launched.  Any C >= 1 (16-byte loads and stores when C % 4 == 0 and the fields
+ * are 16-byte aligned), C % Cb == 0.  Reads nothing outside the tensors, fixed summation order, no atomics, no allocation,
+ * legal under stream capture. */
+int dpot_aa_max_size(int output);
+int64_t dpot_aa_tab_words(int h, int w);
+int64_t dpot_aa_vtab_words(int h, int w, int H, int W);
+int dpot_aa_lrelu_fwd(const float* x, const float* bias, float* out, const int32_t* tab, int N, int h, int w, int C, int Cb,
+                      float slope, dpot_stream_t stream);
+int dpot_aa_lrelu_bwd(const float* x, const float* g, float* dx, float* part, const int32_t* tab, int N, int h, int w, int C,
+                      float slope, dpot_stream_t stream);
+int dpot_aa_up_fwd(const float* z, const float* bias, float* y, const int32_t* vtab, int N, int h, int w, int H, int W, int C,
+                   int Cb, dpot_stream_t stream);
+int dpot_aa_up_adj(const float* dy, float* g, const int32_t* vtab, int N, int h, int w, int H, int W, int C,
+                   dpot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
