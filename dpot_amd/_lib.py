@@ -246,13 +246,6 @@ SIGNATURES = {
     "dpot_afno_wgrad_batch_ws_elems": (c_i64, [c_i] * 4),
     "dpot_afno_wgrad_batch": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i] * 5 + [c_fp] + [c_i] * 4 + [c_fp]),
     "dpot_wgrad_batch_finalize": (c_i, [C.POINTER(WgradBlock)] + [c_i] * 13 + [c_fp]),
-    "dpot_wgrad_lane_init": (c_i, []),
-    "dpot_wgrad_lane_ready": (c_i, []),
-    "dpot_wgrad_lane_pending": (c_i, []),
-    "dpot_wgrad_lane_shutdown": (c_i, []),
-    "dpot_wgrad_flush_async": (c_i, [C.POINTER(C.c_void_p)] * 4 + [c_i] * 4 + [c_fp, c_i] + [C.POINTER(C.c_void_p)] * 4
-                               + [c_i] * 4 + [c_fp] + [c_i] * 3 + [C.POINTER(WgradBlock)] + [c_i] * 5 + [c_fp]),
-    "dpot_wgrad_wait": (c_i, [c_fp]),
     "dpot_lane_init": (c_i, [c_i]),
     "dpot_lane_ready": (c_i, [c_i]),
     "dpot_lane_pending": (c_i, [c_i]),

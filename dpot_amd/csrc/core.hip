@@ -57,7 +57,9 @@ int tune(const char* key, int dflt) {
  * 272: dpot_lane_init, dpot_lane_ready, dpot_lane_pending, dpot_lane_shutdown, dpot_lane_fork, dpot_lane_join (csrc/gemm_tn.hip):
  * a table of library-owned lanes; the weight-gradient lane is lane 0, the side lane of the step's small chains lane 1
  * 273: dpot_aa_lrelu_fwd, dpot_aa_lrelu_bwd, dpot_aa_up_fwd, dpot_aa_up_adj and their queries (csrc/aa_act.hip): the anti-aliased
- * activation of the CDPOT model */
-extern "C" int dpot_version(void) { return 273; }
+ * activation of the CDPOT model
+ * 274: the lanes move to csrc/lane.hip; dpot_wgrad_flush_async, dpot_wgrad_wait and dpot_wgrad_lane_* removed (lane 0 is forked
+ * and joined through dpot_lane_* like lane 1) */
+extern "C" int dpot_version(void) { return 274; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

@@ -110,8 +110,8 @@ class WgradBatch:
 
     The flush is the last thing block 0's backward does; the embed backward that follows is a chain of small launches that reads
     none of its results.  By default (DPOT_TUNE fused_small=4 or 5, `ops.wgrad_lane_scope`) the three launch sets therefore go to the
-    library's weight-gradient lane, a stream of its own that is forked from this one and joined back when the backward ends
-    (`_lane_ok`, ops.wgrad_flush_async).  Same launches, same results."""
+    library's weight-gradient lane (lane 0 of csrc/lane.hip), a stream of its own that is forked from this one and joined back
+    when the backward ends (`_lane_ok`, ops.wgrad_flush_async).  Same launches, same results."""
 
     def __init__(self):
         self.expected = self.delivered = 0
@@ -168,8 +168,8 @@ class WgradBatch:
         """The flush may run beside the rest of the backward (ops.wgrad_flush_async) when nobody looks at its gradients before
         the backward ends - no gradient-ready callbacks (a data-parallel reducer, hooks) - and every sink is the ONLY outstanding
         use of its parameter and writes its slot directly: no temporary to add on the step's stream now, none by a later
-        contribution of this backward (a rollout's further passes).  The wait is the autograd engine's end-of-backward callback;
-        outside a backward there is none to queue."""
+        contribution of this backward (a rollout's further passes).  The join (ops.wgrad_lane_join) is the autograd engine's
+        end-of-backward callback; outside a backward there is none to queue."""
         for j in g:
             for sk in j.sinks.values():
                 if sk.fp.callbacks or sk.fp.pending[sk.i] != 1 or sk.out() is None:

@@ -169,7 +169,7 @@ TUNE_KEYS = {
                        "2 = as 1, but the blocks' weight gradients and their finalising launch per block instead of batched; "
                        "3 = as 1 with the batched launches cut by the one-round rules (another summation order); "
                        "4 = as 1 with the batched launches on the library's own stream beside the embed backward "
-                       "(dpot_wgrad_flush_async); 5 = as 4 with the step's latency-bound side chains on the library's side lane "
+                       "(ops.wgrad_flush_async); 5 = as 4 with the step's latency-bound side chains on the library's side lane "
                        "(ops.side_lane: the weight-only prologue beside the embed forward, the first conv's gradients beside the "
                        "weight-only chain of the embed backward); 1 = the batched launches on the step's stream, one after the other"),
     "embed_implicit": (1, "0 = explicit patch matrix + GEMM instead of the implicit-GEMM patch embedding"),
@@ -211,18 +211,24 @@ def _step_stream() -> int:
 
 
 def _stream() -> int:
-    """the stream every launch of this module goes to: torch's current stream, or - inside a `side_lane` block of this thread -
-    the library's side lane"""
-    s = getattr(_tls, "side_stream", None)
-    return _step_stream() if s is None else s
+    """the stream every launch of this module goes to: torch's current stream, or - inside a lane block of this thread
+    (`_Lane.block`) - that lane of the library"""
+    cur = getattr(_tls, "lane", None)
+    return _step_stream() if cur is None else cur[1]
+
+
+def _hold(*tensors) -> None:
+    """inside a lane block of this thread: keep `tensors` referenced until the lane's join has been issued"""
+    cur = getattr(_tls, "lane", None)
+    if cur is not None:
+        with _lane_lock:
+            cur[0].held.extend(tensors)
 
 
 def _scratch(t: Tensor) -> Tensor:
     """a workspace that its op drops when it returns.  On the step's stream the allocator may hand it out again at once (stream
-    order protects it); inside a `side_lane` block it stays referenced until the join has been issued."""
-    if getattr(_tls, "side_stream", None) is not None:
-        with _lane_lock:
-            _side_held.append(t)
+    order protects it); inside a lane block it stays referenced until the join has been issued."""
+    _hold(t)
     return t
 
 
@@ -962,53 +968,100 @@ def wgrad_lane_enabled() -> bool:
     return tune("fused_small") in (4, 5) if v is None else bool(v)
 
 
-def wgrad_lane_init() -> None:
-    """create the current device's lane now (never legal while a stream of the device is capturing)"""
-    check(_lib.load().dpot_wgrad_lane_init(), "wgrad_lane_init")
+# ---- the library's lanes (csrc/lane.hip) -------------------------------------------------------------------------------------
+_lane_lock = threading.Lock()
 
 
-def wgrad_lane_ready() -> bool:
-    return bool(_lib.load().dpot_wgrad_lane_ready())
+class _Lane:
+    """One lane of the library as this module drives it: a library-owned stream beside the step's.  `block` forks it behind
+    torch's current stream and sends this thread's launches to it, `join` orders the streams that forked behind it.
+    index: the library's lane; forks: forks not joined yet, as this module counts them; streams: the streams that forked;
+    held: what the queued launches touch - allocated on the step's stream and referenced from here until the join has been
+    ISSUED, so whatever the allocator hands out again afterwards is ordered behind the lane.  (`_tls.lane` says which lane, if
+    any, this thread's launches go to.)
+    Known limit: ONE thread and ONE stream per device drive a lane between fork and join.  The library clears its pending count
+    at the first join, so after forks from two streams (or two threads at once) the second stream's join is a no-op."""
+
+    def __init__(self, index: int):
+        self.index, self.forks, self.streams, self.held = index, 0, [], []
+
+    def init(self) -> None:
+        """create the current device's lane now (never legal while a stream of the device is capturing)"""
+        check(_lib.load().dpot_lane_init(self.index), "lane_init")
+
+    def ready(self) -> bool:
+        return bool(_lib.load().dpot_lane_ready(self.index))
+
+    def pending(self) -> int:
+        """forks of the current device's lane since the last join (tests, assertions)"""
+        return _lib.load().dpot_lane_pending(self.index)
+
+    def shutdown(self) -> None:
+        check(_lib.load().dpot_lane_shutdown(self.index), "lane_shutdown")
+
+    def join(self) -> None:
+        """order every stream that forked the lane behind it (dpot_lane_join) and release what the lane's launches use.  The
+        streams are those recorded at the fork, not torch's current one: lane 0 is joined from the autograd engine's
+        end-of-backward callback.  Nothing - no library call - when nothing is forked; may be repeated."""
+        with _lane_lock:
+            if self.forks == 0:
+                return
+            streams, held = self.streams, self.held        # `held` lives until the joins below have been issued
+            self.forks, self.streams, self.held = 0, [], []
+        for stream in dict.fromkeys(streams):
+            check(_lib.load().dpot_lane_join(self.index, stream), "lane_join")
+
+    @contextlib.contextmanager
+    def block(self, join: bool = True, joiner=None):
+        """Fork the lane behind torch's current stream and send every launch of this module made inside the block, on this
+        thread, to the lane (`_stream`).  torch's current stream stays the step's: allocations belong to it, and NO torch op
+        may run inside the block - allocate what one would, or let the ops of this module allocate, before any further work
+        goes to the step's stream.  Nested in another lane block nothing is forked: the launches stay where they were going.
+        join=False leaves the lane forked when the block ends normally - the caller joins before anything reads the block's
+        results; an exception inside always joins.  joiner: what joins (default `self.join`)."""
+        if getattr(_tls, "lane", None) is not None:
+            yield
+            return
+        step = _step_stream()
+        handle = C.c_void_p()
+        check(_lib.load().dpot_lane_fork(self.index, step, C.byref(handle)), "lane_fork")
+        with _lane_lock:
+            self.forks += 1
+            self.streams.append(step)
+        _tls.lane = (self, handle.value or 0)
+        ok = False
+        try:
+            yield
+            ok = True
+        finally:
+            _tls.lane = None
+            if join or not ok:
+                (joiner or self.join)()
 
 
-def wgrad_lane_pending() -> int:
-    """flushes the current device's lane has taken since the last wait (tests, assertions)"""
-    return _lib.load().dpot_wgrad_lane_pending()
+SIDE_LANE = 1
+_WGRAD, _SIDE = _Lane(0), _Lane(SIDE_LANE)
+
+# Lane 0, the weight-gradient lane (`wgrad_flush_async`).  wgrad_lane_join: the end-of-backward callback of functional.WgradBatch
+# and FlatOptimizer.launch call it.
+wgrad_lane_init, wgrad_lane_ready, wgrad_lane_pending, wgrad_lane_join = _WGRAD.init, _WGRAD.ready, _WGRAD.pending, _WGRAD.join
 
 
 def wgrad_lane_shutdown() -> None:
     wgrad_lane_join()
-    check(_lib.load().dpot_wgrad_lane_shutdown(), "wgrad_lane_shutdown")
+    _WGRAD.shutdown()
 
 
-# what the lane's queued launches read and write, [(stream, tensors)]: allocated on the step's stream and referenced from here
-# until the wait has been ISSUED on that stream - whatever the allocator hands out again afterwards is ordered behind the lane
-_lane_held = []
-_lane_lock = threading.Lock()
-
-
-def wgrad_lane_join() -> None:
-    """order the streams that flushed to the lane behind it (dpot_wgrad_wait) and release what the lane's launches use.  Nothing
-    when nothing is pending; the end-of-backward callback of functional.WgradBatch and FlatOptimizer.launch call it."""
-    with _lane_lock:
-        held = _lane_held[:]
-        del _lane_held[:]
-    for stream in dict.fromkeys(st for st, _ in held):
-        check(_lib.load().dpot_wgrad_wait(stream), "wgrad_wait")
-
-
-# ---- the side lane (lane 1 of csrc/gemm_tn.hip) ------------------------------------------------------------------------------
-# Short chains of latency-bound launches that run beside independent work of the step's stream (DESIGN.md section 5):
+# Lane 1, the side lane: short chains of latency-bound launches that run beside independent work of the step's stream (DESIGN.md
+# section 5):
 #   weights  packs.ModelPacks.derive: everything `embed_fwd` does not read, joined by EmbedFn.forward before the fold GEMM
 #   patch    EmbedFn.backward: the first conv's gradients beside the weight-only chain
 # Same launches, same arguments, same results; DPOT_TUNE fused_small=5 (the default) switches on the sites of SIDE_SITES_DEFAULT.
 # (A third site, the classification head beside the de-embed GEMM, measured 11 us against a spread of 9 us and was taken out
 # again: profiles/side_lane_ab.txt, section 2.)
-SIDE_LANE = 1
 SIDE_SITES = ("weights", "patch")
 SIDE_SITES_DEFAULT = SIDE_SITES
-_side_held = []          # what the lane's queued launches touch and their ops have dropped (`_scratch`)
-_side_forks = 0          # forks not joined yet, as this module counts them (a join with none pending costs no library call)
+side_lane_ready, side_lane_pending, side_lane_join = _SIDE.ready, _SIDE.pending, _SIDE.join
 
 
 @contextlib.contextmanager
@@ -1034,61 +1087,19 @@ def side_lane_enabled(site: str) -> bool:
     return site in v
 
 
-def side_lane_ready() -> bool:
-    return bool(_lib.load().dpot_lane_ready(SIDE_LANE))
-
-
-def side_lane_pending() -> int:
-    """forks of the current device's side lane since the last join (tests, assertions)"""
-    return _lib.load().dpot_lane_pending(SIDE_LANE)
-
-
 def side_lane_shutdown() -> None:
     side_lane_join()
-    check(_lib.load().dpot_lane_shutdown(SIDE_LANE), "lane_shutdown")
-
-
-def side_lane_join() -> None:
-    """order torch's current stream behind the side lane (dpot_lane_join) and release what the lane's launches use.  Nothing
-    when nothing is pending; may be repeated."""
-    global _side_forks
-    with _lane_lock:
-        if _side_forks == 0:
-            return
-    check(_lib.load().dpot_lane_join(SIDE_LANE, _step_stream()), "lane_join")
-    with _lane_lock:
-        _side_forks = 0
-        del _side_held[:]
+    _SIDE.shutdown()
 
 
 @contextlib.contextmanager
 def side_lane(site: str, on: Optional[bool] = None, join: bool = True):
-    """Fork the side lane behind torch's current stream and send every launch of this module made inside the block, on this
-    thread, to the lane (`_stream`).  torch's current stream stays the step's: allocations belong to it, and NO torch op may
-    run inside the block - allocate what one would, or let the ops of this module allocate, before any further work goes to
-    the step's stream.  on: whether the site takes the lane (None = `side_lane_enabled(site)`); off, or nested in another
-    block, the launches stay where they were going.  join=False leaves the lane forked when the block ends normally - the
-    caller joins (`side_lane_join`) before anything reads the block's results; an exception inside always joins."""
-    global _side_forks
+    """a `_Lane.block` of the side lane when the site takes the lane (on; None = `side_lane_enabled(site)`), else nothing: the
+    launches stay where they were going.  join=False: the caller joins (`side_lane_join`)."""
     if on is None:
         on = side_lane_enabled(site)
-    if not on or getattr(_tls, "side_stream", None) is not None:
+    with _SIDE.block(join, lambda: side_lane_join()) if on else contextlib.nullcontext():
         yield
-        return
-    step = _step_stream()
-    handle = C.c_void_p()
-    check(_lib.load().dpot_lane_fork(SIDE_LANE, step, C.byref(handle)), "lane_fork")
-    with _lane_lock:
-        _side_forks += 1
-    _tls.side_stream = handle.value or 0
-    ok = False
-    try:
-        yield
-        ok = True
-    finally:
-        _tls.side_stream = None
-        if join or not ok:
-            side_lane_join()
 
 
 def wgrad_batch_max_blocks() -> int:
@@ -1117,14 +1128,6 @@ def mlp_wgrad_batch(do2, Hh, xn2, dHpre, splitk: int, chain: int = 1) -> Tensor:
     returns the workspace [n, elems] - row i in the layout `mlp_wgrad2(defer=True)` leaves, for `wgrad_batch_finalize`.
     chain 2 / 4: a workgroup walks up to that many consecutive token ranges and stores one partial per node of the
     finalising launch's summation tree (same bits; give `wgrad_batch_finalize` the same chain)"""
-    n, T, E, mh, ws = _mlp_wgrad_batch_ws(do2, Hh, xn2, dHpre, splitk, chain)
-    check(_lib.load().dpot_mlp_wgrad_batch(_ptr_array(do2), _ptr_array(Hh), _ptr_array(xn2), _ptr_array(dHpre), n, T, E, mh,
-                                           ws.data_ptr(), splitk, chain, _stream()), "mlp_wgrad_batch")
-    return ws
-
-
-def _mlp_wgrad_batch_ws(do2, Hh, xn2, dHpre, splitk: int, chain: int = 1):
-    """(n, T, E, mh, workspace [n, elems]) of `mlp_wgrad_batch` after its operand checks"""
     n = len(do2)
     T, E = do2[0].shape
     mh = Hh[0].shape[1]
@@ -1133,7 +1136,9 @@ def _mlp_wgrad_batch_ws(do2, Hh, xn2, dHpre, splitk: int, chain: int = 1):
         assert a.is_contiguous() and b.is_contiguous() and c.is_contiguous() and d.is_contiguous()
     ws = torch.empty(n, _lib.load().dpot_mlp_wgrad_chain_ws_elems(E, mh, splitk, chain), dtype=torch.float32,
                      device=do2[0].device)
-    return n, T, E, mh, ws
+    check(_lib.load().dpot_mlp_wgrad_batch(_ptr_array(do2), _ptr_array(Hh), _ptr_array(xn2), _ptr_array(dHpre), n, T, E, mh,
+                                           ws.data_ptr(), splitk, chain, _stream()), "mlp_wgrad_batch")
+    return ws
 
 
 def afno_wgrad_batch_plan(Mm: int, nb: int, bs: int, n: int) -> Tuple[int, int, int]:
@@ -1151,14 +1156,6 @@ def afno_wgrad_batch(S, dO1pre, O1, dO2, nb: int, bs: int, per_launch: int, spli
     """partials of both AFNO weight gradients of len(S) blocks (lists of per-block operands, as `afno_wgrad2`), `per_launch`
     blocks per launch: returns the workspace [n, elems], row i in the layout of `afno_wgrad2(defer=True)`; chain: as
     `mlp_wgrad_batch`"""
-    n, Mm, ld, ws = _afno_wgrad_batch_ws(S, dO1pre, O1, dO2, nb, bs, splitk, chain, splits12)
-    check(_lib.load().dpot_afno_wgrad_batch(_ptr_array(S), _ptr_array(dO1pre), _ptr_array(O1), _ptr_array(dO2), n, ld, Mm, nb,
-                                            bs, ws.data_ptr(), per_launch, splits12, splitk, chain, _stream()), "afno_wgrad_batch")
-    return ws
-
-
-def _afno_wgrad_batch_ws(S, dO1pre, O1, dO2, nb: int, bs: int, splitk: int, chain: int = 1, splits12: int = 0):
-    """(n, Mm, ld, workspace [n, elems]) of `afno_wgrad_batch` after its operand checks"""
     n = len(S)
     Mm, ld = S[0].shape
     for ts in (S, dO1pre, O1, dO2):
@@ -1166,7 +1163,9 @@ def _afno_wgrad_batch_ws(S, dO1pre, O1, dO2, nb: int, bs: int, splitk: int, chai
             assert t.shape == (Mm, ld) and t.is_contiguous()
     ws = torch.empty(n, _lib.load().dpot_afno_wgrad_chain_ws_elems(nb, bs, splits12, splitk, chain), dtype=torch.float32,
                      device=S[0].device)
-    return n, Mm, ld, ws
+    check(_lib.load().dpot_afno_wgrad_batch(_ptr_array(S), _ptr_array(dO1pre), _ptr_array(O1), _ptr_array(dO2), n, ld, Mm, nb,
+                                            bs, ws.data_ptr(), per_launch, splits12, splitk, chain, _stream()), "afno_wgrad_batch")
+    return ws
 
 
 def wgrad_batch_finalize(afno, mlp, gn, mlp_chain: int = 1, afno_chain: int = 1):
@@ -1175,15 +1174,6 @@ def wgrad_batch_finalize(afno, mlp, gn, mlp_chain: int = 1, afno_chain: int = 1)
     afno: None | (ws [n, .], splits12, splitk, nb, bs, [(dw1, db1, dw2, db2)] * n);
     mlp:  None | (ws [n, .], splitk, E, mh, [(dW2, db2, dW1, db1)] * n);
     gn:   [[(part [2, B, E], dgamma, dbeta)] * jobs] * n  (jobs <= 2, outputs allocated by the caller)"""
-    blocks, n, jobs, B, Eg = _wgrad_block_table(afno, mlp, gn)
-    a = afno if afno is not None else (None, 0, 0, 0, 0)
-    m = mlp if mlp is not None else (None, 0, 0, 0)
-    check(_lib.load().dpot_wgrad_batch_finalize(blocks, n, a[1], a[2], a[3], a[4], m[1], m[2], m[3], jobs, B, Eg, mlp_chain,
-                                                afno_chain, _stream()), "wgrad_batch_finalize")
-
-
-def _wgrad_block_table(afno, mlp, gn):
-    """(dpot_wgrad_block table, n, GroupNorm jobs per block, B, E of the GroupNorm partials) of `wgrad_batch_finalize`"""
     n = len(gn)
     blocks = (_lib.WgradBlock * n)()
     jobs, B, Eg = len(gn[0]), 0, 0
@@ -1199,25 +1189,30 @@ def _wgrad_block_table(afno, mlp, gn):
         for j, (part, dg, db) in enumerate(gn[i]):
             _, B, Eg = part.shape
             w.gn_part[j], w.gn_dgamma[j], w.gn_dbeta[j] = part.data_ptr(), dg.data_ptr(), db.data_ptr()
-    return blocks, n, jobs, B, Eg
+    a = afno if afno is not None else (None, 0, 0, 0, 0)
+    m = mlp if mlp is not None else (None, 0, 0, 0)
+    check(_lib.load().dpot_wgrad_batch_finalize(blocks, n, a[1], a[2], a[3], a[4], m[1], m[2], m[3], jobs, B, Eg, mlp_chain,
+                                                afno_chain, _stream()), "wgrad_batch_finalize")
 
 
 def wgrad_flush_async(mlp_ops, skm: int, mouts, afno_ops, nb: int, bs: int, per_launch: int, splits12: int, splitk: int,
                       aouts, gn, mlp_chain: int = 1, afno_chain: int = 1) -> None:
-    """`mlp_wgrad_batch`, `afno_wgrad_batch` and `wgrad_batch_finalize` of one group of blocks on the library's lane, behind
-    the current stream (csrc/gemm_tn.hip dpot_wgrad_flush_async).  mlp_ops / afno_ops: the four operand lists of the two
-    launches; mouts, aouts, gn: the outputs per block as `wgrad_batch_finalize` takes them.  Everything the launches touch
-    stays referenced until `wgrad_lane_join` has ordered the stream behind the lane."""
-    n, T, E, mh, mws = _mlp_wgrad_batch_ws(*mlp_ops, skm, mlp_chain)
-    _, Mm, ld, aws = _afno_wgrad_batch_ws(*afno_ops, nb, bs, splitk, afno_chain, splits12)
-    blocks, _, jobs, B, Eg = _wgrad_block_table((aws, splits12, splitk, nb, bs, aouts), (mws, skm, E, mh, mouts), gn)
-    stream = _stream()
-    with _lane_lock:
-        _lane_held.append((stream, (mlp_ops, afno_ops, aws, mws, mouts, aouts, gn)))
-    check(_lib.load().dpot_wgrad_flush_async(*[_ptr_array(t) for t in mlp_ops], n, T, E, mh, mws.data_ptr(), skm,
-                                             *[_ptr_array(t) for t in afno_ops], ld, Mm, nb, bs, aws.data_ptr(), per_launch,
-                                             splits12, splitk, blocks, jobs, B, Eg, mlp_chain, afno_chain, stream),
-          "wgrad_flush_async")
+    """`afno_wgrad_batch`, `mlp_wgrad_batch` and `wgrad_batch_finalize` of one group of blocks on the library's lane 0, forked
+    behind the current stream and left forked.  mlp_ops / afno_ops: the four operand lists of the two launches; mouts, aouts,
+    gn: the outputs per block as `wgrad_batch_finalize` takes them.  Everything the launches touch stays referenced until
+    `wgrad_lane_join` has ordered the stream behind the lane."""
+    with _WGRAD.block(join=False):
+        # The AFNO launch goes FIRST.  The embed backward beside the lane opens with its two MFMA-bound fold GEMMs (768 and 528
+        # workgroups) and goes on with short latency-bound launches.  Beside the channel-MLP launch the first fold GEMM took
+        # 124 us (38 us alone) - and 334 us beside a chained, one-round MLP launch, whose 256 workgroups hold every CU for
+        # 300 us; beside the AFNO launch (shorter workgroups, a third of them the VALU-heavy sum-product tiles) the fold GEMMs
+        # get through, and the long MLP launch then runs beside the short launches.  Independent workspaces: no result depends
+        # on the order.  DPOT-Tiny step 2.9275 -> 2.8859 ms against the parent commit (profiles/wgrad_chain_ab.txt, section 4)
+        aws = afno_wgrad_batch(*afno_ops, nb, bs, per_launch, splits12, splitk, afno_chain)
+        mws = mlp_wgrad_batch(*mlp_ops, skm, mlp_chain)
+        _hold(mlp_ops, afno_ops, aws, mws, mouts, aouts, gn)
+        E, mh = mlp_ops[0][0].shape[1], mlp_ops[1][0].shape[1]
+        wgrad_batch_finalize((aws, splits12, splitk, nb, bs, aouts), (mws, skm, E, mh, mouts), gn, mlp_chain, afno_chain)
 
 
 def afno_mlp2_supported(nb: int, bs: int) -> bool:

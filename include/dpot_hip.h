@@ -22,8 +22,8 @@
  *   - kernels are enqueued on `stream` (a hipStream_t passed as void*) and never synchronise, so every
  *     call is legal inside HIP stream capture (hipGraph)
  *   - return value: 0 on success, negative DPOT_E* on error; dpot_last_error() gives the message
- *   - re-entrant and stateless (no global state besides the thread-local error string and the weight-gradient lane,
- *     one stream and two events per device behind a mutex: dpot_wgrad_flush_async)
+ *   - re-entrant and stateless (no global state besides the thread-local error string and the lanes, one stream and two
+ *     events per lane and device behind a mutex: dpot_lane_fork)
  */
 #ifndef DPOT_HIP_H
 #define DPOT_HIP_H
@@ -237,42 +237,22 @@ int dpot_afno_wgrad_batch(const float* const* S, const float* const* dO1pre, con
 int dpot_wgrad_batch_finalize(const dpot_wgrad_block* blocks, int n, int afno_splits12, int afno_splitk, int nb, int bs,
                               int mlp_splitk, int E, int mh, int gn_jobs, int B, int Egn, int mlp_chain, int afno_chain,
                               dpot_stream_t stream);
-/* The weight-gradient LANE: the three launch sets above on a library-owned stream beside the caller's (csrc/gemm_tn.hip).
- * Nothing reads a weight gradient before the optimiser, so the caller's stream can go on with the embed backward meanwhile.
- * One lane per device - a non-blocking stream at the default priority (any other measured slower under graph replay) and two events
- * without timing - created by dpot_wgrad_lane_init() or the first flush, never while the caller's stream is capturing (that
- * flush runs on the caller's stream).  This is the library's only state; it is guarded by a mutex.
- * dpot_wgrad_flush_async: the arguments of dpot_mlp_wgrad_batch, dpot_afno_wgrad_batch and dpot_wgrad_batch_finalize (n, the
- *   split factors, the chains, nb, bs, E, mh once; the AFNO launch first, see csrc/gemm_tn.hip).  Records the fork event on `stream`, makes the lane wait for it, issues the three
- *   launch sets on the lane through those entry points, records the done event on the lane and counts one pending flush.
- *   Inside a stream capture the lane becomes a parallel branch of the capture; dpot_wgrad_wait joins it back.
- *   The caller keeps every buffer the launches read or write alive, and unused by others, until it has called dpot_wgrad_wait.
- * dpot_wgrad_wait: makes `stream` wait for the last done event and clears the pending count; nothing when nothing is pending.
- * dpot_wgrad_lane_pending: flushes since the last wait (current device).  dpot_wgrad_lane_ready: 1 when the lane exists.
- * dpot_wgrad_lane_shutdown: drains and destroys the lane of the current device (nothing may be pending). */
-int dpot_wgrad_lane_init(void);
-int dpot_wgrad_lane_ready(void);
-int dpot_wgrad_lane_pending(void);
-int dpot_wgrad_lane_shutdown(void);
-int dpot_wgrad_flush_async(const float* const* do2, const float* const* Hh, const float* const* xn2, const float* const* dHpre,
-                           int n, int T, int E, int mh, float* mlp_ws, int mlp_splitk, const float* const* S,
-                           const float* const* dO1pre, const float* const* O1, const float* const* dO2, int ld, int Mm, int nb,
-                           int bs, float* afno_ws, int per_launch, int afno_splits12, int afno_splitk,
-                           const dpot_wgrad_block* blocks, int gn_jobs, int B, int Egn, int mlp_chain, int afno_chain,
-                           dpot_stream_t stream);
-int dpot_wgrad_wait(dpot_stream_t stream);
-/* The library's LANES: lane 0 is the weight-gradient lane above (the dpot_wgrad_* entry points are its users), lane 1 the SIDE
- * lane for short latency-bound chains that run beside independent work of the caller's stream (csrc/gemm_tn.hip; DESIGN.md
- * section 5).  The same rules: one non-blocking stream at the default priority and two events per lane and device, created by
- * dpot_lane_init or the first fork, never while the caller's stream is capturing; every access under the library's mutex.
+/* The library's LANES (csrc/lane.hip): library-owned streams beside the caller's, for launches of this
+ * library whose results the caller's stream does not read for a while.  Lane 0 is the weight-gradient lane - the three launch
+ * sets above go to it through dpot_lane_fork / dpot_lane_join like any other work, nothing reads a weight gradient before the
+ * optimiser -, lane 1 the SIDE lane for short latency-bound chains that run beside independent work of the caller's stream.
+ * Per lane and device one non-blocking stream at the default priority (any other measured slower under graph replay) and two
+ * events without timing, created by dpot_lane_init or the first fork, never while the caller's stream is capturing.  This is
+ * the library's only state; every access is under a mutex.
  * dpot_lane_fork: records the fork event on `caller`, makes the lane wait for it, stores the lane's stream handle in
- *   *lane_stream - launch the side work with it - and counts one pending fork.  A first use inside a stream capture creates
- *   nothing, counts nothing and stores `caller` itself: the side work then runs serially on the caller's stream.
+ *   *lane_stream - launch the side work with it - and counts one pending fork.  Inside a stream capture the lane becomes a
+ *   parallel branch of the capture.  A first use inside a stream capture creates nothing, counts nothing and stores `caller`
+ *   itself: the side work then runs serially on the caller's stream.
  * dpot_lane_join: records the done event on the lane, makes `caller` wait for it and clears the pending count.  With nothing
  *   pending it does nothing and may be repeated.  Forks made inside a capture that has ended are dropped.
  *   The caller keeps every buffer the side work touches alive, and unused by others, until it has joined - also when a launch
  *   of the side work failed.
- * dpot_lane_pending: forks since the last join (current device; dpot_wgrad_lane_pending counts lane 0's flushes only).
+ * dpot_lane_pending: forks since the last join (current device).
  * dpot_lane_ready: 1 when the lane exists.  dpot_lane_shutdown: drains and destroys it (nothing may be pending). */
 int dpot_lane_init(int lane);
 int dpot_lane_ready(int lane);

@@ -17,7 +17,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_INT = ("dpot_tn_chain_count", "dpot_tn_chain_nodes", "dpot_mlp_wgrad_batch_chain", "dpot_afno_wgrad_batch_chain",
-           "dpot_mlp_wgrad_batch", "dpot_afno_wgrad_batch", "dpot_wgrad_batch_finalize", "dpot_wgrad_flush_async")
+           "dpot_mlp_wgrad_batch", "dpot_afno_wgrad_batch", "dpot_wgrad_batch_finalize")
 NEW_I64 = ("dpot_mlp_wgrad_chain_ws_elems", "dpot_afno_wgrad_chain_ws_elems")
 SPLITS = range(1, 25)
 CHAINS = (1, 2, 4)
@@ -206,5 +206,4 @@ def test_chain_symbols_in_header_table_and_library(built_lib):
     assert names("dpot_mlp_wgrad_batch")[-2:] == ["mlp_chain", "stream"]
     assert names("dpot_afno_wgrad_batch")[-2:] == ["afno_chain", "stream"]
     assert names("dpot_wgrad_batch_finalize")[-3:] == ["mlp_chain", "afno_chain", "stream"]
-    assert names("dpot_wgrad_flush_async")[-3:] == ["mlp_chain", "afno_chain", "stream"]
     assert _lib.load().dpot_version() >= 271

@@ -1,4 +1,4 @@
-"""The side lane (csrc/gemm_tn.hip dpot_lane_fork / dpot_lane_join, lane 1; ops.side_lane): the step's latency-bound side chains
+"""The side lane (csrc/lane.hip dpot_lane_fork / dpot_lane_join, lane 1; ops.side_lane): the step's latency-bound side chains
 - the weight-only prologue (`weights`) and the first conv's gradients (`patch`) - on a library-owned stream beside independent work
 of the step's stream.  (The classification head, `cls`, failed its ablation and has no call site: profiles/side_lane_ab.txt.)
 No kernel, split factor, launch argument or summation order changes, so every comparison here is torch.equal against

@@ -1,4 +1,4 @@
-"""The weight-gradient lane (csrc/gemm_tn.hip dpot_wgrad_flush_async / dpot_wgrad_wait; functional.WgradBatch._flush_group): the
+"""The weight-gradient lane (lane 0 of csrc/lane.hip; ops.wgrad_flush_async / ops.wgrad_lane_join; functional.WgradBatch._flush_group): the
 batched weight gradients on the library's own stream beside the embed backward.  No kernel, split factor or summation order
 changes, so every comparison here is bit for bit against the synchronous schedule: an eager step, a captured step (an unjoined
 lane would end the capture with an error), the pending count between the flush and the end of the backward, the cases that
