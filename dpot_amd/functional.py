@@ -8,6 +8,9 @@ kernels directly (no autograd tracing inside a stage, no eager-PyTorch math):
   AFNO3DFn, GroupNormFn, Mlp2Fn, TimeAggFn, Head3DFn, block3d   the 3-D model's stages          models/dpot3d.py
   AALReLUFn, PatchConvFn, LinearFn, ClsHeadFn, TokenMeanFn      the CDPOT model's stages        models/dpot_res.py
 
+Every chain of Linear layers in the plain stages (Mlp2Fn, LinearFn, ClsHeadFn, PatchConvFn, PatchEmbed3DFn, the pointwise layers of
+Head3DFn, HeadFn's cls_head and unfused tail) runs through _dense_fwd / _dense_bwd: one place where a dense layer is differentiated.
+
 Internal activation layout: channels-last tokens [B, h*w, E] (row-major [B*h*w, E]).
 
 Parameter gradients: when the parameters live in a train.FlatParams buffer, the backward kernels write them straight
@@ -230,6 +233,61 @@ def _check_epoch(ctx, what: str) -> None:
 
 def _sinks(ctx, params, first_index: int):
     return [_Sink(p, ctx.needs_input_grad[first_index + k]) for k, p in enumerate(params)]
+
+
+# ======================================================================================================
+# a chain of dense layers (Linear / 1x1 convolution / k = s = P convolution on a patch matrix): every plain stage below
+# ======================================================================================================
+def _dense_fwd(x, layers, act: int, res=None, res_div: int = 0, res_mod: int = 0):
+    """rows x[M, K] through `layers` = [(W[N, K], b), ...]: y = x W^T + b per layer, `act` after every layer but the last,
+    `res` added by the last (ops.linear_fwd: res[M, N] row by row, or res[R, N] with res_mod = R as res[(m // res_div) % R]).
+    x may be a callable that makes the rows (a patch matrix): they are dropped as soon as the first layer has read them.
+    -> (y, the input of every layer - the callable for such a first one -, the pre-activation of every layer but the last):
+    what _dense_bwd takes"""
+    ins, pres = [], []
+    last = len(layers) - 1
+    for i, (W, b) in enumerate(layers):
+        ins.append(x)
+        xin = x() if callable(x) else x
+        if i < last:
+            x, pre = ops.linear_fwd(xin, W, b, act=act, save_pre=True)
+            pres.append(pre)
+        else:
+            x, _ = ops.linear_fwd(xin, W, b, res=res, res_div=res_div, res_mod=res_mod)
+        del xin
+    return x, ins, pres
+
+
+def _dense_bwd(dy, ins, pres, weights, act: int, need_dx: bool = True, pre0=None, sinks=None):
+    """backward of _dense_fwd from dy[M, N_last] (contiguous), last layer to first; per layer the data gradient - times
+    act'(pre-activation of the layer before) -, then (dW, db) in one launch (ops.linear_bwd_wb).  The first layer's data
+    gradient runs only if need_dx, times act'(pre0) if the chain's input was an activation of pre0.  ins[0] may be a callable
+    that makes the first layer's input: it is called once, right before that layer's weight gradient, and the result dropped
+    right after.  sinks: per layer (_Sink of W, _Sink of b, shape of the parameter W) - where HeadFn delivers.
+    -> (dx | None, [(dW, db) per layer])"""
+    grads = [None] * len(weights)
+    for i in reversed(range(len(weights))):
+        aux = pres[i - 1] if i else pre0
+        d_in = ops.linear_bwd_data(dy, weights[i], act=act if aux is not None else 0, aux=aux) if i or need_dx else None
+        xin = ins[i]() if callable(ins[i]) else ins[i]
+        if sinks is None:
+            grads[i] = ops.linear_bwd_wb(dy, xin)
+        else:
+            s_w, s_b, shape = sinks[i]
+            dW, db = ops.linear_bwd_wb(dy, xin, s_w.out(), s_b.out())
+            grads[i] = s_w.done(dW.view(shape)), s_b.done(db)
+        del xin
+        dy = d_in
+    return dy, grads
+
+
+def _res_bwd(dy, res_div: int, res_mod: int):
+    """gradient of the residual _dense_fwd added: dy itself, or its sum over the rows that share a row of the table"""
+    if not res_mod:
+        return dy
+    M, N = dy.shape
+    res_div = max(res_div, 1)
+    return ops.group_rowsum(dy, M // (res_mod * res_div), res_mod, res_div, N)
 
 
 # ======================================================================================================
@@ -1108,14 +1166,10 @@ class HeadFn(torch.autograd.Function):
                 Upre = torch.empty_like(U)
                 ops.gemm(x, wt, U, M, PP * old, E, lda=E, ldb=PP * old, ldc=PP * old, bias=bexp, act=act,
                          mode=EPI_ACT, preact=Upre, ldpre=PP * old)
-            V, Vpre = ops.linear_fwd(U.view(Mp, old), o2w, o2b, act=act, save_pre=True)
-            Z, _ = ops.linear_fwd(V, o4w, o4b)                                 # [Mp, co]
+            Z, (_, V), (Vpre,) = _dense_fwd(U.view(Mp, old), [(o2w, o2b), (o4w, o4b)], act)     # [Mp, co]
             pred = ops.pixel_shuffle(Z, B, h, w, P, co)                        # [B, X, Y, co]
         # classification head
-        cm = ops.token_mean(x)
-        c1, c1pre = ops.linear_fwd(cm, c0w, c0b, act=act, save_pre=True)
-        c2, c2pre = ops.linear_fwd(c1, c2w, c2b, act=act, save_pre=True)
-        cls, _ = ops.linear_fwd(c2, c4w, c4b)
+        cls, (cm, c1, c2), (c1pre, c2pre) = _dense_fwd(ops.token_mean(x), [(c0w, c0b), (c2w, c2b), (c4w, c4b)], act)
         ctx.save_for_backward(x, wt, U, Upre, V, Vpre, o2w, o2b, o4w, cm, c1, c1pre, c2, c2pre, c0w, c2w, c4w)
         ctx.dims = (B, tok, E, h, w, P, old, co, act)
         ctx.fused = fused
@@ -1136,7 +1190,6 @@ class HeadFn(torch.autograd.Function):
         PP = P * P
         M, Mp = B * tok, B * tok * PP
         dev = x.device
-        o2w2, o4w2 = o2w.view(old, old), o4w.view(co, old)
         do0w = do0b = do2w = do2b = do4w = do4b = dx_out = None
         dc0w = dc0b = dc2w = dc2b = dc4w = dc4b = None
         if dpred is not None:
@@ -1151,12 +1204,9 @@ class HeadFn(torch.autograd.Function):
                 do2b, do0b, do4b = s_o2b.done(g2b), s_o0b.done(g0b), s_o4b.done(g4b)
             else:
                 dZ = ops.pixel_shuffle(dpred.contiguous(), B, h, w, P, co, inverse=True)  # [Mp, co]
-                dVpre = ops.linear_bwd_data(dZ, o4w2, act=act, aux=Vpre)                  # [Mp, old]
-                do4w, do4b = ops.linear_bwd_wb(dZ, V, s_o4w.out(), s_o4b.out())
-                do4w, do4b = s_o4w.done(do4w.view(co, old, 1, 1)), s_o4b.done(do4b)
-                dUpre = ops.linear_bwd_data(dVpre, o2w2, act=act, aux=Upre.view(Mp, old))  # [Mp, old]
-                do2w, do2b = ops.linear_bwd_wb(dVpre, U.view(Mp, old), s_o2w.out(), s_o2b.out())
-                do2w, do2b = s_o2w.done(do2w.view(old, old, 1, 1)), s_o2b.done(do2b)
+                dUpre, ((do2w, do2b), (do4w, do4b)) = _dense_bwd(
+                    dZ, [U.view(Mp, old), V], [Vpre], [o2w.view(old, old), o4w.view(co, old)], act, pre0=Upre.view(Mp, old),
+                    sinks=[(s_o2w, s_o2b, o2w.shape), (s_o4w, s_o4b, o4w.shape)])          # [Mp, old]
                 do0b = s_o0b.done(ops.colsum(dUpre, Mp, old, out=s_o0b.out()))
             dU2 = dUpre.view(M, PP * old)
             if ctx.head_pk is not None:
@@ -1175,17 +1225,10 @@ class HeadFn(torch.autograd.Function):
         dx = dx_out
         if dcls is not None:
             # ---- cls head
-            s_c0w, s_c0b, s_c2w, s_c2b, s_c4w, s_c4b = [_Sink(p, n) for p, n in zip(ctx.cls_params, ctx.cls_needed)]
-            dcls = dcls.contiguous()
-            dc2pre = ops.linear_bwd_data(dcls, c4w, act=act, aux=c2pre)
-            dc4w, dc4b = ops.linear_bwd_wb(dcls, c2, s_c4w.out(), s_c4b.out())
-            dc4w, dc4b = s_c4w.done(dc4w), s_c4b.done(dc4b)
-            dc1pre = ops.linear_bwd_data(dc2pre, c2w, act=act, aux=c1pre)
-            dc2w, dc2b = ops.linear_bwd_wb(dc2pre, c1, s_c2w.out(), s_c2b.out())
-            dc2w, dc2b = s_c2w.done(dc2w), s_c2b.done(dc2b)
-            dcm = ops.linear_bwd_data(dc1pre, c0w)
-            dc0w, dc0b = ops.linear_bwd_wb(dc1pre, cm, s_c0w.out(), s_c0b.out())
-            dc0w, dc0b = s_c0w.done(dc0w), s_c0b.done(dc0b)
+            cs = [_Sink(p, n) for p, n in zip(ctx.cls_params, ctx.cls_needed)]
+            dcm, ((dc0w, dc0b), (dc2w, dc2b), (dc4w, dc4b)) = _dense_bwd(
+                dcls.contiguous(), [cm, c1, c2], [c1pre, c2pre], [c0w, c2w, c4w], act,
+                sinks=[(cs[2 * i], cs[2 * i + 1], W.shape) for i, W in enumerate((c0w, c2w, c4w))])
             dx = ops.token_mean_bwd(dcm, tok, add=dx_out)
         return (dx, do0w, do0b, do2w, do2b, do4w, do4b, dc0w, dc0b, dc2w, dc2b, dc4w, dc4b, None, None, None, None,
                 None)
@@ -1331,9 +1374,8 @@ class Mlp2Fn(torch.autograd.Function):
         ops.capture_precision(ctx)
         x, W1, W2 = x.contiguous(), W1.contiguous(), W2.contiguous()
         res = res.contiguous() if res is not None else None
-        Hh, Hpre = ops.linear_fwd(x, W1, b1, act=act, save_pre=True)
-        y, _ = ops.linear_fwd(Hh, W2, b2, res=res, res_mod=res_mod)
-        ctx.save_for_backward(x, Hh, Hpre, W1, W2)
+        y, ins, pres = _dense_fwd(x, [(W1, b1), (W2, b2)], act, res, 0, res_mod)
+        ctx.save_for_backward(*ins, *pres, W1, W2)
         ctx.act, ctx.res_mod, ctx.has_res = act, res_mod, res is not None
         return y
 
@@ -1342,14 +1384,8 @@ class Mlp2Fn(torch.autograd.Function):
     def backward(ctx, dy):
         x, Hh, Hpre, W1, W2 = ctx.saved_tensors
         dy = dy.contiguous()
-        M, N = dy.shape
-        dHpre = ops.linear_bwd_data(dy, W2, act=ctx.act, aux=Hpre)          # (dy W2) * act'(Hpre)
-        dW2, db2 = ops.linear_bwd_wb(dy, Hh)
-        dW1, db1 = ops.linear_bwd_wb(dHpre, x)
-        dx = ops.linear_bwd_data(dHpre, W1) if ctx.needs_input_grad[0] else None
-        dres = None
-        if ctx.has_res and ctx.needs_input_grad[6]:
-            dres = dy if not ctx.res_mod else ops.group_rowsum(dy, M // ctx.res_mod, ctx.res_mod, 1, N)
+        dx, ((dW1, db1), (dW2, db2)) = _dense_bwd(dy, [x, Hh], [Hpre], [W1, W2], ctx.act, ctx.needs_input_grad[0])
+        dres = _res_bwd(dy, 1, ctx.res_mod) if ctx.has_res and ctx.needs_input_grad[6] else None
         return dx, dW1, db1, dW2, db2, None, dres, None
 
 
@@ -1364,10 +1400,7 @@ class PatchEmbed3DFn(torch.autograd.Function):
     def forward(ctx, x, gs, gt, W1, b1, W2, b2, pos, P: int, act: int):
         ops.capture_precision(ctx)
         x, W1, W2, pos = x.contiguous(), W1.contiguous(), W2.contiguous(), pos.contiguous()
-        A0 = ops.patchify3(x, gs, gt, P)
-        Hh, Hpre = ops.linear_fwd(A0, W1, b1, act=act, save_pre=True)
-        del A0
-        y, _ = ops.linear_fwd(Hh, W2, b2, res=pos, res_mod=pos.shape[0])
+        y, (_, Hh), (Hpre,) = _dense_fwd(lambda: ops.patchify3(x, gs, gt, P), [(W1, b1), (W2, b2)], act, pos, 0, pos.shape[0])
         ctx.save_for_backward(x, gs, gt, Hh, Hpre, W1, W2)
         ctx.P, ctx.act, ctx.tok = P, act, pos.shape[0]
         return y
@@ -1377,17 +1410,13 @@ class PatchEmbed3DFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, gs, gt, Hh, Hpre, W1, W2 = ctx.saved_tensors
         dy = dy.contiguous()
-        M, N = dy.shape
-        dHpre = ops.linear_bwd_data(dy, W2, act=ctx.act, aux=Hpre)          # (dy W2) * act'(Hpre)
-        dW2, db2 = ops.linear_bwd_wb(dy, Hh)
-        A0 = ops.patchify3(x, gs, gt, ctx.P)
-        dW1, db1 = ops.linear_bwd_wb(dHpre, A0)
-        del A0
+        dA0, ((dW1, db1), (dW2, db2)) = _dense_bwd(dy, [lambda: ops.patchify3(x, gs, gt, ctx.P), Hh], [Hpre], [W1, W2], ctx.act,
+                                                   ctx.needs_input_grad[0])
         dx = None
-        if ctx.needs_input_grad[0]:
+        if dA0 is not None:
             B, S, _, _, T, C = x.shape
-            dx = ops.unpatchify3(ops.linear_bwd_data(dHpre, W1), B, S, T, C, ctx.P)
-        dpos = ops.group_rowsum(dy, M // ctx.tok, ctx.tok, 1, N) if ctx.needs_input_grad[7] else None
+            dx = ops.unpatchify3(dA0, B, S, T, C, ctx.P)
+        dpos = _res_bwd(dy, 1, ctx.tok) if ctx.needs_input_grad[7] else None
         return dx, None, None, dW1, db1, dW2, db2, dpos, None, None
 
 
@@ -1465,8 +1494,7 @@ class Head3DFn(torch.autograd.Function):
         del H1
         H1pre_p = ops.fold3(H1pre, B, h, P, old)
         del H1pre
-        H2, H2pre = ops.linear_fwd(H1p, W2, b2, act=act, save_pre=True)
-        out, _ = ops.linear_fwd(H2, W4, b4)
+        out, (_, H2), (H2pre,) = _dense_fwd(H1p, [(W2, b2), (W4, b4)], act)
         ctx.save_for_backward(x, W0, W2, W4, H1p, H1pre_p, H2, H2pre)
         ctx.dims = (B, h, P, old, act)
         return out
@@ -1480,10 +1508,7 @@ class Head3DFn(torch.autograd.Function):
         N0 = old * P ** 3
         dev = x.device
         dout = dout.contiguous()
-        dH2pre = ops.linear_bwd_data(dout, W4, act=act, aux=H2pre)
-        dW4, db4 = ops.linear_bwd_wb(dout, H2)
-        dH1pre_p = ops.linear_bwd_data(dH2pre, W2, act=act, aux=H1pre_p)
-        dW2, db2 = ops.linear_bwd_wb(dH2pre, H1p)
+        dH1pre_p, ((dW2, db2), (dW4, db4)) = _dense_bwd(dout, [H1p, H2], [H2pre], [W2, W4], act, pre0=H1pre_p)
         dH1pre = ops.fold3(dH1pre_p, B, h, P, old, inverse=True)             # [M, old*P^3]
         dW0 = torch.empty(E, N0, dtype=torch.float32, device=dev)
         ops.gemm(x, dH1pre, dW0, E, N0, M, transA=True, lda=E, ldb=N0, ldc=N0, splitk=ops.auto_splitk(E, N0, M, tn=True))
@@ -1537,9 +1562,9 @@ class LinearFn(torch.autograd.Function):
         ops.capture_precision(ctx)
         x, W = x.contiguous(), W.contiguous()
         res = res.contiguous() if res is not None else None
-        y, _ = ops.linear_fwd(x, W, b, res=res, res_div=res_div, res_mod=res_mod)
+        y, _, _ = _dense_fwd(x, [(W, b)], 0, res, res_div, res_mod)
         ctx.save_for_backward(x, W)
-        ctx.res_div, ctx.res_mod, ctx.has_res = max(res_div, 1), res_mod, res is not None
+        ctx.res_div, ctx.res_mod, ctx.has_res = res_div, res_mod, res is not None
         return y
 
     @staticmethod
@@ -1547,12 +1572,8 @@ class LinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, W = ctx.saved_tensors
         dy = dy.contiguous()
-        M, N = dy.shape
-        dW, db = ops.linear_bwd_wb(dy, x)
-        dx = ops.linear_bwd_data(dy, W) if ctx.needs_input_grad[0] else None
-        dres = None
-        if ctx.has_res and ctx.needs_input_grad[3]:
-            dres = dy if not ctx.res_mod else ops.group_rowsum(dy, M // (ctx.res_mod * ctx.res_div), ctx.res_mod, ctx.res_div, N)
+        dx, ((dW, db),) = _dense_bwd(dy, [x], [], [W], 0, ctx.needs_input_grad[0])
+        dres = _res_bwd(dy, ctx.res_div, ctx.res_mod) if ctx.has_res and ctx.needs_input_grad[3] else None
         return dx, dW, db, dres, None, None
 
 
@@ -1562,27 +1583,17 @@ class ClsHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cm, c0w, c0b, c2w, c2b, c4w, c4b, act: int):
         ops.capture_precision(ctx)
-        cm = cm.contiguous()
-        c1, c1pre = ops.linear_fwd(cm, c0w, c0b, act=act, save_pre=True)
-        c2, c2pre = ops.linear_fwd(c1, c2w, c2b, act=act, save_pre=True)
-        cls, _ = ops.linear_fwd(c2, c4w, c4b)
-        ctx.save_for_backward(cm, c1, c1pre, c2, c2pre, c0w, c2w, c4w)
+        cls, ins, pres = _dense_fwd(cm.contiguous(), [(c0w, c0b), (c2w, c2b), (c4w, c4b)], act)
+        ctx.save_for_backward(*ins, *pres, c0w, c2w, c4w)
         ctx.act = act
         return cls
 
     @staticmethod
     @ops.with_ctx_precision
     def backward(ctx, dcls):
-        cm, c1, c1pre, c2, c2pre, c0w, c2w, c4w = ctx.saved_tensors
-        act = ctx.act
-        dcls = dcls.contiguous()
-        dc2pre = ops.linear_bwd_data(dcls, c4w, act=act, aux=c2pre)
-        dc4w, dc4b = ops.linear_bwd_wb(dcls, c2)
-        dc1pre = ops.linear_bwd_data(dc2pre, c2w, act=act, aux=c1pre)
-        dc2w, dc2b = ops.linear_bwd_wb(dc2pre, c1)
-        dcm = ops.linear_bwd_data(dc1pre, c0w) if ctx.needs_input_grad[0] else None
-        dc0w, dc0b = ops.linear_bwd_wb(dc1pre, cm)
-        return dcm, dc0w, dc0b, dc2w, dc2b, dc4w, dc4b, None
+        t = ctx.saved_tensors
+        dcm, grads = _dense_bwd(dcls.contiguous(), t[0:3], t[3:5], t[5:8], ctx.act, ctx.needs_input_grad[0])
+        return (dcm,) + sum(grads, ()) + (None,)
 
 
 class PatchConvFn(torch.autograd.Function):
@@ -1594,8 +1605,7 @@ class PatchConvFn(torch.autograd.Function):
     def forward(ctx, x, gx, gy, gt, W, b, P: int):
         ops.capture_precision(ctx)
         x, W = x.contiguous(), W.contiguous()
-        A0 = ops.patchify(x, gx, gy, gt, P)
-        y, _ = ops.linear_fwd(A0, W, b)
+        y, _, _ = _dense_fwd(lambda: ops.patchify(x, gx, gy, gt, P), [(W, b)], 0)
         ctx.save_for_backward(x, gx, gy, gt, W)
         ctx.P = P
         return y
@@ -1604,14 +1614,12 @@ class PatchConvFn(torch.autograd.Function):
     @ops.with_ctx_precision
     def backward(ctx, dy):
         x, gx, gy, gt, W = ctx.saved_tensors
-        dy = dy.contiguous()
-        A0 = ops.patchify(x, gx, gy, gt, ctx.P)
-        dW, db = ops.linear_bwd_wb(dy, A0)
-        del A0
+        dA0, ((dW, db),) = _dense_bwd(dy.contiguous(), [lambda: ops.patchify(x, gx, gy, gt, ctx.P)], [], [W], 0,
+                                      ctx.needs_input_grad[0])
         dx = None
-        if ctx.needs_input_grad[0]:
+        if dA0 is not None:
             B, X, Y, T, C = x.shape
-            dx = ops.unpatchify(ops.linear_bwd_data(dy, W), B, X, Y, T, C, ctx.P)
+            dx = ops.unpatchify(dA0, B, X, Y, T, C, ctx.P)
         return dx, None, None, None, dW, db, None
 
 

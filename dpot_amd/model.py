@@ -74,10 +74,18 @@ class _TimeAggParams(nn.Module):
             raise ValueError(f"unknown time_agg {kind!r}")
 
 
-class DPOTNet(nn.Module):
-    def __init__(self, img_size=224, patch_size=16, mixing_type='afno', in_channels=1, out_channels=4, in_timesteps=1,
-                 out_timesteps=1, n_blocks=4, embed_dim=768, out_layer_dim=32, depth=12, modes=32, mlp_ratio=1.,
-                 n_cls=12, normalize=False, act='gelu', time_agg='exp_mlp'):
+class _DPOTBase(nn.Module):
+    """What DPOTNet, DPOTNet3D and CDPOTNet share: the reference's attributes and argument checks, the modules all three register
+    in ONE order - patch_embed, pos_embed, blocks, scale_feats_mu / _sigma (normalize=True), cls_head, time_agg_layer, out_layer:
+    the order of ``state_dict()`` and of the train.FlatParams layout - built in that order too (it decides which random numbers
+    initialise which weight), the coordinate tables, the precision scope around ``_forward``, the input check and the
+    normalize=True prologue and epilogue.  A subclass keeps the reference's constructor signature, hands its own patch embedding,
+    Block and output layer over as factories, and writes ``_forward``."""
+    cls_output = True           # forward returns (pred, cls_pred); False: the prediction alone (train.rollout: no classification branch)
+
+    def __init__(self, img_size, patch_size, mixing_type, in_channels, out_channels, in_timesteps, out_timesteps, n_blocks,
+                 embed_dim, out_layer_dim, depth, modes, mlp_ratio, n_cls, normalize, act, time_agg, *, patch_embed, block,
+                 out_layer, coords=("_gx", "_gy")):
         super().__init__()
         if act not in ACTIVATIONS:
             raise KeyError(act)
@@ -91,31 +99,81 @@ class DPOTNet(nn.Module):
         self.normalize, self.time_agg, self.n_cls = normalize, time_agg, n_cls
         self.mixing_type = mixing_type
         self.img_size, self.patch_size = img_size, patch_size
+        self.out_layer_dim = out_layer_dim
         self.act_name, self._act = act, ops.ACT_IDS[act]
 
-        self.patch_embed = _PatchEmbedParams(img_size, patch_size, in_channels + 3, out_channels * patch_size + 3,
-                                             embed_dim)
+        self.patch_embed = patch_embed()
         self.latent_size = self.patch_embed.out_size
-        h = self.latent_size[0]
-        self.pos_embed = nn.Parameter(torch.zeros(1, embed_dim, h, h))
-        self.blocks = nn.ModuleList([_BlockParams(embed_dim, n_blocks, mlp_ratio) for _ in range(depth)])
+        self.pos_embed = nn.Parameter(torch.zeros(1, embed_dim, *self.latent_size))
+        self.blocks = nn.ModuleList([block() for _ in range(depth)])
         if normalize:
             self.scale_feats_mu = nn.Linear(2 * in_channels, embed_dim)
             self.scale_feats_sigma = nn.Linear(2 * in_channels, embed_dim)
+        # (DPOTNet3D constructs it and never calls it, models/dpot3d.py:288-294: it keeps the reference's state_dict, no gradient)
         self.cls_head = nn.Sequential(nn.Linear(embed_dim, embed_dim), nn.Identity(), nn.Linear(embed_dim, embed_dim),
                                       nn.Identity(), nn.Linear(embed_dim, n_cls))
         self.time_agg_layer = _TimeAggParams(in_timesteps, embed_dim, time_agg)
-        self.out_layer = nn.Sequential(
-            nn.ConvTranspose2d(embed_dim, out_layer_dim, patch_size, patch_size), nn.Identity(),
-            nn.Conv2d(out_layer_dim, out_layer_dim, 1), nn.Identity(),
-            nn.Conv2d(out_layer_dim, out_channels * out_timesteps, 1))
+        self.out_layer = out_layer()
         torch.nn.init.trunc_normal_(self.pos_embed, std=.02)
 
-        # coordinate tables of models/dpot.py:350-360 (np.linspace in float64, then cast) - not part of state_dict
-        for name, n in (("_gx", img_size), ("_gy", img_size), ("_gt", in_timesteps)):
+        # coordinate tables of the reference's get_grid_3d / get_grid_4d (np.linspace in float64, then cast) - not part of state_dict
+        for name, n in [(c, img_size) for c in coords] + [("_gt", in_timesteps)]:
             self.register_buffer(name, torch.tensor(np.linspace(0, 1, n), dtype=torch.float32), persistent=False)
         self.register_buffer("_tt", torch.linspace(0, 1, in_timesteps), persistent=False)
+        # precision of the channel-MLP GEMMs of THIS model: None = the process default (ops.set_mlp_precision /
+        # DPOT_MLP_PRECISION), or 'f32' | 'bf16x6' | 'auto' | 'bf16' (BASELINE configs[2]: "bf16 channel-MLP on MFMA")
+        self.mlp_precision = None
+        # precision of every OTHER fp32 GEMM of this model: None = the process default (ops.set_gemm_precision /
+        # DPOT_GEMM_PRECISION), or 'f32' (native fp32 MFMA) | 'bf16x6' | 'auto' (the fp32-accurate operand split where faster)
+        self.gemm_precision = None
+        # every weight-derived copy the kernels read (packed / padded / transposed weights) and when it is fresh
+        self.packs = ModelPacks()
 
+    def forward(self, x):
+        with ops.precision_scope(self.gemm_precision, self.mlp_precision):
+            return self._forward(x)
+
+    def _check_device(self, x) -> None:
+        if not x.is_cuda:
+            raise _lib.DpotHipError(f"{type(self).__name__} (dpot_amd) runs on MI355X only: move the model and the input to "
+                                    "'cuda'. There is no CPU fallback.")
+
+    def _normalize_in(self, x, dims):
+        """normalize=True (models/dpot.py:366-370): per-sample statistics over `dims` + two tiny Linear(2C -> E), O(B*C) host-side
+        glue -> (normalised x, mu, sigma, the AdaIN shift and scale); x and four None without it"""
+        if not self.normalize:
+            return x, None, None, None, None
+        mu = x.mean(dim=dims, keepdim=True)
+        sigma = x.std(dim=dims, keepdim=True) + 1e-6
+        x = (x - mu) / sigma
+        stat = torch.cat([mu, sigma], dim=-1)[(slice(None),) + (0,) * len(dims)]
+        return x, mu, sigma, self.scale_feats_mu(stat), self.scale_feats_sigma(stat)
+
+    def _denormalize(self, pred, mu, sigma):
+        return pred * sigma + mu if self.normalize else pred
+
+    def _time_agg_gamma(self):
+        return self.time_agg_layer.gamma if self.time_agg == "exp_mlp" else None
+
+    def extra_repr(self) -> str:
+        return (f"img_size={self.img_size}, patch_size={self.patch_size}, embed_dim={self.embed_dim}, "
+                f"depth={len(self.blocks)}, n_blocks={self.n_blocks}, modes={self.modes}, act={self.act_name}, "
+                f"backend=libdpot_hip(gfx950)")
+
+
+class DPOTNet(_DPOTBase):
+    def __init__(self, img_size=224, patch_size=16, mixing_type='afno', in_channels=1, out_channels=4, in_timesteps=1,
+                 out_timesteps=1, n_blocks=4, embed_dim=768, out_layer_dim=32, depth=12, modes=32, mlp_ratio=1.,
+                 n_cls=12, normalize=False, act='gelu', time_agg='exp_mlp'):
+        super().__init__(
+            img_size, patch_size, mixing_type, in_channels, out_channels, in_timesteps, out_timesteps, n_blocks, embed_dim,
+            out_layer_dim, depth, modes, mlp_ratio, n_cls, normalize, act, time_agg,
+            patch_embed=lambda: _PatchEmbedParams(img_size, patch_size, in_channels + 3, out_channels * patch_size + 3, embed_dim),
+            block=lambda: _BlockParams(embed_dim, n_blocks, mlp_ratio),
+            out_layer=lambda: nn.Sequential(
+                nn.ConvTranspose2d(embed_dim, out_layer_dim, patch_size, patch_size), nn.Identity(),
+                nn.Conv2d(out_layer_dim, out_layer_dim, 1), nn.Identity(),
+                nn.Conv2d(out_layer_dim, out_channels * out_timesteps, 1)))
         # activation recomputation inside every Block (functional.BlockFn): keep only block inputs between forward
         # and backward - for long auto-regressive rollouts at 256^2 (BASELINE configs[4])
         self.recompute_blocks = False
@@ -125,14 +183,6 @@ class DPOTNet(nn.Module):
         # (bit-identical either way; spends free HBM on time: DPOT-L, 20 steps, batch 16: 112 GB with 0 kept)
         self.recompute_keep_last = 0
         self._ar_pos = None                          # (index, count) of the current AR step, set by train.rollout
-        # precision of the channel-MLP GEMMs of THIS model: None = the process default (ops.set_mlp_precision /
-        # DPOT_MLP_PRECISION), or 'f32' | 'bf16x6' | 'auto' | 'bf16' (BASELINE configs[2]: "bf16 channel-MLP on MFMA")
-        self.mlp_precision = None
-        # precision of every OTHER fp32 GEMM of this model: None = the process default (ops.set_gemm_precision /
-        # DPOT_GEMM_PRECISION), or 'f32' (native fp32 MFMA) | 'bf16x6' | 'auto' (the fp32-accurate operand split where faster)
-        self.gemm_precision = None
-        # every weight-derived copy the kernels read (packed / padded / transposed weights) and when it is fresh
-        self.packs = ModelPacks()
         # optional callable(b, lat) -> lat, called with the latent ENTERING stage b (1..depth = block b-1,
         # depth+1 = the head); train.SegmentedTrainStep cuts the autograd graph there
         self._boundary_hook = None
@@ -148,27 +198,13 @@ class DPOTNet(nn.Module):
         with self.packs.scope(self):
             yield self
 
-    def forward(self, x):
-        with ops.precision_scope(self.gemm_precision, self.mlp_precision):
-            return self._forward(x)
-
     def _forward(self, x):
-        if not x.is_cuda:
-            raise _lib.DpotHipError("DPOTNet (dpot_amd) runs on MI355X only: move the model and the input to 'cuda'. "
-                                    "There is no CPU fallback.")
+        self._check_device(x)
         B, X, Y, T, Cin = x.shape
         assert X == self.img_size and Y == self.img_size, \
             f"Input image size ({X}*{Y}) doesn't match model ({self.img_size}*{self.img_size})."
         assert T == self.in_timesteps and Cin == self.in_channels, "input timesteps / channels mismatch"
-        x = x.float()
-        if self.normalize:
-            # models/dpot.py:366-370 - per-sample statistics + two tiny Linear(2C -> E): O(B*C) host-side glue
-            mu = x.mean(dim=(1, 2, 3), keepdim=True)
-            sigma = x.std(dim=(1, 2, 3), keepdim=True) + 1e-6
-            x = (x - mu) / sigma
-            stat = torch.cat([mu, sigma], dim=-1)[:, 0, 0, 0, :]
-            s_mu = self.scale_feats_mu(stat)
-            s_sigma = self.scale_feats_sigma(stat)
+        x, mu, sigma, s_mu, s_sigma = self._normalize_in(x.float(), (1, 2, 3))
 
         pe, ta = self.patch_embed.proj, self.time_agg_layer
         P = self.patch_size
@@ -176,7 +212,7 @@ class DPOTNet(nn.Module):
         d_emb, pk, d_head, mlp_pk = self.packs.derive(self, defer=True)
         try:       # EmbedFn.forward joins the side lane that `derive` may have left forked, between its two launches
             lat = EmbedFn.apply(x, self.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, ta.w,
-                                ta.gamma if self.time_agg == "exp_mlp" else None, self._gx, self._gy, self._gt, self._tt,
+                                self._time_agg_gamma(), self._gx, self._gy, self._gt, self._tt,
                                 P, self._act, d_emb)
         finally:
             ops.side_lane_join()
@@ -211,11 +247,4 @@ class DPOTNet(nn.Module):
                                       ol[4].bias, ch[0].weight, ch[0].bias, ch[2].weight, ch[2].bias, ch[4].weight,
                                       ch[4].bias, h, h, P, self._act, d_head)
         pred = pred.view(B, X, Y, self.out_timesteps, self.out_channels)
-        if self.normalize:
-            pred = pred * sigma + mu
-        return pred, cls_pred
-
-    def extra_repr(self) -> str:
-        return (f"img_size={self.img_size}, patch_size={self.patch_size}, embed_dim={self.embed_dim}, "
-                f"depth={len(self.blocks)}, n_blocks={self.n_blocks}, modes={self.modes}, act={self.act_name}, "
-                f"backend=libdpot_hip(gfx950)")
+        return self._denormalize(pred, mu, sigma), cls_pred

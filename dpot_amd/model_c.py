@@ -17,7 +17,7 @@ by 2, LeakyReLU(0.01), anti-aliased bilinear down by 2, optionally bilinear up t
                    moves the input by 2.4e-7) - so it is implemented as nothing.
 
 Everything else is the 2-D model's: grid channels, time aggregation, AdaIN (normalize=True), the Blocks through the unchanged
-functional.BlockFn with this model's own AFNO pack table (as DPOTNet3D._afno_packs), cls_head on the token mean.  The drop
+functional.BlockFn with the AFNO pack table of packs.ModelPacks.afno, cls_head on the token mean.  The drop
 arguments are accepted and change nothing, as in the reference, whose forward never uses them.  The torch modules below are
 parameter containers only.  CUDA (ROCm) tensors only; there is no CPU path.
 
@@ -26,14 +26,11 @@ the one-launch embed and de-embed fusions of DPOTNet.
 """
 from __future__ import annotations
 
-import numpy as np
-
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
 from .functional import AALReLUFn, AdaINFn, BlockFn, ClsHeadFn, LinearFn, Mlp2Fn, PatchConvFn, TimeAggFn, TokenMeanFn
-from .model import ACTIVATIONS, _BlockParams, _TimeAggParams
+from .model import _BlockParams, _DPOTBase
 
 AA_SLOPE = 0.01          # nn.LeakyReLU()'s default - not the 0.1 of the model's 'leaky_relu' activation
 
@@ -66,86 +63,26 @@ class _CNOBlockParams(nn.Module):
         self.activation = _AAActParams(out_channels)
 
 
-class CDPOTNet(nn.Module):
+class CDPOTNet(_DPOTBase):
     def __init__(self, img_size=224, patch_size=16, mixing_type='afno', in_channels=1, out_channels=3, in_timesteps=1,
                  out_timesteps=1, n_blocks=4, embed_dim=768, out_layer_dim=32, depth=12, modes=32, mlp_ratio=1.,
                  representation_size=None, uniform_drop=False, drop_rate=0., drop_path_rate=0., dropcls=0, n_cls=1,
                  normalize=False, act='gelu', time_agg='exp_mlp'):
-        super().__init__()
-        if act not in ACTIVATIONS:
-            raise KeyError(act)
-        if mixing_type != 'afno':
-            raise ValueError("only mixing_type='afno' exists in the reference")
-        self.in_channels, self.out_channels = in_channels, out_channels
-        self.in_timesteps, self.out_timesteps = in_timesteps, out_timesteps
-        self.n_blocks, self.modes = n_blocks, modes
-        self.num_features = self.embed_dim = embed_dim
-        self.mlp_ratio = mlp_ratio
-        self.normalize, self.time_agg, self.n_cls = normalize, time_agg, n_cls
-        self.mixing_type = mixing_type
-        self.img_size, self.patch_size = img_size, patch_size
-        self.out_layer_dim = out_layer_dim
-        self.act_name, self._act = act, ops.ACT_IDS[act]
-
-        self.patch_embed = _CNOPatchEmbedParams(img_size, patch_size, in_channels + 3, out_channels * patch_size + 3,
-                                                embed_dim)
-        self.latent_size = self.patch_embed.out_size
-        h = self.latent_size[0]
-        self.pos_embed = nn.Parameter(torch.zeros(1, embed_dim, h, h))
-        self.blocks = nn.ModuleList([_BlockParams(embed_dim, n_blocks, mlp_ratio) for _ in range(depth)])
-        if normalize:
-            self.scale_feats_mu = nn.Linear(2 * in_channels, embed_dim)
-            self.scale_feats_sigma = nn.Linear(2 * in_channels, embed_dim)
-        self.cls_head = nn.Sequential(nn.Linear(embed_dim, embed_dim), nn.Identity(), nn.Linear(embed_dim, embed_dim),
-                                      nn.Identity(), nn.Linear(embed_dim, n_cls))
-        self.time_agg_layer = _TimeAggParams(in_timesteps, embed_dim, time_agg)
-        self.out_layer = nn.Sequential(_CNOBlockParams(embed_dim, out_layer_dim), nn.Conv2d(out_layer_dim, out_layer_dim, 1),
-                                       nn.Identity(), nn.Conv2d(out_layer_dim, out_channels * out_timesteps, 1))
-        torch.nn.init.trunc_normal_(self.pos_embed, std=.02)
-
-        # coordinate tables of get_grid_3d (np.linspace in float64, then cast) - not part of state_dict
-        for name, n in (("_gx", img_size), ("_gy", img_size), ("_gt", in_timesteps)):
-            self.register_buffer(name, torch.tensor(np.linspace(0, 1, n), dtype=torch.float32), persistent=False)
-        self.register_buffer("_tt", torch.linspace(0, 1, in_timesteps), persistent=False)
-        self.gemm_precision = None          # as DPOTNet: None = the process default
-        self._packs = None                  # (key, ops.AfnoPacks): the packed AFNO weights, persistent buffers
-
-    # ------------------------------------------------------------------------------------------------
-    def _afno_packs(self):
-        """packed forms of every block's complex weights: persistent buffers re-filled by ONE launch per forward (so a
-        captured forward replays the refresh with the weights of the day); rebuilt when the parameters move"""
-        pairs = []
-        for blk in self.blocks:
-            f = blk.filter
-            pairs += [(f.w1, f.b1), (f.w2, f.b2)]
-        key = tuple(p.data_ptr() for pr in pairs for p in pr)
-        if self._packs is None or self._packs[0] != key:
-            if torch.cuda.is_current_stream_capturing():
-                raise _lib.DpotHipError("CDPOTNet: run one forward before capturing (the weight-pack tables are built by it)")
-            self._packs = (key, ops.AfnoPacks(pairs))
-        return self._packs[1].refresh()
-
-    def forward(self, x):
-        with ops.precision_scope(self.gemm_precision, None):
-            return self._forward(x)
+        super().__init__(
+            img_size, patch_size, mixing_type, in_channels, out_channels, in_timesteps, out_timesteps, n_blocks, embed_dim,
+            out_layer_dim, depth, modes, mlp_ratio, n_cls, normalize, act, time_agg,
+            patch_embed=lambda: _CNOPatchEmbedParams(img_size, patch_size, in_channels + 3, out_channels * patch_size + 3, embed_dim),
+            block=lambda: _BlockParams(embed_dim, n_blocks, mlp_ratio),
+            out_layer=lambda: nn.Sequential(_CNOBlockParams(embed_dim, out_layer_dim), nn.Conv2d(out_layer_dim, out_layer_dim, 1),
+                                            nn.Identity(), nn.Conv2d(out_layer_dim, out_channels * out_timesteps, 1)))
 
     def _forward(self, x):
-        if not x.is_cuda:
-            raise _lib.DpotHipError("CDPOTNet (dpot_amd) runs on MI355X only: move the model and the input to 'cuda'. "
-                                    "There is no CPU fallback.")
+        self._check_device(x)
         B, X, Y, T, Cin = x.shape
         S, P, h, E = self.img_size, self.patch_size, self.latent_size[0], self.embed_dim
         assert X == S and Y == S, f"Input image size ({X}*{Y}) doesn't match model ({S}*{S})."
         assert T == self.in_timesteps and Cin == self.in_channels, "input timesteps / channels mismatch"
-        x = x.float()
-        if self.normalize:
-            # models/dpot_res.py:541-545 - per-sample statistics + two tiny Linear(2C -> E): O(B*C) glue
-            mu = x.mean(dim=(1, 2, 3), keepdim=True)
-            sigma = x.std(dim=(1, 2, 3), keepdim=True) + 1e-6
-            x = (x - mu) / sigma
-            stat = torch.cat([mu, sigma], dim=-1)[:, 0, 0, 0, :]
-            s_mu = self.scale_feats_mu(stat)
-            s_sigma = self.scale_feats_sigma(stat)
+        x, mu, sigma, s_mu, s_sigma = self._normalize_in(x.float(), (1, 2, 3))
 
         # patch embedding: rows (b, hx, hy, t) throughout, so the field [B, h, h, T*hid] of the operator (bias[c % hid]) and the
         # rows (b, token) x columns (t, e) of the time aggregation are views
@@ -156,12 +93,11 @@ class CDPOTNet(nn.Module):
         hact = AALReLUFn.apply(hpre.view(B, h, h, T * hid), self.patch_embed.act_patching.bias, None, AA_SLOPE)
         posT = self.pos_embed.view(E, tok).t()                                  # [tok, E]
         z = LinearFn.apply(hact.view(B * tok * T, hid), pe[2].weight.view(E, hid), pe[2].bias, posT, T, tok)
-        lat = TimeAggFn.apply(z.view(B * tok, T * E), ta.w, ta.gamma if self.time_agg == "exp_mlp" else None,
-                              self._tt).view(B, tok, E)
+        lat = TimeAggFn.apply(z.view(B * tok, T * E), ta.w, self._time_agg_gamma(), self._tt).view(B, tok, E)
         if self.normalize:
             lat = AdaINFn.apply(lat, s_sigma, s_mu)                             # AdaIN (models/dpot_res.py:563-564)
 
-        pk = self._afno_packs()
+        pk = self.packs.afno(self).refresh()
         grad = torch.is_grad_enabled()
         for i, blk in enumerate(self.blocks):
             f = blk.filter
@@ -181,11 +117,4 @@ class CDPOTNet(nn.Module):
         pred = Mlp2Fn.apply(u.view(B * S * S, old), ol[1].weight.view(old, old), ol[1].bias, ol[3].weight.view(Co, old),
                             ol[3].bias, self._act)
         pred = pred.view(B, X, Y, self.out_timesteps, self.out_channels)
-        if self.normalize:
-            pred = pred * sigma + mu
-        return pred, cls_pred
-
-    def extra_repr(self) -> str:
-        return (f"img_size={self.img_size}, patch_size={self.patch_size}, embed_dim={self.embed_dim}, "
-                f"depth={len(self.blocks)}, n_blocks={self.n_blocks}, modes={self.modes}, act={self.act_name}, "
-                f"backend=libdpot_hip(gfx950)")
+        return self._denormalize(pred, mu, sigma), cls_pred

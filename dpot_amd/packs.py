@@ -1,6 +1,7 @@
-"""The one owner of a DPOTNet's weight-derived copies (``DPOTNet.packs``): the embed grid matrix, the small layout pieces
-(ops.LayoutJobs), the AFNO packs (ops.AfnoPacks), the de-embed matrix and the panel GEMM weight packs (ops.PanelPacks: fp32
-channel MLP + de-embed, bf16, bf16x6).  Each job table is rebuilt only when the tensors it points at move (``_where``).
+"""The one owner of a model's weight-derived copies (``model.packs``): the AFNO packs (ops.AfnoPacks) of all three models and, for a
+DPOTNet, the embed grid matrix, the small layout pieces (ops.LayoutJobs), the de-embed matrix and the panel GEMM weight packs
+(ops.PanelPacks: fp32 channel MLP + de-embed, bf16, bf16x6).  Each job table is rebuilt only when the tensors it points at move
+(``_where``).
 
 Freshness rule: every forward (or once per ``DPOTNet.weights_scope()``) refreshes every set, except the one set the optimiser
 last wrote itself (train.FusedAdam -> dpot_adam_step_packs) while that write is current: same FlatParams epoch, same tensor
@@ -11,7 +12,9 @@ from __future__ import annotations
 
 import contextlib
 
-from . import ops
+import torch
+
+from . import _lib, ops
 from .functional import (embed_derived, embed_grid_matrix, embed_implicit_tables, embed_layout_jobs, head_derived,
                          head_layout_jobs, mlp_pack_kind)
 
@@ -80,7 +83,21 @@ class ModelPacks:
                 self.held = None
                 ops.side_lane_join()                 # a scope that ran no forward
 
-    # -- the derived weights of one forward -------------------------------------------------------------
+    # -- the AFNO packs of any of the three models ---------------------------------------------------------
+    def afno(self, m):
+        """the ops.AfnoPacks of m.blocks: Wbig = [[Wr, Wi], [-Wi, Wr]] of every AFNO layer + its fragment-block-major forms in
+        persistent buffers that ``.refresh()`` re-fills in ONE launch for all layers (so a captured forward replays the refresh
+        with the weights of the day)"""
+        pairs = [p for blk in m.blocks for p in ((blk.filter.w1, blk.filter.b1), (blk.filter.w2, blk.filter.b2))]
+
+        def make():
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.DpotHipError(f"{type(m).__name__}: run one forward before capturing (the weight-pack tables are "
+                                        "built by it)")
+            return ops.AfnoPacks(pairs)
+        return self._table("afno", _where(*(t for p in pairs for t in p)), make)
+
+    # -- the derived weights of one DPOTNet forward -------------------------------------------------------
     def derive(self, m, defer: bool = False):
         """-> (embed products, AFNO items, head products + (de-embed packs,), channel-MLP packs per block | None)
 
@@ -103,20 +120,16 @@ class ModelPacks:
             jobs = je + head_layout_jobs(ol[0].bias, ol[4].weight, ol[4].bias, m.patch_size, ol[0].weight.shape[1])
             lay = self._table("layout", _where(*(j[k] for k in (0, 1) for j in jobs)), lambda: ops.LayoutJobs(jobs)).refresh()
             lay_e, lay_h = lay[:len(je)], lay[len(je):]
-        afno = None
-        if len(m.blocks):
-            pairs = [p for blk in m.blocks for p in ((blk.filter.w1, blk.filter.b1), (blk.filter.w2, blk.filter.b2))]
-            afno = self._table("afno", _where(*(t for p in pairs for t in p)), lambda: ops.AfnoPacks(pairs))
+        afno = self.afno(m) if len(m.blocks) else None
         w0 = ol[0].weight
         wt = self._table("wt", _where(w0), lambda: w0.new_empty(m.embed_dim, m.patch_size ** 2 * w0.shape[1]))
         stale = []
         mlp_pk, head_pk = self._panels(m, wt, stale)
-        eargs = (m.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, ta.w,
-                 ta.gamma if m.time_agg == "exp_mlp" else None, m._tt, m.in_timesteps)
+        eargs = (m.pos_embed, pe[0].weight, pe[0].bias, pe[2].weight, pe[2].bias, ta.w, m._time_agg_gamma(), m._tt,
+                 m.in_timesteps)
         side = lay_e is not None and ops.side_lane_enabled("weights")     # the lane's products read the layout pieces
         with ops.side_lane("weights", on=side, join=False):
             emb = embed_derived(*eargs, grid=grid, layouts=lay_e, implicit_tables=not side)
-            # Wbig = [[Wr, Wi], [-Wi, Wr]] of every AFNO layer + its fragment-block-major forms, ONE launch for all layers
             pk = afno.refresh() if afno is not None else []
             head = head_derived(w0, ol[0].bias, ol[4].weight, ol[4].bias, m.patch_size, wt_out=wt, layouts=lay_h)
             for pp in stale:

@@ -133,7 +133,9 @@ class FlatOptimizer:
         self._part = torch.zeros(1024, dtype=torch.float32, device=dev)
         self.step_count = 0                       # host mirror of step_dev (number of steps ENQUEUED)
         self.param_groups = [{"lr": lr}]          # minimal torch.optim surface for LR schedulers / logging
-        self.packs = getattr(flat.model, "packs", None)       # the model's packs.ModelPacks (None: a model without one)
+        # the model's packs.ModelPacks, or None for a module that is none of the three models.  Only a DPOTNet's ever holds the
+        # "bf16" table `adam_plan` asks for: for DPOTNet3D and CDPOTNet the plan stays None and nothing is marked fresh
+        self.packs = getattr(flat.model, "packs", None)
         self.wrote = None                         # the pack set the last launch() wrote along with the parameters, or None
 
     @property

@@ -159,7 +159,7 @@ class Stages:
     def blocks(self, lat):
         m = self.m
         h = round(lat.shape[1] ** (1 / 3))
-        pk = m._afno_packs()
+        pk = m.packs.afno(m).refresh()
         for i, blk in enumerate(m.blocks):
             f = blk.filter
             lat = block3d(lat, blk.norm1.weight, blk.norm1.bias, f.w1, f.b1, f.w2, f.b2, blk.norm2.weight, blk.norm2.bias,

@@ -1,13 +1,14 @@
 #!/usr/bin/env python
-"""Bit-level fingerprint of the block path (functional.BlockFn / AFNO2DFn / AFNO3DFn / block3d), for comparing two trees that
-must compute the same thing:  python scripts/grad_fingerprint.py > a.txt   in each tree, on the same machine with the same
-built library (DPOT_HIP_LIB), then `diff`.  Run it a second time under DPOT_TUNE=gn_fuse=0,panel=0 (the C library reads those
-two keys once per process); the Python-side DPOT_TUNE keys are set per case here.
+"""Bit-level fingerprint of the three models' training step (DPOTNet, DPOTNet3D, CDPOTNet) and of the block path
+(functional.BlockFn / AFNO2DFn / AFNO3DFn / block3d), for comparing two trees that must compute the same thing:
+python scripts/grad_fingerprint.py > a.txt   in each tree, on the same machine with the same built library (DPOT_HIP_LIB),
+then `diff`.  Run it a second time under DPOT_TUNE=gn_fuse=0,panel=0 (the C library reads those two keys once per process);
+the Python-side DPOT_TUNE keys are set per case here.
 
 One line per case: name, the loss (or sum of the output) as hex, SHA-256 over the bytes of every gradient - and of the flat
 parameter buffer after one FusedAdam step where the case is a model -, and the launch counts that show which route ran.  A
-case asserts its route where the code offers a way to see it.  Inputs and weights: the recipes of oracle/dpot_ref.py and
-tests/afno3d_ref.py, as the tests use them."""
+case asserts its route where the code offers a way to see it.  Inputs and weights: the recipes of oracle/dpot_ref.py,
+tests/afno3d_ref.py and tests/cdpot_ref.py, as the tests use them."""
 import hashlib
 import os
 import sys
@@ -18,14 +19,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import afno3d_ref as A3  # noqa: E402
-from dpot_amd import DPOTNet, DPOTNet3D, _lib, load_3d_components_from_2d, ops  # noqa: E402
-from dpot_amd.functional import AFNO2DFn, AFNO3DFn, block3d, rel_l2_loss  # noqa: E402
-from dpot_amd.train import FlatParams, FusedAdam, rollout  # noqa: E402
+import cdpot_ref as CR  # noqa: E402
+from dpot_amd import CDPOTNet, DPOTNet, DPOTNet3D, _lib, load_3d_components_from_2d, ops  # noqa: E402
+from dpot_amd.functional import AFNO2DFn, AFNO3DFn, block3d  # noqa: E402
+from dpot_amd.train import FlatParams, FusedAdam, rollout, rollout_total  # noqa: E402
 from oracle import dpot_ref as R  # noqa: E402
 
 BASE_TUNE = os.environ.get("DPOT_TUNE", "")
 COUNTED = ("block_finalize", "wgrad_batch_finalize", "groupnorm_param_grads", "afno_fused_fwd", "afno_mlp2", "gn_rfft2",
-           "bf16_pack_both", "groupnorm_bwd_packs", "afno_wgrad2", "mlp_wgrad2")
+           "bf16_pack_both", "groupnorm_bwd_packs", "afno_wgrad2", "mlp_wgrad2", "linear_fwd", "linear_bwd_data", "linear_bwd_wb",
+           "patchify", "patchify3", "unpatchify", "unpatchify3", "fold3", "group_rowsum", "token_mean", "token_mean_bwd", "colsum",
+           "gemm")
 
 
 def set_tune(**kv):
@@ -73,29 +77,36 @@ def report(name, value, tensors, c):
     print(f"{name}: {float(value.detach()).hex()} {digest(tensors)} {c}", flush=True)
 
 
-def model_case(name, kw, B, T_ar, salt=6, tune=None, check=None, **attrs):
-    """one rollout + backward on flat-bound parameters, one FusedAdam step"""
+def model_case(name, kw, B, T_ar, salt=6, tune=None, check=None, model=DPOTNet, cls_weight=0.0, **attrs):
+    """one rollout + backward on flat-bound parameters (cls_weight: with the classification output in the loss), one FusedAdam step"""
     set_tune(**(tune or {}))
     hook = attrs.pop("hook", False)
     cfg = R.DPOTConfig(**kw)
-    m = DPOTNet(**kw)
-    m.load_state_dict(R.recipe_state_dict(cfg, salt=salt))
+    m = model(**kw)
+    if model is DPOTNet:
+        m.load_state_dict(R.recipe_state_dict(cfg, salt=salt))
+    else:
+        m.load_state_dict(CR.recipe_sd({k: tuple(v.shape) for k, v in m.state_dict().items()}, kw, salt))
     m.cuda()
     for k, v in attrs.items():
         setattr(m, k, v)
     if hook:
         m._boundary_hook = lambda b, lat: lat
-    S = cfg.img_size
+    S, Tb = cfg.img_size, cfg.out_timesteps
     xx = R.recipe_input((B, S, S, cfg.in_timesteps, cfg.in_channels), salt=81).cuda()
-    yy = R.recipe_input((B, S, S, T_ar, cfg.out_channels), salt=82).cuda()
+    yy = R.recipe_input((B, S, S, T_ar * Tb, cfg.out_channels), salt=82).cuda()
     msk = torch.ones(B, S, S, 1, cfg.out_channels, device="cuda")
     opt = FusedAdam(FlatParams(m), lr=1e-3, betas=(0.9, 0.9), weight_decay=1e-6, max_norm=10000.0)
     opt.zero_grad()
     with Counts() as c:
-        loss, _ = rollout(m, xx, yy, msk)
+        if cls_weight:
+            labels = torch.arange(B, device="cuda") % cfg.n_cls
+            loss = rollout_total(m, xx, yy, msk, Tb, cls=labels, cls_weight=cls_weight)[2]
+        else:
+            loss, _ = rollout(m, xx, yy, msk, Tb)
         loss.backward()
     torch.cuda.synchronize()
-    left = [k for k, p in zip(opt.fp.names, opt.fp.pending) if p != 0 and not k.startswith("cls_head.")]
+    left = [k for k, p in zip(opt.fp.names, opt.fp.pending) if p != 0 and (cls_weight or not k.startswith("cls_head."))]
     assert not left, f"{name}: gradient sinks never delivered: {left}"
     grads = [p.grad.clone() for _, p in m.named_parameters() if p.grad is not None]
     opt.step()
@@ -159,6 +170,23 @@ def generic_case():
     def check(c, cfg, T_ar):
         assert c["afno_mlp2"] == 0 and c["gn_rfft2"] == 0 and c["afno_fused_fwd"] == 0 and c["afno_wgrad2"] == 0, dict(c)
     model_case("generic mini", R.MINI, 2, 1, salt=3, check=check)
+    # linear_fwd on the generic GEMM route instead of small_linear (which takes K % 512 == 0: the cls_head at 512 channels)
+    model_case("generic mini fused_small=0", R.MINI, 2, 1, salt=3, tune=dict(fused_small=0))
+    for fs in (0, 1):
+        model_case(f"mini E512 cls fused_small={fs}", dict(R.MINI, embed_dim=512), 2, 1, salt=3, tune=dict(fused_small=fs),
+                   cls_weight=0.5)
+
+
+def plain_stage_cases():
+    """the stages built from chains of dense layers: normalize=True, HeadFn's unfused tail (ops.out_tail_supported needs
+    out_layer_dim 32) with and without the classification output in the loss, and both CDPOTNet mini models"""
+    model_case("mini normalize", dict(R.MINI, normalize=True), 2, 2, salt=3)
+    kw = dict(R.MINI, out_layer_dim=16)
+    assert not ops.out_tail_supported(16, kw["out_channels"], 2 * kw["img_size"] ** 2)
+    model_case("mini unfused tail", kw, 2, 2, salt=3)
+    model_case("mini unfused tail cls", kw, 2, 2, salt=3, cls_weight=0.5)
+    for tag, kw in (("mini1", CR.MINI1), ("mini2 normalize", CR.MINI2)):
+        model_case("cdpot " + tag, kw, CR.MODEL_B, 2, salt=CR.STEP["salt"], model=CDPOTNet, cls_weight=0.5)
 
 
 def afno2d_case(name, one_launch):
@@ -204,28 +232,30 @@ def cases_3d():
                     bc["dims"], nb, bc["modes"], act)
         y.backward(g)
     report("block3d", y.sum(), [y, x.grad] + [v.grad for v in p.values()], c)
-    # one fine-tune step of the mini DPOTNet3D: 2-D blocks and time aggregator loaded, two AR steps, clip, fused Adam
-    cfg, st, B = A3.MINI3D, A3.STEP, 2
+    step3d("dpot3d mini fine-tune step", A3.MINI3D, True)
+    step3d("dpot3d mini normalize step", A3.MINI3D_NORM, False)
+
+
+def step3d(name, cfg, from_2d):
+    """one step of a mini DPOTNet3D (from_2d: with a 2-D model's blocks and time aggregator loaded): two AR steps, clip, fused Adam"""
+    st, B = A3.STEP, 2
     m = DPOTNet3D(**cfg)
     m.load_state_dict(A3.recipe_sd({k: tuple(v.shape) for k, v in m.state_dict().items()}, cfg["n_blocks"], 182))
     m.cuda()
-    load_3d_components_from_2d(m, R.recipe_state_dict(R.DPOTConfig(**A3.MINI2D), 183), ["blocks", "time_agg"])
+    if from_2d:
+        load_3d_components_from_2d(m, R.recipe_state_dict(R.DPOTConfig(**A3.MINI2D), 183), ["blocks", "time_agg"])
     S, T, C = cfg["img_size"], cfg["in_timesteps"], cfg["in_channels"]
     xx = R.recipe_input((B, S, S, S, T, C), 182).cuda()
     yy = R.recipe_input((B, S, S, S, st["T_ar"], C), 183).cuda()
     msk = A3.recipe_mask((B, S, S, S, 1, C), 182).cuda()
     opt = FusedAdam(FlatParams(m), lr=st["lr"], betas=st["betas"], weight_decay=st["weight_decay"], max_norm=st["max_norm"])
     opt.zero_grad()
-    loss = 0.
     with Counts() as c:
-        for t in range(st["T_ar"]):
-            im = m(xx)
-            loss = loss + rel_l2_loss(im, yy[..., t:t + 1, :].contiguous(), msk)
-            xx = torch.cat((xx[..., 1:, :], im), dim=-2)
+        loss, _ = rollout(m, xx, yy, msk)
         loss.backward()
     grads = [p.grad.clone() for p in m.parameters() if p.grad is not None]
     opt.step()
-    report("dpot3d mini fine-tune step", loss, grads + [opt.fp.flat], c)
+    report(name, loss, grads + [opt.fp.flat], c)
 
 
 def main():
@@ -237,6 +267,7 @@ def main():
     mixer6_cases()
     afno2d_case("afno2d one-launch layer", True)
     generic_case()
+    plain_stage_cases()
     afno2d_case("afno2d g1_afno_tiny", False)
     cases_3d()
 
