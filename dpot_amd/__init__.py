@@ -9,12 +9,14 @@
     from dpot_amd import DPOTNet3D, load_3d_components_from_2d   # 3-D fine-tuning from a pretrained 2-D checkpoint
     from dpot_amd import DeviceBatcher3D, resize_pad_window3, target_mask3   # the 3-D input pipeline on the device
     from dpot_amd import CDPOTNet           # drop-in for models/dpot_res.py::CDPOTNet (anti-aliased embed and output stages)
+    from dpot_amd import FNO2d              # drop-in for models/fno.py::FNO2d, the baseline (truncated-DFT and per-mode mixing kernels)
 
 The compute path is libdpot_hip.so (hand-written HIP kernels behind the C ABI in include/dpot_hip.h).
 """
 from .model import DPOTNet  # noqa: F401
 from .model3d import DPOTNet3D  # noqa: F401
 from .model_c import CDPOTNet  # noqa: F401
+from .model_fno import FNO2d  # noqa: F401
 from . import _lib  # noqa: F401
 from .functional import ClsCEFn, cls_ce_loss  # noqa: F401
 from .train import StepMetrics  # noqa: F401
@@ -22,7 +24,7 @@ from .infer import GraphedRollout, RolloutEvaluator, load_3d_components_from_2d,
 from .ops import ResizePlan, spectral_resize, spectral_resize_matrices  # noqa: F401
 from .data import DeviceBatcher3D, resize_pad_window3, target_mask3  # noqa: F401
 
-__version__ = "0.2.9"
+__version__ = "0.3.0"
 __all__ = ["DPOTNet", "StepMetrics", "ClsCEFn", "cls_ce_loss", "GraphedRollout", "rollout_eval", "refill_mask",
            "spectral_resize", "spectral_resize_matrices", "ResizePlan", "RolloutEvaluator", "DPOTNet3D",
-           "load_3d_components_from_2d", "DeviceBatcher3D", "resize_pad_window3", "target_mask3", "CDPOTNet"]
+           "load_3d_components_from_2d", "DeviceBatcher3D", "resize_pad_window3", "target_mask3", "CDPOTNet", "FNO2d"]

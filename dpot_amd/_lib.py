@@ -270,6 +270,12 @@ SIGNATURES = {
     "dpot_aa_lrelu_bwd": (c_i, [c_fp] * 5 + [c_i] * 4 + [c_f, c_fp]),
     "dpot_aa_up_fwd": (c_i, [c_fp] * 4 + [c_i] * 7 + [c_fp]),
     "dpot_aa_up_adj": (c_i, [c_fp] * 3 + [c_i] * 6 + [c_fp]),
+    "dpot_fno_max_size": (c_i, [c_i]),
+    "dpot_fno_rfft2": (c_i, [c_fp] * 4 + [c_i] * 7 + [c_f, c_fp]),
+    "dpot_fno_irfft2": (c_i, [c_fp] * 6 + [c_i] * 7 + [c_f, c_i, c_fp]),
+    "dpot_fno_mix": (c_i, [c_fp] * 4 + [c_i] * 6 + [c_fp]),
+    "dpot_fno_mix_wgrad": (c_i, [c_fp] * 4 + [c_i] * 6 + [c_fp]),
+    "dpot_fno_dact": (c_i, [c_fp] * 3 + [c_i64, c_i, c_fp]),
 }
 
 _lib = None

@@ -59,7 +59,9 @@ int tune(const char* key, int dflt) {
  * 273: dpot_aa_lrelu_fwd, dpot_aa_lrelu_bwd, dpot_aa_up_fwd, dpot_aa_up_adj and their queries (csrc/aa_act.hip): the anti-aliased
  * activation of the CDPOT model
  * 274: the lanes move to csrc/lane.hip; dpot_wgrad_flush_async, dpot_wgrad_wait and dpot_wgrad_lane_* removed (lane 0 is forked
- * and joined through dpot_lane_* like lane 1) */
-extern "C" int dpot_version(void) { return 274; }
+ * and joined through dpot_lane_* like lane 1)
+ * 275: dpot_fno_rfft2, dpot_fno_irfft2, dpot_fno_mix, dpot_fno_mix_wgrad, dpot_fno_dact, dpot_fno_max_size (csrc/fno.hip): the
+ * kernels of the FNO baseline; nothing existing changed */
+extern "C" int dpot_version(void) { return 275; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

@@ -1634,3 +1634,119 @@ class TokenMeanFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         return ops.token_mean_bwd(dy.contiguous(), ctx.tok)
+
+
+# ======================================================================================================
+# the FNO baseline (models/fno.py): csrc/fno.hip through ops.fno_*
+# ======================================================================================================
+def _fno_wgrad(X, dO, s1: _Sink, s2: _Sink, need: bool = True):
+    """(dweights1, dweights2) delivered: straight into the flat gradient slots where this is the step's first contribution,
+    ADDED there by the kernel itself in a further pass of a rollout (both slots filled), else as temporaries; need=False (neither
+    weight takes a gradient, frozen spectral weights): nothing is launched"""
+    if not need:
+        s1.skip()
+        s2.skip()
+        return None, None
+    o1, o2 = s1.out(), s2.out()
+    acc = False
+    if o1 is None or o2 is None:
+        o1 = o2 = None
+        if all(s.fp is not None and s.fp.filled[s.i] for s in (s1, s2)):
+            o1, o2, acc = s1.fp.grad_views[s1.i], s2.fp.grad_views[s2.i], True
+    d1, d2 = ops.fno_mix_wgrad(X, dO, o1, o2, acc)
+    return s1.done(d1), s2.done(d2)
+
+
+class SpectralConv2dFn(torch.autograd.Function):
+    """SpectralConv2d_fast (models/fno.py:14-53) on a channels-last field x[B, H, W, Cin] -> [B, H, W, Cout]: truncated rfft2,
+    per-mode mixing with weights1 / weights2 [2, Cin, Cout, m1, m2], irfft2.  Keeps the kept spectrum X, not the field."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2):
+        x, w1, w2 = x.contiguous(), w1.contiguous(), w2.contiguous()
+        m1, m2 = w1.shape[3], w1.shape[4]
+        X = ops.fno_rfft2(x, m1, m2)
+        y, _ = ops.fno_irfft2(ops.fno_mix(X, w1, w2), x.shape[1], x.shape[2])
+        ctx.save_for_backward(X, w1, w2)
+        ctx.sinks = _sinks(ctx, (w1, w2), 1)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        X, w1, w2 = ctx.saved_tensors
+        dy = dy.contiguous()
+        dO = ops.fno_rfft2(dy, w1.shape[3], w1.shape[4], adjoint=True)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx, _ = ops.fno_irfft2(ops.fno_mix(dO, w1, w2, adjoint=True), dy.shape[1], dy.shape[2], adjoint=True)
+        d1, d2 = _fno_wgrad(X, dO, *ctx.sinks, need=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        return dx, d1, d2
+
+
+class FNOLayerFn(torch.autograd.Function):
+    """One layer of FNO2d (models/fno.py:192-196): act(SpectralConv2d_fast(x) + Conv2d 1x1(x)) on x[B, H, W, Cin].  The
+    convolution branch is one GEMM whose result rides into the inverse transform's epilogue (add, activation); the backward
+    forms dpre = dy act'(pre) once, and the convolution's data gradient rides into the adjoint transform the same way."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, cw, cb, act: int):
+        ops.capture_precision(ctx)
+        x, w1, w2, cw = x.contiguous(), w1.contiguous(), w2.contiguous(), cw.contiguous()
+        B, H, W, Cin = x.shape
+        Cout, m1, m2 = w1.shape[2], w1.shape[3], w1.shape[4]
+        conv, _ = ops.linear_fwd(x.view(B * H * W, Cin), cw, cb)
+        X = ops.fno_rfft2(x, m1, m2)
+        y, pre = ops.fno_irfft2(ops.fno_mix(X, w1, w2), H, W, add=conv.view(B, H, W, Cout), act=act, save_pre=True)
+        ctx.save_for_backward(x, X, pre, w1, w2, cw)
+        ctx.act = act
+        ctx.sinks = _sinks(ctx, (w1, w2, cw, cb), 1)
+        return y
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dy):
+        x, X, pre, w1, w2, cw = ctx.saved_tensors
+        B, H, W, Cin = x.shape
+        Cout = w1.shape[2]
+        s1, s2, s_cw, s_cb = ctx.sinks
+        dpre = ops.act_bwd_mul(dy.contiguous(), pre, ctx.act)
+        dO = ops.fno_rfft2(dpre, w1.shape[3], w1.shape[4], adjoint=True)
+        dpre2 = dpre.view(B * H * W, Cout)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dxc = ops.linear_bwd_data(dpre2, cw).view(B, H, W, Cin)
+            dx, _ = ops.fno_irfft2(ops.fno_mix(dO, w1, w2, adjoint=True), H, W, add=dxc, adjoint=True)
+        d1, d2 = _fno_wgrad(X, dO, s1, s2, ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        dcw, dcb = ops.linear_bwd_wb(dpre2, x.view(B * H * W, Cin), s_cw.out(), s_cb.out())
+        return dx, d1, d2, s_cw.done(dcw.view(cw.shape)), s_cb.done(dcb), None
+
+
+class FNOEmbedFn(torch.autograd.Function):
+    """PatchEmbed of FNO2d (models/fno.py:57-82) on x[B, X, Y, 1, K] (K = the T * C input planes; ops.patchify appends the
+    coordinate channels): k = s = P convolution, act, 1x1 convolution, + res[b] (scale_feats, one row per sample) -> rows
+    (b, hx, hy).  W0 [hid, (K + 3) P P] carries a zero column block for the third coordinate channel, which FNO2d lacks."""
+
+    @staticmethod
+    def forward(ctx, x, gx, gy, gt, W0, b0, W2, b2, res, P: int, act: int):
+        ops.capture_precision(ctx)
+        x, W0, W2 = x.contiguous(), W0.contiguous(), W2.contiguous()
+        B, X, Y = x.shape[:3]
+        tok = (X // P) * (Y // P)
+        res = res.contiguous() if res is not None else None
+        y, ins, pres = _dense_fwd(lambda: ops.patchify(x, gx, gy, gt, P), [(W0, b0), (W2, b2)], act, res, tok,
+                                  B if res is not None else 0)
+        ctx.save_for_backward(x, gx, gy, gt, ins[1], pres[0], W0, W2)
+        ctx.P, ctx.act, ctx.tok, ctx.has_res = P, act, tok, res is not None
+        return y
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dy):
+        x, gx, gy, gt, Hh, Hpre, W0, W2 = ctx.saved_tensors
+        dy = dy.contiguous()
+        B, X, Y, T, K = x.shape
+        dA0, ((dW0, db0), (dW2, db2)) = _dense_bwd(dy, [lambda: ops.patchify(x, gx, gy, gt, ctx.P), Hh], [Hpre], [W0, W2],
+                                                   ctx.act, ctx.needs_input_grad[0])
+        dx = ops.unpatchify(dA0, B, X, Y, T, K, ctx.P) if dA0 is not None else None
+        dres = _res_bwd(dy, ctx.tok, B) if ctx.has_res and ctx.needs_input_grad[8] else None
+        return dx, None, None, None, dW0, db0, dW2, db2, dres, None, None

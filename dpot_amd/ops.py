@@ -2703,3 +2703,199 @@ def aa_lrelu_bwd(x: Tensor, dy: Tensor, Cb: int, slope: float = 0.01, out_dbias:
     check(lib.dpot_aa_lrelu_bwd(x.data_ptr(), g.data_ptr(), dx.data_ptr(), part.data_ptr(), plan.tab.data_ptr(), N, h, w, C,
                                 float(slope), _stream()), "aa_lrelu_bwd")
     return dx, colsum(part, N * (C // Cb), Cb, out=out_dbias)
+
+
+# ------------------------------------------------------------------------------------------------------
+# The FNO baseline (csrc/fno.hip; models/fno.py SpectralConv2d_fast): truncated transforms of a channels-last field
+# x [B, H, W, C] to / from the kept spectrum S [B, 2 m1, m2, 2, C] (rows kx < m1 and kx >= H - m1, columns ky < m2, re | im
+# planes, channels innermost) and the per-mode channel mixing.  The twiddle tables are pure numpy: the CPU tests check them.
+# ------------------------------------------------------------------------------------------------------
+def fno_check_modes(H: int, W: int, m1: int, m2: int, what: str = "fno") -> None:
+    """the two refusals: narrower than the reference, which raises on the second only and lets weights2 overwrite the rows it
+    shares with weights1 when 2 m1 > H"""
+    if min(H, W, m1, m2) < 1:
+        raise ValueError(f"{what}: field {H}x{W} and modes ({m1}, {m2}) must be positive")
+    if 2 * m1 > H:
+        raise ValueError(f"{what}: modes1 = {m1} needs 2 * modes1 <= H = {H}: the two kept row blocks would overlap")
+    if m2 > W // 2 + 1:
+        raise ValueError(f"{what}: modes2 = {m2} exceeds the W // 2 + 1 = {W // 2 + 1} columns of the half spectrum of W = {W}")
+
+
+def fno_supported(H: int, W: int, m1: int, m2: int) -> bool:
+    """valid modes for the field, within the sizes the kernels cover (dpot_fno_max_size)"""
+    lib = _lib.load()
+    n, m = lib.dpot_fno_max_size(0), lib.dpot_fno_max_size(1)
+    return (min(H, W, m1, m2) >= 1 and 2 * m1 <= H and m2 <= W // 2 + 1 and max(H, W) <= n and max(m1, m2) <= m)
+
+
+def fno_kept_rows(H: int, m1: int):
+    """the wavenumbers kx of the 2 m1 kept rows, in the spectrum's row order"""
+    import numpy as np
+    return np.concatenate([np.arange(m1), np.arange(H - m1, H)])
+
+
+def fno_twiddles(H: int, W: int, m1: int, m2: int):
+    """float64 (tx [H, 2 m1, 2], ty [W, m2, 2]): cos | sin of 2 pi kx x / H over the kept rows and of 2 pi ky y / W, the
+    angle reduced in integers"""
+    import numpy as np
+    kx = fno_kept_rows(H, m1)
+    ax = 2.0 * np.pi * ((np.arange(H)[:, None] * kx[None, :]) % H) / H
+    ay = 2.0 * np.pi * ((np.arange(W)[:, None] * np.arange(m2)[None, :]) % W) / W
+    return np.stack([np.cos(ax), np.sin(ax)], -1), np.stack([np.cos(ay), np.sin(ay)], -1)
+
+
+def fno_col_weights(W: int, m2: int):
+    """w(ky) of irfft2 for a spectrum that is not Hermitian: 1 at ky = 0 and, for even W, at ky = W / 2, else 2"""
+    import numpy as np
+    w = np.full(m2, 2.0)
+    w[0] = 1.0
+    if W % 2 == 0 and W // 2 < m2:
+        w[W // 2] = 1.0
+    return w
+
+
+class FNOPlan:
+    """The twiddle tables of dpot_fno_rfft2 / dpot_fno_irfft2 for one (H, W, m1, m2), built in float64, rounded to fp32 and kept
+    in device memory."""
+
+    def __init__(self, H: int, W: int, m1: int, m2: int, device):
+        fno_check_modes(H, W, m1, m2, "FNOPlan")
+        if not fno_supported(H, W, m1, m2):
+            lib = _lib.load()
+            raise ValueError(f"FNOPlan: field {H}x{W} with modes ({m1}, {m2}) is beyond the kernels' limits (H, W <= "
+                             f"{lib.dpot_fno_max_size(0)}, modes <= {lib.dpot_fno_max_size(1)})")
+        self.sizes = (H, W, m1, m2)
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DpotHipError(f"FNOPlan {self.sizes}: the tables are uploaded when a size tuple is first used - call "
+                                    "ops.fno_plan(...) (or the operator itself) once before capturing")
+        tx, ty = fno_twiddles(H, W, m1, m2)
+        self.tx = torch.empty(tx.shape, dtype=torch.float32, device=device)
+        self.tx.copy_(torch.from_numpy(tx.astype("float32")))
+        self.ty = torch.empty(ty.shape, dtype=torch.float32, device=device)
+        self.ty.copy_(torch.from_numpy(ty.astype("float32")))
+
+
+_fno_plans = {}
+
+
+def fno_plan(H: int, W: int, m1: int, m2: int, device) -> FNOPlan:
+    """the cached FNOPlan of (H, W, m1, m2, device)"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(H), int(W), int(m1), int(m2), device)
+    plan = _fno_plans.get(key)
+    if plan is None:
+        plan = _fno_plans[key] = FNOPlan(*key)
+    return plan
+
+
+def _fno_field(x: Tensor, what: str):
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"{what}: the field must be a non-empty [B, H, W, C], got {tuple(x.shape)}")
+    return tuple(x.shape)
+
+
+def fno_rfft2(x: Tensor, m1: int, m2: int, adjoint: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """x [B, H, W, C] -> the kept spectrum S [B, 2 m1, m2, 2, C] of the unnormalised rfft2.  adjoint=True: the adjoint of
+    fno_irfft2 instead (the same sums times w(ky) / (H W)): the gradient of the spectrum from the gradient of the field"""
+    B, H, W, Cc = _fno_field(x, "fno_rfft2")
+    fno_check_modes(H, W, m1, m2, "fno_rfft2")
+    _req(x, "fno_rfft2: x")
+    plan = fno_plan(H, W, m1, m2, x.device)
+    shape = (B, 2 * m1, m2, 2, Cc)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(_req(out, "fno_rfft2: out").shape) != shape or out.device != x.device:
+        raise ValueError(f"fno_rfft2: out must be {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    check(_lib.load().dpot_fno_rfft2(x.data_ptr(), out.data_ptr(), plan.tx.data_ptr(), plan.ty.data_ptr(), B, H, W, Cc, m1, m2,
+                                     1 if adjoint else 0, 1.0 / (H * W) if adjoint else 1.0, _stream()), "fno_rfft2")
+    return out
+
+
+def fno_irfft2(S: Tensor, H: int, W: int, add: Optional[Tensor] = None, act: int = 0, save_pre: bool = False,
+               adjoint: bool = False, out: Optional[Tensor] = None):
+    """the kept spectrum S [B, 2 m1, m2, 2, C] -> (y, pre): y [B, H, W, C] = act(irfft2(S, s=(H, W)) + add), pre the value
+    before the activation (save_pre, else None).  adjoint=True: the adjoint of fno_rfft2 instead (column weights 1, no
+    1 / (H W)): the gradient of the field from the gradient of its spectrum"""
+    if S.dim() != 5 or S.shape[3] != 2 or S.shape[1] % 2 or S.numel() == 0:
+        raise ValueError(f"fno_irfft2: the spectrum must be a non-empty [B, 2 m1, m2, 2, C], got {tuple(S.shape)}")
+    B, R, m2, _, Cc = S.shape
+    m1 = R // 2
+    fno_check_modes(H, W, m1, m2, "fno_irfft2")
+    _req(S, "fno_irfft2: S")
+    plan = fno_plan(H, W, m1, m2, S.device)
+    shape = (B, H, W, Cc)
+    if add is not None and (tuple(_req(add, "fno_irfft2: add").shape) != shape or add.device != S.device):
+        raise ValueError(f"fno_irfft2: add must be {shape} on {S.device}, got {tuple(add.shape)} on {add.device}")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=S.device)
+    elif tuple(_req(out, "fno_irfft2: out").shape) != shape or out.device != S.device:
+        raise ValueError(f"fno_irfft2: out must be {shape} on {S.device}, got {tuple(out.shape)} on {out.device}")
+    pre = torch.empty_like(out) if save_pre else None
+    check(_lib.load().dpot_fno_irfft2(S.data_ptr(), _p(add), out.data_ptr(), _p(pre), plan.tx.data_ptr(), plan.ty.data_ptr(),
+                                      B, H, W, Cc, m1, m2, 0 if adjoint else 1, 1.0 if adjoint else 1.0 / (H * W), int(act),
+                                      _stream()), "fno_irfft2")
+    return out, pre
+
+
+def _fno_weights(w1: Tensor, w2: Tensor, what: str):
+    _req(w1, f"{what}: weights1")
+    _req(w2, f"{what}: weights2")
+    if w1.dim() != 5 or w1.shape[0] != 2 or w1.shape != w2.shape or w1.numel() == 0:
+        raise ValueError(f"{what}: weights1 / weights2 must both be [2, Cin, Cout, m1, m2], got {tuple(w1.shape)} and "
+                         f"{tuple(w2.shape)}")
+    return tuple(w1.shape[1:])
+
+
+def fno_mix(X: Tensor, w1: Tensor, w2: Tensor, adjoint: bool = False) -> Tensor:
+    """O[b, r, ky, :, o] = sum_i X[b, r, ky, :, i] W[i, o, r mod m1, ky] (complex), W = w[0] + i w[1], weights1 on the rows
+    below m1 and weights2 above, read in place.  adjoint=True: sum over o with conj(W): the data gradient"""
+    Cin, Cout, m1, m2 = _fno_weights(w1, w2, "fno_mix")
+    K, N = (Cout, Cin) if adjoint else (Cin, Cout)
+    _req(X, "fno_mix: X")
+    if tuple(X.shape[1:]) != (2 * m1, m2, 2, K) or X.shape[0] < 1:
+        raise ValueError(f"fno_mix: the spectrum must be [B, {2 * m1}, {m2}, 2, {K}], got {tuple(X.shape)}")
+    B = X.shape[0]
+    O = torch.empty(B, 2 * m1, m2, 2, N, dtype=torch.float32, device=X.device)
+    check(_lib.load().dpot_fno_mix(X.data_ptr(), w1.data_ptr(), w2.data_ptr(), O.data_ptr(), B, Cin, Cout, m1, m2,
+                                   1 if adjoint else 0, _stream()), "fno_mix")
+    return O
+
+
+def fno_mix_wgrad(X: Tensor, dO: Tensor, out1: Optional[Tensor] = None, out2: Optional[Tensor] = None,
+                  accumulate: bool = False):
+    """(dweights1, dweights2) [2, Cin, Cout, m1, m2] from the layer's input spectrum X [B, 2 m1, m2, 2, Cin] and the gradient
+    dO [B, 2 m1, m2, 2, Cout] of its output spectrum, summed over b in ascending order; accumulate: added to out1 / out2"""
+    _req(X, "fno_mix_wgrad: X")
+    _req(dO, "fno_mix_wgrad: dO")
+    if X.dim() != 5 or dO.dim() != 5 or X.shape[:4] != dO.shape[:4] or X.shape[3] != 2 or X.shape[1] % 2 or X.numel() == 0 \
+            or dO.numel() == 0:
+        raise ValueError(f"fno_mix_wgrad: X [B, 2 m1, m2, 2, Cin] and dO [B, 2 m1, m2, 2, Cout], got {tuple(X.shape)} and "
+                         f"{tuple(dO.shape)}")
+    B, R, m2, _, Cin = X.shape
+    Cout, m1 = dO.shape[4], R // 2
+    shape = (2, Cin, Cout, m1, m2)
+    if accumulate and (out1 is None or out2 is None):
+        raise ValueError("fno_mix_wgrad: accumulate needs out1 and out2")
+    outs = []
+    for o in (out1, out2):
+        if o is None:
+            o = torch.empty(shape, dtype=torch.float32, device=X.device)
+        elif tuple(_req(o, "fno_mix_wgrad: out").shape) != shape or o.device != X.device:
+            raise ValueError(f"fno_mix_wgrad: out must be {shape} on {X.device}, got {tuple(o.shape)} on {o.device}")
+        outs.append(o)
+    check(_lib.load().dpot_fno_mix_wgrad(X.data_ptr(), dO.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), B, Cin, Cout, m1,
+                                         m2, 1 if accumulate else 0, _stream()), "fno_mix_wgrad")
+    return outs[0], outs[1]
+
+
+def act_bwd_mul(dy: Tensor, pre: Tensor, act: int) -> Tensor:
+    """dy * act'(pre), elementwise: the gradient of a pre-activation that feeds no GEMM epilogue"""
+    _req(dy, "act_bwd_mul: dy")
+    _req(pre, "act_bwd_mul: pre")
+    if dy.shape != pre.shape or dy.numel() == 0:
+        raise ValueError(f"act_bwd_mul: dy and pre must have one non-empty shape, got {tuple(dy.shape)} and {tuple(pre.shape)}")
+    out = torch.empty_like(dy)
+    check(_lib.load().dpot_fno_dact(dy.data_ptr(), pre.data_ptr(), out.data_ptr(), dy.numel(), int(act), _stream()), "fno_dact")
+    return out

@@ -981,6 +981,39 @@ int dpot_aa_up_fwd(const float* z, const float* bias, float* y, const int32_t* v
 int dpot_aa_up_adj(const float* dy, float* g, const int32_t* vtab, int N, int h, int w, int H, int W, int C,
                    dpot_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The FNO baseline (csrc/fno.hip; the reference's models/fno.py SpectralConv2d_fast) on channels-last fields x[B, H, W, C]:
+ *   y = act( irfft2( W . rfft2(x) on the kept modes ) + add )
+ * Kept modes: rows kx in [0, m1) and [H - m1, H), columns ky in [0, m2); 2 m1 <= H and m2 <= W/2 + 1 (else DPOT_EINVAL).
+ * Kept spectrum S[B][2 m1][m2][2 = re | im][C]: kept row r is kx = r below m1 and kx = H - 2 m1 + r above.
+ * tx[H][2 m1][2], ty[W][m2][2]: cos | sin of 2 pi kx(r) x / H and of 2 pi ky y / W, device arrays (dpot_amd/ops.py FNOPlan
+ * builds them in float64).  w(ky) = 1 at ky = 0 and, for even W, at ky = W/2, else 2.
+ *   dpot_fno_rfft2   S = scale * (col_weights ? w(ky) : 1) * sum_{x,y} x[x, y] e^{-2 pi i (kx x / H + ky y / W)}
+ *   dpot_fno_irfft2  y = act( scale * Re sum_{r,ky} (col_weights ? w(ky) : 1) S e^{+2 pi i (...)} + add ); add (the 1x1
+ *                    convolution branch, bias included) and pre (the value before the activation) may be NULL.
+ *                    irfft2 of the reference: col_weights = 1, scale = 1 / (H W).  With col_weights = 0, scale = 1, no add
+ *                    and act = 0 each transform is the adjoint of the other.
+ *   dpot_fno_mix     O[b, r, ky, o] = sum_i X[b, r, ky, i] W[i, o, r mod m1, ky], W = w[0] + i w[1] with w = w1 for r < m1 and
+ *                    w2 above, each the parameter [2][Cin][Cout][m1][m2] read in place.  X has Cin channels, O Cout.
+ *                    adjoint = 1: O[b, ., i] = sum_o X[b, ., o] conj(W[i, o]) (X has Cout channels, O Cin): the data gradient.
+ *   dpot_fno_mix_wgrad  dw[0] + i dw[1] = sum_b conj(X[b, ., i]) dO[b, ., o], b ascending, in the parameter's layout;
+ *                    accumulate = 1 adds to dw1 / dw2 (a further step of an auto-regressive rollout).
+ *   dpot_fno_dact    dpre[j] = dy[j] * act'(pre[j]), j < n.
+ * Sizes: H, W <= dpot_fno_max_size(0) (= 256), m1, m2 <= dpot_fno_max_size(1) (= 64): the LDS intermediates of a workgroup -
+ * beyond: DPOT_EUNSUP, nothing is launched.  H and W need not be equal, even or powers of two; any C >= 1 (16-byte accesses
+ * when the channel counts are multiples of 4 and the tensors 16-byte aligned).  One launch each; reads nothing outside the
+ * tensors, fixed summation order, no atomics, no allocation, legal under stream capture. */
+int dpot_fno_max_size(int modes);
+int dpot_fno_rfft2(const float* x, float* S, const float* tx, const float* ty, int B, int H, int W, int C, int m1, int m2,
+                   int col_weights, float scale, dpot_stream_t stream);
+int dpot_fno_irfft2(const float* S, const float* add, float* y, float* pre, const float* tx, const float* ty, int B, int H,
+                    int W, int C, int m1, int m2, int col_weights, float scale, int act, dpot_stream_t stream);
+int dpot_fno_mix(const float* X, const float* w1, const float* w2, float* O, int B, int Cin, int Cout, int m1, int m2,
+                 int adjoint, dpot_stream_t stream);
+int dpot_fno_mix_wgrad(const float* X, const float* dO, float* dw1, float* dw2, int B, int Cin, int Cout, int m1, int m2,
+                       int accumulate, dpot_stream_t stream);
+int dpot_fno_dact(const float* dy, const float* pre, float* dpre, int64_t n, int act, dpot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
