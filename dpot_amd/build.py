@@ -2,6 +2,7 @@
 C-ABI shared object (include/dpot_hip.h) loaded through ctypes."""
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -37,7 +38,7 @@ def _stale(target: str, deps) -> bool:
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = _hipcc()
     os.makedirs(LIBDIR, exist_ok=True)
-    hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "dft_fast.h"), os.path.join(CSRC, "gemm_split.h"), os.path.join(CSRC, "gemm_epi.h"), os.path.join(CSRC, "gemm_bf16p_common.h"), os.path.join(CSRC, "evalmetrics_common.h"), os.path.join(os.path.dirname(HERE), "include", "dpot_hip.h")]
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(os.path.dirname(HERE), "include", "dpot_hip.h")]
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -30,7 +30,6 @@ constexpr int AA_MAX = 64;                // latent size per axis
 constexpr int AA_OUT_MAX = 1024;          // output size per axis
 constexpr int AA_THREADS = 256;
 constexpr int AA_LDS_BUDGET = 64 * 1024;  // planes of a workgroup, where a narrower channel chunk can meet it
-constexpr int AA_LDS_MAX = 160 * 1024;
 
 // word offsets of one axis' tables inside the core table block (32 n words per axis; axis h first, then axis w)
 struct AaAxis {
@@ -318,15 +317,6 @@ static int aa_check_core(const char* what, int N, int h, int w, int C) {
   return DPOT_OK;
 }
 
-template <typename K>
-static int aa_raise_lds(K kernel, size_t lds, const char* what) {
-  if (lds <= 64 * 1024) return DPOT_OK;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           AA_LDS_MAX);
-  DPOT_REQUIRE(e == hipSuccess, "%s: cannot raise the dynamic LDS limit to 160 KiB (%s)", what, hipGetErrorString(e));
-  return DPOT_OK;
-}
-
 }  // namespace dpot
 
 using namespace dpot;
@@ -338,8 +328,7 @@ extern "C" int64_t dpot_aa_vtab_words(int h, int w, int H, int W) { return 8 * (
 extern "C" int dpot_aa_lrelu_fwd(const float* x, const float* bias, float* out, const int32_t* tab, int N, int h, int w, int C, int Cb,
                                  float slope, dpot_stream_t stream) {
   DPOT_REQUIRE(x && out && tab && x != out, "aa_lrelu_fwd: null or aliased pointer");
-  int rc = aa_check_core("aa_lrelu_fwd", N, h, w, C);
-  if (rc) return rc;
+  if (int rc = aa_check_core("aa_lrelu_fwd", N, h, w, C)) return rc;
   DPOT_REQUIRE(!bias || (Cb > 0 && C % Cb == 0), "aa_lrelu_fwd: the bias length %d does not divide C = %d", Cb, C);
   AaCoreArgs a{};
   a.x = x, a.bias = bias, a.out = out, a.tab = tab;
@@ -351,10 +340,10 @@ extern "C" int dpot_aa_lrelu_fwd(const float* x, const float* bias, float* out, 
   const bool vec = C % 4 == 0 && aligned16(x) && aligned16(out);
   const dim3 grid((unsigned)(N * a.nchunk)), block(AA_THREADS);
   if (vec) {
-    if ((rc = aa_raise_lds(aa_core_fwd_kernel<true>, lds, "aa_lrelu_fwd"))) return rc;
+    if (int rc = raise_dynamic_lds<aa_core_fwd_kernel<true>>("aa_lrelu_fwd")) return rc;
     hipLaunchKernelGGL(aa_core_fwd_kernel<true>, grid, block, lds, as_stream(stream), a);
   } else {
-    if ((rc = aa_raise_lds(aa_core_fwd_kernel<false>, lds, "aa_lrelu_fwd"))) return rc;
+    if (int rc = raise_dynamic_lds<aa_core_fwd_kernel<false>>("aa_lrelu_fwd")) return rc;
     hipLaunchKernelGGL(aa_core_fwd_kernel<false>, grid, block, lds, as_stream(stream), a);
   }
   return check_launch("aa_core_fwd_kernel");
@@ -363,8 +352,7 @@ extern "C" int dpot_aa_lrelu_fwd(const float* x, const float* bias, float* out, 
 extern "C" int dpot_aa_lrelu_bwd(const float* x, const float* g, float* dx, float* part, const int* tab, int N, int h, int w,
                                  int C, float slope, dpot_stream_t stream) {
   DPOT_REQUIRE(x && g && dx && part && tab && dx != x && dx != g, "aa_lrelu_bwd: null or aliased pointer");
-  int rc = aa_check_core("aa_lrelu_bwd", N, h, w, C);
-  if (rc) return rc;
+  if (int rc = aa_check_core("aa_lrelu_bwd", N, h, w, C)) return rc;
   AaCoreArgs a{};
   a.x = x, a.g = g, a.out = dx, a.part = part, a.tab = tab;
   a.N = N, a.h = h, a.w = w, a.C = C, a.Cb = 1, a.slope = slope;
@@ -375,10 +363,10 @@ extern "C" int dpot_aa_lrelu_bwd(const float* x, const float* g, float* dx, floa
   const bool vec = C % 4 == 0 && aligned16(x) && aligned16(g) && aligned16(dx);
   const dim3 grid((unsigned)(N * a.nchunk)), block(AA_THREADS);
   if (vec) {
-    if ((rc = aa_raise_lds(aa_core_bwd_kernel<true>, lds, "aa_lrelu_bwd"))) return rc;
+    if (int rc = raise_dynamic_lds<aa_core_bwd_kernel<true>>("aa_lrelu_bwd")) return rc;
     hipLaunchKernelGGL(aa_core_bwd_kernel<true>, grid, block, lds, as_stream(stream), a);
   } else {
-    if ((rc = aa_raise_lds(aa_core_bwd_kernel<false>, lds, "aa_lrelu_bwd"))) return rc;
+    if (int rc = raise_dynamic_lds<aa_core_bwd_kernel<false>>("aa_lrelu_bwd")) return rc;
     hipLaunchKernelGGL(aa_core_bwd_kernel<false>, grid, block, lds, as_stream(stream), a);
   }
   return check_launch("aa_core_bwd_kernel");

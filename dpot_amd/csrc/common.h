@@ -7,6 +7,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
+
 #include "../../include/dpot_hip.h"
 
 namespace dpot {
@@ -30,6 +32,32 @@ static inline hipStream_t as_stream(dpot_stream_t s) { return reinterpret_cast<h
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- LDS -------------------------------------------------------------------------------------------
+constexpr int LDS_BYTES = 160 * 1024;           // what a workgroup may declare on gfx950 (160 KiB per CU)
+constexpr int LDS_DEFAULT_CAP = 64 * 1024;      // a dynamic allocation up to this needs no raise
+constexpr int LDS_GENERIC_BUDGET = 150 * 1024;  // the generic transforms (dft.hip, dft3.hip) size their slabs to this: headroom
+constexpr int LDS_RAISE_DEVICES = 64;           // devices that remember a raise; beyond them it is repeated on every call
+
+// THE way a launcher lifts a kernel's dynamic-LDS cap above LDS_DEFAULT_CAP: once per kernel and device (the attribute belongs
+// to the device's copy of the function, so a process-wide flag would leave a second device without it), checked, and before the
+// launch - `if (int rc = raise_dynamic_lds<kernel>("who")) return rc;`.  The kernel is a template ARGUMENT, so that each one
+// owns a flag table: kernels of one signature (the <true> / <false> forms of a template) share their pointer type.  The flag is
+// set only after the runtime accepted the raise; two host threads racing both set the attribute, which is harmless.  Once warm
+// the call is one hipGetDevice, nothing else - nothing for a graph capture to see.  `cap` is LDS_BYTES less the kernel's static
+// __shared__ bytes where it has any (DESIGN.md lists them); occupancy follows the bytes given at launch, not the cap.
+template <auto Kernel>
+int raise_dynamic_lds(const char* what, int cap = LDS_BYTES) {
+  static std::atomic<bool> raised[LDS_RAISE_DEVICES];
+  int dev = 0;
+  DPOT_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0, "%s: no current device", what);
+  const bool known = dev < LDS_RAISE_DEVICES;
+  if (known && raised[dev].load(std::memory_order_relaxed)) return DPOT_OK;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+  DPOT_REQUIRE(e == hipSuccess, "%s: cannot raise the dynamic LDS limit to %d bytes (%s)", what, cap, hipGetErrorString(e));
+  if (known) raised[dev].store(true, std::memory_order_relaxed);
+  return DPOT_OK;
+}
 
 // ---- activations (models/dpot.py:19) ---------------------------------------------------------------
 // Exact-erf GELU is the DPOT default and sits in every GEMM epilogue and in the fused tail; libm's erff costs ~150

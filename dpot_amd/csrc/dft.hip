@@ -9,24 +9,10 @@
 //
 // Works for any h, w (no power-of-two requirement: img_size/patch_size is arbitrary in the reference).
 #include "common.h"
+#include "dft_common.h"
 #include "dft_fast.h"
 
 namespace dpot {
-
-__device__ __forceinline__ void make_twiddles(float* c, float* s, int n) {
-  for (int t = threadIdx.x; t < n; t += blockDim.x) {
-    const double a = (double)(2 * t) / (double)n;  // angle / pi
-    c[t] = (float)cospi(a);
-    s[t] = (float)sinpi(a);
-  }
-}
-
-__device__ __forceinline__ float col_weight(int colw, int ky, int w) {
-  if (!colw) return 1.f;
-  if (ky == 0) return 1.f;
-  if ((w & 1) == 0 && ky == (w >> 1)) return 1.f;
-  return 2.f;
-}
 
 // x[B,h,w,E] -> spec[B,mx,my,nb,2,bs]
 __global__ __launch_bounds__(256) void rfft2_kernel(const float* __restrict__ x, float* __restrict__ spec, int h,
@@ -86,7 +72,7 @@ __global__ __launch_bounds__(256) void rfft2_kernel(const float* __restrict__ x,
       ti += kx;
       if (ti >= h) ti -= h;
     }
-    const float wgt = scale * col_weight(colw, ky, w);
+    const float wgt = scale * hermitian_weight(colw, ky, w);
     const long long o = ((((long long)b * mx + kx) * my + ky) * nb + blk) * 2 * bs + ci;
     spec[o] = re * wgt;
     spec[o + bs] = im * wgt;
@@ -137,7 +123,7 @@ __global__ __launch_bounds__(256) void irfft2_kernel(const float* __restrict__ s
       ti += xr;
       if (ti >= h) ti -= h;
     }
-    const float wgt = col_weight(colw, ky, w);
+    const float wgt = hermitian_weight(colw, ky, w);
     U[(item * 2 + 0) * CC + c] = ur * wgt;
     U[(item * 2 + 1) * CC + c] = ui * wgt;
   }
@@ -163,20 +149,11 @@ __global__ __launch_bounds__(256) void irfft2_kernel(const float* __restrict__ s
   }
 }
 
-static int pick_cc(int E, long long floats_per_channel, int tw_floats) {
-  const long long budget = 150 * 1024 / 4;  // floats; LDS is 160 KiB per CU, keep headroom
-  for (int cc = 64; cc >= 1; cc >>= 1) {
-    if (E % cc) continue;
-    if (floats_per_channel * cc + tw_floats <= budget) return cc;
-  }
-  return 0;
-}
-
 // channel chunk of the generic kernels: what one channel keeps in LDS, 0 when not even one channel fits
 static int dft2_generic_cc(int h, int w, int E, int mx, int my, int inverse) {
   const int tw = ((2 * w + 2 * h + 3) & ~3);
   const long long per_channel = inverse ? (long long)mx * my * 2 + (long long)h * my * 2 : (long long)h * w + (long long)h * my * 2;
-  return pick_cc(E, per_channel, tw);
+  return lds_slab_cc(E, per_channel, tw);
 }
 
 // THE kernel selection of dpot_rfft2 / dpot_irfft2 (norm = 1: their GroupNorm-on-load forms): H * 1000 + CC for a register
@@ -286,8 +263,7 @@ extern "C" int dpot_dft2_kernel_kinds(int inverse, int* out, int cap) {
 
 extern "C" int dpot_rfft2(const float* x, float* spec, int B, int h, int w, int E, int nb, int mx, int my,
                           int col_weights, dpot_stream_t stream) {
-  int rc = check_dft_args("rfft2", B, h, w, E, nb, mx, my);
-  if (rc) return rc;
+  if (int rc = check_dft_args("rfft2", B, h, w, E, nb, mx, my)) return rc;
   DPOT_REQUIRE(x && spec, "rfft2: null pointer");
   const float scale = (float)(1.0 / sqrt((double)h * (double)w));
   const int kind = dft2_select(B, h, w, E, nb, mx, my, 0, 0);
@@ -301,8 +277,7 @@ extern "C" int dpot_rfft2(const float* x, float* spec, int B, int h, int w, int 
   const int tw = ((2 * w + 2 * h + 3) & ~3);
   const int CC = dft2_generic_cc(h, w, E, mx, my, 0);
   const size_t lds = sizeof(float) * (tw + (size_t)CC * ((size_t)h * w + (size_t)h * my * 2));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rfft2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                      (int)lds);
+  if (int rc = raise_dynamic_lds<rfft2_kernel>("rfft2")) return rc;
   hipLaunchKernelGGL(rfft2_kernel, dim3(E / CC, B), dim3(256), lds, as_stream(stream), x, spec, h, w, E, nb, mx, my,
                      CC, col_weights, scale);
   return check_launch("rfft2_kernel");
@@ -335,8 +310,7 @@ extern "C" int dpot_rfft2_norm(const float* x, const float* mean, const float* r
 
 extern "C" int dpot_irfft2(const float* spec, const float* res, float* y, int B, int h, int w, int E, int nb, int mx,
                            int my, int col_weights, dpot_stream_t stream) {
-  int rc = check_dft_args("irfft2", B, h, w, E, nb, mx, my);
-  if (rc) return rc;
+  if (int rc = check_dft_args("irfft2", B, h, w, E, nb, mx, my)) return rc;
   DPOT_REQUIRE(spec && y, "irfft2: null pointer");
   const float scale = (float)(1.0 / sqrt((double)h * (double)w));
   const int kind = dft2_select(B, h, w, E, nb, mx, my, 1, 0);
@@ -350,8 +324,7 @@ extern "C" int dpot_irfft2(const float* spec, const float* res, float* y, int B,
   const int tw = ((2 * w + 2 * h + 3) & ~3);
   const int CC = dft2_generic_cc(h, w, E, mx, my, 1);
   const size_t lds = sizeof(float) * (tw + (size_t)CC * ((size_t)mx * my * 2 + (size_t)h * my * 2));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(irfft2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                      (int)lds);
+  if (int rc = raise_dynamic_lds<irfft2_kernel>("irfft2")) return rc;
   hipLaunchKernelGGL(irfft2_kernel, dim3(E / CC, B), dim3(256), lds, as_stream(stream), spec, res, y, h, w, E, nb,
                      mx, my, CC, col_weights, scale);
   return check_launch("irfft2_kernel");

@@ -18,23 +18,9 @@
 // LDS layout: channel innermost ([point][re|im][CC]); a wave's lanes are CC channels x 64/CC neighbouring items, the items
 // ordered kz (z) fastest, so the complex passes read consecutive words and the real pass a broadcast.
 #include "common.h"
+#include "dft_common.h"
 
 namespace dpot {
-
-__device__ __forceinline__ void make_twiddles3(float* c, float* s, int n) {
-  for (int t = threadIdx.x; t < n; t += blockDim.x) {
-    const double a = (double)(2 * t) / (double)n;  // angle / pi
-    c[t] = (float)cospi(a);
-    s[t] = (float)sinpi(a);
-  }
-}
-
-__device__ __forceinline__ float z_weight(int colw, int kz, int Z) {
-  if (!colw) return 1.f;
-  if (kz == 0) return 1.f;
-  if ((Z & 1) == 0 && kz == (Z >> 1)) return 1.f;
-  return 2.f;
-}
 
 struct Dft3Tw {
   float *cx, *sx, *cy, *sy, *cz, *sz;
@@ -48,9 +34,9 @@ __device__ __forceinline__ Dft3Tw twiddles3(float* sm, int X, int Y, int Z) {
   t.sy = t.cy + Y;
   t.cz = t.sy + Y;
   t.sz = t.cz + Z;
-  make_twiddles3(t.cx, t.sx, X);
-  make_twiddles3(t.cy, t.sy, Y);
-  make_twiddles3(t.cz, t.sz, Z);
+  make_twiddles(t.cx, t.sx, X);
+  make_twiddles(t.cy, t.sy, Y);
+  make_twiddles(t.cz, t.sz, Z);
   return t;
 }
 
@@ -129,7 +115,7 @@ __global__ __launch_bounds__(256) void rfft3_kernel(const float* __restrict__ x,
       ti += kx;
       if (ti >= X) ti -= X;
     }
-    const float wgt = scale * z_weight(colw, kz, Z);
+    const float wgt = scale * hermitian_weight(colw, kz, Z);
     const long long o = (((long long)b * mx * plane + item) * nb + blk) * 2 * bs + ci;
     spec[o] = re * wgt;
     spec[o + bs] = im * wgt;
@@ -197,7 +183,7 @@ __global__ __launch_bounds__(256) void irfft3_kernel(const float* __restrict__ s
       ti += yy;
       if (ti >= Y) ti -= Y;
     }
-    const float wgt = z_weight(colw, kz, Z);
+    const float wgt = hermitian_weight(colw, kz, Z);
     V[(item * 2 + 0) * CC + c] = vr * wgt;
     V[(item * 2 + 1) * CC + c] = vi * wgt;
   }
@@ -230,8 +216,6 @@ using namespace dpot;
 
 namespace {
 
-constexpr long long kLdsBudgetFloats = 150 * 1024 / 4;  // LDS is 160 KiB per CU, keep headroom (as dft.hip)
-
 long long imax(long long a, long long b) { return a > b ? a : b; }
 int host_tw_floats(int X, int Y, int Z) { return (2 * (X + Y + Z) + 3) & ~3; }
 // floats per channel of the two slab regions: forward {R0, R1}, inverse {R0, R1}
@@ -240,17 +224,10 @@ long long fwd_r1(int X, int Y, int mz) { return (long long)X * Y * mz * 2; }
 long long inv_r0(int X, int Y, int mz) { return (long long)X * Y * mz * 2; }   // >= mx*my*mz*2: mx <= X, my <= Y
 long long inv_r1(int X, int my, int mz) { return (long long)X * my * mz * 2; }
 
-// the largest power-of-two slab width dividing E that fits the budget (0: none)
-int fit_cc(int E, long long floats_per_channel, int tw) {
-  for (int cc = 64; cc >= 1; cc >>= 1) {
-    if (E % cc) continue;
-    if (floats_per_channel * cc + tw <= kLdsBudgetFloats) return cc;
-  }
-  return 0;
-}
-// narrower slabs, down to 16 channels (64-byte runs of the global accesses), while the launch would not fill the chip
+// the widest slab that fits (lds_slab_cc), then narrower ones, down to 16 channels (64-byte runs of the global accesses),
+// while the launch would not fill the chip
 int pick_cc(int E, int B, long long floats_per_channel, int tw) {
-  int cc = fit_cc(E, floats_per_channel, tw);
+  int cc = lds_slab_cc(E, floats_per_channel, tw);
   while (cc > 16 && (long long)(E / cc) * B < 256) cc >>= 1;
   return cc;
 }
@@ -274,14 +251,13 @@ int check_dft3_args(const char* who, int B, int X, int Y, int Z, int E, int nb, 
 extern "C" int dpot_dft3_supported(int X, int Y, int Z, int E, int mx, int my, int mz) {
   if (!shape_ok(X, Y, Z, E, mx, my, mz)) return 0;
   const int tw = host_tw_floats(X, Y, Z);
-  return fit_cc(E, fwd_r0(X, Y, Z, my, mz) + fwd_r1(X, Y, mz), tw) > 0 &&
-         fit_cc(E, inv_r0(X, Y, mz) + inv_r1(X, my, mz), tw) > 0;
+  return lds_slab_cc(E, fwd_r0(X, Y, Z, my, mz) + fwd_r1(X, Y, mz), tw) > 0 &&
+         lds_slab_cc(E, inv_r0(X, Y, mz) + inv_r1(X, my, mz), tw) > 0;
 }
 
 extern "C" int dpot_rfft3(const float* x, float* spec, int B, int X, int Y, int Z, int E, int nb, int mx, int my, int mz,
                           int col_weights, dpot_stream_t stream) {
-  int rc = check_dft3_args("rfft3", B, X, Y, Z, E, nb, mx, my, mz);
-  if (rc) return rc;
+  if (int rc = check_dft3_args("rfft3", B, X, Y, Z, E, nb, mx, my, mz)) return rc;
   if (!dpot_dft3_supported(X, Y, Z, E, mx, my, mz)) {
     set_error("rfft3: latent grid %dx%dx%d (kept %dx%dx%d) does not fit LDS", X, Y, Z, mx, my, mz);
     return DPOT_EUNSUP;
@@ -291,8 +267,7 @@ extern "C" int dpot_rfft3(const float* x, float* spec, int B, int X, int Y, int 
   const long long r0 = fwd_r0(X, Y, Z, my, mz), r1 = fwd_r1(X, Y, mz);
   const int CC = pick_cc(E, B, r0 + r1, tw);
   const size_t lds = sizeof(float) * ((size_t)tw + (size_t)CC * (size_t)(r0 + r1));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rfft3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
+  if (int rc = raise_dynamic_lds<rfft3_kernel>("rfft3")) return rc;
   const float scale = (float)(1.0 / sqrt((double)X * (double)Y * (double)Z));
   hipLaunchKernelGGL(rfft3_kernel, dim3(E / CC, B), dim3(256), lds, as_stream(stream), x, spec, X, Y, Z, E, nb, mx, my,
                      mz, CC, (int)r0, col_weights, scale);
@@ -301,8 +276,7 @@ extern "C" int dpot_rfft3(const float* x, float* spec, int B, int X, int Y, int 
 
 extern "C" int dpot_irfft3(const float* spec, const float* res, float* y, int B, int X, int Y, int Z, int E, int nb,
                            int mx, int my, int mz, int col_weights, dpot_stream_t stream) {
-  int rc = check_dft3_args("irfft3", B, X, Y, Z, E, nb, mx, my, mz);
-  if (rc) return rc;
+  if (int rc = check_dft3_args("irfft3", B, X, Y, Z, E, nb, mx, my, mz)) return rc;
   if (!dpot_dft3_supported(X, Y, Z, E, mx, my, mz)) {
     set_error("irfft3: latent grid %dx%dx%d (kept %dx%dx%d) does not fit LDS", X, Y, Z, mx, my, mz);
     return DPOT_EUNSUP;
@@ -312,8 +286,7 @@ extern "C" int dpot_irfft3(const float* spec, const float* res, float* y, int B,
   const long long r0 = inv_r0(X, Y, mz), r1 = inv_r1(X, my, mz);
   const int CC = pick_cc(E, B, r0 + r1, tw);
   const size_t lds = sizeof(float) * ((size_t)tw + (size_t)CC * (size_t)(r0 + r1));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(irfft3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
+  if (int rc = raise_dynamic_lds<irfft3_kernel>("irfft3")) return rc;
   const float scale = (float)(1.0 / sqrt((double)X * (double)Y * (double)Z));
   hipLaunchKernelGGL(irfft3_kernel, dim3(E / CC, B), dim3(256), lds, as_stream(stream), spec, res, y, X, Y, Z, E, nb, mx,
                      my, mz, CC, col_weights, scale);

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dft_common.h"
 
 namespace dpot {
 
@@ -210,11 +211,6 @@ __device__ __forceinline__ void fft_regs(float (&re)[N], float (&im)[N]) {
   }
 }
 
-__device__ __forceinline__ float colw_f(int colw, int ky, int w) {
-  if (!colw || ky == 0 || ((w & 1) == 0 && ky == (w >> 1))) return 1.f;
-  return 2.f;
-}
-
 // Channel chunk of workgroup x: consecutive workgroups go to different XCDs (8 L2 slices); with CC = 16 channels a
 // workgroup touches 64-byte halves of the 128-byte lines of a token, so the chunk sharing a line must sit on the SAME
 // XCD or every L2 fetches the line for half its bytes.  XCD k gets the contiguous chunks [k*n/8, (k+1)*n/8).
@@ -284,7 +280,7 @@ __global__ __launch_bounds__(256) void rfft2_fast_kernel(const float* __restrict
     }
     const int chn = c0 + c;
     const int blk = chn / bs, ci = chn % bs;
-    const float wgt = scale * colw_f(colw, ky, W);
+    const float wgt = scale * hermitian_weight(colw, ky, W);
     float* out = spec + (((long long)b * mx * my + ky) * nb + blk) * 2 * bs + ci;
     const long long kxstride = (long long)my * nb * 2 * bs;
     fft_regs<H, -1>(zr, zi);
@@ -325,7 +321,7 @@ __global__ __launch_bounds__(256) void irfft2_fast_kernel(const float* __restric
       sr[kx] = kx < mx ? a : 0.f;
       si[kx] = kx < mx ? bq : 0.f;
     }
-    const float wgt = colw_f(colw, ky, W);
+    const float wgt = hermitian_weight(colw, ky, W);
     fft_regs<H, 1>(sr, si);
     fft_sfor<0, H>([&](auto XR) __attribute__((always_inline)) {
       constexpr int xr = decltype(XR)::value;
@@ -444,7 +440,7 @@ __global__ __launch_bounds__(256) void rfft2_128_kernel(const float* __restrict_
     });
     const int chn = c0 + c;
     const int blk = chn / bs, ci = chn % bs;
-    const float wgt = scale * colw_f(colw, ky, W);
+    const float wgt = scale * hermitian_weight(colw, ky, W);
     float* out = spec + (((long long)b * mx * my + ky) * nb + blk) * 2 * bs + ci;
     const long long kxstride = (long long)my * nb * 2 * bs;
     fft_regs<HN, -1>(zr, zi);
@@ -493,7 +489,7 @@ __global__ __launch_bounds__(256) void irfft2_128_kernel(const float* __restrict
       sr[k] = par ? dr * cw - di * sw : ar + br;
       si[k] = par ? dr * sw + di * cw : ai + bi;
     });
-    const float wgt = colw_f(colw, ky, W);
+    const float wgt = hermitian_weight(colw, ky, W);
     fft_regs<HN, 1>(sr, si);
     fft_sfor<0, HN>([&](auto M) __attribute__((always_inline)) {
       constexpr int m = decltype(M)::value;
@@ -546,8 +542,7 @@ template <int H, int W, int CC>
 static int launch_rfft2_fast(const float* x, float* spec, int B, int E, int nb, int mx, int my, int colw, float scale,
                              hipStream_t s, const DftNorm nrm) {
   constexpr size_t lds = sizeof(float) * ((size_t)(W / 2 + 1) * H * 2 * CC);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rfft2_fast_kernel<H, W, CC>),
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (int rc = raise_dynamic_lds<rfft2_fast_kernel<H, W, CC>>("rfft2_fast")) return rc;
   hipLaunchKernelGGL((rfft2_fast_kernel<H, W, CC>), dim3(E / CC, B), dim3(256), lds, s, x, spec, E, nb, mx, my, colw,
                      scale, nrm);
   return check_launch("rfft2_fast_kernel");
@@ -556,8 +551,7 @@ template <int H, int W, int CC>
 static int launch_irfft2_fast(const float* spec, const float* res, float* y, int B, int E, int nb, int mx, int my,
                               int colw, float scale, hipStream_t s, const DftNorm nrm) {
   constexpr size_t lds = sizeof(float) * ((size_t)(W / 2 + 1) * H * 2 * CC);
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(irfft2_fast_kernel<H, W, CC>),
-                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (int rc = raise_dynamic_lds<irfft2_fast_kernel<H, W, CC>>("irfft2_fast")) return rc;
   hipLaunchKernelGGL((irfft2_fast_kernel<H, W, CC>), dim3(E / CC, B), dim3(256), lds, s, spec, res, y, E, nb, mx, my,
                      colw, scale, nrm);
   return check_launch("irfft2_fast_kernel");
@@ -567,9 +561,7 @@ template <int CC>
 static int launch_rfft2_128(const float* x, float* spec, int B, int E, int nb, int mx, int my, int colw, float scale,
                             hipStream_t s) {
   const size_t lds = sizeof(float) * ((size_t)my * 128 * 2 * CC);
-  const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(rfft2_128_kernel<CC>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  DPOT_REQUIRE(ae == hipSuccess, "rfft2_128: cannot raise the dynamic LDS limit to 160 KiB (%s)", hipGetErrorString(ae));
+  if (int rc = raise_dynamic_lds<rfft2_128_kernel<CC>>("rfft2_128")) return rc;
   hipLaunchKernelGGL((rfft2_128_kernel<CC>), dim3(E / CC, B), dim3(256), lds, s, x, spec, E, nb, mx, my, colw, scale);
   return check_launch("rfft2_128_kernel");
 }
@@ -577,9 +569,7 @@ template <int CC>
 static int launch_irfft2_128(const float* spec, const float* res, float* y, int B, int E, int nb, int mx, int my, int colw,
                              float scale, hipStream_t s) {
   const size_t lds = sizeof(float) * ((size_t)my * 128 * 2 * CC);
-  const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(irfft2_128_kernel<CC>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  DPOT_REQUIRE(ae == hipSuccess, "irfft2_128: cannot raise the dynamic LDS limit to 160 KiB (%s)", hipGetErrorString(ae));
+  if (int rc = raise_dynamic_lds<irfft2_128_kernel<CC>>("irfft2_128")) return rc;
   hipLaunchKernelGGL((irfft2_128_kernel<CC>), dim3(E / CC, B), dim3(256), lds, s, spec, res, y, E, nb, mx, my, colw,
                      scale);
   return check_launch("irfft2_128_kernel");

@@ -33,9 +33,8 @@ constexpr int EV_PC = EVAL_PC;             // planes per workgroup
 constexpr int EV_ROWS = 2 * EV_IS * EV_PC; // rows (P|Q, i, pc) of the LDS intermediate
 constexpr int EV_NW = EVAL_NW;             // waves
 constexpr int EV_CT = 3;                   // j tiles a wave can hold in registers: ny/2 <= 16 * EV_NW * EV_CT
-constexpr int EV_LDS_MAX = 160 * 1024;
 constexpr int EV_TAIL = EV_NW * EV_PC * 8 * 8;                     // bytes behind the intermediate: the waves' statistics
-constexpr int EV_LD_MAX = (EV_LDS_MAX - EV_TAIL) / 4 / EV_ROWS;    // LDS row length nyp + 4 a workgroup can hold
+constexpr int EV_LD_MAX = (LDS_BYTES - EV_TAIL) / 4 / EV_ROWS;    // LDS row length nyp + 4 a workgroup can hold
 constexpr int EV_NY_MAX = (EV_LD_MAX - 4) / 16 * 16;               // 304
 constexpr int EV_NX_MAX = 1024;
 
@@ -286,15 +285,14 @@ extern "C" int dpot_eval_metrics_stats(const float* pred, const float* target, c
   static_assert(EV_PC * EV_IS * (EV_NY_MAX / 2 + 16 + 1) <= EV_ROWS * (EV_NY_MAX + 4), "|E|^2 must fit over P and Q");
   const size_t lds = sizeof(float) * (size_t)EV_ROWS * (a.nyp + 4) + EV_TAIL;
   const bool vec = TC % 4 == 0 && aligned16(pred) && aligned16(target);
-  const void* fn = vec ? reinterpret_cast<const void*>(eval_stats_kernel<true>)
-                       : reinterpret_cast<const void*>(eval_stats_kernel<false>);
-  const hipError_t ae = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, EV_LDS_MAX);
-  DPOT_REQUIRE(ae == hipSuccess, "eval_metrics_stats: cannot raise the dynamic LDS limit to 160 KiB (%s)", hipGetErrorString(ae));
   const dim3 grid(a.hxp / EV_IS, cdiv(TC, EV_PC), B);
-  if (vec)
+  if (vec) {
+    if (int rc = raise_dynamic_lds<eval_stats_kernel<true>>("eval_metrics_stats")) return rc;
     hipLaunchKernelGGL(eval_stats_kernel<true>, grid, dim3(64 * EV_NW), lds, as_stream(stream), a);
-  else
+  } else {
+    if (int rc = raise_dynamic_lds<eval_stats_kernel<false>>("eval_metrics_stats")) return rc;
     hipLaunchKernelGGL(eval_stats_kernel<false>, grid, dim3(64 * EV_NW), lds, as_stream(stream), a);
+  }
   return check_launch("eval_stats_kernel");
 }
 

@@ -44,7 +44,6 @@ constexpr int E3_IS = 16;                  // wavenumbers i per workgroup of the
 constexpr int E3_KC = 2;                   // wavenumbers k per workgroup of the xy pass
 constexpr int E3_ROWS = 2 * E3_IS * E3_KC; // rows (Re|Im, i, k) of the LDS intermediate
 constexpr int E3_CT = 4;                   // j tiles a wave can hold in registers: ny/2 <= 16 * E3_NW * E3_CT
-constexpr int E3_LDS_MAX = 160 * 1024;
 constexpr int E3_NY_MAX = 512;             // (E3_NY_MAX + 4) * E3_ROWS floats = 129 KiB of LDS
 constexpr int E3_NX_MAX = 512;
 constexpr int E3_NZ_MAX = 512;
@@ -421,12 +420,10 @@ extern "C" int dpot_eval3_stats(const float* pred, const float* target, const fl
                "eval3_stats: B=%d with T*C=%d planes is beyond the launch grid (B * T*C <= 65535)", B, TC);
   static_assert(E3_NY_MAX / 2 <= 16 * E3_NW * E3_CT, "a wave cannot hold its j tiles");
   static_assert(E3_KC * E3_IS * (E3_NY_MAX / 2 + 16 + 1) <= E3_ROWS * (E3_NY_MAX + 4), "|E|^2 must fit over U");
-  static_assert(sizeof(float) * E3_ROWS * (E3_NY_MAX + 4) <= E3_LDS_MAX, "the LDS intermediate of the largest ny");
+  static_assert(sizeof(float) * E3_ROWS * (E3_NY_MAX + 4) <= LDS_BYTES, "the LDS intermediate of the largest ny");
   const size_t lds = sizeof(float) * (size_t)E3_ROWS * (g.nyp + 4);
-  DPOT_REQUIRE(lds <= (size_t)E3_LDS_MAX, "eval3_stats: ny=%d needs %zu bytes of LDS, a workgroup has %d", ny, lds, E3_LDS_MAX);
-  const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(eval3_xy_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, E3_LDS_MAX);
-  DPOT_REQUIRE(ae == hipSuccess, "eval3_stats: cannot raise the dynamic LDS limit to 160 KiB (%s)", hipGetErrorString(ae));
+  DPOT_REQUIRE(lds <= (size_t)LDS_BYTES, "eval3_stats: ny=%d needs %zu bytes of LDS, a workgroup has %d", ny, lds, LDS_BYTES);
+  if (int rc = raise_dynamic_lds<eval3_xy_kernel>("eval3_stats")) return rc;
 
   Eval3ZArgs z;
   z.pred = pred, z.target = target, z.czT = czT, z.szT = szT, z.G = G, z.statp = statp;

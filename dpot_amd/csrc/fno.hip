@@ -30,6 +30,7 @@
 // Nothing outside the tensors is read: every load past H, W, C, m2 or B is predicated to 0.0f (table indices are clamped into
 // the table), stores are masked.  Fixed summation order (one fma chain per output), no atomics, no allocation.
 #include "common.h"
+#include "dft_common.h"
 
 namespace dpot {
 
@@ -42,7 +43,6 @@ constexpr int FNO_KYC = 4;            // rfft2: columns ky per workgroup
 constexpr int FNO_XS = 16;            // irfft2: rows x per workgroup
 constexpr int FNO_NT = 256;           // threads of irfft2
 constexpr int FNO_NTF = 512;          // threads of rfft2: one sweep of the (row, channel quad) items of a 128-row field
-constexpr int FNO_LDS_MAX = 160 * 1024;
 
 struct FnoArgs {
   const float* x;      // field in (rfft2)
@@ -90,10 +90,6 @@ __device__ __forceinline__ bool fno_xcd_item(int id, int n_groups, int n_members
   return g < n_groups;
 }
 static inline int64_t fno_xcd_grid(int n_groups, int n_members) { return (int64_t)cdiv(n_groups, 8) * 8 * n_members; }
-
-__device__ __forceinline__ float fno_colw(int colw, int ky, int W) {
-  return (!colw || ky == 0 || ((W & 1) == 0 && ky == W / 2)) ? 1.f : 2.f;
-}
 
 // ---- field -> kept spectrum ----------------------------------------------------------------------------------------------
 template <bool VEC>
@@ -165,7 +161,7 @@ __global__ __launch_bounds__(FNO_NTF) void fno_rfft2_kernel(const FnoArgs a) {
       im1 += ti * cb;
       im1 -= tr * sb;
     }
-    const float w = a.scale * fno_colw(a.colw, ky, a.W);
+    const float w = a.scale * hermitian_weight(a.colw, ky, a.W);
     float* d0 = a.S + ((((size_t)b * R + r) * a.m2 + ky) * 2) * a.C + c;
     float* d1 = a.S + ((((size_t)b * R + r + a.m1) * a.m2 + ky) * 2) * a.C + c;
     fno_st4<VEC>(d0, re0 * w, nc);
@@ -211,7 +207,7 @@ __global__ __launch_bounds__(FNO_NT) void fno_irfft2_kernel(const FnoArgs a) {
         bi += si * cb;
       }
     }
-    const float w = a.scale * fno_colw(a.colw, ky, a.W);
+    const float w = a.scale * hermitian_weight(a.colw, ky, a.W);
     float* d = fno_lds + xp * LDX + ky * 2 * FNO_CC + 4 * q;
     *reinterpret_cast<f32x4*>(d) = ar * w;
     *reinterpret_cast<f32x4*>(d + FNO_CC) = ai * w;
@@ -397,19 +393,6 @@ static int fno_check_sizes(const char* what, int B, int H, int W, int C, int m1,
   return DPOT_OK;
 }
 
-// once per kernel and device (the attribute belongs to the device's copy of the function)
-template <typename Kern>
-static int fno_raise_lds(Kern k, const char* what) {
-  static bool raised[64] = {};
-  int dev = 0;
-  DPOT_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0, "%s: no current device", what);
-  if (dev < 64 && raised[dev]) return DPOT_OK;
-  const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, FNO_LDS_MAX);
-  DPOT_REQUIRE(ae == hipSuccess, "%s: cannot raise the dynamic LDS limit to 160 KiB (%s)", what, hipGetErrorString(ae));
-  if (dev < 64) raised[dev] = true;
-  return DPOT_OK;
-}
-
 }  // namespace dpot
 
 using namespace dpot;
@@ -419,8 +402,7 @@ extern "C" int dpot_fno_max_size(int modes) { return modes ? FNO_MAX_MODES : FNO
 extern "C" int dpot_fno_rfft2(const float* x, float* S, const float* tx, const float* ty, int B, int H, int W, int C, int m1,
                               int m2, int col_weights, float scale, dpot_stream_t stream) {
   DPOT_REQUIRE(x && S && x != S && tx && ty, "fno_rfft2: null or aliased pointer");
-  const int rc = fno_check_sizes("fno_rfft2", B, H, W, C, m1, m2);
-  if (rc != DPOT_OK) return rc;
+  if (int rc = fno_check_sizes("fno_rfft2", B, H, W, C, m1, m2)) return rc;
   FnoArgs a = {};
   a.x = x, a.S = S, a.tx = tx, a.ty = ty;
   a.B = B, a.H = H, a.W = W, a.C = C, a.m1 = m1, a.m2 = m2, a.colw = col_weights, a.scale = scale;
@@ -430,10 +412,10 @@ extern "C" int dpot_fno_rfft2(const float* x, float* S, const float* tx, const f
   DPOT_REQUIRE(nwg <= 0x7fffffff, "fno_rfft2: too many workgroups");
   const dim3 grid((unsigned)nwg);
   if (vec) {
-    if (fno_raise_lds(fno_rfft2_kernel<true>, "fno_rfft2") != DPOT_OK) return DPOT_EINVAL;
+    if (int rc = raise_dynamic_lds<fno_rfft2_kernel<true>>("fno_rfft2")) return rc;
     hipLaunchKernelGGL(fno_rfft2_kernel<true>, grid, dim3(FNO_NTF), lds, as_stream(stream), a);
   } else {
-    if (fno_raise_lds(fno_rfft2_kernel<false>, "fno_rfft2") != DPOT_OK) return DPOT_EINVAL;
+    if (int rc = raise_dynamic_lds<fno_rfft2_kernel<false>>("fno_rfft2")) return rc;
     hipLaunchKernelGGL(fno_rfft2_kernel<false>, grid, dim3(FNO_NTF), lds, as_stream(stream), a);
   }
   return check_launch("fno_rfft2_kernel");
@@ -444,8 +426,7 @@ extern "C" int dpot_fno_irfft2(const float* S, const float* add, float* y, float
                                dpot_stream_t stream) {
   DPOT_REQUIRE(S && y && S != y && tx && ty && y != pre, "fno_irfft2: null or aliased pointer");
   DPOT_REQUIRE(act >= DPOT_ACT_NONE && act <= DPOT_ACT_SILU, "fno_irfft2: unknown activation %d", act);
-  const int rc = fno_check_sizes("fno_irfft2", B, H, W, C, m1, m2);
-  if (rc != DPOT_OK) return rc;
+  if (int rc = fno_check_sizes("fno_irfft2", B, H, W, C, m1, m2)) return rc;
   FnoArgs a = {};
   a.S = const_cast<float*>(S), a.add = add, a.y = y, a.pre = pre, a.tx = tx, a.ty = ty;
   a.B = B, a.H = H, a.W = W, a.C = C, a.m1 = m1, a.m2 = m2, a.colw = col_weights, a.scale = scale, a.act = act;
@@ -453,10 +434,10 @@ extern "C" int dpot_fno_irfft2(const float* S, const float* add, float* y, float
   const bool vec = C % 4 == 0 && aligned16(S) && aligned16(y) && aligned16(add) && aligned16(pre);
   const dim3 grid(cdiv(H, FNO_XS), cdiv(C, FNO_CC), B);
   if (vec) {
-    if (fno_raise_lds(fno_irfft2_kernel<true>, "fno_irfft2") != DPOT_OK) return DPOT_EINVAL;
+    if (int rc = raise_dynamic_lds<fno_irfft2_kernel<true>>("fno_irfft2")) return rc;
     hipLaunchKernelGGL(fno_irfft2_kernel<true>, grid, dim3(FNO_NT), lds, as_stream(stream), a);
   } else {
-    if (fno_raise_lds(fno_irfft2_kernel<false>, "fno_irfft2") != DPOT_OK) return DPOT_EINVAL;
+    if (int rc = raise_dynamic_lds<fno_irfft2_kernel<false>>("fno_irfft2")) return rc;
     hipLaunchKernelGGL(fno_irfft2_kernel<false>, grid, dim3(FNO_NT), lds, as_stream(stream), a);
   }
   return check_launch("fno_irfft2_kernel");

@@ -46,7 +46,7 @@ __device__ __forceinline__ void gemm_bf16p_body(const Bf16pArgs& p, const int bi
   constexpr int SLABB = (PB_ROWT + COLT) * 2 * 1024;              // bytes of one 32-k slab
   static_assert(2 * (PB_ROWT + COLT) % PB_NLOAD == 0, "pieces must divide among the loader waves");
   // ring of PB_RING slabs; the epilogue stages through it afterwards (8 waves x 2 x 32 x EPI_LD floats = 72 KiB)
-  static_assert(PB_RING >= 3 && PB_RING * SLABB <= 160 * 1024, "slab ring must fit the 160 KiB LDS");
+  static_assert(PB_RING >= 3 && PB_RING * SLABB <= LDS_BYTES, "slab ring must fit the 160 KiB LDS");
   __shared__ __attribute__((aligned(16))) unsigned char lds[PB_RING * SLABB];
   const int tid = threadIdx.x;
   const int lane = tid & 63;

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(GD_T) void irfft2_gn_kernel(const float* __restrict
   const long long base = (long long)b * GD_H * GD_W * E + g * CG;
   for (int it = tid; it < my * CG; it += GD_T) {
     const int c2 = it % CG, ky = it / CG;
-    col_ifft_store<CG>(spec, U, b, g * CG + c2, c2, ky, nb, bs, mx, my, colw_f(colw, ky, GD_W));
+    col_ifft_store<CG>(spec, U, b, g * CG + c2, c2, ky, nb, bs, mx, my, hermitian_weight(colw, ky, GD_W));
   }
   __syncthreads();
   const int c = tid % CG, xr0 = tid / CG;
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(GD_T) void gn_bwd_rfft2_kernel(const float* __restr
   const int bs = E / nb;
   for (int it = tid; it < my * CG; it += GD_T) {
     const int c2 = it % CG, ky = it / CG;
-    col_fft_out<CG>(Z, spec, b, g * CG + c2, c2, ky, nb, bs, mx, my, scale * colw_f(colw, ky, GD_W), 0.f);
+    col_fft_out<CG>(Z, spec, b, g * CG + c2, c2, ky, nb, bs, mx, my, scale * hermitian_weight(colw, ky, GD_W), 0.f);
   }
 }
 
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(GD_T) void irfft2_gn_bwd_kernel(const float* __rest
   const long long base = (long long)b * GD_H * GD_W * E + g * CG;
   for (int it = tid; it < my * CG; it += GD_T) {
     const int c2 = it % CG, ky = it / CG;
-    col_ifft_store<CG>(spec, U, b, g * CG + c2, c2, ky, nb, bs, mx, my, colw_f(colw, ky, GD_W));
+    col_ifft_store<CG>(spec, U, b, g * CG + c2, c2, ky, nb, bs, mx, my, hermitian_weight(colw, ky, GD_W));
   }
   __syncthreads();
   const int c = tid % CG, xr0 = tid / CG;
@@ -455,10 +455,8 @@ template <int CG>
 static size_t gd_lds() {
   return sizeof(float) * (size_t)GD_WF * GD_H * 2 * CG;
 }
-template <typename K>
-static void gd_attr(K kernel, size_t lds) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-}
+// the dynamic-LDS cap of the four kernels: they also declare a static `shd` of up to 48 doubles
+constexpr int GD_LDS_CAP = LDS_BYTES - 48 * (int)sizeof(double);
 
 }  // namespace dpot
 
@@ -480,16 +478,15 @@ static int gd_check(const char* what, int B, int h, int w, int E, int G, int nb,
 
 extern "C" int dpot_gn_rfft2(const float* x, const float* gamma, const float* beta, float* spec, float* mean, float* rstd,
                              int B, int h, int w, int E, int G, int nb, int mx, int my, float eps, dpot_stream_t stream) {
-  int rc = gd_check("gn_rfft2", B, h, w, E, G, nb, mx, my);
-  if (rc) return rc;
+  if (int rc = gd_check("gn_rfft2", B, h, w, E, G, nb, mx, my)) return rc;
   DPOT_REQUIRE(x && gamma && beta && spec && mean && rstd, "gn_rfft2: null pointer");
   const float scale = 1.0f / 16.0f;                           // ortho: 1 / sqrt(16 * 16)
   if (E / G == 64) {
-    gd_attr(gn_rfft2_kernel<64>, gd_lds<64>());
+    if (int rc = raise_dynamic_lds<gn_rfft2_kernel<64>>("gn_rfft2", GD_LDS_CAP)) return rc;
     hipLaunchKernelGGL(gn_rfft2_kernel<64>, dim3(G, B), dim3(GD_T), gd_lds<64>(), as_stream(stream), x, gamma, beta, spec,
                        mean, rstd, E, G, nb, mx, my, eps, scale);
   } else {
-    gd_attr(gn_rfft2_kernel<128>, gd_lds<128>());
+    if (int rc = raise_dynamic_lds<gn_rfft2_kernel<128>>("gn_rfft2", GD_LDS_CAP)) return rc;
     hipLaunchKernelGGL(gn_rfft2_kernel<128>, dim3(G, B), dim3(GD_T), gd_lds<128>(), as_stream(stream), x, gamma, beta, spec,
                        mean, rstd, E, G, nb, mx, my, eps, scale);
   }
@@ -500,17 +497,16 @@ extern "C" int dpot_irfft2_gn(const float* spec, const float* x, const float* me
                               const float* gamma1, const float* beta1, const float* gamma2, const float* beta2, float* y1,
                               float* xn2, float* mean2, float* rstd2, int B, int h, int w, int E, int G, int nb, int mx,
                               int my, int col_weights, float eps, dpot_stream_t stream) {
-  int rc = gd_check("irfft2_gn", B, h, w, E, G, nb, mx, my);
-  if (rc) return rc;
+  if (int rc = gd_check("irfft2_gn", B, h, w, E, G, nb, mx, my)) return rc;
   DPOT_REQUIRE(spec && x && mean1 && rstd1 && gamma1 && beta1 && gamma2 && beta2 && y1 && mean2 && rstd2,
                "irfft2_gn: null pointer");                  // xn2 may be NULL: statistics only (dpot_bf16_pack_both_norm)
   const float scale = 1.0f / 16.0f;
   if (E / G == 64) {
-    gd_attr(irfft2_gn_kernel<64>, gd_lds<64>());
+    if (int rc = raise_dynamic_lds<irfft2_gn_kernel<64>>("irfft2_gn", GD_LDS_CAP)) return rc;
     hipLaunchKernelGGL(irfft2_gn_kernel<64>, dim3(G, B), dim3(GD_T), gd_lds<64>(), as_stream(stream), spec, x, mean1, rstd1,
                        gamma1, beta1, gamma2, beta2, y1, xn2, mean2, rstd2, E, G, nb, mx, my, col_weights, eps, scale);
   } else {
-    gd_attr(irfft2_gn_kernel<128>, gd_lds<128>());
+    if (int rc = raise_dynamic_lds<irfft2_gn_kernel<128>>("irfft2_gn", GD_LDS_CAP)) return rc;
     hipLaunchKernelGGL(irfft2_gn_kernel<128>, dim3(G, B), dim3(GD_T), gd_lds<128>(), as_stream(stream), spec, x, mean1,
                        rstd1, gamma1, beta1, gamma2, beta2, y1, xn2, mean2, rstd2, E, G, nb, mx, my, col_weights, eps,
                        scale);
@@ -521,16 +517,15 @@ extern "C" int dpot_irfft2_gn(const float* spec, const float* x, const float* me
 extern "C" int dpot_gn_bwd_rfft2(const float* dy, const float* xin, const float* mean, const float* rstd,
                                  const float* gamma, float* dx, float* part, float* spec, int B, int h, int w, int E, int G,
                                  int nb, int mx, int my, int col_weights, dpot_stream_t stream) {
-  int rc = gd_check("gn_bwd_rfft2", B, h, w, E, G, nb, mx, my);
-  if (rc) return rc;
+  if (int rc = gd_check("gn_bwd_rfft2", B, h, w, E, G, nb, mx, my)) return rc;
   DPOT_REQUIRE(dy && xin && mean && rstd && gamma && dx && part && spec, "gn_bwd_rfft2: null pointer");
   const float scale = 1.0f / 16.0f;
   if (E / G == 64) {
-    gd_attr(gn_bwd_rfft2_kernel<64>, gd_lds<64>());
+    if (int rc = raise_dynamic_lds<gn_bwd_rfft2_kernel<64>>("gn_bwd_rfft2", GD_LDS_CAP)) return rc;
     hipLaunchKernelGGL(gn_bwd_rfft2_kernel<64>, dim3(G, B), dim3(GD_T), gd_lds<64>(), as_stream(stream), dy, xin, mean, rstd,
                        gamma, dx, part, spec, B, E, G, nb, mx, my, col_weights, scale);
   } else {
-    gd_attr(gn_bwd_rfft2_kernel<128>, gd_lds<128>());
+    if (int rc = raise_dynamic_lds<gn_bwd_rfft2_kernel<128>>("gn_bwd_rfft2", GD_LDS_CAP)) return rc;
     hipLaunchKernelGGL(gn_bwd_rfft2_kernel<128>, dim3(G, B), dim3(GD_T), gd_lds<128>(), as_stream(stream), dy, xin, mean,
                        rstd, gamma, dx, part, spec, B, E, G, nb, mx, my, col_weights, scale);
   }
@@ -541,16 +536,15 @@ extern "C" int dpot_irfft2_gn_bwd(const float* spec, const float* res, const flo
                                   const float* rstd, const float* gamma, const float* add, float* dx, float* part, int B,
                                   int h, int w, int E, int G, int nb, int mx, int my, int col_weights,
                                   dpot_stream_t stream) {
-  int rc = gd_check("irfft2_gn_bwd", B, h, w, E, G, nb, mx, my);
-  if (rc) return rc;
+  if (int rc = gd_check("irfft2_gn_bwd", B, h, w, E, G, nb, mx, my)) return rc;
   DPOT_REQUIRE(spec && res && xin && mean && rstd && gamma && dx && part, "irfft2_gn_bwd: null pointer");
   const float scale = 1.0f / 16.0f;
   if (E / G == 64) {
-    gd_attr(irfft2_gn_bwd_kernel<64>, gd_lds<64>());
+    if (int rc = raise_dynamic_lds<irfft2_gn_bwd_kernel<64>>("irfft2_gn_bwd", GD_LDS_CAP)) return rc;
     hipLaunchKernelGGL(irfft2_gn_bwd_kernel<64>, dim3(G, B), dim3(GD_T), gd_lds<64>(), as_stream(stream), spec, res, xin,
                        mean, rstd, gamma, add, dx, part, B, E, G, nb, mx, my, col_weights, scale);
   } else {
-    gd_attr(irfft2_gn_bwd_kernel<128>, gd_lds<128>());
+    if (int rc = raise_dynamic_lds<irfft2_gn_bwd_kernel<128>>("irfft2_gn_bwd", GD_LDS_CAP)) return rc;
     hipLaunchKernelGGL(irfft2_gn_bwd_kernel<128>, dim3(G, B), dim3(GD_T), gd_lds<128>(), as_stream(stream), spec, res, xin,
                        mean, rstd, gamma, add, dx, part, B, E, G, nb, mx, my, col_weights, scale);
   }

@@ -597,9 +597,7 @@ extern "C" int dpot_small_linear(const float* x, int ldx, const float* W, int ld
   DPOT_REQUIRE(ldx >= K && ldw >= K && ldy >= N && ldx % 4 == 0 && ldw % 4 == 0 && aligned16(x) && aligned16(W),
                "small_linear: bad leading dimension / alignment");
   const size_t lds = sizeof(float) * SL_ROWS * SL_KCH;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(small_linear_kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  DPOT_REQUIRE(attr == hipSuccess, "small_linear: cannot reserve %zu bytes of LDS", lds);
+  if (int rc = raise_dynamic_lds<small_linear_kernel>("small_linear")) return rc;
   hipLaunchKernelGGL(small_linear_kernel, dim3((unsigned)cdiv(N, SL_WAVES)), dim3(64 * SL_WAVES), lds, as_stream(stream),
                      x, ldx, W, ldw, bias, y, pre, ldy, M, N, K, act);
   return check_launch("small_linear_kernel");

@@ -35,7 +35,6 @@ constexpr int RS_XS = 32;                 // output rows x' per workgroup (two 1
 constexpr int RS_PC = 4;                  // planes per workgroup
 constexpr int RS_ROWS = RS_XS * RS_PC;    // rows (x', pc) of the LDS intermediate
 constexpr int RS_NW = 4;                  // waves
-constexpr int RS_LDS_MAX = 160 * 1024;
 
 struct ResizeArgs {
   const float* in;
@@ -202,12 +201,10 @@ template <bool EVEN, bool VEC>
 static int launch_spectral_resize(const ResizeArgs& a, int B, hipStream_t s) {
   const size_t lds = sizeof(float) * (size_t)(RS_ROWS + (EVEN ? 16 : 0)) * (a.nyp + 4);
   // one limit for both forms (the two-term form's 16 extra rows decide it): a size pair's parity must not change what fits
-  constexpr int ld_max = RS_LDS_MAX / 4 / (RS_ROWS + 16);
+  constexpr int ld_max = LDS_BYTES / 4 / (RS_ROWS + 16);
   DPOT_REQUIRE(a.nyp + 4 <= ld_max, "spectral_resize: ny = %d is beyond the LDS intermediate of a workgroup (ny <= %d)", a.ny,
                (ld_max - 4) / 16 * 16);
-  const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void*>(spectral_resize_kernel<EVEN, VEC>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, RS_LDS_MAX);
-  DPOT_REQUIRE(ae == hipSuccess, "spectral_resize: cannot raise the dynamic LDS limit to 160 KiB (%s)", hipGetErrorString(ae));
+  if (int rc = raise_dynamic_lds<spectral_resize_kernel<EVEN, VEC>>("spectral_resize")) return rc;
   hipLaunchKernelGGL((spectral_resize_kernel<EVEN, VEC>), dim3(a.mxp / RS_XS, cdiv(a.TC, RS_PC), B), dim3(64 * RS_NW), lds, s,
                      a);
   return check_launch("spectral_resize_kernel");

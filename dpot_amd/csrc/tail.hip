@@ -523,9 +523,7 @@ template <bool GELU, bool CO4>
 static int tail_launch_bwd(const float* upre, const float* dout, const float* w2, const float* b2, const float* w4,
                            float* dupre, float* partials, long long ntiles, TailGeom g, int act, hipStream_t s) {
   const size_t lds = tail_lds_bwd(CO4);
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(out_tail_bwd_kernel<GELU, CO4>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  DPOT_REQUIRE(attr == hipSuccess, "out_tail_bwd: cannot reserve %zu bytes of LDS", lds);
+  if (int rc = raise_dynamic_lds<out_tail_bwd_kernel<GELU, CO4>>("out_tail_bwd")) return rc;
   hipLaunchKernelGGL((out_tail_bwd_kernel<GELU, CO4>), dim3(tail_grid_bwd(ntiles, CO4)), dim3(256), lds, s, upre, dout,
                      w2, b2, w4, dupre, partials, ntiles, g, act);
   return check_launch("out_tail_bwd_kernel");

@@ -10,8 +10,10 @@ parameter buffer after one FusedAdam step where the case is a model -, and the l
 case asserts its route where the code offers a way to see it.  Inputs and weights: the recipes of oracle/dpot_ref.py,
 tests/afno3d_ref.py and tests/cdpot_ref.py, as the tests use them."""
 import hashlib
+import itertools
 import os
 import sys
+from collections import OrderedDict
 
 import torch
 
@@ -20,10 +22,15 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 import afno3d_ref as A3  # noqa: E402
 import cdpot_ref as CR  # noqa: E402
-from dpot_amd import CDPOTNet, DPOTNet, DPOTNet3D, _lib, load_3d_components_from_2d, ops  # noqa: E402
+import dft_cases as DC  # noqa: E402
+import eval3d_ref as E3  # noqa: E402
+import eval_ref as E2  # noqa: E402
+import fno_ref as FR  # noqa: E402
+from dpot_amd import CDPOTNet, DPOTNet, DPOTNet3D, FNO2d, RolloutEvaluator, _lib, load_3d_components_from_2d, ops  # noqa: E402
 from dpot_amd.functional import AFNO2DFn, AFNO3DFn, block3d  # noqa: E402
-from dpot_amd.train import FlatParams, FusedAdam, rollout, rollout_total  # noqa: E402
+from dpot_amd.train import FlatParams, FusedAdam, rollout, rollout_total, train_step  # noqa: E402
 from oracle import dpot_ref as R  # noqa: E402
+from resize_ref import hash_field  # noqa: E402
 
 BASE_TUNE = os.environ.get("DPOT_TUNE", "")
 COUNTED = ("block_finalize", "wgrad_batch_finalize", "groupnorm_param_grads", "afno_fused_fwd", "afno_mlp2", "gn_rfft2",
@@ -258,10 +265,63 @@ def step3d(name, cfg, from_2d):
     report(name, loss, grads + [opt.fp.flat], c)
 
 
+def fno_case():
+    """the recorded two-AR-step training step of tests/test_gpu_fno.py (csrc/fno.hip)"""
+    set_tune()
+    st = FR.STEP
+    m = FNO2d(**FR.MINI1)
+    m.load_state_dict(FR.recipe_sd(OrderedDict((k, tuple(v.shape)) for k, v in m.state_dict().items()), st["salt"]), strict=True)
+    m.cuda()
+    xx, yy, msk = (t.cuda() for t in FR.step_inputs())
+    opt = FusedAdam(FlatParams(m), lr=st["lr"], betas=st["betas"], weight_decay=st["weight_decay"], max_norm=st["max_norm"])
+    with Counts() as c:
+        loss, pred = train_step(m, opt, xx, yy, msk, lr=st["lr"])
+    report("fno2d mini step", loss, [pred] + [p.grad for p in m.parameters() if p.grad is not None] + [opt.fp.flat], c)
+
+
+def operator_cases():
+    """the spectral operators no model case reaches, each at the smallest shapes its GPU test uses: the Fourier resize (one even
+    and one odd size pair, scalar and 16-byte loads), the rollout evaluator in 2-D and 3-D, rfft2 / irfft2 once per compiled
+    kernel kind (the smallest case tests/dft_cases.py has for it) and at a 20 x 20 grid of the generic kernels, rfft3 / irfft3"""
+    set_tune()
+    with Counts() as c:
+        for (nx, ny, mx, my), TC in itertools.product([(16, 16, 9, 9), (10, 10, 16, 16)], (1, 4)):
+            x = torch.from_numpy(hash_field((1, nx, ny, TC), 8 + TC)).cuda()
+            y = ops.spectral_resize(x, (mx, my))
+            report(f"spectral_resize {nx}x{ny}->{mx}x{my} TC={TC}", y.sum(), [y], c)
+        for shape, ilow, ihigh in (((1, 16, 16, 1, 1), 2, 5), ((1, 16, 16, 10, 4), 2, 5), ((1, 6, 5, 7, 1, 1), 1, 2),
+                                   ((1, 6, 5, 7, 10, 4), 1, 2)):
+            p, t = E3.independent_pair(shape, 5) if len(shape) == 6 else E2.hashed_pair(shape, 5, hash_field)
+            ev = RolloutEvaluator("cuda", n_channels=shape[-1], T_max=12, ilow=ilow, ihigh=ihigh)
+            ev.update(torch.from_numpy(p).cuda(), torch.from_numpy(t).cuda())
+            report(f"evaluator {'x'.join(map(str, shape))}", ev.acc[0], [ev.acc], c)
+        for inverse in (False, True):
+            cases = [min((d for d in DC.RUNNABLE if (d.kind_inv if inverse else d.kind_fwd) == k), key=lambda d: d.B * d.h * d.w * d.E)
+                     for k in ops.dft2_kernel_kinds(inverse)] + [DC.Case(2, 20, 20, 24, 3, 20, 11, 0, 0)]
+            for d in cases:
+                kind = ops.dft2_kernel_kind(d.B, d.h, d.w, d.E, d.nb, d.mx, d.my, inverse)
+                assert kind == (d.kind_inv if inverse else d.kind_fwd), (d, kind)
+                x = R.recipe_input((d.B, d.h * d.w, d.E), 31).cuda()
+                if inverse:
+                    spec = R.recipe_input((d.B * d.mx * d.my, 2 * d.E), 32).cuda()
+                    out = ops.irfft2(spec, d.B, d.h, d.w, d.E, d.nb, d.mx, d.my, 1, res=x)
+                else:
+                    out = ops.rfft2(x, d.h, d.w, d.nb, d.mx, d.my, 1)
+                report(f"{'irfft2' if inverse else 'rfft2'} kind={kind} {DC.case_id(d)}", out.sum(), [out], c)
+        B, dims, E, nb, m3 = 2, (5, 3, 7), 16, 1, (2, 2, 4)
+        x = R.recipe_input((B, dims[0] * dims[1] * dims[2], E), 33).cuda()
+        spec = ops.rfft3(x, dims, nb, m3, 1)
+        report("rfft3 5x3x7", spec.sum(), [spec], c)
+        y = ops.irfft3(R.recipe_input(tuple(spec.shape), 34).cuda(), B, dims, E, nb, m3, 1, res=x)
+        report("irfft3 5x3x7", y.sum(), [y], c)
+
+
 def main():
     if not torch.cuda.is_available():
         raise SystemExit("grad_fingerprint: needs the GPU")
     print(f"# DPOT_TUNE={BASE_TUNE!r}", flush=True)
+    fno_case()
+    operator_cases()
     wgrad_cases()
     bf16_cases()
     mixer6_cases()

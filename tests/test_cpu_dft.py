@@ -8,7 +8,7 @@ import pytest
 import dft_cases as DC
 
 LDS_BYTES = 160 * 1024                 # per workgroup on gfx950
-GENERIC_BUDGET = 150 * 1024 // 4       # floats the generic kernels allow themselves (csrc/dft.hip pick_cc)
+GENERIC_BUDGET = 150 * 1024 // 4       # floats the generic kernels allow themselves (csrc/common.h LDS_GENERIC_BUDGET)
 
 
 @pytest.fixture(scope="module")

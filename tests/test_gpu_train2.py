@@ -819,3 +819,46 @@ def test_eager_and_replayed_steps_share_one_body_and_warm_up_is_undone(kind):
     for k, v in eager[0].items():
         assert torch.equal(v, replayed[0][k]), f"{k}: replayed steps differ from eager steps"
     assert met2.read()["opt_steps"] == 2 and met2.read()["ar_steps"] == 4
+
+
+_COLD_GRAPH_CHILD = """
+import sys
+sys.path.insert(0, {root!r})
+import torch
+from dpot_amd import DPOTNet
+from dpot_amd.train import FlatParams, FusedAdam, GraphedTrainStep, train_step
+from oracle import dpot_ref as R
+cfg = R.DPOTConfig(**R.MINI)
+S, B = cfg.img_size, 2
+xx = R.recipe_input((B, S, S, cfg.in_timesteps, cfg.in_channels), salt=1).cuda()
+yy = R.recipe_input((B, S, S, 2, cfg.out_channels), salt=2).cuda()
+msk = torch.ones(B, S, S, 1, cfg.out_channels, device="cuda")
+def fresh():
+    m = DPOTNet(**R.MINI)
+    m.load_state_dict(R.recipe_state_dict(cfg, salt=5))
+    m.cuda()
+    return m, FusedAdam(FlatParams(m), lr=1e-3, betas=(0.9, 0.9), weight_decay=1e-6, max_norm=10000.0)
+m, opt = fresh()
+g = GraphedTrainStep(m, opt, xx, yy, msk, warmup=1)        # the first kernel launches of this process
+for lr in (1e-3, 2e-3):
+    loss = g.replay(lr)
+m2, opt2 = fresh()
+for lr in (1e-3, 2e-3):
+    loss2, _ = train_step(m2, opt2, xx, yy, msk, lr=lr)
+torch.cuda.synchronize()
+assert loss.item() == loss2.item(), (loss.item(), loss2.item())
+assert torch.equal(opt.fp.flat, opt2.fp.flat) and torch.equal(opt.exp_avg, opt2.exp_avg)
+print("cold graph step ok")
+"""
+
+
+def test_graph_step_captured_in_a_cold_process_equals_the_eager_step():
+    """a fresh process whose first launches are GraphedTrainStep's warm-up: the warm-up is what lifts every kernel's dynamic-LDS
+    cap (csrc/common.h raise_dynamic_lds, once per kernel and device), inside the capture behind it the helper only reads the
+    current device, and the replays leave the parameters and moments of the eager steps, bit for bit (those run after them in the
+    same child)"""
+    import subprocess
+    code = _COLD_GRAPH_CHILD.format(root=ROOT)
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and "cold graph step ok" in r.stdout, r.stdout[-3000:]
