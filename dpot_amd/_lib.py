@@ -132,6 +132,9 @@ SIGNATURES = {
     "dpot_afno_block_weights": (c_i, [c_fp] * 3 + [c_i, c_i, c_fp]),
     "dpot_afno_pack_all": (c_i, [c_fp, c_i, c_i, c_i, c_i, c_fp]),
     "dpot_groupnorm_ws_elems": (c_i64, [c_i] * 4),
+    "dpot_groupnorm_kernel_kind": (c_i, [c_i] * 7),
+    "dpot_groupnorm_kernel_kinds": (c_i, [c_i, C.POINTER(c_i), c_i]),
+    "dpot_groupnorm_chunks": (c_i, [c_i] * 4 + [C.POINTER(c_i)] * 2),
     "dpot_groupnorm_fwd": (c_i, [c_fp] * 7 + [c_i] * 4 + [c_f, c_fp]),
     "dpot_groupnorm_bwd": (c_i, [c_fp] * 11 + [c_i] * 4 + [c_fp]),
     "dpot_groupnorm_bwd_packs_supported": (c_i, [c_i] * 3),

@@ -61,7 +61,9 @@ int tune(const char* key, int dflt) {
  * 274: the lanes move to csrc/lane.hip; dpot_wgrad_flush_async, dpot_wgrad_wait and dpot_wgrad_lane_* removed (lane 0 is forked
  * and joined through dpot_lane_* like lane 1)
  * 275: dpot_fno_rfft2, dpot_fno_irfft2, dpot_fno_mix, dpot_fno_mix_wgrad, dpot_fno_dact, dpot_fno_max_size (csrc/fno.hip): the
- * kernels of the FNO baseline; nothing existing changed */
-extern "C" int dpot_version(void) { return 275; }
+ * kernels of the FNO baseline; nothing existing changed
+ * 276: dpot_groupnorm_kernel_kind, dpot_groupnorm_kernel_kinds, dpot_groupnorm_chunks (csrc/norm.hip): host-only queries of the
+ * GroupNorm route selection the launchers read; nothing existing changed */
+extern "C" int dpot_version(void) { return 276; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

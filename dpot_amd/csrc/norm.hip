@@ -754,6 +754,58 @@ static GnChunks gn_chunking(int B, int T, int E, int G) {
   return c;
 }
 
+// column-sum partial rows per sample of the pack-writing backward: 1 = a cached kernel, chunks = the chunked one, 0 = no form
+static int gn_packs_rows(int B, int T, int E, int G) {
+  if (B <= 0 || T <= 0 || E <= 0 || G <= 0 || E % G || T % 32 || E % 32) return 0;
+  const int cg = E / G;
+  const int items = gn_cached_items(T, E, G);
+  if (cg == 128 && (items == 4 || items == 8)) return 1;
+  const GnChunks ck = gn_chunking(B, T, E, G);
+  if (ck.chunks && cg % 32 == 0 && cg <= 256 && ck.TC % 32 == 0) return ck.chunks;
+  return 0;
+}
+
+// ---- route selection in ONE place: dpot_groupnorm_fwd / _bwd / _bwd_packs launch what gn_select names, and
+// dpot_groupnorm_kernel_kind reports it (tests/gn_cases.py holds a case for every route) ---------------------------------
+//   direction   fwd, bwd: every kind below;  bwd_packs: CACHED4, CACHED8, CHUNKED;  stats (fwd with y == NULL): CHUNKED
+//   has_ws      a 16-byte aligned workspace of dpot_groupnorm_ws_elems was passed
+//   aligned     every tensor pointer the direction reads or writes with 16-byte accesses is 16-byte aligned
+// fwd / bwd:  E/G % 4 != 0 or !aligned -> SCALAR; else gn_chunking(...) and has_ws -> CHUNKED; else gn_cached_items -> CACHED4 /
+// CACHED8; else VEC4.  bwd_packs: refused unless aligned and gn_packs_rows > 0; 128 channels per group in a cached slab -> CACHED4 /
+// CACHED8, else CHUNKED (refused without has_ws).
+enum { GN_DIR_FWD = 0, GN_DIR_BWD = 1, GN_DIR_BWD_PACKS = 2, GN_DIR_STATS = 3 };
+enum { GN_KIND_SCALAR = 0, GN_KIND_VEC4 = 1, GN_KIND_CACHED4 = 4, GN_KIND_CACHED8 = 8, GN_KIND_CHUNKED = 16 };
+struct GnRoute {
+  int kind;            // GN_KIND_*, or -1: refused
+  GnChunks ck;         // the chunking of GN_KIND_CHUNKED
+};
+static GnRoute gn_select(int B, int T, int E, int G, int direction, bool has_ws, bool aligned) {
+  GnRoute r{-1, GnChunks{0, 0}};
+  if (B <= 0 || T <= 0 || E <= 0 || G <= 0 || E % G || B > 65535) return r;
+  if (direction == GN_DIR_BWD_PACKS) {
+    if (!aligned || gn_packs_rows(B, T, E, G) == 0) return r;
+    const int items = gn_cached_items(T, E, G);
+    if (E / G == 128 && (items == 4 || items == 8)) {
+      r.kind = items;
+      return r;
+    }
+    if (!has_ws) return r;
+    r.ck = gn_chunking(B, T, E, G);
+    r.kind = GN_KIND_CHUNKED;
+    return r;
+  }
+  if (direction != GN_DIR_FWD && direction != GN_DIR_BWD && direction != GN_DIR_STATS) return r;
+  const bool vec = ((E / G) % 4 == 0) && aligned;
+  const int items = vec ? gn_cached_items(T, E, G) : 0;
+  if (vec && has_ws) r.ck = gn_chunking(B, T, E, G);
+  if (r.ck.chunks) r.kind = GN_KIND_CHUNKED;
+  else if (direction == GN_DIR_STATS) r.kind = -1;       // the statistics-only form exists in the chunked kernels alone
+  else if (items == 4) r.kind = GN_KIND_CACHED4;
+  else if (items == 8) r.kind = GN_KIND_CACHED8;
+  else r.kind = vec ? GN_KIND_VEC4 : GN_KIND_SCALAR;
+  return r;
+}
+
 }  // namespace dpot
 
 using namespace dpot;
@@ -764,15 +816,38 @@ extern "C" int64_t dpot_groupnorm_ws_elems(int B, int T, int E, int G) {
   return c.chunks ? (int64_t)B * c.chunks * 2 * E : 0;    // backward partials (the forward needs B*G*chunks*2 <= this)
 }
 
+extern "C" int dpot_groupnorm_kernel_kind(int B, int T, int E, int G, int direction, int has_workspace, int aligned) {
+  return gn_select(B, T, E, G, direction, has_workspace != 0, aligned != 0).kind;
+}
+
+extern "C" int dpot_groupnorm_kernel_kinds(int direction, int* out, int cap) {
+  // the pack-writing backward has the first three, the statistics-only forward the chunked route alone
+  static const int kinds[] = {GN_KIND_CHUNKED, GN_KIND_CACHED4, GN_KIND_CACHED8, GN_KIND_VEC4, GN_KIND_SCALAR};
+  const int n = direction == GN_DIR_FWD || direction == GN_DIR_BWD ? 5
+                : direction == GN_DIR_BWD_PACKS                    ? 3
+                : direction == GN_DIR_STATS                        ? 1
+                                                                   : 0;
+  for (int i = 0; i < n && out && i < cap; ++i) out[i] = kinds[i];
+  return n;
+}
+
+extern "C" int dpot_groupnorm_chunks(int B, int T, int E, int G, int* TC, int* chunks) {
+  GnChunks c{0, 0};
+  if (B > 0 && T > 0 && E > 0 && G > 0 && E % G == 0) c = gn_chunking(B, T, E, G);
+  if (TC) *TC = c.TC;
+  if (chunks) *chunks = c.chunks;
+  return c.chunks;
+}
+
 extern "C" int dpot_groupnorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean,
                                   float* rstd, float* workspace, int B, int T, int E, int G, float eps,
                                   dpot_stream_t stream) {
   DPOT_REQUIRE(x && gamma && beta && mean && rstd, "groupnorm_fwd: null pointer");
   DPOT_REQUIRE(B > 0 && T > 0 && E > 0 && G > 0 && E % G == 0 && B <= 65535, "groupnorm_fwd: bad shape");
-  const bool vec = ((E / G) % 4 == 0) && aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta);
-  const int items = vec ? gn_cached_items(T, E, G) : 0;
-  const GnChunks ck = vec && workspace && aligned16(workspace) ? gn_chunking(B, T, E, G) : GnChunks{0, 0};
-  if (ck.chunks) {
+  const GnRoute r = gn_select(B, T, E, G, y ? GN_DIR_FWD : GN_DIR_STATS, workspace && aligned16(workspace),
+                              aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta));
+  if (r.kind == GN_KIND_CHUNKED) {
+    const GnChunks ck = r.ck;
     const dim3 grid(ck.chunks, G, B);
     hipLaunchKernelGGL(gn_chunk_stats_kernel, grid, dim3(GN_THREADS), 0, as_stream(stream), x, workspace, T, E, G, ck);
     int rc = check_launch("gn_chunk_stats_kernel");
@@ -783,14 +858,15 @@ extern "C" int dpot_groupnorm_fwd(const float* x, const float* gamma, const floa
                        beta, y, mean, rstd, (const float*)workspace, T, E, G, ck, eps);
     return check_launch("gn_chunk_apply_kernel");
   }
-  DPOT_REQUIRE(y, "groupnorm_fwd: statistics-only calls (y == NULL) need the chunked path (dpot_groupnorm_ws_elems > 0)");
-  if (items == 4)
+  DPOT_REQUIRE(y && r.kind >= 0,
+               "groupnorm_fwd: statistics-only calls (y == NULL) need the chunked path (dpot_groupnorm_ws_elems > 0)");
+  if (r.kind == GN_KIND_CACHED4)
     hipLaunchKernelGGL(groupnorm_fwd_cached_kernel<4>, dim3(G, B), dim3(GN_THREADS), 0, as_stream(stream), x, gamma, beta,
                        y, mean, rstd, T, E, G, eps);
-  else if (items == 8)
+  else if (r.kind == GN_KIND_CACHED8)
     hipLaunchKernelGGL(groupnorm_fwd_cached_kernel<8>, dim3(G, B), dim3(GN_THREADS), 0, as_stream(stream), x, gamma, beta,
                        y, mean, rstd, T, E, G, eps);
-  else if (vec)
+  else if (r.kind == GN_KIND_VEC4)
     hipLaunchKernelGGL(groupnorm_fwd_kernel<4>, dim3(G, B), dim3(GN_THREADS), 0, as_stream(stream), x, gamma, beta, y,
                        mean, rstd, T, E, G, eps);
   else
@@ -805,11 +881,11 @@ extern "C" int dpot_groupnorm_bwd(const float* dy, const float* x, const float* 
   DPOT_REQUIRE(dy && x && mean && rstd && gamma && dx && part && ((dgamma == nullptr) == (dbeta == nullptr)),
                "groupnorm_bwd: null pointer");
   DPOT_REQUIRE(B > 0 && T > 0 && E > 0 && G > 0 && E % G == 0 && B <= 65535, "groupnorm_bwd: bad shape");
-  const bool vec = ((E / G) % 4 == 0) && aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(gamma) &&
-                   (add == nullptr || aligned16(add));
-  const int items = vec ? gn_cached_items(T, E, G) : 0;
-  const GnChunks ck = vec && workspace && aligned16(workspace) ? gn_chunking(B, T, E, G) : GnChunks{0, 0};
-  if (ck.chunks) {
+  const GnRoute r = gn_select(B, T, E, G, GN_DIR_BWD, workspace && aligned16(workspace),
+                              aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(gamma) &&
+                                  (add == nullptr || aligned16(add)));
+  if (r.kind == GN_KIND_CHUNKED) {
+    const GnChunks ck = r.ck;
     const dim3 grid(ck.chunks, G, B);
     hipLaunchKernelGGL(gn_chunk_bwd_part_kernel, grid, dim3(GN_THREADS), 0, as_stream(stream), dy, x, mean, rstd, workspace,
                        T, E, G, ck);
@@ -817,13 +893,13 @@ extern "C" int dpot_groupnorm_bwd(const float* dy, const float* x, const float* 
     if (rc0) return rc0;
     hipLaunchKernelGGL(gn_chunk_bwd_apply_kernel, grid, dim3(GN_THREADS), 0, as_stream(stream), dy, x, mean, rstd, gamma, add,
                        dx, part, (const float*)workspace, B, T, E, G, ck);
-  } else if (items == 4)
+  } else if (r.kind == GN_KIND_CACHED4)
     hipLaunchKernelGGL((groupnorm_bwd_cached_kernel<4, false>), dim3(G, B), dim3(GN_THREADS), 0, as_stream(stream), dy, x, mean,
                        rstd, gamma, add, dx, part, B, T, E, G, GnBwdPacks{nullptr, nullptr, nullptr});
-  else if (items == 8)
+  else if (r.kind == GN_KIND_CACHED8)
     hipLaunchKernelGGL((groupnorm_bwd_cached_kernel<8, false>), dim3(G, B), dim3(GN_THREADS), 0, as_stream(stream), dy, x, mean,
                        rstd, gamma, add, dx, part, B, T, E, G, GnBwdPacks{nullptr, nullptr, nullptr});
-  else if (vec)
+  else if (r.kind == GN_KIND_VEC4)
     hipLaunchKernelGGL(groupnorm_bwd_kernel<4>, dim3(G, B), dim3(GN_THREADS), 0, as_stream(stream), dy, x, mean, rstd,
                        gamma, add, dx, part, B, T, E, G);
   else
@@ -841,15 +917,7 @@ extern "C" int dpot_groupnorm_bwd(const float* dy, const float* x, const float* 
 // packs + per-sample column sums of the previous block's channel-MLP backward (see groupnorm_bwd_cached_kernel<.., PK>)
 // (returns the number of column-sum partial ROWS per sample the call writes: 1 for the one-workgroup-per-slab kernel, the number
 // of chunks for the chunked one; 0 = not supported)
-extern "C" int dpot_groupnorm_bwd_packs_rows(int B, int T, int E, int G) {
-  if (B <= 0 || T <= 0 || E <= 0 || G <= 0 || E % G || T % 32 || E % 32) return 0;
-  const int cg = E / G;
-  const int items = gn_cached_items(T, E, G);
-  if (cg == 128 && (items == 4 || items == 8)) return 1;
-  const GnChunks ck = gn_chunking(B, T, E, G);
-  if (ck.chunks && cg % 32 == 0 && cg <= 256 && ck.TC % 32 == 0) return ck.chunks;
-  return 0;
-}
+extern "C" int dpot_groupnorm_bwd_packs_rows(int B, int T, int E, int G) { return gn_packs_rows(B, T, E, G); }
 extern "C" int dpot_groupnorm_bwd_packs_supported(int T, int E, int G) {
   if (T <= 0 || E <= 0 || G <= 0 || E % G || E / G != 128 || T % 32 || E % 32) return 0;
   const int items = gn_cached_items(T, E, G);
@@ -869,8 +937,9 @@ extern "C" int dpot_groupnorm_bwd_packs(const float* dy, const float* x, const f
                    aligned16(dx_trans_bf16),
                "groupnorm_bwd_packs: pointers must be 16-byte aligned");
   const GnBwdPacks pk{reinterpret_cast<uint4*>(dx_rows_bf16), reinterpret_cast<uint4*>(dx_trans_bf16), dx_colsum};
-  if (dpot_groupnorm_bwd_packs_supported(T, E, G)) {
-    if (gn_cached_items(T, E, G) == 4)
+  const GnRoute r = gn_select(B, T, E, G, GN_DIR_BWD_PACKS, workspace && aligned16(workspace), true);
+  if (r.kind == GN_KIND_CACHED4 || r.kind == GN_KIND_CACHED8) {
+    if (r.kind == GN_KIND_CACHED4)
       hipLaunchKernelGGL((groupnorm_bwd_cached_kernel<4, true>), dim3(G, B), dim3(GN_THREADS), 0, as_stream(stream), dy, x, mean,
                          rstd, gamma, add, dx, part, B, T, E, G, pk);
     else
@@ -878,8 +947,8 @@ extern "C" int dpot_groupnorm_bwd_packs(const float* dy, const float* x, const f
                          rstd, gamma, add, dx, part, B, T, E, G, pk);
     return check_launch("groupnorm_bwd_cached_kernel");
   }
-  DPOT_REQUIRE(workspace && aligned16(workspace), "groupnorm_bwd_packs: the chunked form needs the workspace of dpot_groupnorm_ws_elems");
-  const GnChunks ck = gn_chunking(B, T, E, G);
+  DPOT_REQUIRE(r.kind == GN_KIND_CHUNKED, "groupnorm_bwd_packs: the chunked form needs the workspace of dpot_groupnorm_ws_elems");
+  const GnChunks ck = r.ck;
   const dim3 grid(ck.chunks, G, B);
   hipLaunchKernelGGL(gn_chunk_bwd_part_kernel, grid, dim3(GN_THREADS), 0, as_stream(stream), dy, x, mean, rstd, workspace, T, E,
                      G, ck);

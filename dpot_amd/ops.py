@@ -1280,6 +1280,35 @@ def groupnorm_ws_elems(B: int, T: int, E: int, G: int) -> int:
     return int(_lib.load().dpot_groupnorm_ws_elems(B, T, E, G))
 
 
+GN_DIRECTIONS = {"fwd": 0, "bwd": 1, "bwd_packs": 2, "stats": 3}
+GN_SCALAR, GN_VEC4, GN_CACHED4, GN_CACHED8, GN_CHUNKED = 0, 1, 4, 8, 16
+
+
+def groupnorm_kernel_kind(B: int, T: int, E: int, G: int = 8, direction: str = "fwd", has_workspace: bool = True,
+                          aligned: bool = True) -> int:
+    """the kernel route groupnorm_fwd / groupnorm_bwd / groupnorm_bwd_packs / groupnorm_stats (direction "fwd", "bwd",
+    "bwd_packs", "stats") take for this call, from the library's own selection (dpot_groupnorm_kernel_kind): GN_SCALAR,
+    GN_VEC4 (generic kernels), GN_CACHED4 / GN_CACHED8 (register-cached, 4 / 8 items), GN_CHUNKED, or -1 where the call is
+    refused.  has_workspace: chunked=True; aligned: every tensor of the call starts on a 16-byte boundary"""
+    return _lib.load().dpot_groupnorm_kernel_kind(B, T, E, G, GN_DIRECTIONS.get(direction, -1), int(has_workspace),
+                                                  int(aligned))
+
+
+def groupnorm_kernel_kinds(direction: str = "fwd") -> Tuple[int, ...]:
+    """every kind groupnorm_kernel_kind can return >= 0 for this direction"""
+    buf = (C.c_int * 16)()
+    n = _lib.load().dpot_groupnorm_kernel_kinds(GN_DIRECTIONS.get(direction, -1), buf, 16)
+    assert n <= 16
+    return tuple(buf[:n])
+
+
+def groupnorm_chunks(B: int, T: int, E: int, G: int = 8) -> Tuple[int, int]:
+    """(tokens per chunk, chunks per (sample, group) slab) of the chunked kernels; (0, 0): the shape is never chunked"""
+    tc, ch = C.c_int(0), C.c_int(0)
+    _lib.load().dpot_groupnorm_chunks(B, T, E, G, C.byref(tc), C.byref(ch))
+    return tc.value, ch.value
+
+
 def groupnorm_fwd(x: Tensor, gamma: Tensor, beta: Tensor, G: int = 8, eps: float = 1e-5, chunked: bool = True):
     """chunked=False: never the chunked kernels (no workspace is passed)"""
     B, T, E = x.shape
@@ -1312,15 +1341,16 @@ def groupnorm_stats(x: Tensor, gamma: Tensor, beta: Tensor, G: int = 8, eps: flo
 
 def groupnorm_bwd(dy: Tensor, x: Tensor, mean: Tensor, rstd: Tensor, gamma: Tensor, G: int = 8,
                   add: Optional[Tensor] = None, out_dgamma: Optional[Tensor] = None,
-                  out_dbeta: Optional[Tensor] = None, defer: bool = False):
+                  out_dbeta: Optional[Tensor] = None, defer: bool = False, chunked: bool = True):
     """defer=False: returns (dx, dgamma, dbeta).  defer=True: returns (dx, part) - the per-sample partials [2,B,E] of the
-    parameter gradients, to be reduced later by groupnorm_param_grads (several layers in one launch)"""
+    parameter gradients, to be reduced later by groupnorm_param_grads (several layers in one launch).
+    chunked=False: never the chunked kernels (no workspace is passed)"""
     B, T, E = x.shape
     dx = torch.empty_like(x)
     part = torch.empty(2, B, E, dtype=torch.float32, device=x.device)
     dgamma = None if defer else _out(out_dgamma, (E,), x.device)
     dbeta = None if defer else _out(out_dbeta, (E,), x.device)
-    ws = _gn_workspace(B, T, E, G, x.device)
+    ws = _gn_workspace(B, T, E, G, x.device) if chunked else None
     check(_lib.load().dpot_groupnorm_bwd(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
                                          gamma.data_ptr(), _p(add), dx.data_ptr(), _p(dgamma), _p(dbeta),
                                          part.data_ptr(), _p(ws), B, T, E, G, _stream()), "groupnorm_bwd")

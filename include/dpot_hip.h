@@ -361,6 +361,17 @@ int dpot_afno_unpack_grad(const float* dwbig, const float* dbbig, float* dw, flo
  * that >= 512 workgroups run, and the group statistics are merged through the workspace (two launches per call).
  * Passing NULL always selects the one-workgroup-per-slab kernels. */
 int64_t dpot_groupnorm_ws_elems(int B, int T, int E, int G);
+/* The kernel route dpot_groupnorm_fwd (direction 0; 3: its statistics-only form, y == NULL), dpot_groupnorm_bwd (1) and
+ * dpot_groupnorm_bwd_packs (2) take for a call, from the library's own selection - the launchers read the same function.
+ * has_workspace: a 16-byte aligned workspace is passed; aligned: every tensor pointer of the call is 16-byte aligned.
+ * Kinds: 0 generic scalar, 1 generic float4, 4 / 8 register-cached with 4 / 8 items per thread, 16 chunked; -1: refused (bad
+ * shape, a statistics-only call off the chunked route, a pack-writing call with rows == 0, misaligned pointers or a chunked
+ * slab without workspace).  dpot_groupnorm_kernel_kinds: every kind of a direction into out[0..cap), returns their number.
+ * dpot_groupnorm_chunks: tokens per chunk and chunks per (sample, group) slab of the chunked route ((0, 0): the shape is never
+ * chunked); returns chunks. */
+int dpot_groupnorm_kernel_kind(int B, int T, int E, int G, int direction, int has_workspace, int aligned);
+int dpot_groupnorm_kernel_kinds(int direction, int* out, int cap);
+int dpot_groupnorm_chunks(int B, int T, int E, int G, int* TC, int* chunks);
 int dpot_groupnorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean,
                        float* rstd, float* workspace, int B, int T, int E, int G, float eps, dpot_stream_t stream);
 int dpot_groupnorm_bwd(const float* dy, const float* x, const float* mean, const float* rstd,
