@@ -179,6 +179,7 @@ SIGNATURES = {
     "dpot_rel_l2_bwd": (c_i, [c_fp] * 6 + [c_i] * 4 + [c_fp]),
     "dpot_sumsq": (c_i, [c_fp, c_i64, c_fp, c_fp, c_i, c_fp]),
     "dpot_adam_step": (c_i, [c_fp] * 4 + [c_i64, c_fp, c_fp, c_f, c_fp]),
+    "dpot_adam_step_pairs": (c_i, [c_fp] * 4 + [c_i64, c_fp, c_fp, c_f, c_fp, c_i, c_fp]),
     "dpot_adam_stage": (c_i, [c_fp, c_fp, c_f, c_d, c_d, c_f, c_f, c_f, c_i, c_fp]),
     "dpot_lamb_chunk_elems": (c_i, []),
     "dpot_lamb_step": (c_i, [c_fp] * 5 + [c_fp, c_f, c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_i, c_fp]),
@@ -279,6 +280,12 @@ SIGNATURES = {
     "dpot_fno_mix": (c_i, [c_fp] * 4 + [c_i] * 6 + [c_fp]),
     "dpot_fno_mix_wgrad": (c_i, [c_fp] * 4 + [c_i] * 6 + [c_fp]),
     "dpot_fno_dact": (c_i, [c_fp] * 3 + [c_i64, c_i, c_fp]),
+    "dpot_fno3_max_size": (c_i, [c_i]),
+    "dpot_fno3_ws_elems": (c_i64, [c_i] * 5),
+    "dpot_fno3_rfft3": (c_i, [c_fp] * 6 + [c_i] * 9 + [c_f, c_fp]),
+    "dpot_fno3_irfft3": (c_i, [c_fp] * 8 + [c_i] * 9 + [c_f, c_i, c_fp]),
+    "dpot_fno3_mix": (c_i, [c_fp] * 6 + [c_i] * 7 + [c_fp]),
+    "dpot_fno3_mix_wgrad": (c_i, [c_fp] * 6 + [c_i] * 7 + [c_fp]),
 }
 
 _lib = None

@@ -63,7 +63,10 @@ int tune(const char* key, int dflt) {
  * 275: dpot_fno_rfft2, dpot_fno_irfft2, dpot_fno_mix, dpot_fno_mix_wgrad, dpot_fno_dact, dpot_fno_max_size (csrc/fno.hip): the
  * kernels of the FNO baseline; nothing existing changed
  * 276: dpot_groupnorm_kernel_kind, dpot_groupnorm_kernel_kinds, dpot_groupnorm_chunks (csrc/norm.hip): host-only queries of the
- * GroupNorm route selection the launchers read; nothing existing changed */
-extern "C" int dpot_version(void) { return 276; }
+ * GroupNorm route selection the launchers read; nothing existing changed
+ * 277: dpot_fno3_rfft3, dpot_fno3_irfft3, dpot_fno3_mix, dpot_fno3_mix_wgrad, dpot_fno3_max_size, dpot_fno3_ws_elems
+ * (csrc/fno3.hip): the kernels of the 3-D FNO baseline; dpot_adam_step_pairs (csrc/loss_opt.hip): Adam with one second moment
+ * per complex pair; nothing existing changed */
+extern "C" int dpot_version(void) { return 277; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

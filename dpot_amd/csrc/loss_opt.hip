@@ -230,6 +230,45 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
+// Adam over a flat buffer that holds COMPLEX parameters stored as (re, im) pairs (FNO3d's spectral weights, the view_as_real of
+// the reference's cfloat tensors): utils/optimizer.py:41 accumulates grad * conj(grad), so a pair shares ONE second moment
+// |g'|^2 = g're^2 + g'im^2, kept in both of its slots; everything else is adam_update component by component.  A thread owns
+// two neighbouring floats; ranges[nr][2] (DEVICE, ascending, even bounds) are the [lo, hi) float ranges that hold pairs - tensors
+// start on 4-float boundaries, so a thread's two floats are one pair or two ordinary elements, never half of each.
+__global__ __launch_bounds__(256) void adam_pairs_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ m, float* __restrict__ v, long long n,
+                                                         const float* __restrict__ hyper, const float* __restrict__ sumsq,
+                                                         float grad_scale, const long long* __restrict__ ranges, int nr) {
+  const AdamCoef c = adam_coef(hyper, sumsq, grad_scale);
+  for (long long i = 2 * (blockIdx.x * 256ll + threadIdx.x); i < n; i += 2ll * gridDim.x * 256) {
+    bool pair = false;
+    for (int k = 0; k < nr; ++k) pair = pair || (i >= ranges[2 * k] && i < ranges[2 * k + 1]);
+    float2 pv = *reinterpret_cast<const float2*>(p + i), mv = *reinterpret_cast<const float2*>(m + i);
+    float2 vv = *reinterpret_cast<const float2*>(v + i);
+    const float2 gv = *reinterpret_cast<const float2*>(g + i);
+    if (pair) {
+      float gr = gv.x * c.gs, gi = gv.y * c.gs;
+      if (c.wd != 0.f) {
+        gr = fmaf(c.wd, pv.x, gr);
+        gi = fmaf(c.wd, pv.y, gi);
+      }
+      mv.x = fmaf(c.b1, mv.x, c.omb1 * gr);
+      mv.y = fmaf(c.b1, mv.y, c.omb1 * gi);
+      const float vs = fmaf(c.b2, vv.x, c.omb2 * fmaf(gr, gr, gi * gi));
+      vv.x = vv.y = vs;
+      const float denom = sqrtf(vs) / c.sb2 + c.eps;
+      pv.x = pv.x - c.step * (mv.x / denom);
+      pv.y = pv.y - c.step * (mv.y / denom);
+    } else {
+      adam_update(c, pv.x, gv.x, mv.x, vv.x);
+      adam_update(c, pv.y, gv.y, mv.y, vv.y);
+    }
+    *reinterpret_cast<float2*>(m + i) = mv;
+    *reinterpret_cast<float2*>(v + i) = vv;
+    *reinterpret_cast<float2*>(p + i) = pv;
+  }
+}
+
 // host side of a step without a host buffer: all hyper-parameters travel BY VALUE in the kernarg segment of this
 // one-thread launch (copied at enqueue time), and the step counter / bias corrections live on the device - so a host
 // that runs several graph replays ahead of the GPU can never overwrite the values a queued step still has to read
@@ -700,6 +739,18 @@ extern "C" int dpot_adam_step(float* p, const float* g, float* m, float* v, int6
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 8192)), dim3(256), 0, as_stream(stream), p, g, m, v, (long long)n,
                      hyper, sumsq, grad_scale);
   return check_launch("adam_kernel");
+}
+
+extern "C" int dpot_adam_step_pairs(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
+                                    const float* sumsq, float grad_scale, const int64_t* ranges, int n_ranges,
+                                    dpot_stream_t stream) {
+  DPOT_REQUIRE(p && g && m && v && hyper && ranges && n > 0 && n_ranges > 0, "adam_step_pairs: bad argument");
+  DPOT_REQUIRE(n % 2 == 0 && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                               reinterpret_cast<uintptr_t>(v)) & 7) == 0,
+               "adam_step_pairs: the buffers must be 8-byte aligned and hold an even number of floats");
+  hipLaunchKernelGGL(adam_pairs_kernel, dim3(grid_for(n / 2, 8192)), dim3(256), 0, as_stream(stream), p, g, m, v, (long long)n,
+                     hyper, sumsq, grad_scale, reinterpret_cast<const long long*>(ranges), n_ranges);
+  return check_launch("adam_pairs_kernel");
 }
 
 extern "C" int dpot_adam_stage(float* hyper, int64_t* step, float lr, double beta1, double beta2, float eps,

@@ -1750,3 +1750,87 @@ class FNOEmbedFn(torch.autograd.Function):
         dx = ops.unpatchify(dA0, B, X, Y, T, K, ctx.P) if dA0 is not None else None
         dres = _res_bwd(dy, ctx.tok, B) if ctx.has_res and ctx.needs_input_grad[8] else None
         return dx, None, None, None, dW0, db0, dW2, db2, dres, None, None
+
+
+# ======================================================================================================
+# the 3-D FNO baseline (models/fno.py:290-435): csrc/fno3.hip through ops.fno3_*
+# ======================================================================================================
+def _fno3_wgrad(X, dO, sinks, need: bool = True):
+    """(dweights1..dweights4) delivered as _fno_wgrad does for two: straight into the flat gradient slots where this is the
+    step's first contribution, ADDED there by the kernel in a further pass of a rollout (all four slots filled), else as
+    temporaries; need=False (frozen spectral weights): nothing is launched"""
+    if not need:
+        for s in sinks:
+            s.skip()
+        return (None,) * 4
+    outs, acc = [s.out() for s in sinks], False
+    if any(o is None for o in outs):
+        outs = None
+        if all(s.fp is not None and s.fp.filled[s.i] for s in sinks):
+            outs, acc = [s.fp.grad_views[s.i] for s in sinks], True
+    ds = ops.fno3_mix_wgrad(X, dO, outs, acc)
+    return tuple(s.done(d) for s, d in zip(sinks, ds))
+
+
+class SpectralConv3dFn(torch.autograd.Function):
+    """SpectralConv3d (models/fno.py:290-342) on a channels-last field x[B, X, Y, Z, Cin] -> [B, X, Y, Z, Cout]: truncated
+    rfftn, per-mode mixing with the four corner weights [Cin, Cout, m1, m2, m3, 2] (real pairs), irfftn.  Keeps the kept
+    spectrum, not the field."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, w3, w4):
+        x, ws = x.contiguous(), tuple(w.contiguous() for w in (w1, w2, w3, w4))
+        m1, m2, m3 = ws[0].shape[2:5]
+        S = ops.fno3_rfft3(x, m1, m2, m3)
+        y, _ = ops.fno3_irfft3(ops.fno3_mix(S, ws), *x.shape[1:4])
+        ctx.save_for_backward(S, *ws)
+        ctx.sinks = _sinks(ctx, ws, 1)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        S, *ws = ctx.saved_tensors
+        dy = dy.contiguous()
+        dO = ops.fno3_rfft3(dy, *ws[0].shape[2:5], adjoint=True)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx, _ = ops.fno3_irfft3(ops.fno3_mix(dO, ws, adjoint=True), *dy.shape[1:4], adjoint=True)
+        return (dx,) + _fno3_wgrad(S, dO, ctx.sinks, any(ctx.needs_input_grad[1:5]))
+
+
+class FNO3dLayerFn(torch.autograd.Function):
+    """One layer of FNO3d (models/fno.py:407-411): act(SpectralConv3d(x) + Conv3d 1x1x1(x)) on x[B, X, Y, Z, Cin].  As
+    FNOLayerFn: the convolution is one GEMM whose result rides into the inverse transform's epilogue (add, activation); the
+    backward forms dpre = dy act'(pre) once, and the convolution's data gradient rides into the adjoint transform."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, w3, w4, cw, cb, act: int):
+        ops.capture_precision(ctx)
+        x, cw, ws = x.contiguous(), cw.contiguous(), tuple(w.contiguous() for w in (w1, w2, w3, w4))
+        B, X, Y, Z, Cin = x.shape
+        Cout, m1, m2, m3 = ws[0].shape[1:5]
+        conv, _ = ops.linear_fwd(x.view(B * X * Y * Z, Cin), cw, cb)
+        S = ops.fno3_rfft3(x, m1, m2, m3)
+        y, pre = ops.fno3_irfft3(ops.fno3_mix(S, ws), X, Y, Z, add=conv.view(B, X, Y, Z, Cout), act=act, save_pre=True)
+        ctx.save_for_backward(x, S, pre, cw, *ws)
+        ctx.act = act
+        ctx.sinks = _sinks(ctx, ws + (cw, cb), 1)
+        return y
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dy):
+        x, S, pre, cw, *ws = ctx.saved_tensors
+        B, X, Y, Z, Cin = x.shape
+        Cout, m1, m2, m3 = ws[0].shape[1:5]
+        s_cw, s_cb = ctx.sinks[4:]
+        dpre = ops.act_bwd_mul(dy.contiguous(), pre, ctx.act)
+        dO = ops.fno3_rfft3(dpre, m1, m2, m3, adjoint=True)
+        dpre2 = dpre.view(B * X * Y * Z, Cout)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dxc = ops.linear_bwd_data(dpre2, cw).view(B, X, Y, Z, Cin)
+            dx, _ = ops.fno3_irfft3(ops.fno3_mix(dO, ws, adjoint=True), X, Y, Z, add=dxc, adjoint=True)
+        dws = _fno3_wgrad(S, dO, ctx.sinks[:4], any(ctx.needs_input_grad[1:5]))
+        dcw, dcb = ops.linear_bwd_wb(dpre2, x.view(B * X * Y * Z, Cin), s_cw.out(), s_cb.out())
+        return (dx,) + dws + (s_cw.done(dcw.view(cw.shape)), s_cb.done(dcb), None)

@@ -19,7 +19,7 @@ overwrite the rows it shares with weights1) and modes2 <= (Y/P) // 2 + 1 (the re
 The spectral weights are read in place by the kernels: the model owns no derived copy (no ``packs``).  The torch modules are
 parameter containers only.  CUDA (ROCm) tensors only; there is no CPU path.
 
-Not here (see README): FNO3d, SegmentedTrainStep / make_dp_step (they read ``model.blocks``), bf16 modes for the FNO layers.
+Not here (see README): SegmentedTrainStep / make_dp_step (they read ``model.blocks``), bf16 modes for the FNO layers.
 """
 from __future__ import annotations
 

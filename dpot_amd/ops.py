@@ -1923,6 +1923,25 @@ def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, sumsq_:
                                      hyper.data_ptr(), _p(sumsq_), grad_scale, _stream()), "adam_step")
 
 
+def adam_pair_ranges(ranges, device) -> Tensor:
+    """the device table of dpot_adam_step_pairs: int64 [n, 2] of the [lo, hi) float ranges of a flat buffer that hold complex
+    numbers as (re, im) pairs; ascending, disjoint, even bounds"""
+    ranges = sorted((int(lo), int(hi)) for lo, hi in ranges)
+    if not ranges or any(lo % 2 or hi % 2 or hi <= lo for lo, hi in ranges) \
+            or any(a[1] > b[0] for a, b in zip(ranges, ranges[1:])):
+        raise ValueError(f"adam_pair_ranges: non-empty, disjoint [lo, hi) ranges with even bounds, got {ranges}")
+    return torch.tensor(ranges, dtype=torch.int64).to(device)
+
+
+def adam_step_pairs(p: Tensor, g: Tensor, m: Tensor, v: Tensor, hyper: Tensor, sumsq_: Optional[Tensor], ranges_dev: Tensor,
+                    grad_scale: float = 1.0) -> None:
+    """dpot_adam_step with ONE second moment per (re, im) pair inside `ranges_dev` (adam_pair_ranges), the reference's Adam on
+    complex parameters (utils/optimizer.py:41)"""
+    check(_lib.load().dpot_adam_step_pairs(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), hyper.data_ptr(),
+                                           _p(sumsq_), grad_scale, ranges_dev.data_ptr(), ranges_dev.shape[0], _stream()),
+          "adam_step_pairs")
+
+
 class AdamPackPlan:
     """Device tables of dpot_adam_step_packs for one (flat parameter buffer, PanelPacks of 1-plane bf16 weight packs): every
     weight W [R, K] (row-major inside the flat buffer) that the pack set holds as the pair (W, R, K, K, False) / (W, K, R, K,
@@ -2929,3 +2948,179 @@ def act_bwd_mul(dy: Tensor, pre: Tensor, act: int) -> Tensor:
     out = torch.empty_like(dy)
     check(_lib.load().dpot_fno_dact(dy.data_ptr(), pre.data_ptr(), out.data_ptr(), dy.numel(), int(act), _stream()), "fno_dact")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------
+# The 3-D FNO baseline (csrc/fno3.hip; models/fno.py SpectralConv3d): truncated transforms of a channels-last field
+# x [B, X, Y, Z, C] to / from the kept spectrum S [B, 2 m1, 2 m2, m3, 2, C] (kx and ky below m and above N - m, kz < m3, re | im
+# planes, channels innermost) and the per-mode mixing with the four corner weights [Cin, Cout, m1, m2, m3, 2] (real pairs).
+# Each transform is two launches around a workspace this module allocates.  The twiddle tables are pure numpy.
+# ------------------------------------------------------------------------------------------------------
+def fno3_check_modes(X: int, Y: int, Z: int, m1: int, m2: int, m3: int, what: str = "fno3") -> None:
+    """the two refusals: the corner blocks must not overlap (the reference silently lets later ones overwrite earlier ones) and
+    modes3 must fit the half spectrum (the reference raises inside its slice assignment)"""
+    if min(X, Y, Z, m1, m2, m3) < 1:
+        raise ValueError(f"{what}: field {X}x{Y}x{Z} and modes ({m1}, {m2}, {m3}) must be positive")
+    if 2 * m1 > X:
+        raise ValueError(f"{what}: modes1 = {m1} needs 2 * modes1 <= X = {X}: the kept corner blocks would overlap")
+    if 2 * m2 > Y:
+        raise ValueError(f"{what}: modes2 = {m2} needs 2 * modes2 <= Y = {Y}: the kept corner blocks would overlap")
+    if m3 > Z // 2 + 1:
+        raise ValueError(f"{what}: modes3 = {m3} exceeds the Z // 2 + 1 = {Z // 2 + 1} planes of the half spectrum of Z = {Z}")
+
+
+def fno3_supported(X: int, Y: int, Z: int, m1: int, m2: int, m3: int) -> bool:
+    """valid modes for the field, within the sizes the kernels cover (dpot_fno3_max_size)"""
+    lib = _lib.load()
+    n, m = lib.dpot_fno3_max_size(0), lib.dpot_fno3_max_size(1)
+    return (min(X, Y, Z, m1, m2, m3) >= 1 and 2 * m1 <= X and 2 * m2 <= Y and m3 <= Z // 2 + 1 and max(X, Y, Z) <= n
+            and max(m1, m2, m3) <= m)
+
+
+def fno3_twiddles(X: int, Y: int, Z: int, m1: int, m2: int, m3: int):
+    """float64 (tx [X, 2 m1, 2], ty [Y, 2 m2, 2], tz [Z, m3, 2]): cos | sin of 2 pi k n / N over the kept wavenumbers, the angle
+    reduced in integers.  (tx, tz) and (ty, tz) are fno_twiddles tables: the plane kernels are FNO2d's"""
+    tx, tz = fno_twiddles(X, Z, m1, m3)
+    ty, _ = fno_twiddles(Y, Z, m2, m3)
+    return tx, ty, tz
+
+
+class FNO3Plan:
+    """The twiddle tables of dpot_fno3_rfft3 / dpot_fno3_irfft3 for one (X, Y, Z, m1, m2, m3), built in float64, rounded to fp32
+    and kept in device memory."""
+
+    def __init__(self, X: int, Y: int, Z: int, m1: int, m2: int, m3: int, device):
+        fno3_check_modes(X, Y, Z, m1, m2, m3, "FNO3Plan")
+        if not fno3_supported(X, Y, Z, m1, m2, m3):
+            lib = _lib.load()
+            raise ValueError(f"FNO3Plan: field {X}x{Y}x{Z} with modes ({m1}, {m2}, {m3}) is beyond the kernels' limits (X, Y, Z "
+                             f"<= {lib.dpot_fno3_max_size(0)}, modes <= {lib.dpot_fno3_max_size(1)})")
+        self.sizes = (X, Y, Z, m1, m2, m3)
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DpotHipError(f"FNO3Plan {self.sizes}: the tables are uploaded when a size tuple is first used - call "
+                                    "ops.fno3_plan(...) (or the operator itself) once before capturing")
+        for name, t in zip(("tx", "ty", "tz"), fno3_twiddles(X, Y, Z, m1, m2, m3)):
+            dev = torch.empty(t.shape, dtype=torch.float32, device=device)
+            dev.copy_(torch.from_numpy(t.astype("float32")))
+            setattr(self, name, dev)
+
+
+_fno3_plans = {}
+
+
+def fno3_plan(X: int, Y: int, Z: int, m1: int, m2: int, m3: int, device) -> FNO3Plan:
+    """the cached FNO3Plan of (X, Y, Z, m1, m2, m3, device)"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(X), int(Y), int(Z), int(m1), int(m2), int(m3), device)
+    plan = _fno3_plans.get(key)
+    if plan is None:
+        plan = _fno3_plans[key] = FNO3Plan(*key)
+    return plan
+
+
+def _fno3_ws(B: int, X: int, C: int, m2: int, m3: int, device) -> Tensor:
+    """the workspace between the two launches of a transform: [B, X, 2 m2, m3, 2, C], dropped when the operator returns"""
+    n = _lib.load().dpot_fno3_ws_elems(B, X, C, m2, m3)
+    return _scratch(torch.empty(n, dtype=torch.float32, device=device))
+
+
+def fno3_rfft3(x: Tensor, m1: int, m2: int, m3: int, adjoint: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """x [B, X, Y, Z, C] -> the kept spectrum S [B, 2 m1, 2 m2, m3, 2, C] of the unnormalised rfftn.  adjoint=True: the adjoint
+    of fno3_irfft3 instead (the same sums times w(kz) / (X Y Z)): the gradient of the spectrum from the gradient of the field"""
+    if x.dim() != 5 or x.numel() == 0:
+        raise ValueError(f"fno3_rfft3: the field must be a non-empty [B, X, Y, Z, C], got {tuple(x.shape)}")
+    B, X, Y, Z, Cc = x.shape
+    fno3_check_modes(X, Y, Z, m1, m2, m3, "fno3_rfft3")
+    _req(x, "fno3_rfft3: x")
+    plan = fno3_plan(X, Y, Z, m1, m2, m3, x.device)
+    shape = (B, 2 * m1, 2 * m2, m3, 2, Cc)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif tuple(_req(out, "fno3_rfft3: out").shape) != shape or out.device != x.device:
+        raise ValueError(f"fno3_rfft3: out must be {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
+    ws = _fno3_ws(B, X, Cc, m2, m3, x.device)
+    check(_lib.load().dpot_fno3_rfft3(x.data_ptr(), out.data_ptr(), ws.data_ptr(), plan.tx.data_ptr(), plan.ty.data_ptr(),
+                                      plan.tz.data_ptr(), B, X, Y, Z, Cc, m1, m2, m3, 1 if adjoint else 0,
+                                      1.0 / (X * Y * Z) if adjoint else 1.0, _stream()), "fno3_rfft3")
+    return out
+
+
+def fno3_irfft3(S: Tensor, X: int, Y: int, Z: int, add: Optional[Tensor] = None, act: int = 0, save_pre: bool = False,
+                adjoint: bool = False, out: Optional[Tensor] = None):
+    """the kept spectrum S [B, 2 m1, 2 m2, m3, 2, C] -> (y, pre): y [B, X, Y, Z, C] = act(irfftn(S, s=(X, Y, Z)) + add), pre
+    the value before the activation (save_pre, else None).  adjoint=True: the adjoint of fno3_rfft3 instead (weights 1, no
+    1 / (X Y Z)): the gradient of the field from the gradient of its spectrum"""
+    if S.dim() != 6 or S.shape[4] != 2 or S.shape[1] % 2 or S.shape[2] % 2 or S.numel() == 0:
+        raise ValueError(f"fno3_irfft3: the spectrum must be a non-empty [B, 2 m1, 2 m2, m3, 2, C], got {tuple(S.shape)}")
+    B, R, Q, m3, _, Cc = S.shape
+    m1, m2 = R // 2, Q // 2
+    fno3_check_modes(X, Y, Z, m1, m2, m3, "fno3_irfft3")
+    _req(S, "fno3_irfft3: S")
+    plan = fno3_plan(X, Y, Z, m1, m2, m3, S.device)
+    shape = (B, X, Y, Z, Cc)
+    if add is not None and (tuple(_req(add, "fno3_irfft3: add").shape) != shape or add.device != S.device):
+        raise ValueError(f"fno3_irfft3: add must be {shape} on {S.device}, got {tuple(add.shape)} on {add.device}")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=S.device)
+    elif tuple(_req(out, "fno3_irfft3: out").shape) != shape or out.device != S.device:
+        raise ValueError(f"fno3_irfft3: out must be {shape} on {S.device}, got {tuple(out.shape)} on {out.device}")
+    pre = torch.empty_like(out) if save_pre else None
+    ws = _fno3_ws(B, X, Cc, m2, m3, S.device)
+    check(_lib.load().dpot_fno3_irfft3(S.data_ptr(), _p(add), out.data_ptr(), _p(pre), ws.data_ptr(), plan.tx.data_ptr(),
+                                       plan.ty.data_ptr(), plan.tz.data_ptr(), B, X, Y, Z, Cc, m1, m2, m3, 0 if adjoint else 1,
+                                       1.0 if adjoint else 1.0 / (X * Y * Z), int(act), _stream()), "fno3_irfft3")
+    return out, pre
+
+
+def _fno3_weights(ws, what: str):
+    if len(ws) != 4:
+        raise ValueError(f"{what}: four corner weights (weights1..weights4), got {len(ws)}")
+    for k, w in enumerate(ws):
+        _req(w, f"{what}: weights{k + 1}")
+        if w.dim() != 6 or w.shape[5] != 2 or w.shape != ws[0].shape or w.numel() == 0:
+            raise ValueError(f"{what}: every weight must be the real-pair [Cin, Cout, m1, m2, m3, 2], got "
+                             f"{[tuple(t.shape) for t in ws]}")
+    return tuple(ws[0].shape[:5])
+
+
+def fno3_mix(X: Tensor, ws, adjoint: bool = False) -> Tensor:
+    """O[b, r, q, kz, :, o] = sum_i X[b, r, q, kz, :, i] W[i, o, r mod m1, q mod m2, kz] (complex), W the corner weight
+    1 + (r >= m1) + 2 (q >= m2) of `ws` = (weights1..weights4), read in place.  adjoint=True: sum over o with conj(W)"""
+    Cin, Cout, m1, m2, m3 = _fno3_weights(ws, "fno3_mix")
+    K, N = (Cout, Cin) if adjoint else (Cin, Cout)
+    _req(X, "fno3_mix: X")
+    if tuple(X.shape[1:]) != (2 * m1, 2 * m2, m3, 2, K) or X.shape[0] < 1:
+        raise ValueError(f"fno3_mix: the spectrum must be [B, {2 * m1}, {2 * m2}, {m3}, 2, {K}], got {tuple(X.shape)}")
+    B = X.shape[0]
+    O = torch.empty(B, 2 * m1, 2 * m2, m3, 2, N, dtype=torch.float32, device=X.device)
+    check(_lib.load().dpot_fno3_mix(X.data_ptr(), *(w.data_ptr() for w in ws), O.data_ptr(), B, Cin, Cout, m1, m2, m3,
+                                    1 if adjoint else 0, _stream()), "fno3_mix")
+    return O
+
+
+def fno3_mix_wgrad(X: Tensor, dO: Tensor, outs=None, accumulate: bool = False):
+    """(dweights1..dweights4) [Cin, Cout, m1, m2, m3, 2] from the layer's input spectrum X [B, 2 m1, 2 m2, m3, 2, Cin] and the
+    gradient dO [.., Cout] of its output spectrum, summed over b in ascending order; outs: four buffers to write (None entries are
+    allocated); accumulate: added to them"""
+    _req(X, "fno3_mix_wgrad: X")
+    _req(dO, "fno3_mix_wgrad: dO")
+    if X.dim() != 6 or dO.dim() != 6 or X.shape[:5] != dO.shape[:5] or X.shape[4] != 2 or X.shape[1] % 2 or X.shape[2] % 2 \
+            or X.numel() == 0 or dO.numel() == 0:
+        raise ValueError(f"fno3_mix_wgrad: X [B, 2 m1, 2 m2, m3, 2, Cin] and dO [B, 2 m1, 2 m2, m3, 2, Cout], got "
+                         f"{tuple(X.shape)} and {tuple(dO.shape)}")
+    B, R, Q, m3, _, Cin = X.shape
+    Cout, m1, m2 = dO.shape[5], R // 2, Q // 2
+    shape = (Cin, Cout, m1, m2, m3, 2)
+    outs = list(outs) if outs is not None else [None] * 4
+    if len(outs) != 4 or (accumulate and any(o is None for o in outs)):
+        raise ValueError("fno3_mix_wgrad: outs holds four buffers, and accumulate needs all of them")
+    for k, o in enumerate(outs):
+        if o is None:
+            outs[k] = torch.empty(shape, dtype=torch.float32, device=X.device)
+        elif tuple(_req(o, "fno3_mix_wgrad: out").shape) != shape or o.device != X.device:
+            raise ValueError(f"fno3_mix_wgrad: out must be {shape} on {X.device}, got {tuple(o.shape)} on {o.device}")
+    check(_lib.load().dpot_fno3_mix_wgrad(X.data_ptr(), dO.data_ptr(), *(o.data_ptr() for o in outs), B, Cin, Cout, m1, m2, m3,
+                                          1 if accumulate else 0, _stream()), "fno3_mix_wgrad")
+    return tuple(outs)

@@ -102,6 +102,14 @@ class FlatParams:
         self.epoch += 1
 
 
+def complex_pair_ranges(flat: FlatParams, n_active: int):
+    """[(name, (lo, hi))] of the updated tensors of ``flat`` whose parameter is marked ``_dpot_complex_pairs`` (a complex tensor
+    stored as its view_as_real: FNO3d's spectral weights): float ranges of the flat buffer.  Tensors start on 4-float
+    boundaries and hold whole pairs, so no pair straddles a tensor"""
+    return [(n, (off, off + p.numel())) for n, p, off in zip(flat.names, flat.params, flat.offsets)
+            if getattr(p, "_dpot_complex_pairs", False) and off < n_active]
+
+
 class FlatOptimizer:
     """The fused optimisers over a FlatParams buffer: everything but the update rule.  Moments, the device-side step counter,
     the global-norm clip, snapshot / restore and the reference's torch.optim checkpoint layout live here.  A subclass sets
@@ -263,7 +271,9 @@ class FusedAdam(FlatOptimizer):
     """Adam with L2 weight decay folded into the gradient (utils/optimizer.py:9-52 semantics) + global-norm clip
     (train_temporal.py:228), as ONE kernel over the flat buffer.  ``update_tail=False`` reproduces the single-GPU
     reference where cls_head has no gradient and is therefore skipped by the optimiser.  Checkpoint state per tensor:
-    'step', 'exp_avg', 'exp_avg_sq' (utils/optimizer.py:101-164)."""
+    'step', 'exp_avg', 'exp_avg_sq' (utils/optimizer.py:101-164).  Parameters marked ``_dpot_complex_pairs`` (FNO3d's spectral
+    weights) get ONE second moment per (re, im) pair, the reference's rule for complex parameters - still one launch
+    (ops.adam_step_pairs); their moments are kept, and saved, as real pairs."""
     HYPER = 8
     GROUP_EXTRA = {"amsgrad": False}
 
@@ -271,16 +281,26 @@ class FusedAdam(FlatOptimizer):
                  eps: float = 1e-8, weight_decay: float = 0.0, max_norm: Optional[float] = None,
                  update_tail: bool = False):
         super().__init__(flat, lr, betas, eps, weight_decay, max_norm, update_tail)
+        # complex parameters stored as (re, im) pairs (FNO3d's spectral weights): one second moment per pair, as the reference's
+        # Adam forms it (utils/optimizer.py:41).  The table is built once; without such a tensor nothing changes
+        pairs = complex_pair_ranges(flat, self.n_active)
+        self.pair_ranges = ops.adam_pair_ranges([r for _, r in pairs], flat.flat.device) if pairs else None
 
     def _stage(self, max_norm: float, advance: int) -> None:
         ops.adam_stage(self.hyper, self.step_dev, self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
                        max_norm, advance)
 
     def _pack_plan(self):
+        if self.pair_ranges is not None:
+            return None
         return self.packs.adam_plan(self.fp.flat, self.n_active) if self.packs is not None else None
 
     def _update(self, plan, sumsq: Optional[Tensor], grad_scale: float) -> None:
-        if plan is not None:
+        if self.pair_ranges is not None:
+            n = self.n_active
+            ops.adam_step_pairs(self.fp.flat[:n], self.fp.grad[:n], self.exp_avg[:n], self.exp_avg_sq[:n], self.hyper, sumsq,
+                                self.pair_ranges, grad_scale)
+        elif plan is not None:
             # round 6: the channel-MLP weights leave the optimiser ALSO as their two bf16 packs - the next forward's pack
             # launch (a second read of every weight written here) disappears (the owner sees them fresh)
             ops.adam_step_packs(plan, self.fp.flat, self.fp.grad, self.exp_avg, self.exp_avg_sq, self.hyper, sumsq,
@@ -319,6 +339,10 @@ class FusedLamb(FlatOptimizer):
         if clamp_value < 0.0:
             raise ValueError(f"Invalid clamp value: {clamp_value}")
         super().__init__(flat, lr, tuple(betas), eps, weight_decay, max_norm, update_tail)
+        pairs = complex_pair_ranges(flat, self.n_active)
+        if pairs:
+            raise ValueError(f"FusedLamb: parameter {pairs[0][0]!r} holds complex numbers as (re, im) pairs ({len(pairs)} such "
+                             "tensors); LAMB's per-pair second moment and complex norms are not built - use FusedAdam")
         self.clamp_value, self.adam, self.debias = clamp_value, adam, debias
         n_act, dev = self.n_active, flat.flat.device
         # the tensors the optimiser updates (FlatParams.offsets are ordered; the tail starts at n_head): a prefix of flat.params

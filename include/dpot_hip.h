@@ -564,6 +564,14 @@ int dpot_sumsq(const float* g, int64_t n, float* out, float* part, int accumulat
 int dpot_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
                    const float* sumsq, float grad_scale, dpot_stream_t stream);
 
+/* dpot_adam_step over a flat buffer that holds complex parameters stored as (re, im) float pairs (FNO3d's spectral weights):
+ * inside the float ranges [ranges[2k], ranges[2k+1]) (DEVICE int64 table, n_ranges entries, ascending, even bounds) the second
+ * moment of a pair is shared, v = b2*v + (1-b2)*(g're^2 + g'im^2) written to both slots (utils/optimizer.py:41 accumulates
+ * grad * conj(grad)); g', m and the update are per component.  Outside the ranges: dpot_adam_step, bit for bit.  n even, the
+ * buffers 8-byte aligned.  One launch, capturable. */
+int dpot_adam_step_pairs(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, const float* sumsq,
+                         float grad_scale, const int64_t* ranges, int n_ranges, dpot_stream_t stream);
+
 /* Host side of an optimiser step (utils/optimizer.py:139-141: state['step'] += 1, bias corrections) as ONE one-thread
  * launch whose arguments travel by value: step[0] += advance (DEVICE int64), hyper = {lr, beta1, beta2, eps,
  * weight_decay, 1-beta1^step, 1-beta2^step, max_norm (0 = no clip)}; the betas are doubles so that the bias
@@ -1024,6 +1032,39 @@ int dpot_fno_mix(const float* X, const float* w1, const float* w2, float* O, int
 int dpot_fno_mix_wgrad(const float* X, const float* dO, float* dw1, float* dw2, int B, int Cin, int Cout, int m1, int m2,
                        int accumulate, dpot_stream_t stream);
 int dpot_fno_dact(const float* dy, const float* pre, float* dpre, int64_t n, int act, dpot_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The 3-D FNO baseline (csrc/fno3.hip; the reference's models/fno.py SpectralConv3d) on channels-last fields x[B, X, Y, Z, C]:
+ *   y = act( irfftn( W . rfftn(x) on the kept modes ) + add )
+ * Kept modes: kx in [0, m1) and [X - m1, X), ky in [0, m2) and [Y - m2, Y), kz in [0, m3); 2 m1 <= X, 2 m2 <= Y and
+ * m3 <= Z/2 + 1 (else DPOT_EINVAL).  Kept spectrum S[B][2 m1][2 m2][m3][2 = re | im][C]: kept row r is kx = r below m1 and
+ * kx = X - 2 m1 + r above, the same rule for q and ky.  The weight block of a kept mode is 1 + (r >= m1) + 2 (q >= m2).
+ * tx[X][2 m1][2], ty[Y][2 m2][2], tz[Z][m3][2]: cos | sin of 2 pi k n / N over the kept wavenumbers, device arrays
+ * (dpot_amd/ops.py FNO3Plan builds them in float64).  w(kz) = 1 at kz = 0 and, for even Z, at kz = Z/2, else 2.
+ * ws: dpot_fno3_ws_elems(B, X, C, m2, m3) = B X 2 m2 m3 2 C floats owned by the caller, (2 m2 / Y)(2 m3 / Z) of the field.
+ *   dpot_fno3_rfft3   S = scale * (col_weights ? w(kz) : 1) * sum_{x,y,z} x e^{-2 pi i (kx x / X + ky y / Y + kz z / Z)}
+ *   dpot_fno3_irfft3  y = act( scale * Re sum (col_weights ? w(kz) : 1) S e^{+2 pi i (...)} + add ); add and pre may be NULL.
+ *                     irfftn of the reference: col_weights = 1, scale = 1 / (X Y Z).  With col_weights = 0, scale = 1, no add
+ *                     and act = 0 each transform is the adjoint of the other.
+ *   dpot_fno3_mix     O[b, g, o] = sum_i X[b, g, i] W[i, o, g'] per kept mode g, W the block's parameter
+ *                     [Cin][Cout][m1][m2][m3][2 = re | im] (the view_as_real of a cfloat tensor) read in place.
+ *                     adjoint = 1: O[b, g, i] = sum_o X[b, g, o] conj(W[i, o, g']): the data gradient.
+ *   dpot_fno3_mix_wgrad  dW[i, o, g'] = sum_b conj(X[b, g, i]) dO[b, g, o], b ascending, in the parameters' layout;
+ *                     accumulate = 1 adds to dw1..dw4.
+ * Sizes: X, Y, Z <= dpot_fno3_max_size(0) (= 128), m1, m2, m3 <= dpot_fno3_max_size(1) (= 32) - beyond: DPOT_EUNSUP, nothing
+ * is launched; B * X <= 65535.  Two launches per transform, one per mixing; reads nothing outside the tensors, fixed summation
+ * order, no atomics, no allocation, legal under stream capture. */
+int dpot_fno3_max_size(int modes);
+int64_t dpot_fno3_ws_elems(int B, int X, int C, int m2, int m3);
+int dpot_fno3_rfft3(const float* x, float* S, float* ws, const float* tx, const float* ty, const float* tz, int B, int X, int Y,
+                    int Z, int C, int m1, int m2, int m3, int col_weights, float scale, dpot_stream_t stream);
+int dpot_fno3_irfft3(const float* S, const float* add, float* y, float* pre, float* ws, const float* tx, const float* ty,
+                     const float* tz, int B, int X, int Y, int Z, int C, int m1, int m2, int m3, int col_weights, float scale,
+                     int act, dpot_stream_t stream);
+int dpot_fno3_mix(const float* X, const float* w1, const float* w2, const float* w3, const float* w4, float* O, int B, int Cin,
+                  int Cout, int m1, int m2, int m3, int adjoint, dpot_stream_t stream);
+int dpot_fno3_mix_wgrad(const float* X, const float* dO, float* dw1, float* dw2, float* dw3, float* dw4, int B, int Cin,
+                        int Cout, int m1, int m2, int m3, int accumulate, dpot_stream_t stream);
 
 #ifdef __cplusplus
 }
