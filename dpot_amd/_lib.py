@@ -124,6 +124,8 @@ SIGNATURES = {
     "dpot_afno_unpack_grad": (c_i, [c_fp] * 4 + [c_i, c_i, c_fp]),
     "dpot_afno_mlp2_supported": (c_i, [c_i, c_i]),
     "dpot_afno_mlp2": (c_i, [c_fp] * 9 + [c_i] * 8 + [c_fp]),
+    "dpot_afno_mlp2_plan": (c_i, [c_i] * 5 + [C.POINTER(c_i)]),
+    "dpot_afno_mlp2_plans": (c_i, [C.POINTER(c_i), c_i]),
     "dpot_afno_mlp3_supported": (c_i, [c_i, c_i]),
     "dpot_afno_mlp6_supported": (c_i, [c_i, c_i]),
     "dpot_afno_pack6_elems": (c_i64, [c_i, c_i]),

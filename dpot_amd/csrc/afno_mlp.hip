@@ -849,6 +849,17 @@ __global__ __launch_bounds__(256) void afno_pack_all_kernel(const dpot_afno_pack
 
 constexpr int AFNO_NUM_CU = 256;
 
+// ---- kernel selection in ONE place: dpot_afno_mlp2 launches what afno_plan names, dpot_afno_mlp2_plan reports it and
+// dpot_afno_mlp2_plans lists every instantiation it can name (tests/afno_mixer_cases.py holds a case for each) ---------------
+enum { AFNO_FORM_REFUSED = -1, AFNO_FORM_FOUR = 0, AFNO_FORM_THREE = 1, AFNO_FORM_THREE_SPLIT = 2 };
+struct AfnoPlan {
+  int form;     // AFNO_FORM_*
+  int rt;       // 16-row tiles per panel
+  int panels;   // ceil(M / (16 rt)); the grid is nb * panels workgroups
+  int waves;    // compute waves: bs / 16, or 8 in the split form
+  int gelu;     // 1: the GELU instantiation; 0: every other activation goes through the run-time switch
+};
+
 // rows per panel (multiple of 16, <= 80): fewest rounds of (panels * nb) workgroups over the CUs, one workgroup per CU
 static int pick_rt(int M, int nb) {
   long long best_cost = -1;
@@ -866,10 +877,35 @@ static int pick_rt(int M, int nb) {
   return best;
 }
 
+// the form of (bs, layout) at rt row tiles, AFNO_FORM_REFUSED where no kernel exists: layout 0 is the four-product kernel for
+// 2*bs in {64, 128, 192, 256}; layout 1 the three-product kernel for bs in {64, 96, 128}, whose six column tiles of bs = 96 go
+// on eight compute waves from two row tiles on
+static int afno_form(int bs, int layout, int rt) {
+  if (rt < 1 || rt > 5) return AFNO_FORM_REFUSED;
+  if (layout == 0) return bs == 32 || bs == 64 || bs == 96 || bs == 128 ? AFNO_FORM_FOUR : AFNO_FORM_REFUSED;
+  if (layout != 1 || !(bs == 64 || bs == 96 || bs == 128)) return AFNO_FORM_REFUSED;
+  return bs == 96 && rt >= 2 ? AFNO_FORM_THREE_SPLIT : AFNO_FORM_THREE;
+}
+
+static AfnoPlan afno_plan(int M, int nb, int bs, int layout, int act) {
+  AfnoPlan pl{AFNO_FORM_REFUSED, 0, 0, 0, 0};
+  if (M <= 0 || nb <= 0) return pl;
+  const int rt = pick_rt(M, nb);
+  const int form = afno_form(bs, layout, rt);
+  if (form == AFNO_FORM_REFUSED) return pl;
+  pl.form = form;
+  pl.rt = rt;
+  pl.panels = (M + 16 * rt - 1) / (16 * rt);
+  pl.waves = form == AFNO_FORM_THREE_SPLIT ? 8 : bs / 16;
+  pl.gelu = act == DPOT_ACT_GELU ? 1 : 0;
+  return pl;
+}
+
+// the instantiation of a plan: every template argument comes from the plan, none from the call's arguments
 template <int NW, int ACTK>
-static int launch_rt(const AfnoMlpArgs& p, int rt, hipStream_t s) {
-  const dim3 grid((unsigned)(p.nb * p.panels)), blk(64 * (NW + 2));
-  switch (rt) {
+static int launch_rt(const AfnoMlpArgs& p, const AfnoPlan& pl, hipStream_t s) {
+  const dim3 grid((unsigned)(p.nb * pl.panels)), blk(64 * (NW + 2));
+  switch (pl.rt) {
     case 1: hipLaunchKernelGGL((afno_mlp2_kernel<1, NW, ACTK>), grid, blk, 0, s, p); break;
     case 2: hipLaunchKernelGGL((afno_mlp2_kernel<2, NW, ACTK>), grid, blk, 0, s, p); break;
     case 3: hipLaunchKernelGGL((afno_mlp2_kernel<3, NW, ACTK>), grid, blk, 0, s, p); break;
@@ -879,38 +915,51 @@ static int launch_rt(const AfnoMlpArgs& p, int rt, hipStream_t s) {
   return check_launch("afno_mlp2_kernel");
 }
 template <int BS, int ACTK>
-static int launch3_rt(const AfnoMlpArgs& p, int rt, hipStream_t s) {
-  const dim3 grid((unsigned)(p.nb * p.panels)), blk(64 * (BS / 16 + 2));
+static int launch3_rt(const AfnoMlpArgs& p, const AfnoPlan& pl, hipStream_t s) {
+  const dim3 grid((unsigned)(p.nb * pl.panels)), blk(64 * (BS / 16 + 2));
   if constexpr (BS == 96) {
-    // six column tiles on eight compute waves (afno_mlp3_kernel<.., SPLIT>)
-    if (rt >= 2) {
-      const dim3 blk8(64 * 10);
-      switch (rt) {
+    // six column tiles: one wave each at RT = 1, on eight compute waves (afno_mlp3_kernel<.., SPLIT>) from RT = 2 on
+    const dim3 blk8(64 * 10);
+    if (pl.form == AFNO_FORM_THREE_SPLIT) {
+      switch (pl.rt) {
         case 2: hipLaunchKernelGGL((afno_mlp3_kernel<2, BS, ACTK, true>), grid, blk8, 0, s, p); break;
         case 3: hipLaunchKernelGGL((afno_mlp3_kernel<3, BS, ACTK, true>), grid, blk8, 0, s, p); break;
         case 4: hipLaunchKernelGGL((afno_mlp3_kernel<4, BS, ACTK, true>), grid, blk8, 0, s, p); break;
         default: hipLaunchKernelGGL((afno_mlp3_kernel<5, BS, ACTK, true>), grid, blk8, 0, s, p); break;
       }
-      return check_launch("afno_mlp3_kernel");
+    } else {
+      hipLaunchKernelGGL((afno_mlp3_kernel<1, BS, ACTK>), grid, blk, 0, s, p);
     }
-  }
-  switch (rt) {
-    case 1: hipLaunchKernelGGL((afno_mlp3_kernel<1, BS, ACTK>), grid, blk, 0, s, p); break;
-    case 2: hipLaunchKernelGGL((afno_mlp3_kernel<2, BS, ACTK>), grid, blk, 0, s, p); break;
-    case 3: hipLaunchKernelGGL((afno_mlp3_kernel<3, BS, ACTK>), grid, blk, 0, s, p); break;
-    case 4: hipLaunchKernelGGL((afno_mlp3_kernel<4, BS, ACTK>), grid, blk, 0, s, p); break;
-    default: hipLaunchKernelGGL((afno_mlp3_kernel<5, BS, ACTK>), grid, blk, 0, s, p); break;
+  } else {
+    switch (pl.rt) {
+      case 1: hipLaunchKernelGGL((afno_mlp3_kernel<1, BS, ACTK>), grid, blk, 0, s, p); break;
+      case 2: hipLaunchKernelGGL((afno_mlp3_kernel<2, BS, ACTK>), grid, blk, 0, s, p); break;
+      case 3: hipLaunchKernelGGL((afno_mlp3_kernel<3, BS, ACTK>), grid, blk, 0, s, p); break;
+      case 4: hipLaunchKernelGGL((afno_mlp3_kernel<4, BS, ACTK>), grid, blk, 0, s, p); break;
+      default: hipLaunchKernelGGL((afno_mlp3_kernel<5, BS, ACTK>), grid, blk, 0, s, p); break;
+    }
   }
   return check_launch("afno_mlp3_kernel");
 }
 template <int BS>
-static int launch3(const AfnoMlpArgs& p, int rt, hipStream_t s) {
-  return p.act == DPOT_ACT_GELU ? launch3_rt<BS, DPOT_ACT_GELU>(p, rt, s) : launch3_rt<BS, -1>(p, rt, s);
+static int launch3(const AfnoMlpArgs& p, const AfnoPlan& pl, hipStream_t s) {
+  return pl.gelu ? launch3_rt<BS, DPOT_ACT_GELU>(p, pl, s) : launch3_rt<BS, -1>(p, pl, s);
 }
 template <int NW>
-static int launch_nw(const AfnoMlpArgs& p, int rt, hipStream_t s) {
+static int launch_nw(const AfnoMlpArgs& p, const AfnoPlan& pl, hipStream_t s) {
   // GELU (the DPOT default) gets its own instantiation; every other activation goes through the run-time switch
-  return p.act == DPOT_ACT_GELU ? launch_rt<NW, DPOT_ACT_GELU>(p, rt, s) : launch_rt<NW, -1>(p, rt, s);
+  return pl.gelu ? launch_rt<NW, DPOT_ACT_GELU>(p, pl, s) : launch_rt<NW, -1>(p, pl, s);
+}
+static int launch_plan(const AfnoMlpArgs& p, const AfnoPlan& pl, int bs, hipStream_t s) {
+  if (pl.form == AFNO_FORM_FOUR) {
+    switch (bs / 16) {                                  // = NW, the compute waves
+      case 2: return launch_nw<2>(p, pl, s);
+      case 4: return launch_nw<4>(p, pl, s);
+      case 6: return launch_nw<6>(p, pl, s);
+      default: return launch_nw<8>(p, pl, s);
+    }
+  }
+  return bs == 128 ? launch3<128>(p, pl, s) : bs == 96 ? launch3<96>(p, pl, s) : launch3<64>(p, pl, s);
 }
 
 }  // namespace dpot
@@ -959,17 +1008,36 @@ extern "C" int dpot_afno_mlp2(const float* X, const float* WaT, const float* ba,
   DPOT_REQUIRE(aligned16(X) && aligned16(WaT) && aligned16(WbT) && aligned16(Y) && aligned16(ba) && aligned16(bb) &&
                    aligned16(aux) && aligned16(pre) && aligned16(mid),
                "afno_mlp2: pointers must be 16-byte aligned");
+  const AfnoPlan pl = afno_plan(M, nb, bs, layout, act);
+  DPOT_REQUIRE(pl.form != AFNO_FORM_REFUSED, "afno_mlp2: no kernel for nb=%d bs=%d layout=%d", nb, bs, layout);
   AfnoMlpArgs p;
   p.X = X; p.Wa = WaT; p.Wb = WbT; p.ba = ba; p.bb = bb; p.aux = aux; p.pre = pre; p.mid = mid; p.Y = Y;
   p.ldx = ldx; p.ldo = ldo; p.M = M; p.nb = nb; p.act = act; p.mode = mode;
-  const int rt = pick_rt(M, nb);
-  p.panels = (M + 16 * rt - 1) / (16 * rt);
-  hipStream_t s = as_stream(stream);
-  if (layout == 1) return bs == 128 ? launch3<128>(p, rt, s) : bs == 96 ? launch3<96>(p, rt, s) : launch3<64>(p, rt, s);
-  switch (N / 64) {
-    case 1: return launch_nw<2>(p, rt, s);
-    case 2: return launch_nw<4>(p, rt, s);
-    case 3: return launch_nw<6>(p, rt, s);
-    default: return launch_nw<8>(p, rt, s);
+  p.panels = pl.panels;
+  return launch_plan(p, pl, bs, as_stream(stream));
+}
+
+extern "C" int dpot_afno_mlp2_plan(int M, int nb, int bs, int layout, int act, int* out) {
+  const AfnoPlan pl = afno_plan(M, nb, bs, layout, act);
+  if (out) {
+    out[0] = pl.form; out[1] = pl.rt; out[2] = pl.panels; out[3] = pl.waves; out[4] = pl.gelu;
   }
+  return pl.form;
+}
+
+extern "C" int dpot_afno_mlp2_plans(int* out, int cap) {
+  // every (bs, layout, RT, gelu) afno_form admits: the tuples launch_plan has an instantiation for
+  static const int widths[] = {32, 64, 96, 128};
+  int n = 0;
+  for (int layout = 0; layout < 2; ++layout)
+    for (int bs : widths)
+      for (int rt = 1; rt <= 5; ++rt) {
+        const int form = afno_form(bs, layout, rt);
+        if (form == AFNO_FORM_REFUSED) continue;
+        for (int gelu = 1; gelu >= 0; --gelu, ++n)
+          if (out && n < cap) {
+            out[4 * n] = form; out[4 * n + 1] = bs; out[4 * n + 2] = rt; out[4 * n + 3] = gelu;
+          }
+      }
+  return n;
 }

@@ -66,7 +66,9 @@ int tune(const char* key, int dflt) {
  * GroupNorm route selection the launchers read; nothing existing changed
  * 277: dpot_fno3_rfft3, dpot_fno3_irfft3, dpot_fno3_mix, dpot_fno3_mix_wgrad, dpot_fno3_max_size, dpot_fno3_ws_elems
  * (csrc/fno3.hip): the kernels of the 3-D FNO baseline; dpot_adam_step_pairs (csrc/loss_opt.hip): Adam with one second moment
- * per complex pair; nothing existing changed */
-extern "C" int dpot_version(void) { return 277; }
+ * per complex pair; nothing existing changed
+ * 278: dpot_afno_mlp2_plan, dpot_afno_mlp2_plans (csrc/afno_mlp.hip): host-only queries of the mixer's kernel selection the
+ * launcher reads; nothing existing changed */
+extern "C" int dpot_version(void) { return 278; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

@@ -1236,24 +1236,88 @@ def afno_mlp6_wanted() -> bool:
     return _cur_gemm() in (GEMM_AUTO, GEMM_BF16X6)
 
 
+AFNO_FOUR, AFNO_THREE, AFNO_THREE_SPLIT, AFNO_REFUSED = 0, 1, 2, -1
+
+
+class AfnoPlan(NamedTuple):
+    """what dpot_afno_mlp2_plan reports: form (AFNO_FOUR / AFNO_THREE / AFNO_THREE_SPLIT / AFNO_REFUSED), 16-row tiles per
+    panel, panels per block (the grid is nb * panels), compute waves, GELU instantiation (else the run-time switch)"""
+    form: int
+    rt: int
+    panels: int
+    waves: int
+    gelu: bool
+
+
+def afno_mlp2_plan(M: int, nb: int, bs: int, layout: int = 0, act: int = 1) -> AfnoPlan:
+    """the kernel instantiation afno_mlp2 (layout 0 / 1) launches for this call, from the library's own selection
+    (dpot_afno_mlp2_plan); form AFNO_REFUSED where the call is refused"""
+    buf = (C.c_int * 5)()
+    _lib.load().dpot_afno_mlp2_plan(M, nb, bs, layout, act, buf)
+    return AfnoPlan(buf[0], buf[1], buf[2], buf[3], bool(buf[4]))
+
+
+def afno_mlp2_plans() -> Tuple[Tuple[int, int, int, bool], ...]:
+    """every instantiation afno_mlp2_plan can name, as (form, bs, rt, gelu)"""
+    cap = 128
+    buf = (C.c_int * (4 * cap))()
+    n = _lib.load().dpot_afno_mlp2_plans(buf, cap)
+    assert n <= cap
+    return tuple((buf[4 * i], buf[4 * i + 1], buf[4 * i + 2], bool(buf[4 * i + 3])) for i in range(n))
+
+
+def _afno_ld(t: Tensor, name: str, M: int, cols: int) -> int:
+    """the leading dimension of a [M, >= cols] operand of afno_mlp2 (its row stride), or a ValueError for what the kernels
+    cannot express: they read and write rows of unit-stride floats in 16-byte pieces"""
+    if t.dim() != 2 or t.shape[0] != M or t.shape[1] < cols or t.dtype != torch.float32:
+        raise ValueError(f"afno_mlp2: {name} must be float32 [{M}, >= {cols}], got {t.dtype} {tuple(t.shape)}")
+    if t.stride(1) != 1:
+        raise ValueError(f"afno_mlp2: {name} has inner stride {t.stride(1)}: the rows must be contiguous")
+    ld = t.stride(0) if M > 1 else t.shape[1]            # a single row has no row stride
+    if ld < cols or ld % 4:
+        raise ValueError(f"afno_mlp2: {name} has row stride {ld}: it must be a multiple of 4 and at least {cols}")
+    if t.data_ptr() % 16:
+        raise ValueError(f"afno_mlp2: {name} does not start on a 16-byte boundary")
+    return ld
+
+
 def afno_mlp2(X: Tensor, WaT: Tensor, ba: Optional[Tensor], WbT: Tensor, bb: Optional[Tensor], nb: int, bs: int,
               act: int, mode: int = 0, aux: Optional[Tensor] = None, want_pre: bool = False, want_mid: bool = False,
-              layout: int = 0):
+              layout: int = 0, out_Y: Optional[Tensor] = None, out_pre: Optional[Tensor] = None,
+              out_mid: Optional[Tensor] = None):
     """both layers of the AFNO block-diagonal complex MLP in one launch (csrc/afno_mlp.hip).
     mode 0: pre = X Wa + ba, mid = act(pre), Y = mid Wb + bb;  mode 1: mid = (X Wa) * act'(aux), Y = mid Wb, and with
     want_pre the `pre` output is act(aux) (the forward's activated layer-1 output, re-derived for the weight gradient).
     X / outputs: [M, nb*2*bs]; WaT / WbT: [nb, 2bs, 2bs] fragment-block-major weights from afno_block_weights (`fwd`
-    to multiply by W, `bwd` to multiply by W^T).  Returns (Y, pre | None, mid | None)."""
-    M, ld = X.shape
-    Y = torch.empty_like(X)
-    pre = torch.empty_like(X) if want_pre else None
-    mid = torch.empty_like(X) if want_mid else None
+    to multiply by W, `bwd` to multiply by W^T).  Returns (Y, pre | None, mid | None).
+    X may be a view with a row stride of its own (ldx); the outputs are fresh contiguous tensors, or out_Y / out_pre / out_mid
+    (an out_pre / out_mid implies want_pre / want_mid), whose common row stride is ldo - aux, which the kernels address with
+    ldo as well, must have it too.  Anything else (an inner stride, a row stride that is no multiple of 4, a base off a
+    16-byte boundary, strides that differ) is a ValueError before anything is launched."""
+    M, cols = X.shape[0], nb * 2 * bs
+    ldx = _afno_ld(X, "X", M, cols)
+    given = [(n, t) for n, t in (("out_Y", out_Y), ("out_pre", out_pre), ("out_mid", out_mid), ("aux", aux)) if t is not None]
+    lds = {n: _afno_ld(t, n, M, cols) for n, t in given}
+    ldo = lds.get("out_Y", lds.get("out_pre", lds.get("out_mid", X.shape[1])))
+    if M > 1 and any(v != ldo for v in lds.values()):
+        raise ValueError(f"afno_mlp2: aux and the outputs share one row stride, got {lds} against {ldo}"
+                         + ("" if out_Y is not None else " of the fresh outputs"))
+    if ldo < cols or ldo % 4:
+        raise ValueError(f"afno_mlp2: output row stride {ldo}: it must be a multiple of 4 and at least {cols}")
+
+    def fresh():
+        t = torch.empty((M, ldo), dtype=torch.float32, device=X.device)
+        return t if ldo == X.shape[1] else t[:, :X.shape[1]]
+
+    Y = out_Y if out_Y is not None else fresh()
+    pre = out_pre if out_pre is not None else fresh() if want_pre else None
+    mid = out_mid if out_mid is not None else fresh() if want_mid else None
     if layout == 2:      # WaT / WbT: the bf16x6 packs of AfnoPacks (item.p6), csrc/afno_mlp6.hip
         check(_lib.load().dpot_afno_mlp6(X.data_ptr(), WaT.data_ptr(), _p(ba), WbT.data_ptr(), _p(bb), _p(aux), _p(pre),
-                                         _p(mid), Y.data_ptr(), M, nb, bs, ld, ld, act, mode, _stream()), "afno_mlp6")
+                                         _p(mid), Y.data_ptr(), M, nb, bs, ldx, ldo, act, mode, _stream()), "afno_mlp6")
         return Y, pre, mid
     check(_lib.load().dpot_afno_mlp2(X.data_ptr(), WaT.data_ptr(), _p(ba), WbT.data_ptr(), _p(bb), _p(aux), _p(pre),
-                                     _p(mid), Y.data_ptr(), M, nb, bs, ld, ld, act, mode, layout, _stream()),
+                                     _p(mid), Y.data_ptr(), M, nb, bs, ldx, ldo, act, mode, layout, _stream()),
           "afno_mlp2")
     return Y, pre, mid
 

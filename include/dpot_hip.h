@@ -679,6 +679,15 @@ int dpot_afno_mlp3_supported(int nb, int bs);
 int dpot_afno_mlp2(const float* X, const float* Wa, const float* ba, const float* Wb, const float* bb,
                    const float* aux, float* pre, float* mid, float* Y, int M, int nb, int bs, int ldx, int ldo,
                    int act, int mode, int layout, dpot_stream_t stream);
+/* Host-only: the kernel instantiation dpot_afno_mlp2 launches for (M, nb, bs, layout, act) - the launcher reads the same
+ * function.  Returns the form: 0 four-product (afno_mlp2_kernel), 1 three-product (afno_mlp3_kernel), 2 three-product on eight
+ * compute waves (the SPLIT form: bs = 96 at RT >= 2), -1 refused (what dpot_afno_mlp2's checks of M, nb, bs, layout refuse).
+ * out (may be NULL) = {form, RT (16-row tiles per panel, 1..5), panels (= ceil(M / 16 RT); the grid is nb * panels),
+ * compute waves (bs / 16, or 8 in the SPLIT form), 1 when the GELU instantiation is taken / 0 for the run-time switch}.
+ * dpot_afno_mlp2_plans: every reachable instantiation as (form, bs, RT, gelu) quadruples into out[0 .. 4 * cap), returns
+ * their number. */
+int dpot_afno_mlp2_plan(int M, int nb, int bs, int layout, int act, int* out);
+int dpot_afno_mlp2_plans(int* out, int cap);
 /* The same two-layer mixer MLP on the BF16 matrix cores at fp32 accuracy (csrc/afno_mlp6.hip, "bf16x6": every operand split
  * into three bf16 planes, the six plane products of weight >= 2^-16 accumulated in fp32 on v_mfma_f32_32x32x16_bf16; results
  * agree with dpot_afno_mlp2 to fp32 rounding - same tests, same tolerance).  Arguments, modes and outputs exactly as
