@@ -23,9 +23,11 @@
 // dpot_fno_mix     O[b, g, o] = sum_i X[b, g, i] W[i, o, g] (complex) per kept mode g; lanes run over the modes, so the weights
 //                  - the dominant bytes, mode index innermost in the parameter - are read coalesced IN PLACE: no packed copy.
 //                  A thread keeps 4 samples x 4 outputs (32 accumulators).  adjoint = 1: the data gradient, sum over o with
-//                  conj(W[i, o]).
+//                  conj(W[i, o]).  The kernel is fno_mix_kernel of fno_common.h, which FNO3d runs too; FnoWeights2 below is
+//                  this rank's weight addressing.
 // dpot_fno_mix_wgrad  dW[i, o, g] = sum_b conj(X[b, g, i]) dO[b, g, o], b ascending, a thread keeps a 4 x 4 (i, o) tile of one
-//                  mode; written (or added) coalesced in the parameter's own layout [2][Cin][Cout][m1][m2].
+//                  mode; written (or added) coalesced in the parameter's own layout [2][Cin][Cout][m1][m2]
+//                  (fno_mix_wgrad_kernel of fno_common.h).
 // dpot_fno_dact    dpre = dy act'(pre), elementwise.
 // Nothing outside the tensors is read: every load past H, W, C, m2 or B is predicated to 0.0f (table indices are clamped into
 // the table), stores are masked.  Fixed summation order (one fma chain per output), no atomics, no allocation.
@@ -221,115 +223,31 @@ __global__ __launch_bounds__(FNO_NT) void fno_irfft2_kernel(const FnoArgs a) {
   }
 }
 
-// ---- per-mode channel mixing ---------------------------------------------------------------------------------------------
-// X[B][G][2][K], O[B][G][2][N], G = 2 M kept modes (mode g < M reads w1, the others w2); the weight of (reduced index a,
-// output index n) of mode gm sits at w[a * sa + n * sn + gm], its imaginary part `plane` floats further, times sgn
-template <bool VEC>
-__global__ __launch_bounds__(256) void fno_mix_kernel(const float* __restrict__ X, const float* __restrict__ w1,
-                                                      const float* __restrict__ w2, float* __restrict__ O, int B, int K, int N,
-                                                      int M, size_t sa, size_t sn, size_t plane, float sgn) {
-  const int G = 2 * M;
-  const int gx = (G + 63) / 64, gy = ((N + 3) / 4 + 3) / 4;
-  int grp, bt;                                       // the sample tiles of a (mode block, output tile) re-read its weights: one XCD
-  if (!fno_xcd_item(blockIdx.x, gx * gy, (B + 3) / 4, grp, bt)) return;
-  const int g = (grp % gx) * 64 + threadIdx.x, o0 = ((grp / gx) * 4 + threadIdx.y) * 4, b0 = bt * 4;
-  if (g >= G || o0 >= N) return;
-  const float* __restrict__ w = g < M ? w1 + g : w2 + (g - M);
-  const int no = N - o0;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 accr[4], acci[4];                             // per sample, over the 4 outputs
-#pragma unroll
-  for (int bb = 0; bb < 4; ++bb) accr[bb] = acci[bb] = zero4;
-  for (int i0 = 0; i0 < K; i0 += 4) {
-    const int ni = K - i0;
-    f32x4 xr[4], xi[4];
-#pragma unroll
-    for (int bb = 0; bb < 4; ++bb) {
-      const float* p = X + (((size_t)(b0 + bb) * G + g) * 2) * K + i0;
-      const int n = b0 + bb < B ? ni : 0;
-      xr[bb] = fno_ld4<VEC>(p, n);
-      xi[bb] = fno_ld4<VEC>(p + K, n);
-    }
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      if (ii < ni) {
-        f32x4 wr = zero4, wi = zero4;
-#pragma unroll
-        for (int oo = 0; oo < 4; ++oo) {
-          if (oo < no) {
-            const float* wp = w + (size_t)(i0 + ii) * sa + (size_t)(o0 + oo) * sn;
-            wr[oo] = wp[0];
-            wi[oo] = sgn * wp[plane];
-          }
-        }
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-          accr[bb] += wr * xr[bb][ii];
-          accr[bb] -= wi * xi[bb][ii];
-          acci[bb] += wi * xr[bb][ii];
-          acci[bb] += wr * xi[bb][ii];
-        }
-      }
+// ---- per-mode channel mixing: the weight addressing of fno_mix_kernel / fno_mix_wgrad_kernel (fno_common.h) ---------------------
+// G = 2 M kept modes (mode g < M reads weights1, the others weights2); the parameter is planar [2 = re | im][Cin][Cout][M]: the
+// imaginary part sits `plane` = Cin Cout M floats after the real part.  T = const float (weights) or float (their gradients)
+template <class T>
+struct FnoWeights2 {
+  static constexpr int BLOCKS = 2;
+  T *w1, *w2;
+  int M;
+  size_t plane;
+  __host__ __device__ int block_modes() const { return M; }
+  __device__ __forceinline__ T* at(int g) const { return g < M ? w1 + g : w2 + (g - M); }
+  __device__ __forceinline__ void load(const float* p, size_t off, float& re, float& im) const {
+    re = p[off];
+    im = p[off + plane];
+  }
+  __device__ __forceinline__ void store(float* p, size_t off, float re, float im, int accumulate) const {
+    if (accumulate) {
+      p[off] += re;
+      p[off + plane] += im;
+    } else {
+      p[off] = re;
+      p[off + plane] = im;
     }
   }
-#pragma unroll
-  for (int bb = 0; bb < 4; ++bb) {
-    if (b0 + bb < B) {
-      float* p = O + (((size_t)(b0 + bb) * G + g) * 2) * N + o0;
-      fno_st4<VEC>(p, accr[bb], no);
-      fno_st4<VEC>(p + N, acci[bb], no);
-    }
-  }
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void fno_mix_wgrad_kernel(const float* __restrict__ X, const float* __restrict__ dO,
-                                                            float* __restrict__ dw1, float* __restrict__ dw2, int B, int Cin,
-                                                            int Cout, int M, int accumulate) {
-  const int G = 2 * M;
-  const int nto = (Cout + 3) / 4, nti = (Cin + 3) / 4;
-  int mb, tr;                                        // the channel tiles of a mode block re-read its rows of X and dO: one XCD
-  if (!fno_xcd_item(blockIdx.x, (G + 63) / 64, (nti * nto + 3) / 4, mb, tr)) return;
-  const int g = mb * 64 + threadIdx.x, t = tr * 4 + threadIdx.y;
-  if (g >= G || t >= nti * nto) return;
-  const int i0 = (t / nto) * 4, o0 = (t % nto) * 4;
-  const int ni = Cin - i0, no = Cout - o0;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 ar[4], ai[4];                                 // per input channel, over the 4 outputs
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) ar[ii] = ai[ii] = zero4;
-  for (int b = 0; b < B; ++b) {
-    const float* px = X + (((size_t)b * G + g) * 2) * Cin + i0;
-    const float* pd = dO + (((size_t)b * G + g) * 2) * Cout + o0;
-    const f32x4 xr = fno_ld4<VEC>(px, ni), xi = fno_ld4<VEC>(px + Cin, ni);
-    const f32x4 dr = fno_ld4<VEC>(pd, no), di = fno_ld4<VEC>(pd + Cout, no);
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      ar[ii] += dr * xr[ii];
-      ar[ii] += di * xi[ii];
-      ai[ii] += di * xr[ii];
-      ai[ii] -= dr * xi[ii];
-    }
-  }
-  float* __restrict__ out = g < M ? dw1 + g : dw2 + (g - M);
-  const size_t plane = (size_t)Cin * Cout * M;
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-#pragma unroll
-    for (int oo = 0; oo < 4; ++oo) {
-      if (ii < ni && oo < no) {
-        float* p = out + ((size_t)(i0 + ii) * Cout + o0 + oo) * M;
-        if (accumulate) {
-          p[0] += ar[ii][oo];
-          p[plane] += ai[ii][oo];
-        } else {
-          p[0] = ar[ii][oo];
-          p[plane] = ai[ii][oo];
-        }
-      }
-    }
-  }
-}
+};
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void fno_dact_kernel(const float* __restrict__ dy, const float* __restrict__ pre,
@@ -412,21 +330,8 @@ extern "C" int dpot_fno_mix(const float* X, const float* w1, const float* w2, fl
   DPOT_REQUIRE(X && w1 && w2 && O && X != O, "fno_mix: null or aliased pointer");
   DPOT_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && m1 > 0 && m2 > 0 && (int64_t)m1 * m2 <= (1 << 24),
                "fno_mix: bad sizes B=%d Cin=%d Cout=%d modes (%d, %d)", B, Cin, Cout, m1, m2);
-  const int M = m1 * m2;
-  // forward: reduce the layer's inputs i, produce its outputs o; adjoint: reduce o, produce i, conj(W)
-  const int K = adjoint ? Cout : Cin, N = adjoint ? Cin : Cout;
-  const size_t si = (size_t)Cout * M, so = (size_t)M, plane = (size_t)Cin * Cout * M;
-  const size_t sa = adjoint ? so : si, sn = adjoint ? si : so;
-  const int64_t nwg = fno_xcd_grid(cdiv(2 * M, 64) * cdiv(cdiv(N, 4), 4), cdiv(B, 4));
-  DPOT_REQUIRE((int64_t)cdiv(2 * M, 64) * cdiv(cdiv(N, 4), 4) <= (1 << 24) && nwg <= 0x7fffffff, "fno_mix: too many workgroups");
-  const bool vec = K % 4 == 0 && N % 4 == 0 && aligned16(X) && aligned16(O);
-  const dim3 grid((unsigned)nwg), block(64, 4);
-  const float sgn = adjoint ? -1.f : 1.f;
-  if (vec)
-    hipLaunchKernelGGL(fno_mix_kernel<true>, grid, block, 0, as_stream(stream), X, w1, w2, O, B, K, N, M, sa, sn, plane, sgn);
-  else
-    hipLaunchKernelGGL(fno_mix_kernel<false>, grid, block, 0, as_stream(stream), X, w1, w2, O, B, K, N, M, sa, sn, plane, sgn);
-  return check_launch("fno_mix_kernel");
+  const FnoWeights2<const float> w = {w1, w2, m1 * m2, (size_t)Cin * Cout * m1 * m2};
+  return fno_mix_launch("fno_mix", "fno_mix_kernel", X, w, O, B, Cin, Cout, adjoint, stream);
 }
 
 extern "C" int dpot_fno_mix_wgrad(const float* X, const float* dO, float* dw1, float* dw2, int B, int Cin, int Cout, int m1,
@@ -434,18 +339,8 @@ extern "C" int dpot_fno_mix_wgrad(const float* X, const float* dO, float* dw1, f
   DPOT_REQUIRE(X && dO && dw1 && dw2 && dw1 != dw2, "fno_mix_wgrad: null or aliased pointer");
   DPOT_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && m1 > 0 && m2 > 0 && (int64_t)m1 * m2 <= (1 << 24),
                "fno_mix_wgrad: bad sizes B=%d Cin=%d Cout=%d modes (%d, %d)", B, Cin, Cout, m1, m2);
-  const int M = m1 * m2;
-  const int64_t tiles = (int64_t)cdiv(Cin, 4) * cdiv(Cout, 4);
-  DPOT_REQUIRE(cdiv64(tiles, 4) <= (1 << 20), "fno_mix_wgrad: too many channel pairs (%d x %d)", Cin, Cout);
-  const int64_t nwg = fno_xcd_grid(cdiv(2 * M, 64), (int)cdiv64(tiles, 4));
-  DPOT_REQUIRE(nwg <= 0x7fffffff, "fno_mix_wgrad: too many workgroups");
-  const bool vec = Cin % 4 == 0 && Cout % 4 == 0 && aligned16(X) && aligned16(dO);
-  const dim3 grid((unsigned)nwg), block(64, 4);
-  if (vec)
-    hipLaunchKernelGGL(fno_mix_wgrad_kernel<true>, grid, block, 0, as_stream(stream), X, dO, dw1, dw2, B, Cin, Cout, M, accumulate);
-  else
-    hipLaunchKernelGGL(fno_mix_wgrad_kernel<false>, grid, block, 0, as_stream(stream), X, dO, dw1, dw2, B, Cin, Cout, M, accumulate);
-  return check_launch("fno_mix_wgrad_kernel");
+  const FnoWeights2<float> dw = {dw1, dw2, m1 * m2, (size_t)Cin * Cout * m1 * m2};
+  return fno_mix_wgrad_launch("fno_mix_wgrad", "fno_mix_wgrad_kernel", X, dO, dw, B, Cin, Cout, accumulate, stream);
 }
 
 extern "C" int dpot_fno_dact(const float* dy, const float* pre, float* dpre, int64_t n, int act, dpot_stream_t stream) {

@@ -20,9 +20,10 @@
 // dpot_fno3_mix     O[b, g, o] = sum_i X[b, g, i] W_blk(g)[i, o, g'] (complex) per kept mode, G = 4 m1 m2 m3 modes; lanes run
 //                   over the modes and read the weights IN PLACE in the parameter's layout [Cin][Cout][m1][m2][m3][2] (the
 //                   view_as_real of the reference's cfloat parameter): one coalesced float2 per lane.  adjoint = 1: the data
-//                   gradient, sum over o with conj(W).  The arithmetic is that of fno_mix_kernel (fno.hip).
+//                   gradient, sum over o with conj(W).  The kernel is fno_mix_kernel of fno_common.h, the one FNO2d runs;
+//                   FnoWeights3 below is this rank's weight addressing (corner decode, float2).
 // dpot_fno3_mix_wgrad  dW[i, o, g'] = sum_b conj(X[b, g, i]) dO[b, g, o], b ascending; written (or added) as float2 into the
-//                   four parameters' own layout.
+//                   four parameters' own layout (fno_mix_wgrad_kernel of fno_common.h).
 // Nothing outside the tensors is read: every load past an extent is predicated to 0.0f (table indices are clamped into the
 // table), stores are masked.  Fixed summation order, no atomics, no allocation (the caller owns ws).
 #include "common.h"
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(256) void fno3_axis_kernel(const float* __restrict_
   }
 }
 
-// ---- per-mode channel mixing ---------------------------------------------------------------------------------------------
+// ---- per-mode channel mixing: the weight addressing of fno_mix_kernel / fno_mix_wgrad_kernel (fno_common.h) ---------------------
 struct Fno3Modes {
   int m1, m2, m3;
 };
@@ -92,119 +93,35 @@ __device__ __forceinline__ void fno3_mode(const Fno3Modes m, int g, int& blk, in
   gm = ((r - hi_r * m.m1) * m.m2 + (q - hi_q * m.m2)) * m.m3 + kz;
 }
 
-// X[B][G][2][K], O[B][G][2][N], G = 4 M kept modes; the weight of (reduced index a, output index n) of mode gm of a block is
-// the float2 (re, im) at w[2 (a * sa + n * sn + gm)], its imaginary part times sgn
-template <bool VEC>
-__global__ __launch_bounds__(256) void fno3_mix_kernel(const float* __restrict__ X, const float* __restrict__ w1,
-                                                       const float* __restrict__ w2, const float* __restrict__ w3,
-                                                       const float* __restrict__ w4, float* __restrict__ O, int B, int K, int N,
-                                                       const Fno3Modes md, size_t sa, size_t sn, float sgn) {
-  const int G = 4 * md.m1 * md.m2 * md.m3;
-  const int gx = (G + 63) / 64, gy = ((N + 3) / 4 + 3) / 4;
-  int grp, bt;                                       // the sample tiles of a (mode block, output tile) re-read its weights: one XCD
-  if (!fno_xcd_item(blockIdx.x, gx * gy, (B + 3) / 4, grp, bt)) return;
-  const int g = (grp % gx) * 64 + threadIdx.x, o0 = ((grp / gx) * 4 + threadIdx.y) * 4, b0 = bt * 4;
-  if (g >= G || o0 >= N) return;
-  int blk, gm;
-  fno3_mode(md, g, blk, gm);
-  const float* __restrict__ w = (blk == 0 ? w1 : blk == 1 ? w2 : blk == 2 ? w3 : w4) + 2 * (size_t)gm;
-  const int no = N - o0;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 accr[4], acci[4];                             // per sample, over the 4 outputs
-#pragma unroll
-  for (int bb = 0; bb < 4; ++bb) accr[bb] = acci[bb] = zero4;
-  for (int i0 = 0; i0 < K; i0 += 4) {
-    const int ni = K - i0;
-    f32x4 xr[4], xi[4];
-#pragma unroll
-    for (int bb = 0; bb < 4; ++bb) {
-      const float* p = X + (((size_t)(b0 + bb) * G + g) * 2) * K + i0;
-      const int n = b0 + bb < B ? ni : 0;
-      xr[bb] = fno_ld4<VEC>(p, n);
-      xi[bb] = fno_ld4<VEC>(p + K, n);
-    }
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      if (ii < ni) {
-        f32x4 wr = zero4, wi = zero4;
-#pragma unroll
-        for (int oo = 0; oo < 4; ++oo) {
-          if (oo < no) {
-            const float2 wv = *reinterpret_cast<const float2*>(w + 2 * ((size_t)(i0 + ii) * sa + (size_t)(o0 + oo) * sn));
-            wr[oo] = wv.x;
-            wi[oo] = sgn * wv.y;
-          }
-        }
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-          accr[bb] += wr * xr[bb][ii];
-          accr[bb] -= wi * xi[bb][ii];
-          acci[bb] += wi * xr[bb][ii];
-          acci[bb] += wr * xi[bb][ii];
-        }
-      }
-    }
+// G = 4 M kept modes over the four corner parameters [Cin][Cout][M][2]: one complex weight is the float2 (re, im).
+// T = const float (weights) or float (their gradients)
+template <class T>
+struct FnoWeights3 {
+  static constexpr int BLOCKS = 4;
+  T *w1, *w2, *w3, *w4;
+  Fno3Modes md;
+  __host__ __device__ int block_modes() const { return md.m1 * md.m2 * md.m3; }
+  __device__ __forceinline__ T* at(int g) const {
+    int blk, gm;
+    fno3_mode(md, g, blk, gm);
+    return (blk == 0 ? w1 : blk == 1 ? w2 : blk == 2 ? w3 : w4) + 2 * (size_t)gm;
   }
-#pragma unroll
-  for (int bb = 0; bb < 4; ++bb) {
-    if (b0 + bb < B) {
-      float* p = O + (((size_t)(b0 + bb) * G + g) * 2) * N + o0;
-      fno_st4<VEC>(p, accr[bb], no);
-      fno_st4<VEC>(p + N, acci[bb], no);
-    }
+  __device__ __forceinline__ void load(const float* p, size_t off, float& re, float& im) const {
+    const float2 wv = *reinterpret_cast<const float2*>(p + 2 * off);
+    re = wv.x;
+    im = wv.y;
   }
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void fno3_mix_wgrad_kernel(const float* __restrict__ X, const float* __restrict__ dO,
-                                                             float* __restrict__ dw1, float* __restrict__ dw2,
-                                                             float* __restrict__ dw3, float* __restrict__ dw4, int B, int Cin,
-                                                             int Cout, const Fno3Modes md, int accumulate) {
-  const int M = md.m1 * md.m2 * md.m3, G = 4 * M;
-  const int nto = (Cout + 3) / 4, nti = (Cin + 3) / 4;
-  int mb, tr;                                        // the channel tiles of a mode block re-read its rows of X and dO: one XCD
-  if (!fno_xcd_item(blockIdx.x, (G + 63) / 64, (nti * nto + 3) / 4, mb, tr)) return;
-  const int g = mb * 64 + threadIdx.x, t = tr * 4 + threadIdx.y;
-  if (g >= G || t >= nti * nto) return;
-  const int i0 = (t / nto) * 4, o0 = (t % nto) * 4;
-  const int ni = Cin - i0, no = Cout - o0;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 ar[4], ai[4];                                 // per input channel, over the 4 outputs
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) ar[ii] = ai[ii] = zero4;
-  for (int b = 0; b < B; ++b) {
-    const float* px = X + (((size_t)b * G + g) * 2) * Cin + i0;
-    const float* pd = dO + (((size_t)b * G + g) * 2) * Cout + o0;
-    const f32x4 xr = fno_ld4<VEC>(px, ni), xi = fno_ld4<VEC>(px + Cin, ni);
-    const f32x4 dr = fno_ld4<VEC>(pd, no), di = fno_ld4<VEC>(pd + Cout, no);
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      ar[ii] += dr * xr[ii];
-      ar[ii] += di * xi[ii];
-      ai[ii] += di * xr[ii];
-      ai[ii] -= dr * xi[ii];
+  __device__ __forceinline__ void store(float* p, size_t off, float re, float im, int accumulate) const {
+    float2* d = reinterpret_cast<float2*>(p + 2 * off);
+    float2 v = make_float2(re, im);
+    if (accumulate) {
+      const float2 old = *d;
+      v.x = old.x + v.x;
+      v.y = old.y + v.y;
     }
+    *d = v;
   }
-  int blk, gm;
-  fno3_mode(md, g, blk, gm);
-  float* __restrict__ out = (blk == 0 ? dw1 : blk == 1 ? dw2 : blk == 2 ? dw3 : dw4) + 2 * (size_t)gm;
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) {
-#pragma unroll
-    for (int oo = 0; oo < 4; ++oo) {
-      if (ii < ni && oo < no) {
-        float2* p = reinterpret_cast<float2*>(out + 2 * (((size_t)(i0 + ii) * Cout + o0 + oo) * M));
-        float2 v = make_float2(ar[ii][oo], ai[ii][oo]);
-        if (accumulate) {
-          const float2 old = *p;
-          v.x = old.x + v.x;
-          v.y = old.y + v.y;
-        }
-        *p = v;
-      }
-    }
-  }
-}
+};
 
 static int fno3_check_sizes(const char* what, int B, int X, int Y, int Z, int C, int m1, int m2, int m3) {
   DPOT_REQUIRE(B > 0 && X > 0 && Y > 0 && Z > 0 && C > 0 && m1 > 0 && m2 > 0 && m3 > 0,
@@ -285,23 +202,8 @@ extern "C" int dpot_fno3_mix(const float* X, const float* w1, const float* w2, c
   DPOT_REQUIRE(X && w1 && w2 && w3 && w4 && O && X != O, "fno3_mix: null or aliased pointer");
   DPOT_REQUIRE(aligned8(w1) && aligned8(w2) && aligned8(w3) && aligned8(w4), "fno3_mix: the weights must be 8-byte aligned");
   if (int rc = fno3_mix_check("fno3_mix", B, Cin, Cout, m1, m2, m3)) return rc;
-  const int M = m1 * m2 * m3;
-  // forward: reduce the layer's inputs i, produce its outputs o; adjoint: reduce o, produce i, conj(W)
-  const int K = adjoint ? Cout : Cin, N = adjoint ? Cin : Cout;
-  const size_t si = (size_t)Cout * M, so = (size_t)M;
-  const size_t sa = adjoint ? so : si, sn = adjoint ? si : so;
-  const int64_t groups = (int64_t)cdiv(4 * M, 64) * cdiv(cdiv(N, 4), 4);
-  const int64_t nwg = groups <= (1 << 24) ? fno_xcd_grid((int)groups, cdiv(B, 4)) : -1;
-  DPOT_REQUIRE(nwg > 0 && nwg <= 0x7fffffff, "fno3_mix: too many workgroups");
-  const bool vec = K % 4 == 0 && N % 4 == 0 && aligned16(X) && aligned16(O);
-  const dim3 grid((unsigned)nwg), block(64, 4);
-  const float sgn = adjoint ? -1.f : 1.f;
-  const Fno3Modes md = {m1, m2, m3};
-  if (vec)
-    hipLaunchKernelGGL(fno3_mix_kernel<true>, grid, block, 0, as_stream(stream), X, w1, w2, w3, w4, O, B, K, N, md, sa, sn, sgn);
-  else
-    hipLaunchKernelGGL(fno3_mix_kernel<false>, grid, block, 0, as_stream(stream), X, w1, w2, w3, w4, O, B, K, N, md, sa, sn, sgn);
-  return check_launch("fno3_mix_kernel");
+  const FnoWeights3<const float> w = {w1, w2, w3, w4, {m1, m2, m3}};
+  return fno_mix_launch("fno3_mix", "fno3_mix_kernel", X, w, O, B, Cin, Cout, adjoint, stream);
 }
 
 extern "C" int dpot_fno3_mix_wgrad(const float* X, const float* dO, float* dw1, float* dw2, float* dw3, float* dw4, int B,
@@ -312,19 +214,6 @@ extern "C" int dpot_fno3_mix_wgrad(const float* X, const float* dO, float* dw1, 
   DPOT_REQUIRE(aligned8(dw1) && aligned8(dw2) && aligned8(dw3) && aligned8(dw4),
                "fno3_mix_wgrad: the gradients must be 8-byte aligned");
   if (int rc = fno3_mix_check("fno3_mix_wgrad", B, Cin, Cout, m1, m2, m3)) return rc;
-  const int M = m1 * m2 * m3;
-  const int64_t tiles = (int64_t)cdiv(Cin, 4) * cdiv(Cout, 4);
-  DPOT_REQUIRE(cdiv64(tiles, 4) <= (1 << 20), "fno3_mix_wgrad: too many channel pairs (%d x %d)", Cin, Cout);
-  const int64_t nwg = fno_xcd_grid(cdiv(4 * M, 64), (int)cdiv64(tiles, 4));
-  DPOT_REQUIRE(nwg <= 0x7fffffff, "fno3_mix_wgrad: too many workgroups");
-  const bool vec = Cin % 4 == 0 && Cout % 4 == 0 && aligned16(X) && aligned16(dO);
-  const dim3 grid((unsigned)nwg), block(64, 4);
-  const Fno3Modes md = {m1, m2, m3};
-  if (vec)
-    hipLaunchKernelGGL(fno3_mix_wgrad_kernel<true>, grid, block, 0, as_stream(stream), X, dO, dw1, dw2, dw3, dw4, B, Cin, Cout, md,
-                       accumulate);
-  else
-    hipLaunchKernelGGL(fno3_mix_wgrad_kernel<false>, grid, block, 0, as_stream(stream), X, dO, dw1, dw2, dw3, dw4, B, Cin, Cout,
-                       md, accumulate);
-  return check_launch("fno3_mix_wgrad_kernel");
+  const FnoWeights3<float> dw = {dw1, dw2, dw3, dw4, {m1, m2, m3}};
+  return fno_mix_wgrad_launch("fno3_mix_wgrad", "fno3_mix_wgrad_kernel", X, dO, dw, B, Cin, Cout, accumulate, stream);
 }

@@ -1637,24 +1637,88 @@ class TokenMeanFn(torch.autograd.Function):
 
 
 # ======================================================================================================
-# the FNO baseline (models/fno.py): csrc/fno.hip through ops.fno_*
+# the FNO baselines (models/fno.py): csrc/fno.hip through ops.fno_*, csrc/fno3.hip through ops.fno3_*.  One forward and one
+# backward serve both ranks and both forms (the spectral convolution alone, the whole layer); a rank is its four operators
+# (rfft, irfft, mix, wgrad), looked up on `ops` when a pass runs, and its weight tuple
 # ======================================================================================================
-def _fno_wgrad(X, dO, s1: _Sink, s2: _Sink, need: bool = True):
-    """(dweights1, dweights2) delivered: straight into the flat gradient slots where this is the step's first contribution,
-    ADDED there by the kernel itself in a further pass of a rollout (both slots filled), else as temporaries; need=False (neither
-    weight takes a gradient, frozen spectral weights): nothing is launched"""
+def _fno2_ops():
+    return (ops.fno_rfft2, ops.fno_irfft2, lambda X, ws, adjoint=False: ops.fno_mix(X, *ws, adjoint),
+            lambda X, dO, outs, acc: ops.fno_mix_wgrad(X, dO, *(outs or (None, None)), acc))
+
+
+def _fno3_ops():
+    return ops.fno3_rfft3, ops.fno3_irfft3, ops.fno3_mix, ops.fno3_mix_wgrad
+
+
+def _fno_sizes(ws):
+    """(Cout, modes) of two planar weights [2, Cin, Cout, m1, m2] or four real-pair weights [Cin, Cout, m1, m2, m3, 2]"""
+    Cout, *modes = ws[0].shape[2:] if len(ws) == 2 else ws[0].shape[1:5]
+    return Cout, modes
+
+
+def _fno_wgrad(X, dO, sinks, wgrad, need: bool = True):
+    """the spectral weights' gradients delivered: straight into the flat gradient slots where this is the step's first
+    contribution, ADDED there by the kernel itself in a further pass of a rollout (every slot filled), else as temporaries;
+    need=False (no weight takes a gradient, frozen spectral weights): nothing is launched"""
     if not need:
-        s1.skip()
-        s2.skip()
-        return None, None
-    o1, o2 = s1.out(), s2.out()
-    acc = False
-    if o1 is None or o2 is None:
-        o1 = o2 = None
-        if all(s.fp is not None and s.fp.filled[s.i] for s in (s1, s2)):
-            o1, o2, acc = s1.fp.grad_views[s1.i], s2.fp.grad_views[s2.i], True
-    d1, d2 = ops.fno_mix_wgrad(X, dO, o1, o2, acc)
-    return s1.done(d1), s2.done(d2)
+        for s in sinks:
+            s.skip()
+        return (None,) * len(sinks)
+    outs, acc = [s.out() for s in sinks], False
+    if any(o is None for o in outs):
+        outs = None
+        if all(s.fp is not None and s.fp.filled[s.i] for s in sinks):
+            outs, acc = [s.fp.grad_views[s.i] for s in sinks], True
+    return tuple(s.done(d) for s, d in zip(sinks, wgrad(X, dO, outs, acc)))
+
+
+def _fno_forward(ctx, x, ws, fno_ops, cw=None, cb=None, act: int = 0):
+    """SpectralConv2dFn / SpectralConv3dFn: irfft(mix(rfft(x))) on a channels-last field; with the 1x1 convolution (cw, cb),
+    FNOLayerFn / FNO3dLayerFn: act(that + conv(x)) - the convolution is one GEMM whose result rides into the inverse
+    transform's epilogue (add, activation).  Keeps the kept spectrum X; the layer keeps x and the pre-activation too."""
+    rfft, irfft, mix, _ = fno_ops
+    x, ws = x.contiguous(), tuple(w.contiguous() for w in ws)
+    B, *dims, Cin = x.shape
+    Cout, modes = _fno_sizes(ws)
+    conv = None
+    if cw is not None:
+        cw = cw.contiguous()
+        conv = ops.linear_fwd(x.view(-1, Cin), cw, cb)[0].view(B, *dims, Cout)
+    X = rfft(x, *modes)
+    y, pre = irfft(mix(X, ws), *dims, add=conv, act=act, save_pre=cw is not None)
+    if cw is None:
+        ctx.save_for_backward(X, *ws)
+        ctx.sinks = _sinks(ctx, ws, 1)
+    else:
+        ctx.save_for_backward(X, *ws, x, pre, cw)
+        ctx.sinks = _sinks(ctx, ws + (cw, cb), 1)
+    ctx.act, ctx.n_weights = act, len(ws)
+    return y
+
+
+def _fno_backward(ctx, dy, fno_ops):
+    """adjoint of _fno_forward: (dx, the spectral weights' gradients) and, for a layer, (dcw, dcb): dpre = dy act'(pre) is
+    formed once, and the convolution's data gradient rides into the adjoint transform as its result rode into the forward's"""
+    rfft, irfft, mix, wgrad = fno_ops
+    X, *rest = ctx.saved_tensors
+    n = ctx.n_weights
+    ws, layer = tuple(rest[:n]), rest[n:]
+    Cout, modes = _fno_sizes(ws)
+    g = dy.contiguous()
+    if layer:
+        x, pre, cw = layer
+        g = ops.act_bwd_mul(g, pre, ctx.act)
+    dO = rfft(g, *modes, adjoint=True)
+    dx = None
+    if ctx.needs_input_grad[0]:
+        dxc = ops.linear_bwd_data(g.view(-1, Cout), cw).view(x.shape) if layer else None
+        dx, _ = irfft(mix(dO, ws, adjoint=True), *g.shape[1:-1], add=dxc, adjoint=True)
+    grads = (dx,) + _fno_wgrad(X, dO, ctx.sinks[:n], wgrad, any(ctx.needs_input_grad[1:1 + n]))
+    if layer:
+        s_cw, s_cb = ctx.sinks[n:]
+        dcw, dcb = ops.linear_bwd_wb(g.view(-1, Cout), x.view(-1, x.shape[-1]), s_cw.out(), s_cb.out())
+        grads += (s_cw.done(dcw.view(cw.shape)), s_cb.done(dcb))
+    return grads
 
 
 class SpectralConv2dFn(torch.autograd.Function):
@@ -1663,62 +1727,25 @@ class SpectralConv2dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, w2):
-        x, w1, w2 = x.contiguous(), w1.contiguous(), w2.contiguous()
-        m1, m2 = w1.shape[3], w1.shape[4]
-        X = ops.fno_rfft2(x, m1, m2)
-        y, _ = ops.fno_irfft2(ops.fno_mix(X, w1, w2), x.shape[1], x.shape[2])
-        ctx.save_for_backward(X, w1, w2)
-        ctx.sinks = _sinks(ctx, (w1, w2), 1)
-        return y
+        return _fno_forward(ctx, x, (w1, w2), _fno2_ops())
 
     @staticmethod
     def backward(ctx, dy):
-        X, w1, w2 = ctx.saved_tensors
-        dy = dy.contiguous()
-        dO = ops.fno_rfft2(dy, w1.shape[3], w1.shape[4], adjoint=True)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx, _ = ops.fno_irfft2(ops.fno_mix(dO, w1, w2, adjoint=True), dy.shape[1], dy.shape[2], adjoint=True)
-        d1, d2 = _fno_wgrad(X, dO, *ctx.sinks, need=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        return dx, d1, d2
+        return _fno_backward(ctx, dy, _fno2_ops())
 
 
 class FNOLayerFn(torch.autograd.Function):
-    """One layer of FNO2d (models/fno.py:192-196): act(SpectralConv2d_fast(x) + Conv2d 1x1(x)) on x[B, H, W, Cin].  The
-    convolution branch is one GEMM whose result rides into the inverse transform's epilogue (add, activation); the backward
-    forms dpre = dy act'(pre) once, and the convolution's data gradient rides into the adjoint transform the same way."""
+    """One layer of FNO2d (models/fno.py:192-196): act(SpectralConv2d_fast(x) + Conv2d 1x1(x)) on x[B, H, W, Cin]."""
 
     @staticmethod
     def forward(ctx, x, w1, w2, cw, cb, act: int):
         ops.capture_precision(ctx)
-        x, w1, w2, cw = x.contiguous(), w1.contiguous(), w2.contiguous(), cw.contiguous()
-        B, H, W, Cin = x.shape
-        Cout, m1, m2 = w1.shape[2], w1.shape[3], w1.shape[4]
-        conv, _ = ops.linear_fwd(x.view(B * H * W, Cin), cw, cb)
-        X = ops.fno_rfft2(x, m1, m2)
-        y, pre = ops.fno_irfft2(ops.fno_mix(X, w1, w2), H, W, add=conv.view(B, H, W, Cout), act=act, save_pre=True)
-        ctx.save_for_backward(x, X, pre, w1, w2, cw)
-        ctx.act = act
-        ctx.sinks = _sinks(ctx, (w1, w2, cw, cb), 1)
-        return y
+        return _fno_forward(ctx, x, (w1, w2), _fno2_ops(), cw, cb, act)
 
     @staticmethod
     @ops.with_ctx_precision
     def backward(ctx, dy):
-        x, X, pre, w1, w2, cw = ctx.saved_tensors
-        B, H, W, Cin = x.shape
-        Cout = w1.shape[2]
-        s1, s2, s_cw, s_cb = ctx.sinks
-        dpre = ops.act_bwd_mul(dy.contiguous(), pre, ctx.act)
-        dO = ops.fno_rfft2(dpre, w1.shape[3], w1.shape[4], adjoint=True)
-        dpre2 = dpre.view(B * H * W, Cout)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dxc = ops.linear_bwd_data(dpre2, cw).view(B, H, W, Cin)
-            dx, _ = ops.fno_irfft2(ops.fno_mix(dO, w1, w2, adjoint=True), H, W, add=dxc, adjoint=True)
-        d1, d2 = _fno_wgrad(X, dO, s1, s2, ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        dcw, dcb = ops.linear_bwd_wb(dpre2, x.view(B * H * W, Cin), s_cw.out(), s_cb.out())
-        return dx, d1, d2, s_cw.done(dcw.view(cw.shape)), s_cb.done(dcb), None
+        return _fno_backward(ctx, dy, _fno2_ops()) + (None,)
 
 
 class FNOEmbedFn(torch.autograd.Function):
@@ -1752,26 +1779,6 @@ class FNOEmbedFn(torch.autograd.Function):
         return dx, None, None, None, dW0, db0, dW2, db2, dres, None, None
 
 
-# ======================================================================================================
-# the 3-D FNO baseline (models/fno.py:290-435): csrc/fno3.hip through ops.fno3_*
-# ======================================================================================================
-def _fno3_wgrad(X, dO, sinks, need: bool = True):
-    """(dweights1..dweights4) delivered as _fno_wgrad does for two: straight into the flat gradient slots where this is the
-    step's first contribution, ADDED there by the kernel in a further pass of a rollout (all four slots filled), else as
-    temporaries; need=False (frozen spectral weights): nothing is launched"""
-    if not need:
-        for s in sinks:
-            s.skip()
-        return (None,) * 4
-    outs, acc = [s.out() for s in sinks], False
-    if any(o is None for o in outs):
-        outs = None
-        if all(s.fp is not None and s.fp.filled[s.i] for s in sinks):
-            outs, acc = [s.fp.grad_views[s.i] for s in sinks], True
-    ds = ops.fno3_mix_wgrad(X, dO, outs, acc)
-    return tuple(s.done(d) for s, d in zip(sinks, ds))
-
-
 class SpectralConv3dFn(torch.autograd.Function):
     """SpectralConv3d (models/fno.py:290-342) on a channels-last field x[B, X, Y, Z, Cin] -> [B, X, Y, Z, Cout]: truncated
     rfftn, per-mode mixing with the four corner weights [Cin, Cout, m1, m2, m3, 2] (real pairs), irfftn.  Keeps the kept
@@ -1779,58 +1786,22 @@ class SpectralConv3dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, w2, w3, w4):
-        x, ws = x.contiguous(), tuple(w.contiguous() for w in (w1, w2, w3, w4))
-        m1, m2, m3 = ws[0].shape[2:5]
-        S = ops.fno3_rfft3(x, m1, m2, m3)
-        y, _ = ops.fno3_irfft3(ops.fno3_mix(S, ws), *x.shape[1:4])
-        ctx.save_for_backward(S, *ws)
-        ctx.sinks = _sinks(ctx, ws, 1)
-        return y
+        return _fno_forward(ctx, x, (w1, w2, w3, w4), _fno3_ops())
 
     @staticmethod
     def backward(ctx, dy):
-        S, *ws = ctx.saved_tensors
-        dy = dy.contiguous()
-        dO = ops.fno3_rfft3(dy, *ws[0].shape[2:5], adjoint=True)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx, _ = ops.fno3_irfft3(ops.fno3_mix(dO, ws, adjoint=True), *dy.shape[1:4], adjoint=True)
-        return (dx,) + _fno3_wgrad(S, dO, ctx.sinks, any(ctx.needs_input_grad[1:5]))
+        return _fno_backward(ctx, dy, _fno3_ops())
 
 
 class FNO3dLayerFn(torch.autograd.Function):
-    """One layer of FNO3d (models/fno.py:407-411): act(SpectralConv3d(x) + Conv3d 1x1x1(x)) on x[B, X, Y, Z, Cin].  As
-    FNOLayerFn: the convolution is one GEMM whose result rides into the inverse transform's epilogue (add, activation); the
-    backward forms dpre = dy act'(pre) once, and the convolution's data gradient rides into the adjoint transform."""
+    """One layer of FNO3d (models/fno.py:407-411): act(SpectralConv3d(x) + Conv3d 1x1x1(x)) on x[B, X, Y, Z, Cin]."""
 
     @staticmethod
     def forward(ctx, x, w1, w2, w3, w4, cw, cb, act: int):
         ops.capture_precision(ctx)
-        x, cw, ws = x.contiguous(), cw.contiguous(), tuple(w.contiguous() for w in (w1, w2, w3, w4))
-        B, X, Y, Z, Cin = x.shape
-        Cout, m1, m2, m3 = ws[0].shape[1:5]
-        conv, _ = ops.linear_fwd(x.view(B * X * Y * Z, Cin), cw, cb)
-        S = ops.fno3_rfft3(x, m1, m2, m3)
-        y, pre = ops.fno3_irfft3(ops.fno3_mix(S, ws), X, Y, Z, add=conv.view(B, X, Y, Z, Cout), act=act, save_pre=True)
-        ctx.save_for_backward(x, S, pre, cw, *ws)
-        ctx.act = act
-        ctx.sinks = _sinks(ctx, ws + (cw, cb), 1)
-        return y
+        return _fno_forward(ctx, x, (w1, w2, w3, w4), _fno3_ops(), cw, cb, act)
 
     @staticmethod
     @ops.with_ctx_precision
     def backward(ctx, dy):
-        x, S, pre, cw, *ws = ctx.saved_tensors
-        B, X, Y, Z, Cin = x.shape
-        Cout, m1, m2, m3 = ws[0].shape[1:5]
-        s_cw, s_cb = ctx.sinks[4:]
-        dpre = ops.act_bwd_mul(dy.contiguous(), pre, ctx.act)
-        dO = ops.fno3_rfft3(dpre, m1, m2, m3, adjoint=True)
-        dpre2 = dpre.view(B * X * Y * Z, Cout)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dxc = ops.linear_bwd_data(dpre2, cw).view(B, X, Y, Z, Cin)
-            dx, _ = ops.fno3_irfft3(ops.fno3_mix(dO, ws, adjoint=True), X, Y, Z, add=dxc, adjoint=True)
-        dws = _fno3_wgrad(S, dO, ctx.sinks[:4], any(ctx.needs_input_grad[1:5]))
-        dcw, dcb = ops.linear_bwd_wb(dpre2, x.view(B * X * Y * Z, Cin), s_cw.out(), s_cb.out())
-        return (dx,) + dws + (s_cw.done(dcw.view(cw.shape)), s_cb.done(dcb), None)
+        return _fno_backward(ctx, dy, _fno3_ops()) + (None,)

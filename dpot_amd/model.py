@@ -74,13 +74,34 @@ class _TimeAggParams(nn.Module):
             raise ValueError(f"unknown time_agg {kind!r}")
 
 
-class _DPOTBase(nn.Module):
+class _ModelBase(nn.Module):
+    """What every model of the package shares (the DPOT family below, FNO2d, FNO3d): the precision scope around ``_forward``,
+    its two settings and the input check.  It registers nothing: module order, ``state_dict()`` and the train.FlatParams layout
+    are the subclass's alone."""
+    # precision of the channel-MLP GEMMs of THIS model: None = the process default (ops.set_mlp_precision /
+    # DPOT_MLP_PRECISION), or 'f32' | 'bf16x6' | 'auto' | 'bf16' (BASELINE configs[2]: "bf16 channel-MLP on MFMA")
+    mlp_precision = None
+    # precision of every OTHER fp32 GEMM of this model: None = the process default (ops.set_gemm_precision /
+    # DPOT_GEMM_PRECISION), or 'f32' (native fp32 MFMA) | 'bf16x6' | 'auto' (the fp32-accurate operand split where faster)
+    gemm_precision = None
+
+    def forward(self, x):
+        with ops.precision_scope(self.gemm_precision, self.mlp_precision):
+            return self._forward(x)
+
+    def _check_device(self, x) -> None:
+        if not x.is_cuda:
+            raise _lib.DpotHipError(f"{type(self).__name__} (dpot_amd) runs on MI355X only: move the model and the input to "
+                                    "'cuda'. There is no CPU fallback.")
+
+
+class _DPOTBase(_ModelBase):
     """What DPOTNet, DPOTNet3D and CDPOTNet share: the reference's attributes and argument checks, the modules all three register
     in ONE order - patch_embed, pos_embed, blocks, scale_feats_mu / _sigma (normalize=True), cls_head, time_agg_layer, out_layer:
     the order of ``state_dict()`` and of the train.FlatParams layout - built in that order too (it decides which random numbers
-    initialise which weight), the coordinate tables, the precision scope around ``_forward``, the input check and the
-    normalize=True prologue and epilogue.  A subclass keeps the reference's constructor signature, hands its own patch embedding,
-    Block and output layer over as factories, and writes ``_forward``."""
+    initialise which weight), the coordinate tables and the normalize=True prologue and epilogue.  A subclass keeps the
+    reference's constructor signature, hands its own patch embedding, Block and output layer over as factories, and writes
+    ``_forward``."""
     cls_output = True           # forward returns (pred, cls_pred); False: the prediction alone (train.rollout: no classification branch)
 
     def __init__(self, img_size, patch_size, mixing_type, in_channels, out_channels, in_timesteps, out_timesteps, n_blocks,
@@ -120,23 +141,8 @@ class _DPOTBase(nn.Module):
         for name, n in [(c, img_size) for c in coords] + [("_gt", in_timesteps)]:
             self.register_buffer(name, torch.tensor(np.linspace(0, 1, n), dtype=torch.float32), persistent=False)
         self.register_buffer("_tt", torch.linspace(0, 1, in_timesteps), persistent=False)
-        # precision of the channel-MLP GEMMs of THIS model: None = the process default (ops.set_mlp_precision /
-        # DPOT_MLP_PRECISION), or 'f32' | 'bf16x6' | 'auto' | 'bf16' (BASELINE configs[2]: "bf16 channel-MLP on MFMA")
-        self.mlp_precision = None
-        # precision of every OTHER fp32 GEMM of this model: None = the process default (ops.set_gemm_precision /
-        # DPOT_GEMM_PRECISION), or 'f32' (native fp32 MFMA) | 'bf16x6' | 'auto' (the fp32-accurate operand split where faster)
-        self.gemm_precision = None
         # every weight-derived copy the kernels read (packed / padded / transposed weights) and when it is fresh
         self.packs = ModelPacks()
-
-    def forward(self, x):
-        with ops.precision_scope(self.gemm_precision, self.mlp_precision):
-            return self._forward(x)
-
-    def _check_device(self, x) -> None:
-        if not x.is_cuda:
-            raise _lib.DpotHipError(f"{type(self).__name__} (dpot_amd) runs on MI355X only: move the model and the input to "
-                                    "'cuda'. There is no CPU fallback.")
 
     def _normalize_in(self, x, dims):
         """normalize=True (models/dpot.py:366-370): per-sample statistics over `dims` + two tiny Linear(2C -> E), O(B*C) host-side

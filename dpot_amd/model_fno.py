@@ -28,7 +28,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
+from .model import _ModelBase
 from .functional import ClsHeadFn, FNOEmbedFn, FNOLayerFn, GroupNormFn, Mlp2Fn, TokenMeanFn
 
 GELU = ops.ACT_IDS["gelu"]
@@ -57,7 +58,7 @@ class _FNOPatchEmbedParams(nn.Module):
                                   nn.Conv2d(hidden, out_dim, 1))
 
 
-class FNO2d(nn.Module):
+class FNO2d(_ModelBase):
     cls_output = True
 
     def __init__(self, modes1, modes2, width, img_size=64, n_channels=1, in_timesteps=10, out_timesteps=1, n_layers=4,
@@ -89,17 +90,6 @@ class FNO2d(nn.Module):
         for name, n in (("_gx", img_size), ("_gy", img_size)):
             self.register_buffer(name, torch.tensor(np.linspace(0, 1, n), dtype=torch.float32), persistent=False)
         self.register_buffer("_gt", torch.zeros(1), persistent=False)
-        self.mlp_precision = None        # as DPOTNet: None = the process default
-        self.gemm_precision = None
-
-    def forward(self, x):
-        with ops.precision_scope(self.gemm_precision, self.mlp_precision):
-            return self._forward(x)
-
-    def _check_device(self, x) -> None:
-        if not x.is_cuda:
-            raise _lib.DpotHipError(f"{type(self).__name__} (dpot_amd) runs on MI355X only: move the model and the input to "
-                                    "'cuda'. There is no CPU fallback.")
 
     def _forward(self, x):
         self._check_device(x)

@@ -36,7 +36,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import ops
+from .model import _ModelBase
 from .functional import FNO3dLayerFn, GroupNormFn, LinearFn, Mlp2Fn
 
 GELU = ops.ACT_IDS["gelu"]
@@ -86,7 +87,7 @@ class _SpectralConv3dParams(nn.Module):
                     unexpected_keys.append(key)
 
 
-class FNO3d(nn.Module):
+class FNO3d(_ModelBase):
     cls_output = False          # forward returns the prediction alone (train.rollout: no classification branch)
 
     def __init__(self, modes1, modes2, modes3, width, img_size=64, n_channels=1, in_timesteps=10, out_timesteps=1, n_layers=4,
@@ -112,17 +113,6 @@ class FNO3d(nn.Module):
         self.fc1 = nn.Linear(width, width)
         self.fc2 = nn.Linear(width, n_channels * out_timesteps)
         self._grids = {}                 # (X, Y, Z, device) -> the unit grid [X, Y, Z, 3]
-        self.mlp_precision = None        # as DPOTNet: None = the process default
-        self.gemm_precision = None
-
-    def forward(self, x):
-        with ops.precision_scope(self.gemm_precision, self.mlp_precision):
-            return self._forward(x)
-
-    def _check_device(self, x) -> None:
-        if not x.is_cuda:
-            raise _lib.DpotHipError(f"{type(self).__name__} (dpot_amd) runs on MI355X only: move the model and the input to "
-                                    "'cuda'. There is no CPU fallback.")
 
     def grid(self, X: int, Y: int, Z: int, device):
         """get_grid (models/fno.py:427-435) without the batch axis: np.linspace in float64 per axis, cast to fp32; cached per

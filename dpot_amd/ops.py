@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import contextlib
 import functools
+import math
 import threading
 import os
 from typing import NamedTuple, Optional, Tuple
@@ -2819,26 +2820,64 @@ def aa_lrelu_bwd(x: Tensor, dy: Tensor, Cb: int, slope: float = 0.01, out_dbias:
 
 
 # ------------------------------------------------------------------------------------------------------
-# The FNO baseline (csrc/fno.hip; models/fno.py SpectralConv2d_fast): truncated transforms of a channels-last field
-# x [B, H, W, C] to / from the kept spectrum S [B, 2 m1, m2, 2, C] (rows kx < m1 and kx >= H - m1, columns ky < m2, re | im
-# planes, channels innermost) and the per-mode channel mixing.  The twiddle tables are pure numpy: the CPU tests check them.
+# The FNO baselines (csrc/fno.hip, csrc/fno3.hip; models/fno.py SpectralConv2d_fast and SpectralConv3d): truncated transforms of
+# a channels-last field x [B, H, W, C] or [B, X, Y, Z, C] to / from the kept spectrum S [B, 2 m1, m2, 2, C] or
+# [B, 2 m1, 2 m2, m3, 2, C] (every axis but the last keeps k < m and k >= N - m, the last k < m; re | im planes, channels
+# innermost) and the per-mode channel mixing: two weights [2, Cin, Cout, m1, m2] (planar) in 2-D, four corner weights
+# [Cin, Cout, m1, m2, m3, 2] (real pairs) in 3-D.  ONE host path serves both ranks: `dims` and `modes` are tuples of 2 or 3,
+# and `what`, the caller's name in every message, is the library entry point without its prefix.  A 3-D transform is two launches
+# around a workspace this module allocates.  The twiddle tables are pure numpy: the CPU tests check them.
 # ------------------------------------------------------------------------------------------------------
+_FNO_AXES = {2: "HW", 3: "XYZ"}
+_FNO_WORDS = {2: ("two kept row blocks", "columns"), 3: ("kept corner blocks", "planes")}     # as each rank's messages say it
+
+
+def _fno_check_modes(dims, modes, what: str) -> None:
+    """the two refusals, narrower than the reference: the kept blocks of a two-sided axis must not overlap (the reference lets
+    later weights silently overwrite what they share with earlier ones) and the last axis' modes must fit the half spectrum (the
+    reference raises inside its slice assignment)"""
+    axes, (blocks, last) = _FNO_AXES[len(dims)], _FNO_WORDS[len(dims)]
+    if min(*dims, *modes) < 1:
+        raise ValueError(f"{what}: field {'x'.join(map(str, dims))} and modes {tuple(modes)} must be positive")
+    for k, (n, m) in enumerate(zip(dims[:-1], modes[:-1])):
+        if 2 * m > n:
+            raise ValueError(f"{what}: modes{k + 1} = {m} needs 2 * modes{k + 1} <= {axes[k]} = {n}: the {blocks} would "
+                             "overlap")
+    n, m, k = dims[-1], modes[-1], len(dims)
+    if m > n // 2 + 1:
+        raise ValueError(f"{what}: modes{k} = {m} exceeds the {axes[-1]} // 2 + 1 = {n // 2 + 1} {last} of the half "
+                         f"spectrum of {axes[-1]} = {n}")
+
+
+def _fno_limits(rank: int):
+    """(largest axis, largest mode count) the kernels of a rank cover (dpot_fno_max_size / dpot_fno3_max_size)"""
+    lib = _lib.load()
+    max_size = lib.dpot_fno_max_size if rank == 2 else lib.dpot_fno3_max_size
+    return max_size(0), max_size(1)
+
+
+def _fno_supported(dims, modes) -> bool:
+    n, m = _fno_limits(len(dims))
+    return (min(*dims, *modes) >= 1 and all(2 * mk <= nk for nk, mk in zip(dims[:-1], modes[:-1]))
+            and modes[-1] <= dims[-1] // 2 + 1 and max(dims) <= n and max(modes) <= m)
+
+
 def fno_check_modes(H: int, W: int, m1: int, m2: int, what: str = "fno") -> None:
-    """the two refusals: narrower than the reference, which raises on the second only and lets weights2 overwrite the rows it
-    shares with weights1 when 2 m1 > H"""
-    if min(H, W, m1, m2) < 1:
-        raise ValueError(f"{what}: field {H}x{W} and modes ({m1}, {m2}) must be positive")
-    if 2 * m1 > H:
-        raise ValueError(f"{what}: modes1 = {m1} needs 2 * modes1 <= H = {H}: the two kept row blocks would overlap")
-    if m2 > W // 2 + 1:
-        raise ValueError(f"{what}: modes2 = {m2} exceeds the W // 2 + 1 = {W // 2 + 1} columns of the half spectrum of W = {W}")
+    _fno_check_modes((H, W), (m1, m2), what)
+
+
+def fno3_check_modes(X: int, Y: int, Z: int, m1: int, m2: int, m3: int, what: str = "fno3") -> None:
+    _fno_check_modes((X, Y, Z), (m1, m2, m3), what)
 
 
 def fno_supported(H: int, W: int, m1: int, m2: int) -> bool:
     """valid modes for the field, within the sizes the kernels cover (dpot_fno_max_size)"""
-    lib = _lib.load()
-    n, m = lib.dpot_fno_max_size(0), lib.dpot_fno_max_size(1)
-    return (min(H, W, m1, m2) >= 1 and 2 * m1 <= H and m2 <= W // 2 + 1 and max(H, W) <= n and max(m1, m2) <= m)
+    return _fno_supported((H, W), (m1, m2))
+
+
+def fno3_supported(X: int, Y: int, Z: int, m1: int, m2: int, m3: int) -> bool:
+    """valid modes for the field, within the sizes the kernels cover (dpot_fno3_max_size)"""
+    return _fno_supported((X, Y, Z), (m1, m2, m3))
 
 
 def fno_kept_rows(H: int, m1: int):
@@ -2857,6 +2896,14 @@ def fno_twiddles(H: int, W: int, m1: int, m2: int):
     return np.stack([np.cos(ax), np.sin(ax)], -1), np.stack([np.cos(ay), np.sin(ay)], -1)
 
 
+def fno3_twiddles(X: int, Y: int, Z: int, m1: int, m2: int, m3: int):
+    """float64 (tx [X, 2 m1, 2], ty [Y, 2 m2, 2], tz [Z, m3, 2]): cos | sin of 2 pi k n / N over the kept wavenumbers, the angle
+    reduced in integers.  (tx, tz) and (ty, tz) are fno_twiddles tables: the plane kernels are FNO2d's"""
+    tx, tz = fno_twiddles(X, Z, m1, m3)
+    ty, _ = fno_twiddles(Y, Z, m2, m3)
+    return tx, ty, tz
+
+
 def fno_col_weights(W: int, m2: int):
     """w(ky) of irfft2 for a spectrum that is not Hermitian: 1 at ky = 0 and, for even W, at ky = W / 2, else 2"""
     import numpy as np
@@ -2868,62 +2915,140 @@ def fno_col_weights(W: int, m2: int):
 
 
 class FNOPlan:
-    """The twiddle tables of dpot_fno_rfft2 / dpot_fno_irfft2 for one (H, W, m1, m2), built in float64, rounded to fp32 and kept
-    in device memory."""
+    """The twiddle tables of the truncated transforms for one (H, W, m1, m2, device) or (X, Y, Z, m1, m2, m3, device): .tx, .ty
+    (and .tz), one per axis, built in float64, rounded to fp32 and kept in device memory.  FNO3Plan is the same class: the
+    number of sizes gives the rank."""
 
-    def __init__(self, H: int, W: int, m1: int, m2: int, device):
-        fno_check_modes(H, W, m1, m2, "FNOPlan")
-        if not fno_supported(H, W, m1, m2):
-            lib = _lib.load()
-            raise ValueError(f"FNOPlan: field {H}x{W} with modes ({m1}, {m2}) is beyond the kernels' limits (H, W <= "
-                             f"{lib.dpot_fno_max_size(0)}, modes <= {lib.dpot_fno_max_size(1)})")
-        self.sizes = (H, W, m1, m2)
+    def __init__(self, *sizes_device):
+        *sizes, device = sizes_device
+        rank = len(sizes) // 2
+        dims, modes = tuple(sizes[:rank]), tuple(sizes[rank:])
+        name, entry = ("FNOPlan", "fno_plan") if rank == 2 else ("FNO3Plan", "fno3_plan")
+        _fno_check_modes(dims, modes, name)
+        if not _fno_supported(dims, modes):
+            n, m = _fno_limits(rank)
+            raise ValueError(f"{name}: field {'x'.join(map(str, dims))} with modes {modes} is beyond the kernels' limits "
+                             f"({', '.join(_FNO_AXES[rank])} <= {n}, modes <= {m})")
+        self.sizes = dims + modes
         if torch.cuda.is_current_stream_capturing():
-            raise _lib.DpotHipError(f"FNOPlan {self.sizes}: the tables are uploaded when a size tuple is first used - call "
-                                    "ops.fno_plan(...) (or the operator itself) once before capturing")
-        tx, ty = fno_twiddles(H, W, m1, m2)
-        self.tx = torch.empty(tx.shape, dtype=torch.float32, device=device)
-        self.tx.copy_(torch.from_numpy(tx.astype("float32")))
-        self.ty = torch.empty(ty.shape, dtype=torch.float32, device=device)
-        self.ty.copy_(torch.from_numpy(ty.astype("float32")))
+            raise _lib.DpotHipError(f"{name} {self.sizes}: the tables are uploaded when a size tuple is first used - call "
+                                    f"ops.{entry}(...) (or the operator itself) once before capturing")
+        self.tables = []
+        for axis, t in zip(("tx", "ty", "tz"), (fno_twiddles if rank == 2 else fno3_twiddles)(*self.sizes)):
+            dev = torch.empty(t.shape, dtype=torch.float32, device=device)
+            dev.copy_(torch.from_numpy(t.astype("float32")))
+            setattr(self, axis, dev)
+            self.tables.append(dev)
 
 
+FNO3Plan = FNOPlan
 _fno_plans = {}
 
 
-def fno_plan(H: int, W: int, m1: int, m2: int, device) -> FNOPlan:
-    """the cached FNOPlan of (H, W, m1, m2, device)"""
+def _fno_plan(dims, modes, device) -> FNOPlan:
+    """the cached plan of (dims, modes, device)"""
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    key = (int(H), int(W), int(m1), int(m2), device)
+    key = tuple(int(n) for n in (*dims, *modes)) + (device,)
     plan = _fno_plans.get(key)
     if plan is None:
         plan = _fno_plans[key] = FNOPlan(*key)
     return plan
 
 
-def _fno_field(x: Tensor, what: str):
-    if x.dim() != 4 or x.numel() == 0:
-        raise ValueError(f"{what}: the field must be a non-empty [B, H, W, C], got {tuple(x.shape)}")
-    return tuple(x.shape)
+def fno_plan(H: int, W: int, m1: int, m2: int, device) -> FNOPlan:
+    """the cached FNOPlan of (H, W, m1, m2, device)"""
+    return _fno_plan((H, W), (m1, m2), device)
+
+
+def fno3_plan(X: int, Y: int, Z: int, m1: int, m2: int, m3: int, device) -> FNOPlan:
+    """the cached FNO3Plan of (X, Y, Z, m1, m2, m3, device)"""
+    return _fno_plan((X, Y, Z), (m1, m2, m3), device)
+
+
+def _fno_buf(t: Optional[Tensor], what: str, name: str, shape, device) -> Tensor:
+    """`t`, checked to be a kernel-ready tensor of `shape` on `device`; a fresh one when it is None"""
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(_req(t, f"{what}: {name}").shape) != tuple(shape) or t.device != device:
+        raise ValueError(f"{what}: {name} must be {tuple(shape)} on {device}, got {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _fno_kept(modes):
+    """the kept-mode axes of a spectrum: (2 m1, m2) or (2 m1, 2 m2, m3)"""
+    return tuple(2 * m for m in modes[:-1]) + (modes[-1],)
+
+
+def _fno_kept_text(rank: int) -> str:
+    """the same axes as the messages spell them"""
+    return ", ".join([f"2 m{k + 1}" for k in range(rank - 1)] + [f"m{rank}"])
+
+
+def _fno_kept_modes(S: Tensor, rank: int):
+    """the modes of a spectrum [B, kept axes, 2, C]; None unless it is one of this rank"""
+    if S.dim() != rank + 3 or S.shape[-2] != 2 or any(n % 2 for n in S.shape[1:rank]) or S.numel() == 0:
+        return None
+    return tuple(n // 2 for n in S.shape[1:rank]) + (S.shape[rank],)
+
+
+def _fno_transform(what: str, head, B: int, dims, Cc: int, modes, tail, device) -> None:
+    """one transform entry point: dpot_<what>(*head, [ws,] tables, B, dims, C, modes, *tail, stream).  The 3-D workspace
+    [B, X, 2 m2, m3, 2, C] between the two launches is a local here: it lives until both launches have been issued and is
+    dropped when the operator returns"""
+    lib = _lib.load()
+    plan = _fno_plan(dims, modes, device)
+    entry = getattr(lib, "dpot_" + what)
+    tables = [t.data_ptr() for t in plan.tables]
+    sizes = (B, *dims, Cc, *modes, *tail, _stream())
+    if len(dims) == 2:
+        check(entry(*head, *tables, *sizes), what)
+    else:
+        ws = _scratch(torch.empty(lib.dpot_fno3_ws_elems(B, dims[0], Cc, modes[1], modes[2]), dtype=torch.float32, device=device))
+        check(entry(*head, ws.data_ptr(), *tables, *sizes), what)
+
+
+def _fno_rfft(what: str, x: Tensor, modes, adjoint: bool, out: Optional[Tensor]) -> Tensor:
+    rank = len(modes)
+    if x.dim() != rank + 2 or x.numel() == 0:
+        raise ValueError(f"{what}: the field must be a non-empty [B, {', '.join(_FNO_AXES[rank])}, C], got {tuple(x.shape)}")
+    B, *dims, Cc = x.shape
+    _fno_check_modes(dims, modes, what)
+    _req(x, f"{what}: x")
+    out = _fno_buf(out, what, "out", (B,) + _fno_kept(modes) + (2, Cc), x.device)
+    _fno_transform(what, (x.data_ptr(), out.data_ptr()), B, dims, Cc, modes,
+                   (1 if adjoint else 0, 1.0 / math.prod(dims) if adjoint else 1.0), x.device)
+    return out
+
+
+def _fno_irfft(what: str, S: Tensor, dims, add, act: int, save_pre: bool, adjoint: bool, out):
+    modes = _fno_kept_modes(S, len(dims))
+    if modes is None:
+        raise ValueError(f"{what}: the spectrum must be a non-empty [B, {_fno_kept_text(len(dims))}, 2, C], got {tuple(S.shape)}")
+    B, Cc = S.shape[0], S.shape[-1]
+    _fno_check_modes(dims, modes, what)
+    _req(S, f"{what}: S")
+    shape = (B, *dims, Cc)
+    if add is not None:
+        _fno_buf(add, what, "add", shape, S.device)
+    out = _fno_buf(out, what, "out", shape, S.device)
+    pre = torch.empty_like(out) if save_pre else None
+    _fno_transform(what, (S.data_ptr(), _p(add), out.data_ptr(), _p(pre)), B, tuple(dims), Cc, modes,
+                   (0 if adjoint else 1, 1.0 if adjoint else 1.0 / math.prod(dims), int(act)), S.device)
+    return out, pre
 
 
 def fno_rfft2(x: Tensor, m1: int, m2: int, adjoint: bool = False, out: Optional[Tensor] = None) -> Tensor:
     """x [B, H, W, C] -> the kept spectrum S [B, 2 m1, m2, 2, C] of the unnormalised rfft2.  adjoint=True: the adjoint of
     fno_irfft2 instead (the same sums times w(ky) / (H W)): the gradient of the spectrum from the gradient of the field"""
-    B, H, W, Cc = _fno_field(x, "fno_rfft2")
-    fno_check_modes(H, W, m1, m2, "fno_rfft2")
-    _req(x, "fno_rfft2: x")
-    plan = fno_plan(H, W, m1, m2, x.device)
-    shape = (B, 2 * m1, m2, 2, Cc)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif tuple(_req(out, "fno_rfft2: out").shape) != shape or out.device != x.device:
-        raise ValueError(f"fno_rfft2: out must be {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
-    check(_lib.load().dpot_fno_rfft2(x.data_ptr(), out.data_ptr(), plan.tx.data_ptr(), plan.ty.data_ptr(), B, H, W, Cc, m1, m2,
-                                     1 if adjoint else 0, 1.0 / (H * W) if adjoint else 1.0, _stream()), "fno_rfft2")
-    return out
+    return _fno_rfft("fno_rfft2", x, (m1, m2), adjoint, out)
+
+
+def fno3_rfft3(x: Tensor, m1: int, m2: int, m3: int, adjoint: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """x [B, X, Y, Z, C] -> the kept spectrum S [B, 2 m1, 2 m2, m3, 2, C] of the unnormalised rfftn.  adjoint=True: the adjoint
+    of fno3_irfft3 instead (the same sums times w(kz) / (X Y Z)): the gradient of the spectrum from the gradient of the field"""
+    return _fno_rfft("fno3_rfft3", x, (m1, m2, m3), adjoint, out)
 
 
 def fno_irfft2(S: Tensor, H: int, W: int, add: Optional[Tensor] = None, act: int = 0, save_pre: bool = False,
@@ -2931,76 +3056,94 @@ def fno_irfft2(S: Tensor, H: int, W: int, add: Optional[Tensor] = None, act: int
     """the kept spectrum S [B, 2 m1, m2, 2, C] -> (y, pre): y [B, H, W, C] = act(irfft2(S, s=(H, W)) + add), pre the value
     before the activation (save_pre, else None).  adjoint=True: the adjoint of fno_rfft2 instead (column weights 1, no
     1 / (H W)): the gradient of the field from the gradient of its spectrum"""
-    if S.dim() != 5 or S.shape[3] != 2 or S.shape[1] % 2 or S.numel() == 0:
-        raise ValueError(f"fno_irfft2: the spectrum must be a non-empty [B, 2 m1, m2, 2, C], got {tuple(S.shape)}")
-    B, R, m2, _, Cc = S.shape
-    m1 = R // 2
-    fno_check_modes(H, W, m1, m2, "fno_irfft2")
-    _req(S, "fno_irfft2: S")
-    plan = fno_plan(H, W, m1, m2, S.device)
-    shape = (B, H, W, Cc)
-    if add is not None and (tuple(_req(add, "fno_irfft2: add").shape) != shape or add.device != S.device):
-        raise ValueError(f"fno_irfft2: add must be {shape} on {S.device}, got {tuple(add.shape)} on {add.device}")
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=S.device)
-    elif tuple(_req(out, "fno_irfft2: out").shape) != shape or out.device != S.device:
-        raise ValueError(f"fno_irfft2: out must be {shape} on {S.device}, got {tuple(out.shape)} on {out.device}")
-    pre = torch.empty_like(out) if save_pre else None
-    check(_lib.load().dpot_fno_irfft2(S.data_ptr(), _p(add), out.data_ptr(), _p(pre), plan.tx.data_ptr(), plan.ty.data_ptr(),
-                                      B, H, W, Cc, m1, m2, 0 if adjoint else 1, 1.0 if adjoint else 1.0 / (H * W), int(act),
-                                      _stream()), "fno_irfft2")
-    return out, pre
+    return _fno_irfft("fno_irfft2", S, (H, W), add, act, save_pre, adjoint, out)
 
 
-def _fno_weights(w1: Tensor, w2: Tensor, what: str):
-    _req(w1, f"{what}: weights1")
-    _req(w2, f"{what}: weights2")
-    if w1.dim() != 5 or w1.shape[0] != 2 or w1.shape != w2.shape or w1.numel() == 0:
-        raise ValueError(f"{what}: weights1 / weights2 must both be [2, Cin, Cout, m1, m2], got {tuple(w1.shape)} and "
-                         f"{tuple(w2.shape)}")
-    return tuple(w1.shape[1:])
+def fno3_irfft3(S: Tensor, X: int, Y: int, Z: int, add: Optional[Tensor] = None, act: int = 0, save_pre: bool = False,
+                adjoint: bool = False, out: Optional[Tensor] = None):
+    """the kept spectrum S [B, 2 m1, 2 m2, m3, 2, C] -> (y, pre): y [B, X, Y, Z, C] = act(irfftn(S, s=(X, Y, Z)) + add), pre
+    the value before the activation (save_pre, else None).  adjoint=True: the adjoint of fno3_rfft3 instead (weights 1, no
+    1 / (X Y Z)): the gradient of the field from the gradient of its spectrum"""
+    return _fno_irfft("fno3_irfft3", S, (X, Y, Z), add, act, save_pre, adjoint, out)
+
+
+def _fno_weights(ws, what: str, planar: bool):
+    """(Cin, Cout, modes) of a layer's spectral weights: planar [2, Cin, Cout, m1, m2] or real-pair [Cin, Cout, m1, m2, m3, 2]"""
+    w0 = ws[0]
+    ok = w0.dim() == 5 and w0.shape[0] == 2 if planar else w0.dim() == 6 and w0.shape[-1] == 2
+    for k, w in enumerate(ws):
+        _req(w, f"{what}: weights{k + 1}")
+        if not ok or w.shape != w0.shape or w.numel() == 0:
+            if planar:
+                raise ValueError(f"{what}: weights1 / weights2 must both be [2, Cin, Cout, m1, m2], got {tuple(ws[0].shape)} and "
+                                 f"{tuple(ws[1].shape)}")
+            raise ValueError(f"{what}: every weight must be the real-pair [Cin, Cout, m1, m2, m3, 2], got "
+                             f"{[tuple(t.shape) for t in ws]}")
+    Cin, Cout, *modes = w0.shape[1:] if planar else w0.shape[:-1]
+    return Cin, Cout, tuple(modes)
+
+
+def _fno_mix(what: str, X: Tensor, ws, adjoint: bool, planar: bool) -> Tensor:
+    Cin, Cout, modes = _fno_weights(ws, what, planar)
+    K, N = (Cout, Cin) if adjoint else (Cin, Cout)
+    _req(X, f"{what}: X")
+    kept = _fno_kept(modes)
+    if tuple(X.shape[1:]) != kept + (2, K) or X.shape[0] < 1:
+        raise ValueError(f"{what}: the spectrum must be [B, {', '.join(map(str, kept))}, 2, {K}], got {tuple(X.shape)}")
+    B = X.shape[0]
+    O = torch.empty((B,) + kept + (2, N), dtype=torch.float32, device=X.device)
+    check(getattr(_lib.load(), "dpot_" + what)(X.data_ptr(), *(w.data_ptr() for w in ws), O.data_ptr(), B, Cin, Cout, *modes,
+                                               1 if adjoint else 0, _stream()), what)
+    return O
+
+
+def _fno_mix_wgrad(what: str, X: Tensor, dO: Tensor, outs, accumulate: bool, planar: bool):
+    rank = 2 if planar else 3
+    _req(X, f"{what}: X")
+    _req(dO, f"{what}: dO")
+    modes = _fno_kept_modes(X, rank)
+    if modes is None or dO.dim() != X.dim() or X.shape[:-1] != dO.shape[:-1] or dO.numel() == 0:
+        kept = _fno_kept_text(rank)
+        raise ValueError(f"{what}: X [B, {kept}, 2, Cin] and dO [B, {kept}, 2, Cout], got {tuple(X.shape)} and {tuple(dO.shape)}")
+    B, Cin, Cout = X.shape[0], X.shape[-1], dO.shape[-1]
+    shape = (2, Cin, Cout, *modes) if planar else (Cin, Cout, *modes, 2)
+    outs = [_fno_buf(o, what, "out", shape, X.device) for o in outs]
+    check(getattr(_lib.load(), "dpot_" + what)(X.data_ptr(), dO.data_ptr(), *(o.data_ptr() for o in outs), B, Cin, Cout, *modes,
+                                               1 if accumulate else 0, _stream()), what)
+    return tuple(outs)
 
 
 def fno_mix(X: Tensor, w1: Tensor, w2: Tensor, adjoint: bool = False) -> Tensor:
     """O[b, r, ky, :, o] = sum_i X[b, r, ky, :, i] W[i, o, r mod m1, ky] (complex), W = w[0] + i w[1], weights1 on the rows
     below m1 and weights2 above, read in place.  adjoint=True: sum over o with conj(W): the data gradient"""
-    Cin, Cout, m1, m2 = _fno_weights(w1, w2, "fno_mix")
-    K, N = (Cout, Cin) if adjoint else (Cin, Cout)
-    _req(X, "fno_mix: X")
-    if tuple(X.shape[1:]) != (2 * m1, m2, 2, K) or X.shape[0] < 1:
-        raise ValueError(f"fno_mix: the spectrum must be [B, {2 * m1}, {m2}, 2, {K}], got {tuple(X.shape)}")
-    B = X.shape[0]
-    O = torch.empty(B, 2 * m1, m2, 2, N, dtype=torch.float32, device=X.device)
-    check(_lib.load().dpot_fno_mix(X.data_ptr(), w1.data_ptr(), w2.data_ptr(), O.data_ptr(), B, Cin, Cout, m1, m2,
-                                   1 if adjoint else 0, _stream()), "fno_mix")
-    return O
+    return _fno_mix("fno_mix", X, (w1, w2), adjoint, planar=True)
+
+
+def fno3_mix(X: Tensor, ws, adjoint: bool = False) -> Tensor:
+    """O[b, r, q, kz, :, o] = sum_i X[b, r, q, kz, :, i] W[i, o, r mod m1, q mod m2, kz] (complex), W the corner weight
+    1 + (r >= m1) + 2 (q >= m2) of `ws` = (weights1..weights4), read in place.  adjoint=True: sum over o with conj(W)"""
+    if len(ws) != 4:
+        raise ValueError(f"fno3_mix: four corner weights (weights1..weights4), got {len(ws)}")
+    return _fno_mix("fno3_mix", X, tuple(ws), adjoint, planar=False)
 
 
 def fno_mix_wgrad(X: Tensor, dO: Tensor, out1: Optional[Tensor] = None, out2: Optional[Tensor] = None,
                   accumulate: bool = False):
     """(dweights1, dweights2) [2, Cin, Cout, m1, m2] from the layer's input spectrum X [B, 2 m1, m2, 2, Cin] and the gradient
     dO [B, 2 m1, m2, 2, Cout] of its output spectrum, summed over b in ascending order; accumulate: added to out1 / out2"""
-    _req(X, "fno_mix_wgrad: X")
-    _req(dO, "fno_mix_wgrad: dO")
-    if X.dim() != 5 or dO.dim() != 5 or X.shape[:4] != dO.shape[:4] or X.shape[3] != 2 or X.shape[1] % 2 or X.numel() == 0 \
-            or dO.numel() == 0:
-        raise ValueError(f"fno_mix_wgrad: X [B, 2 m1, m2, 2, Cin] and dO [B, 2 m1, m2, 2, Cout], got {tuple(X.shape)} and "
-                         f"{tuple(dO.shape)}")
-    B, R, m2, _, Cin = X.shape
-    Cout, m1 = dO.shape[4], R // 2
-    shape = (2, Cin, Cout, m1, m2)
     if accumulate and (out1 is None or out2 is None):
         raise ValueError("fno_mix_wgrad: accumulate needs out1 and out2")
-    outs = []
-    for o in (out1, out2):
-        if o is None:
-            o = torch.empty(shape, dtype=torch.float32, device=X.device)
-        elif tuple(_req(o, "fno_mix_wgrad: out").shape) != shape or o.device != X.device:
-            raise ValueError(f"fno_mix_wgrad: out must be {shape} on {X.device}, got {tuple(o.shape)} on {o.device}")
-        outs.append(o)
-    check(_lib.load().dpot_fno_mix_wgrad(X.data_ptr(), dO.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), B, Cin, Cout, m1,
-                                         m2, 1 if accumulate else 0, _stream()), "fno_mix_wgrad")
-    return outs[0], outs[1]
+    return _fno_mix_wgrad("fno_mix_wgrad", X, dO, (out1, out2), accumulate, planar=True)
+
+
+def fno3_mix_wgrad(X: Tensor, dO: Tensor, outs=None, accumulate: bool = False):
+    """(dweights1..dweights4) [Cin, Cout, m1, m2, m3, 2] from the layer's input spectrum X [B, 2 m1, 2 m2, m3, 2, Cin] and the
+    gradient dO [.., Cout] of its output spectrum, summed over b in ascending order; outs: four buffers to write (None entries are
+    allocated); accumulate: added to them"""
+    outs = list(outs) if outs is not None else [None] * 4
+    if len(outs) != 4 or (accumulate and any(o is None for o in outs)):
+        raise ValueError("fno3_mix_wgrad: outs holds four buffers, and accumulate needs all of them")
+    return _fno_mix_wgrad("fno3_mix_wgrad", X, dO, outs, accumulate, planar=False)
 
 
 def act_bwd_mul(dy: Tensor, pre: Tensor, act: int) -> Tensor:
@@ -3012,179 +3155,3 @@ def act_bwd_mul(dy: Tensor, pre: Tensor, act: int) -> Tensor:
     out = torch.empty_like(dy)
     check(_lib.load().dpot_fno_dact(dy.data_ptr(), pre.data_ptr(), out.data_ptr(), dy.numel(), int(act), _stream()), "fno_dact")
     return out
-
-
-# ------------------------------------------------------------------------------------------------------
-# The 3-D FNO baseline (csrc/fno3.hip; models/fno.py SpectralConv3d): truncated transforms of a channels-last field
-# x [B, X, Y, Z, C] to / from the kept spectrum S [B, 2 m1, 2 m2, m3, 2, C] (kx and ky below m and above N - m, kz < m3, re | im
-# planes, channels innermost) and the per-mode mixing with the four corner weights [Cin, Cout, m1, m2, m3, 2] (real pairs).
-# Each transform is two launches around a workspace this module allocates.  The twiddle tables are pure numpy.
-# ------------------------------------------------------------------------------------------------------
-def fno3_check_modes(X: int, Y: int, Z: int, m1: int, m2: int, m3: int, what: str = "fno3") -> None:
-    """the two refusals: the corner blocks must not overlap (the reference silently lets later ones overwrite earlier ones) and
-    modes3 must fit the half spectrum (the reference raises inside its slice assignment)"""
-    if min(X, Y, Z, m1, m2, m3) < 1:
-        raise ValueError(f"{what}: field {X}x{Y}x{Z} and modes ({m1}, {m2}, {m3}) must be positive")
-    if 2 * m1 > X:
-        raise ValueError(f"{what}: modes1 = {m1} needs 2 * modes1 <= X = {X}: the kept corner blocks would overlap")
-    if 2 * m2 > Y:
-        raise ValueError(f"{what}: modes2 = {m2} needs 2 * modes2 <= Y = {Y}: the kept corner blocks would overlap")
-    if m3 > Z // 2 + 1:
-        raise ValueError(f"{what}: modes3 = {m3} exceeds the Z // 2 + 1 = {Z // 2 + 1} planes of the half spectrum of Z = {Z}")
-
-
-def fno3_supported(X: int, Y: int, Z: int, m1: int, m2: int, m3: int) -> bool:
-    """valid modes for the field, within the sizes the kernels cover (dpot_fno3_max_size)"""
-    lib = _lib.load()
-    n, m = lib.dpot_fno3_max_size(0), lib.dpot_fno3_max_size(1)
-    return (min(X, Y, Z, m1, m2, m3) >= 1 and 2 * m1 <= X and 2 * m2 <= Y and m3 <= Z // 2 + 1 and max(X, Y, Z) <= n
-            and max(m1, m2, m3) <= m)
-
-
-def fno3_twiddles(X: int, Y: int, Z: int, m1: int, m2: int, m3: int):
-    """float64 (tx [X, 2 m1, 2], ty [Y, 2 m2, 2], tz [Z, m3, 2]): cos | sin of 2 pi k n / N over the kept wavenumbers, the angle
-    reduced in integers.  (tx, tz) and (ty, tz) are fno_twiddles tables: the plane kernels are FNO2d's"""
-    tx, tz = fno_twiddles(X, Z, m1, m3)
-    ty, _ = fno_twiddles(Y, Z, m2, m3)
-    return tx, ty, tz
-
-
-class FNO3Plan:
-    """The twiddle tables of dpot_fno3_rfft3 / dpot_fno3_irfft3 for one (X, Y, Z, m1, m2, m3), built in float64, rounded to fp32
-    and kept in device memory."""
-
-    def __init__(self, X: int, Y: int, Z: int, m1: int, m2: int, m3: int, device):
-        fno3_check_modes(X, Y, Z, m1, m2, m3, "FNO3Plan")
-        if not fno3_supported(X, Y, Z, m1, m2, m3):
-            lib = _lib.load()
-            raise ValueError(f"FNO3Plan: field {X}x{Y}x{Z} with modes ({m1}, {m2}, {m3}) is beyond the kernels' limits (X, Y, Z "
-                             f"<= {lib.dpot_fno3_max_size(0)}, modes <= {lib.dpot_fno3_max_size(1)})")
-        self.sizes = (X, Y, Z, m1, m2, m3)
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.DpotHipError(f"FNO3Plan {self.sizes}: the tables are uploaded when a size tuple is first used - call "
-                                    "ops.fno3_plan(...) (or the operator itself) once before capturing")
-        for name, t in zip(("tx", "ty", "tz"), fno3_twiddles(X, Y, Z, m1, m2, m3)):
-            dev = torch.empty(t.shape, dtype=torch.float32, device=device)
-            dev.copy_(torch.from_numpy(t.astype("float32")))
-            setattr(self, name, dev)
-
-
-_fno3_plans = {}
-
-
-def fno3_plan(X: int, Y: int, Z: int, m1: int, m2: int, m3: int, device) -> FNO3Plan:
-    """the cached FNO3Plan of (X, Y, Z, m1, m2, m3, device)"""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (int(X), int(Y), int(Z), int(m1), int(m2), int(m3), device)
-    plan = _fno3_plans.get(key)
-    if plan is None:
-        plan = _fno3_plans[key] = FNO3Plan(*key)
-    return plan
-
-
-def _fno3_ws(B: int, X: int, C: int, m2: int, m3: int, device) -> Tensor:
-    """the workspace between the two launches of a transform: [B, X, 2 m2, m3, 2, C], dropped when the operator returns"""
-    n = _lib.load().dpot_fno3_ws_elems(B, X, C, m2, m3)
-    return _scratch(torch.empty(n, dtype=torch.float32, device=device))
-
-
-def fno3_rfft3(x: Tensor, m1: int, m2: int, m3: int, adjoint: bool = False, out: Optional[Tensor] = None) -> Tensor:
-    """x [B, X, Y, Z, C] -> the kept spectrum S [B, 2 m1, 2 m2, m3, 2, C] of the unnormalised rfftn.  adjoint=True: the adjoint
-    of fno3_irfft3 instead (the same sums times w(kz) / (X Y Z)): the gradient of the spectrum from the gradient of the field"""
-    if x.dim() != 5 or x.numel() == 0:
-        raise ValueError(f"fno3_rfft3: the field must be a non-empty [B, X, Y, Z, C], got {tuple(x.shape)}")
-    B, X, Y, Z, Cc = x.shape
-    fno3_check_modes(X, Y, Z, m1, m2, m3, "fno3_rfft3")
-    _req(x, "fno3_rfft3: x")
-    plan = fno3_plan(X, Y, Z, m1, m2, m3, x.device)
-    shape = (B, 2 * m1, 2 * m2, m3, 2, Cc)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    elif tuple(_req(out, "fno3_rfft3: out").shape) != shape or out.device != x.device:
-        raise ValueError(f"fno3_rfft3: out must be {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
-    ws = _fno3_ws(B, X, Cc, m2, m3, x.device)
-    check(_lib.load().dpot_fno3_rfft3(x.data_ptr(), out.data_ptr(), ws.data_ptr(), plan.tx.data_ptr(), plan.ty.data_ptr(),
-                                      plan.tz.data_ptr(), B, X, Y, Z, Cc, m1, m2, m3, 1 if adjoint else 0,
-                                      1.0 / (X * Y * Z) if adjoint else 1.0, _stream()), "fno3_rfft3")
-    return out
-
-
-def fno3_irfft3(S: Tensor, X: int, Y: int, Z: int, add: Optional[Tensor] = None, act: int = 0, save_pre: bool = False,
-                adjoint: bool = False, out: Optional[Tensor] = None):
-    """the kept spectrum S [B, 2 m1, 2 m2, m3, 2, C] -> (y, pre): y [B, X, Y, Z, C] = act(irfftn(S, s=(X, Y, Z)) + add), pre
-    the value before the activation (save_pre, else None).  adjoint=True: the adjoint of fno3_rfft3 instead (weights 1, no
-    1 / (X Y Z)): the gradient of the field from the gradient of its spectrum"""
-    if S.dim() != 6 or S.shape[4] != 2 or S.shape[1] % 2 or S.shape[2] % 2 or S.numel() == 0:
-        raise ValueError(f"fno3_irfft3: the spectrum must be a non-empty [B, 2 m1, 2 m2, m3, 2, C], got {tuple(S.shape)}")
-    B, R, Q, m3, _, Cc = S.shape
-    m1, m2 = R // 2, Q // 2
-    fno3_check_modes(X, Y, Z, m1, m2, m3, "fno3_irfft3")
-    _req(S, "fno3_irfft3: S")
-    plan = fno3_plan(X, Y, Z, m1, m2, m3, S.device)
-    shape = (B, X, Y, Z, Cc)
-    if add is not None and (tuple(_req(add, "fno3_irfft3: add").shape) != shape or add.device != S.device):
-        raise ValueError(f"fno3_irfft3: add must be {shape} on {S.device}, got {tuple(add.shape)} on {add.device}")
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=S.device)
-    elif tuple(_req(out, "fno3_irfft3: out").shape) != shape or out.device != S.device:
-        raise ValueError(f"fno3_irfft3: out must be {shape} on {S.device}, got {tuple(out.shape)} on {out.device}")
-    pre = torch.empty_like(out) if save_pre else None
-    ws = _fno3_ws(B, X, Cc, m2, m3, S.device)
-    check(_lib.load().dpot_fno3_irfft3(S.data_ptr(), _p(add), out.data_ptr(), _p(pre), ws.data_ptr(), plan.tx.data_ptr(),
-                                       plan.ty.data_ptr(), plan.tz.data_ptr(), B, X, Y, Z, Cc, m1, m2, m3, 0 if adjoint else 1,
-                                       1.0 if adjoint else 1.0 / (X * Y * Z), int(act), _stream()), "fno3_irfft3")
-    return out, pre
-
-
-def _fno3_weights(ws, what: str):
-    if len(ws) != 4:
-        raise ValueError(f"{what}: four corner weights (weights1..weights4), got {len(ws)}")
-    for k, w in enumerate(ws):
-        _req(w, f"{what}: weights{k + 1}")
-        if w.dim() != 6 or w.shape[5] != 2 or w.shape != ws[0].shape or w.numel() == 0:
-            raise ValueError(f"{what}: every weight must be the real-pair [Cin, Cout, m1, m2, m3, 2], got "
-                             f"{[tuple(t.shape) for t in ws]}")
-    return tuple(ws[0].shape[:5])
-
-
-def fno3_mix(X: Tensor, ws, adjoint: bool = False) -> Tensor:
-    """O[b, r, q, kz, :, o] = sum_i X[b, r, q, kz, :, i] W[i, o, r mod m1, q mod m2, kz] (complex), W the corner weight
-    1 + (r >= m1) + 2 (q >= m2) of `ws` = (weights1..weights4), read in place.  adjoint=True: sum over o with conj(W)"""
-    Cin, Cout, m1, m2, m3 = _fno3_weights(ws, "fno3_mix")
-    K, N = (Cout, Cin) if adjoint else (Cin, Cout)
-    _req(X, "fno3_mix: X")
-    if tuple(X.shape[1:]) != (2 * m1, 2 * m2, m3, 2, K) or X.shape[0] < 1:
-        raise ValueError(f"fno3_mix: the spectrum must be [B, {2 * m1}, {2 * m2}, {m3}, 2, {K}], got {tuple(X.shape)}")
-    B = X.shape[0]
-    O = torch.empty(B, 2 * m1, 2 * m2, m3, 2, N, dtype=torch.float32, device=X.device)
-    check(_lib.load().dpot_fno3_mix(X.data_ptr(), *(w.data_ptr() for w in ws), O.data_ptr(), B, Cin, Cout, m1, m2, m3,
-                                    1 if adjoint else 0, _stream()), "fno3_mix")
-    return O
-
-
-def fno3_mix_wgrad(X: Tensor, dO: Tensor, outs=None, accumulate: bool = False):
-    """(dweights1..dweights4) [Cin, Cout, m1, m2, m3, 2] from the layer's input spectrum X [B, 2 m1, 2 m2, m3, 2, Cin] and the
-    gradient dO [.., Cout] of its output spectrum, summed over b in ascending order; outs: four buffers to write (None entries are
-    allocated); accumulate: added to them"""
-    _req(X, "fno3_mix_wgrad: X")
-    _req(dO, "fno3_mix_wgrad: dO")
-    if X.dim() != 6 or dO.dim() != 6 or X.shape[:5] != dO.shape[:5] or X.shape[4] != 2 or X.shape[1] % 2 or X.shape[2] % 2 \
-            or X.numel() == 0 or dO.numel() == 0:
-        raise ValueError(f"fno3_mix_wgrad: X [B, 2 m1, 2 m2, m3, 2, Cin] and dO [B, 2 m1, 2 m2, m3, 2, Cout], got "
-                         f"{tuple(X.shape)} and {tuple(dO.shape)}")
-    B, R, Q, m3, _, Cin = X.shape
-    Cout, m1, m2 = dO.shape[5], R // 2, Q // 2
-    shape = (Cin, Cout, m1, m2, m3, 2)
-    outs = list(outs) if outs is not None else [None] * 4
-    if len(outs) != 4 or (accumulate and any(o is None for o in outs)):
-        raise ValueError("fno3_mix_wgrad: outs holds four buffers, and accumulate needs all of them")
-    for k, o in enumerate(outs):
-        if o is None:
-            outs[k] = torch.empty(shape, dtype=torch.float32, device=X.device)
-        elif tuple(_req(o, "fno3_mix_wgrad: out").shape) != shape or o.device != X.device:
-            raise ValueError(f"fno3_mix_wgrad: out must be {shape} on {X.device}, got {tuple(o.shape)} on {o.device}")
-    check(_lib.load().dpot_fno3_mix_wgrad(X.data_ptr(), dO.data_ptr(), *(o.data_ptr() for o in outs), B, Cin, Cout, m1, m2, m3,
-                                          1 if accumulate else 0, _stream()), "fno3_mix_wgrad")
-    return tuple(outs)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""Bit-level fingerprint of the three models' training step (DPOTNet, DPOTNet3D, CDPOTNet) and of the block path
-(functional.BlockFn / AFNO2DFn / AFNO3DFn / block3d), for comparing two trees that must compute the same thing:
+"""Bit-level fingerprint of the models' training step (DPOTNet, DPOTNet3D, CDPOTNet, FNO2d, FNO3d), of the block path
+(functional.BlockFn / AFNO2DFn / AFNO3DFn / block3d) and of the FNO mixing operators, for comparing two trees that must compute
+the same thing:
 python scripts/grad_fingerprint.py > a.txt   in each tree, on the same machine with the same built library (DPOT_HIP_LIB),
 then `diff`.  Run it a second time under DPOT_TUNE=gn_fuse=0,panel=0 (the C library reads those two keys once per process);
 the Python-side DPOT_TUNE keys are set per case here.
@@ -11,6 +12,7 @@ case asserts its route where the code offers a way to see it.  Inputs and weight
 tests/afno3d_ref.py and tests/cdpot_ref.py, as the tests use them."""
 import hashlib
 import itertools
+import math
 import os
 import sys
 from collections import OrderedDict
@@ -25,8 +27,11 @@ import cdpot_ref as CR  # noqa: E402
 import dft_cases as DC  # noqa: E402
 import eval3d_ref as E3  # noqa: E402
 import eval_ref as E2  # noqa: E402
+import fno3d_ref as F3  # noqa: E402
+import fno3d_time  # noqa: E402  (scripts/: the shapes it times)
 import fno_ref as FR  # noqa: E402
-from dpot_amd import CDPOTNet, DPOTNet, DPOTNet3D, FNO2d, RolloutEvaluator, _lib, load_3d_components_from_2d, ops  # noqa: E402
+import fno_time  # noqa: E402  (scripts/)
+from dpot_amd import CDPOTNet, DPOTNet, DPOTNet3D, FNO2d, FNO3d, RolloutEvaluator, _lib, load_3d_components_from_2d, ops  # noqa: E402
 from dpot_amd.functional import AFNO2DFn, AFNO3DFn, block3d  # noqa: E402
 from dpot_amd.train import FlatParams, FusedAdam, rollout, rollout_total, train_step  # noqa: E402
 from oracle import dpot_ref as R  # noqa: E402
@@ -279,6 +284,58 @@ def fno_case():
     report("fno2d mini step", loss, [pred] + [p.grad for p in m.parameters() if p.grad is not None] + [opt.fp.flat], c)
 
 
+def fno3d_case():
+    """the recorded two-AR-step training step of tests/test_gpu_fno3d.py (csrc/fno3.hip)"""
+    set_tune()
+    st = F3.STEP
+    m = FNO3d(**F3.MINI1)
+    m.load_state_dict(F3.recipe_sd(OrderedDict((k, (tuple(v.shape), v.dtype)) for k, v in m.state_dict().items()), st["salt"]),
+                      strict=True)
+    m.cuda()
+    xx, yy, msk = (t.cuda() for t in F3.step_inputs())
+    opt = FusedAdam(FlatParams(m), lr=st["lr"], betas=st["betas"], weight_decay=st["weight_decay"], max_norm=st["max_norm"])
+    with Counts() as c:
+        loss, pred = train_step(m, opt, xx, yy, msk, lr=st["lr"])
+    report("fno3d mini step", loss, [pred] + [p.grad for p in m.parameters() if p.grad is not None] + [opt.fp.flat], c)
+
+
+def device_hash(shape, salt):
+    """fp32 in [-0.5, 0.5) from exact int64 arithmetic on the element index, drawn on the device: the weights of the timed 3-D
+    shape are gigabytes"""
+    i = torch.arange(math.prod(shape), device="cuda", dtype=torch.int64)
+    return (((i * 2654435761 + salt * 40503) % 65521).float() / 65521.0 - 0.5).view(shape)
+
+
+def mix_cases():
+    """ops.fno_mix / fno3_mix (forward and adjoint) and ops.fno_mix_wgrad / fno3_mix_wgrad (plain, and accumulate=True onto a
+    hashed base) over every mixing case of the GPU tests and at the four shapes scripts/fno_time.py and scripts/fno3d_time.py
+    time; every weight and every base its own salt"""
+    set_tune()
+    timed2 = [(B, C, C, m1, m2) for _, B, _, _, C, m1, m2 in fno_time.SHAPES]
+    timed3 = [(B, C, C, m, m, m) for _, B, _, C, m in fno3d_time.SHAPES]
+    with Counts() as c:
+        for cases, planar in ((list(FR.MIX_CASES) + timed2, True), (list(F3.MIX_CASES) + timed3, False)):
+            for B, Cin, Cout, *modes in cases:
+                kept = tuple(2 * m for m in modes[:-1]) + (modes[-1],)
+                wshape = (2, Cin, Cout, *modes) if planar else (Cin, Cout, *modes, 2)
+                X, dO = device_hash((B, *kept, 2, Cin), 41), device_hash((B, *kept, 2, Cout), 42)
+                ws = [device_hash(wshape, 43 + k) for k in range(2 if planar else 4)]
+                if planar:
+                    op, fwd, adj = "fno_mix", ops.fno_mix(X, *ws), ops.fno_mix(dO, *ws, adjoint=True)
+                    ds = ops.fno_mix_wgrad(X, dO)
+                    acc = ops.fno_mix_wgrad(X, dO, *(device_hash(wshape, 47 + k) for k in range(2)), accumulate=True)
+                else:
+                    op, fwd, adj = "fno3_mix", ops.fno3_mix(X, ws), ops.fno3_mix(dO, ws, adjoint=True)
+                    ds = ops.fno3_mix_wgrad(X, dO)
+                    acc = ops.fno3_mix_wgrad(X, dO, [device_hash(wshape, 47 + k) for k in range(4)], accumulate=True)
+                tag = f"B{B} {Cin}->{Cout} modes {'x'.join(map(str, modes))}"
+                report(f"{op} {tag}", fwd.sum(), [fwd], c)
+                report(f"{op} adjoint {tag}", adj.sum(), [adj], c)
+                report(f"{op}_wgrad {tag}", ds[0].sum(), ds, c)
+                report(f"{op}_wgrad accumulate {tag}", acc[0].sum(), acc, c)
+                del X, dO, ws, fwd, adj, ds, acc
+
+
 def operator_cases():
     """the spectral operators no model case reaches, each at the smallest shapes its GPU test uses: the Fourier resize (one even
     and one odd size pair, scalar and 16-byte loads), the rollout evaluator in 2-D and 3-D, rfft2 / irfft2 once per compiled
@@ -321,6 +378,8 @@ def main():
         raise SystemExit("grad_fingerprint: needs the GPU")
     print(f"# DPOT_TUNE={BASE_TUNE!r}", flush=True)
     fno_case()
+    fno3d_case()
+    mix_cases()
     operator_cases()
     wgrad_cases()
     bf16_cases()

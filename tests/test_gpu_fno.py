@@ -135,6 +135,41 @@ def test_mixing_vs_float64_and_the_reference_float32_error(case, guarded):
     guard.check()
 
 
+def _ints(shape, salt):
+    """float32 integers in [-3, 3] from the hash recipe: floor(7 u) - 3 with u = hash / 3 + 1 / 2 in [0, 1)"""
+    u = FR.hash_input(shape, salt).double() / 3.0 + 0.5
+    return (torch.floor(7.0 * u).clamp_(0.0, 6.0) - 3.0).float()
+
+
+def test_mixing_is_exact_on_integers_past_the_first_mode_block(guarded):
+    """B 5, Cin 8, Cout 4, modes (5, 7): G = 70 kept modes, so modes 64..69 (all of weights2) sit in the second 64-mode block of
+    the grid, on the 16-byte path (both channel counts are multiples of 4, the buffers aligned); B = 5 is a ragged second sample
+    tile.  Integer operands in [-3, 3], both weights and both accumulate bases their own salt: each partial sum is an integer of
+    magnitude at most 8 * 2 * 9 = 144 < 2^24, so fp32 is exact whatever the summation order and so is the float64
+    restatement - every result must EQUAL it."""
+    from dpot_amd import ops
+    B, Cin, Cout, m1, m2 = 5, 8, 4, 5, 7
+    X0, dO0 = _ints((B, 2 * m1, m2, 2, Cin), 996), _ints((B, 2 * m1, m2, 2, Cout), 997)
+    ws0 = [_ints((2, Cin, Cout, m1, m2), 998 + k) for k in range(2)]
+    bases = [_ints((2, Cin, Cout, m1, m2), 1000 + k) for k in range(2)]
+    X, dO = guard.wrap(X0, "cuda"), guard.wrap(dO0, "cuda")
+    w1, w2 = (guard.wrap(w, "cuda") for w in ws0)
+    fwd, dgrad = ops.fno_mix(X, w1, w2), ops.fno_mix(dO, w1, w2, adjoint=True)
+    ds = ops.fno_mix_wgrad(X, dO)
+    accs = ops.fno_mix_wgrad(X, dO, *(guard.wrap(b, "cuda") for b in bases), accumulate=True)
+    nans = ops.fno_mix_wgrad(X, dO, *(guard.full_nan(tuple(w.shape)) for w in ws0))
+    torch.cuda.synchronize()
+    Xc, dOc = FR.from_planes(X0.double()), FR.from_planes(dO0.double())
+    wd = [w.double() for w in ws0]
+    assert torch.equal(fwd.cpu().double(), FR.to_planes(FR.mix(Xc, *wd)))
+    assert torch.equal(dgrad.cpu().double(), FR.to_planes(FR.mix(dOc, *wd, adjoint=True)))
+    for k, ref in enumerate(FR.mix_wgrad(Xc, dOc)):
+        assert torch.equal(ds[k].cpu().double(), ref), k
+        assert torch.equal(nans[k].cpu().double(), ref), k
+        assert torch.equal(accs[k].cpu().double(), bases[k].double() + ref), k
+    guard.check()
+
+
 def test_act_bwd_mul(guarded):
     from dpot_amd import ops
     for n in (1, 7, 1024, 4099):

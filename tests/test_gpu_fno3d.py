@@ -153,6 +153,62 @@ def test_mixing_vs_float64_and_the_reference_float32_error(case, guarded):
     guard.check()
 
 
+def _ints(shape, salt):
+    """float32 integers in [-3, 3] from the hash recipe: floor(7 u) - 3 with u = hash / 3 + 1 / 2 in [0, 1)"""
+    u = FR.hash_input(shape, salt).double() / 3.0 + 0.5
+    return (torch.floor(7.0 * u).clamp_(0.0, 6.0) - 3.0).float()
+
+
+def test_mixing_is_exact_on_integers_past_the_first_mode_block(guarded):
+    """B 5, Cin 8, Cout 4, modes (3, 2, 3): G = 72 kept modes, so modes 64..71 sit in the second 64-mode block of the grid, on the
+    16-byte path (both channel counts are multiples of 4, the buffers aligned) - where the corner decode of g >= 64 meets
+    VEC = true; B = 5 is a ragged second sample tile.  Integer operands in [-3, 3], every corner's weights and every accumulate
+    base their own salt: each partial sum is an integer of magnitude at most 8 * 2 * 9 = 144 < 2^24, so fp32 is exact
+    whatever the summation order and so is the float64 restatement - every result must EQUAL it."""
+    from dpot_amd import ops
+    B, Cin, Cout, m1, m2, m3 = 5, 8, 4, 3, 2, 3
+    X0, dO0 = _ints((B, 2 * m1, 2 * m2, m3, 2, Cin), 1993), _ints((B, 2 * m1, 2 * m2, m3, 2, Cout), 1994)
+    ws0 = [_ints((Cin, Cout, m1, m2, m3, 2), 1995 + k) for k in range(4)]
+    bases = [_ints((Cin, Cout, m1, m2, m3, 2), 1999 + k) for k in range(4)]
+    X, dO = guard.wrap(X0, "cuda"), guard.wrap(dO0, "cuda")
+    ws = [guard.wrap(w, "cuda") for w in ws0]
+    fwd, dgrad = ops.fno3_mix(X, ws), ops.fno3_mix(dO, ws, adjoint=True)
+    ds = ops.fno3_mix_wgrad(X, dO)
+    accs = ops.fno3_mix_wgrad(X, dO, [guard.wrap(b, "cuda") for b in bases], accumulate=True)
+    nans = ops.fno3_mix_wgrad(X, dO, [guard.full_nan(tuple(w.shape)) for w in ws0])
+    torch.cuda.synchronize()
+    Xc, dOc = FR.from_planes(X0.double()), FR.from_planes(dO0.double())
+    wc = [torch.view_as_complex(w.double()) for w in ws0]
+    assert torch.equal(fwd.cpu().double(), FR.to_planes(FR.mix(Xc, wc)))
+    assert torch.equal(dgrad.cpu().double(), FR.to_planes(FR.mix(dOc, wc, adjoint=True)))
+    for k, d in enumerate(FR.mix_wgrad(Xc, dOc)):
+        ref = FR.pairs(d)
+        assert torch.equal(ds[k].cpu().double(), ref), k
+        assert torch.equal(nans[k].cpu().double(), ref), k
+        assert torch.equal(accs[k].cpu().double(), bases[k].double() + ref), k
+    guard.check()
+
+
+def test_transform_workspace_outlives_its_launches(monkeypatch):
+    """the workspace between the two launches of a 3-D transform must still be referenced when the library is called: a raw
+    pointer alone would let the allocator free (or re-issue) it before the kernels run"""
+    import weakref
+    from dpot_amd import _lib, ops
+    lib = _lib.load()
+    B, X, Y, Z, C, m1, m2, m3 = FR.TRANSFORM_CASES[0]
+    x0, S0 = FR.transform_inputs(FR.TRANSFORM_CASES[0])
+    x, S = x0.cuda(), S0.cuda()
+    refs, alive = [], []
+    real_scratch = ops._scratch
+    monkeypatch.setattr(ops, "_scratch", lambda t: refs.append(weakref.ref(t)) or real_scratch(t))
+    for name in ("dpot_fno3_rfft3", "dpot_fno3_irfft3"):
+        monkeypatch.setattr(lib, name, lambda *a, _r=getattr(lib, name): alive.append(refs[-1]() is not None) or _r(*a))
+    ops.fno3_rfft3(x, m1, m2, m3)
+    ops.fno3_irfft3(S, X, Y, Z)
+    torch.cuda.synchronize()
+    assert len(refs) == 2 and alive == [True, True]
+
+
 def test_argument_checks_and_limits():
     from dpot_amd import _lib, ops
     lib = _lib.load()
