@@ -200,6 +200,10 @@ SIGNATURES = {
     "dpot_resize_pad_window3": (c_i, [c_fp, c_i, c_fp, c_fp] + [c_i] * 7 + [c_fp]),
     "dpot_spectral_resize_pad": (c_i, [c_i, c_i]),
     "dpot_spectral_resize": (c_i, [c_fp] * 7 + [c_i] * 6 + [c_fp]),
+    "dpot_spectral_resize3_pad": (c_i, [c_i, c_i]),
+    "dpot_spectral_resize3_max_size": (c_i, []),
+    "dpot_spectral_resize3_ws_elems": (c_i64, [c_i] * 8),
+    "dpot_spectral_resize3": (c_i, [c_fp] * 11 + [c_i] * 8 + [c_fp]),
     "dpot_eval_metrics_pad": (c_i, [c_i, c_i]),
     "dpot_eval_metrics_max_size": (c_i, [c_i]),
     "dpot_eval_metrics_acc_elems": (c_i64, [c_i] * 4),

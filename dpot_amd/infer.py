@@ -17,6 +17,9 @@
   griddata=True, component='all')``: per-channel and per-step normalised errors, the boundary error and the error spectrum
   in three wavenumber bands, accumulated on the device (csrc/evalmetrics.hip); ``evaluator=`` hands every rollout to it.
   3-D rollouts [B, X, Y, Z, T, C] take the same keys, column c being ``Evaluator(..., component=c)`` (csrc/evalmetrics3d.hip).
+* ``Resized3D`` - the resolution-generalisation rollout in 3-D: a wrapper that Fourier-resizes a 6-D window up to the wrapped
+  model's resolution (ops.spectral_resize3), runs the model there and resizes the prediction back, so that ``rollout_eval``
+  and ``GraphedRollout`` take it as any 3-D model.  ``model_res=`` itself stays a keyword of 2-D windows.
 """
 from __future__ import annotations
 
@@ -249,7 +252,7 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
     evaluator: a RolloutEvaluator - `evaluator.update(pred, yy)` runs on the assembled prediction at the DATA resolution, on
     the same stream, without a synchronisation; the returned values are untouched by it.  None: nothing is enqueued.
     6-D windows take `evaluator=` as well - a RolloutEvaluator, anything else is a ValueError before the rollout starts;
-    `model_res=` does not exist for them (there is no 3-D spectral resize)."""
+    `model_res=` does not exist for them: a 3-D model is evaluated at another data resolution by wrapping it, Resized3D."""
     # weight-only products (packed AFNO weights, folded embed matrices, ...) once per rollout, not once per AR step
     scope = model.weights_scope() if (step is None and hasattr(model, "weights_scope")) else contextlib.nullcontext()
     def forward(x):                      # DPOTNet returns (pred, cls_pred), DPOTNet3D the prediction alone
@@ -258,7 +261,7 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
 
     step = step or forward
     if xx.dim() == 6 and model_res is not None:
-        # the test loop of finetune3d.py:252-278 has no resize; the spectral resize is a 2-D kernel
+        # the test loop of finetune3d.py:252-278 has no resize; model_res= drives the 2-D kernel, Resized3D wraps a 3-D model
         raise ValueError(f"rollout_eval: model_res= exists for 2-D windows [B,X,Y,T,C] only, got a 6-D window "
                          f"{tuple(xx.shape)}")
     if xx.dim() == 6 and evaluator is not None and not isinstance(evaluator, RolloutEvaluator):
@@ -302,6 +305,35 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
     return pred, loss_steps, loss_full
 
 
+class Resized3D(nn.Module):
+    """A 3-D model evaluated at any data resolution: forward on a window [B, X, Y, Z, T, C] is ops.spectral_resize3 up (or
+    down) to `model_res`, the wrapped model, and ops.spectral_resize3 of its prediction back to (X, Y, Z) - the 3-D form of
+    the loop body of evaluate_varyingres.py:228-248.  Returns one tensor, as DPOTNet3D and FNO3d do.  No parameters of its own.
+    rollout_eval and GraphedRollout take it as any 3-D model (metrics= and evaluator= included), so loss, metrics and the
+    window slide run at the DATA resolution; a GraphedRollout of it is captured at the data resolution with both resizes
+    inside the graph, and its warm-up builds the two resize plans.  As in the reference's 2-D loop, `model_res` equal to the
+    data resolution still resizes (the identity up to rounding).  model_res: one int or (res_x, res_y, res_z)."""
+
+    def __init__(self, model: nn.Module, model_res):
+        super().__init__()
+        if not isinstance(model_res, int) and len(tuple(model_res)) != 3:
+            raise ValueError(f"Resized3D: model_res must be one int or (res_x, res_y, res_z), got {model_res!r}")
+        self.model = model
+        self.model_res = (int(model_res),) * 3 if isinstance(model_res, int) else tuple(int(r) for r in model_res)
+
+    def weights_scope(self):
+        """the wrapped model's weight-only products once per rollout (rollout_eval), where it has them"""
+        return self.model.weights_scope() if hasattr(self.model, "weights_scope") else contextlib.nullcontext()
+
+    def forward(self, xx: Tensor) -> Tensor:
+        if xx.dim() != 6:
+            raise ValueError(f"Resized3D: needs a 6-D window [B, X, Y, Z, T, C], got {tuple(xx.shape)}")
+        data_res = tuple(xx.shape[1:4])
+        out = self.model(ops.spectral_resize3(xx.contiguous(), self.model_res))
+        out = out if torch.is_tensor(out) else out[0]
+        return ops.spectral_resize3(out.contiguous(), data_res)
+
+
 class GraphedRollout:
     """One hipGraph of the forward step for a fixed input shape, replayed for every AR step.  The model's forward returns
     (pred, cls_pred) as DPOTNet does, or the prediction alone as DPOTNet3D does (`cls` is then None)."""
@@ -334,7 +366,8 @@ class GraphedRollout:
                  evaluator=None):
         """model_res: the graph's own resolution - xx, yy, msk may then live at any data resolution; the two resizes of an
         AR step run outside the captured graph, on the same stream (rollout_eval).  evaluator: as in rollout_eval.  A graph
-        captured for 6-D windows [B, X, Y, Z, T, C] takes metrics= and evaluator=, not model_res="""
+        captured for 6-D windows [B, X, Y, Z, T, C] takes metrics= and evaluator=, not model_res= (wrap the model in
+        Resized3D and capture at the data resolution instead: both resizes are then inside the graph)"""
         want = tuple(self.x.shape)
         if model_res is not None:
             if xx.dim() != 5:

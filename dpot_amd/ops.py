@@ -2359,6 +2359,161 @@ def spectral_resize(x: Tensor, out_size, out: Optional[Tensor] = None) -> Tensor
     return out
 
 
+# ---- three axes (csrc/resize3.hip): X and Y are full-spectrum axes ("axis 0" matrices), Z is the half-spectrum axis ("axis 1")
+def _size3(out_size):
+    if isinstance(out_size, int):
+        return (int(out_size),) * 3
+    if len(out_size) != 3:
+        raise _lib.DpotHipError(f"spectral_resize3: out_size must be one int or (m_x, m_y, m_z), got {tuple(out_size)}")
+    return tuple(int(s) for s in out_size)
+
+
+def spectral_resize3_terms(nx: int, ny: int, nz: int, mx: int, my: int, mz: int):
+    """The float64 terms of the 3-D Fourier resize (n_x, n_y, n_z) -> (m_x, m_y, m_z): a list of (sign, Ax [m_x, n_x],
+    Ay [m_y, n_y], Az [m_z, n_z]) with operator = sum sign * Ax (x) Ay (x) Az / (n_x n_y n_z).  The operator is
+    Re(Dx (x) Dy (x) Dz): the products with an even number of imaginary factors, Rx Ry Rz - Rx Iy Iz - Ix Ry Iz - Ix Iy Rz,
+    and a term is listed only where it survives: Ix (Iy) is u v^T of spectral_resize_im_factors or zero (min(n, m) odd, or
+    n == m), Iz is general.  Neither vanishing: all four; Ix = 0: the first two; Iy = 0: the first and the third; both: one."""
+    import numpy as np
+    rx, _ = spectral_resize_matrices(nx, mx, 0)
+    ry, _ = spectral_resize_matrices(ny, my, 0)
+    rz, iz = spectral_resize_matrices(nz, mz, 1)
+    fx, fy = spectral_resize_im_factors(nx, mx), spectral_resize_im_factors(ny, my)
+    ix = None if fx is None else np.outer(*fx)
+    iy = None if fy is None else np.outer(*fy)
+    terms = [(1.0, rx, ry, rz)]
+    if iy is not None:
+        terms.append((-1.0, rx, iy, iz))
+    if ix is not None:
+        terms.append((-1.0, ix, ry, iz))
+    if ix is not None and iy is not None:
+        terms.append((-1.0, ix, iy, rz))
+    return terms
+
+
+class Resize3Plan:
+    """The operator matrices of dpot_spectral_resize3 for one size tuple, built in float64, rounded once to fp32, zero-padded
+    to the kernels' tile multiples (include/dpot_hip.h) and kept in device memory.  `host_matrices` is the host part alone."""
+
+    @staticmethod
+    def pads(nx: int, ny: int, nz: int, mx: int, my: int, mz: int):
+        """(nxp, nyp, nzp, mxp, myp, mzp): contraction extents and z' in multiples of 16, the output rows x' (axis launch) and
+        y' (plane launch) in multiples of 32 - the values dpot_spectral_resize3_pad returns (checked when a plan is built)"""
+        r = lambda n, q: (n + q - 1) // q * q
+        return r(nx, 16), r(ny, 16), r(nz, 16), r(mx, 32), r(my, 32), r(mz, 16)
+
+    @staticmethod
+    def host_matrices(nx: int, ny: int, nz: int, mx: int, my: int, mz: int):
+        """dict of fp32 numpy arrays: rxT [nxp, mxp], ryT [nyp, myp], rzT and izT [nzp, mzp] (both / (nx ny nz); izT None where
+        neither X nor Y has an imaginary term), nux [mxp] = -ux and vx [nxp] (None where Im Dx = 0), uy2 [2, myp] = (+uy, -uy)
+        and vy [nyp] (None where Im Dy = 0)"""
+        import numpy as np
+        nxp, nyp, nzp, mxp, myp, mzp = Resize3Plan.pads(nx, ny, nz, mx, my, mz)
+        rx, _ = spectral_resize_matrices(nx, mx, 0)
+        ry, _ = spectral_resize_matrices(ny, my, 0)
+        rz, iz = spectral_resize_matrices(nz, mz, 1)
+        scale = 1.0 / (nx * ny * nz)
+
+        def padded(a, shape):
+            outp = np.zeros(shape, dtype=np.float32)
+            outp[tuple(slice(0, s) for s in a.shape)] = a.astype(np.float32)
+            return outp
+
+        h = {"rxT": padded(rx.T, (nxp, mxp)), "ryT": padded(ry.T, (nyp, myp)), "rzT": padded(rz.T * scale, (nzp, mzp)),
+             "izT": None, "nux": None, "vx": None, "uy2": None, "vy": None}
+        fx, fy = spectral_resize_im_factors(nx, mx), spectral_resize_im_factors(ny, my)
+        if fx is not None or fy is not None:
+            h["izT"] = padded(iz.T * scale, (nzp, mzp))
+        if fx is not None:
+            h["nux"], h["vx"] = padded(-fx[0], (mxp,)), padded(fx[1], (nxp,))
+        if fy is not None:
+            h["uy2"], h["vy"] = padded(np.stack([fy[0], -fy[0]]), (2, myp)), padded(fy[1], (nyp,))
+        return h
+
+    def __init__(self, nx: int, ny: int, nz: int, mx: int, my: int, mz: int, device):
+        lib = _lib.load()
+        self.sizes = (nx, ny, nz, mx, my, mz)
+        pad = lib.dpot_spectral_resize3_pad
+        want = (pad(nx, 0), pad(ny, 0), pad(nz, 0), pad(mx, 1), pad(my, 1), pad(mz, 0))
+        if want != self.pads(*self.sizes):
+            raise _lib.DpotHipError(f"Resize3Plan: the library pads {self.sizes} to {want}, this module to "
+                                    f"{self.pads(*self.sizes)}")
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.DpotHipError(f"Resize3Plan {self.sizes}: the matrices are uploaded when a size tuple is first used - "
+                                    "call ops.resize3_plan(...) (or the resize itself) once before capturing")
+        self.dev = {}
+        for name, a in self.host_matrices(*self.sizes).items():
+            if a is None:
+                self.dev[name] = None
+                continue
+            t = torch.empty(a.shape, dtype=torch.float32, device=device)
+            t.copy_(torch.from_numpy(a))
+            self.dev[name] = t
+        self.terms = 1 + (self.dev["nux"] is not None) + (self.dev["uy2"] is not None) \
+            + (self.dev["nux"] is not None and self.dev["uy2"] is not None)
+
+
+_resize3_plans = {}
+
+
+def _check_resize3_sizes(sizes):
+    if min(sizes) < 2:
+        raise _lib.DpotHipError(f"spectral_resize3: every spatial size must be >= 2, got {sizes[:3]} -> {sizes[3:]}")
+    cap = _lib.load().dpot_spectral_resize3_max_size()
+    if max(sizes) > cap:
+        raise _lib.DpotHipError(f"spectral_resize3: {sizes[:3]} -> {sizes[3:]}: the size {max(sizes)} is beyond the LDS "
+                                f"intermediate of a workgroup (every size <= {cap})")
+
+
+def resize3_plan(nx: int, ny: int, nz: int, mx: int, my: int, mz: int, device) -> Resize3Plan:
+    """the cached Resize3Plan of (n_x, n_y, n_z, m_x, m_y, m_z, device)"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    sizes = tuple(int(s) for s in (nx, ny, nz, mx, my, mz))
+    plan = _resize3_plans.get(sizes + (device,))
+    if plan is None:
+        _check_resize3_sizes(sizes)
+        plan = _resize3_plans[sizes + (device,)] = Resize3Plan(*sizes, device)
+    return plan
+
+
+def spectral_resize3(x: Tensor, out_size, out: Optional[Tensor] = None) -> Tensor:
+    """Fourier resize of x [B, n_x, n_y, n_z, T, C] (or [B, n_x, n_y, n_z, TC]) to out_size = (m_x, m_y, m_z) or one int for
+    all three: the three-axis form of the reference's resize (utils/utilities.py:277-305) - rfftn over X, Y, Z, the four
+    corner blocks of the full-spectrum axes X, Y and the low columns of the half-spectrum axis Z, irfftn, rescale.  Two to
+    five launches around a workspace this call allocates (dpot_spectral_resize3_ws_elems)."""
+    _req(x, "spectral_resize3: x")
+    if x.dim() not in (5, 6):
+        raise _lib.DpotHipError(f"spectral_resize3: x must be [B, X, Y, Z, T, C] or [B, X, Y, Z, TC], got {tuple(x.shape)}")
+    mx, my, mz = _size3(out_size)
+    B, nx, ny, nz = x.shape[:4]
+    TC = x.numel() // max(B * nx * ny * nz, 1)
+    if min(B, TC) < 1:
+        raise _lib.DpotHipError(f"spectral_resize3: cannot resize {tuple(x.shape)}: no dimension may be empty")
+    _check_resize3_sizes((nx, ny, nz, mx, my, mz))
+    shape = (B, mx, my, mz) + tuple(x.shape[4:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    else:
+        _req(out, "spectral_resize3: out")
+        if tuple(out.shape) != shape or out.device != x.device:
+            raise _lib.DpotHipError(f"spectral_resize3: out must be {shape} on {x.device}, got {tuple(out.shape)} on "
+                                    f"{out.device}")
+        if out.data_ptr() == x.data_ptr():
+            raise _lib.DpotHipError("spectral_resize3: out must not alias x")
+    lib = _lib.load()
+    d = resize3_plan(nx, ny, nz, mx, my, mz, x.device).dev
+    n_ws = lib.dpot_spectral_resize3_ws_elems(B, nx, ny, nz, mx, my, mz, TC)
+    if n_ws <= 0:
+        raise _lib.DpotHipError(f"spectral_resize3: no workspace size: {(lib.dpot_last_error() or b'?').decode()}")
+    ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
+    check(lib.dpot_spectral_resize3(x.data_ptr(), out.data_ptr(), ws.data_ptr(), d["rxT"].data_ptr(), d["ryT"].data_ptr(),
+                                    d["rzT"].data_ptr(), _p(d["izT"]), _p(d["nux"]), _p(d["vx"]), _p(d["uy2"]), _p(d["vy"]),
+                                    B, nx, ny, nz, mx, my, mz, TC, _stream()), "spectral_resize3")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------
 # Rollout evaluation metrics: the reference's Evaluator (utils/criterion.py:189-239, compute_fourier_error :246-360) on the
 # device, for 2-D rollouts [B, X, Y, T, C] (csrc/evalmetrics.hip) and 3-D ones [B, X, Y, Z, T, C] (csrc/evalmetrics3d.hip) through

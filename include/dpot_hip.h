@@ -909,6 +909,30 @@ int dpot_spectral_resize(const float* in, float* out, const float* axT, const fl
                          const float* v, int B, int nx, int ny, int mx, int my, int TC, dpot_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Fourier resize of channels-last 3-D fields (csrc/resize3.hip): the three-axis form of the same operator (rfftn over
+ * X, Y, Z, the four corner blocks of the two full-spectrum axes and the low columns of the half-spectrum axis Z, irfftn,
+ * rescale),   out[B, mx, my, mz, TC] = Re(Dx (x) Dy (x) Dz) / (nx ny nz) in[B, nx, ny, nz, TC],
+ * as a plane launch (Y and Z of every (b, x) plane, the 2-D kernel) and an axis launch (X, a dense product) around a
+ * workspace; the launch that shrinks the field more runs first.
+ * Device matrices, ZERO-padded, pad = dpot_spectral_resize3_pad (output_rows = 0: to 16, 1: to 32):
+ *   rxT [pad(nx,0)][pad(mx,1)] = (Re Dx)^T     ryT [pad(ny,0)][pad(my,1)] = (Re Dy)^T
+ *   rzT, izT [pad(nz,0)][pad(mz,0)] = (Re Dz)^T, (Im Dz)^T, both / (nx ny nz)
+ *   Im Dx = ux vx^T:  nux [pad(mx,1)] = -ux, vx [pad(nx,0)]          NULL when Im Dx = 0 (min(nx, mx) odd or nx == mx)
+ *   Im Dy = uy vy^T:  uy2 [2][pad(my,1)] = +uy | -uy, vy [pad(ny,0)]  NULL when Im Dy = 0
+ *   izT may be NULL when both vanish.
+ * ws: dpot_spectral_resize3_ws_elems(...) floats, 16-byte aligned (0: the sizes are refused; dpot_last_error says why).
+ * in != out; every spatial size >= 2 and <= dpot_spectral_resize3_max_size() (= 272, the LDS intermediate of the plane
+ * launch) - beyond: DPOT_EUNSUP, nothing is launched; B * max(nx, mx) <= 65535.  Any TC >= 1 (16-byte loads and stores when
+ * TC % 4 == 0 and the fields are 16-byte aligned).  Two to five launches; reads and writes nothing outside the tensors and
+ * ws, fixed reduction order, no atomics, no allocation, legal under stream capture. */
+int dpot_spectral_resize3_pad(int n, int output_rows);
+int dpot_spectral_resize3_max_size(void);
+int64_t dpot_spectral_resize3_ws_elems(int B, int nx, int ny, int nz, int mx, int my, int mz, int TC);
+int dpot_spectral_resize3(const float* in, float* out, float* ws, const float* rxT, const float* ryT, const float* rzT,
+                          const float* izT, const float* nux, const float* vx, const float* uy2, const float* vy, int B,
+                          int nx, int ny, int nz, int mx, int my, int mz, int TC, dpot_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Rollout evaluation metrics (csrc/evalmetrics.hip): the reference's Evaluator(temporal=True, griddata=True,
  * component='all') (utils/criterion.py:189-239, compute_fourier_error :246-360) for pred, target [B, nx, ny, T, C],
  * accumulated over batches on the device.  Two launches per batch:
