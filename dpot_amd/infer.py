@@ -124,7 +124,7 @@ def load_3d_components_from_2d(model: nn.Module, state_dict: Union[str, Mapping]
 
 # ------------------------------------------------------------------------------------------------------
 def _size2(res) -> Tuple[int, int]:
-    return (int(res), int(res)) if isinstance(res, int) else (int(res[0]), int(res[1]))
+    return ops.size_tuple(res, 2)
 
 
 def refill_mask(msk: Tensor, res) -> Tensor:
@@ -316,10 +316,10 @@ class Resized3D(nn.Module):
 
     def __init__(self, model: nn.Module, model_res):
         super().__init__()
-        if not isinstance(model_res, int) and len(tuple(model_res)) != 3:
-            raise ValueError(f"Resized3D: model_res must be one int or (res_x, res_y, res_z), got {model_res!r}")
         self.model = model
-        self.model_res = (int(model_res),) * 3 if isinstance(model_res, int) else tuple(int(r) for r in model_res)
+        self.model_res = ops.size_tuple(model_res, 3, strict=True)
+        if self.model_res is None:
+            raise ValueError(f"Resized3D: model_res must be one int or (res_x, res_y, res_z), got {model_res!r}")
 
     def weights_scope(self):
         """the wrapped model's weight-only products once per rollout (rollout_eval), where it has them"""

@@ -2212,6 +2212,90 @@ def window_slide_bwd(dout: Tensor, Tb: int, need_xx: bool, need_im: bool):
 
 
 # ------------------------------------------------------------------------------------------------------
+# Table plans: what the table-driven operators below (spectral resize, rollout metrics, anti-aliased activation, FNO transforms)
+# share on the host - how a plan is built, guarded and cached, the output buffer check and the size parser
+# ------------------------------------------------------------------------------------------------------
+class _TablePlan:
+    """The device-resident tables of one operator for one size tuple.  A subclass gives its `words` for the messages (class
+    name, accessor, what the tables are called, what a size tuple is called, what else builds the plan), checks its sizes
+    against the library (`_check`) and computes its tables on the host (`_host(*sizes)`: an ordered dict name -> numpy array or
+    None; where a class has a public host function, that is it).
+    The constructor does the rest, always in this order: `sizes`, the checks, the refusal to build while the stream is capturing
+    (an upload is no graph node), the upload into `dev` - int32 tables as they are, every other one rounded once to fp32 on the
+    host, None kept, in the host dict's order.  Plans are made through `_plan`, which caches them."""
+
+    def __init__(self, sizes, device):
+        self.sizes = tuple(sizes)
+        self._check()
+        if torch.cuda.is_current_stream_capturing():
+            name, entry, tables, noun, instead = self.words
+            raise _lib.DpotHipError(f"{name} {self.sizes}: the {tables} are uploaded when a {noun} is first used - call "
+                                    f"ops.{entry}(...) {instead} before capturing")
+        self.dev = {}
+        for key, a in self._host(*self.sizes).items():
+            if a is not None:
+                h = torch.from_numpy(a if a.dtype == "int32" else a.astype("float32"))
+                a = torch.empty(h.shape, dtype=h.dtype, device=device).copy_(h)
+            self.dev[key] = a
+
+    def _check_pads(self, pad, output_rows, sizes=None) -> None:
+        """the class's pads() must be what the library's `pad` entry point answers for each size and its output_rows flag"""
+        want = tuple(pad(n, rows) for n, rows in zip(sizes or self.sizes, output_rows))
+        if want != self.pads(*self.sizes):
+            raise _lib.DpotHipError(f"{self.words[0]}: the library pads {self.sizes} to {want}, this module to "
+                                    f"{self.pads(*self.sizes)}")
+
+
+_plans = {}
+
+
+def _plan(cls, sizes, device, check=None):
+    """the cached plan of (class, sizes, device): `cuda` without an index is the current device, the sizes are plain ints;
+    built - after `check(sizes)` - when the key is first seen, and kept only if the constructor returns"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (cls, *(int(n) for n in sizes), device)
+    plan = _plans.get(key)
+    if plan is None:
+        if check is not None:
+            check(key[1:-1])
+        plan = _plans[key] = cls(*key[1:])
+    return plan
+
+
+def _out_buf(t: Optional[Tensor], what: str, name: str, shape, device, exc=_lib.DpotHipError,
+             x: Optional[Tensor] = None) -> Tensor:
+    """`t`, checked to be a kernel-ready tensor of `shape` on `device` that does not start where `x` does; a fresh one when it is
+    None.  `exc`: the caller's exception type"""
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(_req(t, f"{what}: {name}").shape) != tuple(shape) or t.device != device:
+        raise exc(f"{what}: {name} must be {tuple(shape)} on {device}, got {tuple(t.shape)} on {t.device}")
+    if x is not None and t.data_ptr() == x.data_ptr():
+        raise exc(f"{what}: {name} must not alias x")
+    return t
+
+
+def size_tuple(size, rank: int, strict: bool = False):
+    """`size` as `rank` ints: one int for every axis, or a sequence whose first `rank` entries are taken.  strict: None for a
+    sequence of another length (the caller words the refusal)"""
+    if isinstance(size, int):
+        return (int(size),) * rank
+    if strict and len(size) != rank:
+        return None
+    return tuple(int(size[k]) for k in range(rank))
+
+
+def padded(a, shape):
+    """`a` rounded to fp32 in the low corner of a zero array of `shape`"""
+    import numpy as np
+    out = np.zeros(shape, dtype=np.float32)
+    out[tuple(slice(0, s) for s in a.shape)] = a.astype(np.float32)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------
 # Fourier ("spectral") resize: utils/utilities.py:277-305 as dense products (csrc/resize.hip)
 # ------------------------------------------------------------------------------------------------------
 def _resize_freqs(n: int, m: int, axis: int):
@@ -2259,9 +2343,10 @@ def spectral_resize_im_factors(n: int, m: int):
     return u, v
 
 
-class ResizePlan:
+class ResizePlan(_TablePlan):
     """The operator matrices of dpot_spectral_resize for one size pair, built in float64, rounded to fp32, zero-padded to
     the kernel's tile multiples (include/dpot_hip.h) and kept in device memory.  `host_matrices` is the host part alone."""
+    words = ("ResizePlan", "resize_plan", "matrices", "size pair", "(or the resize itself) once")
 
     @staticmethod
     def pads(nx: int, ny: int, mx: int, my: int):
@@ -2274,17 +2359,10 @@ class ResizePlan:
     def host_matrices(nx: int, ny: int, mx: int, my: int):
         """dict of fp32 numpy arrays: axT [nxp, mxp], ayT [nyp, myp] and, for the two-term size pairs, byT [nyp, myp],
         u [mxp], v [nxp] (else None)"""
-        import numpy as np
         nxp, nyp, mxp, myp = ResizePlan.pads(nx, ny, mx, my)
         re_x, _ = spectral_resize_matrices(nx, mx, 0)
         re_y, im_y = spectral_resize_matrices(ny, my, 1)
         scale = 1.0 / (nx * ny)
-
-        def padded(a, shape):
-            outp = np.zeros(shape, dtype=np.float32)
-            outp[tuple(slice(0, s) for s in a.shape)] = a.astype(np.float32)
-            return outp
-
         h = {"axT": padded(re_x.T, (nxp, mxp)), "ayT": padded(re_y.T * scale, (nyp, myp)), "byT": None, "u": None,
              "v": None}
         uv = spectral_resize_im_factors(nx, mx)
@@ -2294,40 +2372,18 @@ class ResizePlan:
         return h
 
     def __init__(self, nx: int, ny: int, mx: int, my: int, device):
-        lib = _lib.load()
-        self.sizes = (nx, ny, mx, my)
-        want = (lib.dpot_spectral_resize_pad(nx, 0), lib.dpot_spectral_resize_pad(ny, 0),
-                lib.dpot_spectral_resize_pad(mx, 1), lib.dpot_spectral_resize_pad(my, 0))
-        if want != self.pads(nx, ny, mx, my):
-            raise _lib.DpotHipError(f"ResizePlan: the library pads {self.sizes} to {want}, this module to "
-                                    f"{self.pads(nx, ny, mx, my)}")
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.DpotHipError(f"ResizePlan {self.sizes}: the matrices are uploaded when a size pair is first used - "
-                                    "call ops.resize_plan(...) (or the resize itself) once before capturing")
-        self.dev = {}
-        for name, a in self.host_matrices(nx, ny, mx, my).items():
-            if a is None:
-                self.dev[name] = None
-                continue
-            t = torch.empty(a.shape, dtype=torch.float32, device=device)
-            t.copy_(torch.from_numpy(a))
-            self.dev[name] = t
+        super().__init__((nx, ny, mx, my), device)
         self.two_terms = self.dev["byT"] is not None
 
+    def _check(self) -> None:
+        self._check_pads(_lib.load().dpot_spectral_resize_pad, (0, 0, 1, 0))
 
-_resize_plans = {}
+    _host = host_matrices
 
 
 def resize_plan(nx: int, ny: int, mx: int, my: int, device) -> ResizePlan:
     """the cached ResizePlan of (n_x, n_y, m_x, m_y, device)"""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (int(nx), int(ny), int(mx), int(my), device)
-    plan = _resize_plans.get(key)
-    if plan is None:
-        plan = _resize_plans[key] = ResizePlan(*key)
-    return plan
+    return _plan(ResizePlan, (nx, ny, mx, my), device)
 
 
 def spectral_resize(x: Tensor, out_size, out: Optional[Tensor] = None) -> Tensor:
@@ -2336,22 +2392,13 @@ def spectral_resize(x: Tensor, out_size, out: Optional[Tensor] = None) -> Tensor
     _req(x, "spectral_resize: x")
     if x.dim() not in (4, 5):
         raise _lib.DpotHipError(f"spectral_resize: x must be [B, X, Y, T, C] or [B, X, Y, TC], got {tuple(x.shape)}")
-    mx, my = (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
+    mx, my = size_tuple(out_size, 2)
     B, nx, ny = x.shape[:3]
     TC = x.numel() // max(B * nx * ny, 1)
     if min(B, nx, ny, mx, my, TC) < 1 or min(nx, ny, mx, my) < 2:
         raise _lib.DpotHipError(f"spectral_resize: cannot resize {tuple(x.shape)} to {(mx, my)}: every spatial size must be "
                                 ">= 2 and no dimension empty")
-    shape = (B, mx, my) + tuple(x.shape[3:])
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    else:
-        _req(out, "spectral_resize: out")
-        if tuple(out.shape) != shape or out.device != x.device:
-            raise _lib.DpotHipError(f"spectral_resize: out must be {shape} on {x.device}, got {tuple(out.shape)} on "
-                                    f"{out.device}")
-        if out.data_ptr() == x.data_ptr():
-            raise _lib.DpotHipError("spectral_resize: out must not alias x")
+    out = _out_buf(out, "spectral_resize", "out", (B, mx, my) + tuple(x.shape[3:]), x.device, x=x)
     d = resize_plan(nx, ny, mx, my, x.device).dev
     check(_lib.load().dpot_spectral_resize(x.data_ptr(), out.data_ptr(), d["axT"].data_ptr(), d["ayT"].data_ptr(),
                                            _p(d["byT"]), _p(d["u"]), _p(d["v"]), B, nx, ny, mx, my, TC, _stream()),
@@ -2360,14 +2407,6 @@ def spectral_resize(x: Tensor, out_size, out: Optional[Tensor] = None) -> Tensor
 
 
 # ---- three axes (csrc/resize3.hip): X and Y are full-spectrum axes ("axis 0" matrices), Z is the half-spectrum axis ("axis 1")
-def _size3(out_size):
-    if isinstance(out_size, int):
-        return (int(out_size),) * 3
-    if len(out_size) != 3:
-        raise _lib.DpotHipError(f"spectral_resize3: out_size must be one int or (m_x, m_y, m_z), got {tuple(out_size)}")
-    return tuple(int(s) for s in out_size)
-
-
 def spectral_resize3_terms(nx: int, ny: int, nz: int, mx: int, my: int, mz: int):
     """The float64 terms of the 3-D Fourier resize (n_x, n_y, n_z) -> (m_x, m_y, m_z): a list of (sign, Ax [m_x, n_x],
     Ay [m_y, n_y], Az [m_z, n_z]) with operator = sum sign * Ax (x) Ay (x) Az / (n_x n_y n_z).  The operator is
@@ -2391,9 +2430,10 @@ def spectral_resize3_terms(nx: int, ny: int, nz: int, mx: int, my: int, mz: int)
     return terms
 
 
-class Resize3Plan:
+class Resize3Plan(_TablePlan):
     """The operator matrices of dpot_spectral_resize3 for one size tuple, built in float64, rounded once to fp32, zero-padded
     to the kernels' tile multiples (include/dpot_hip.h) and kept in device memory.  `host_matrices` is the host part alone."""
+    words = ("Resize3Plan", "resize3_plan", "matrices", "size tuple", "(or the resize itself) once")
 
     @staticmethod
     def pads(nx: int, ny: int, nz: int, mx: int, my: int, mz: int):
@@ -2413,12 +2453,6 @@ class Resize3Plan:
         ry, _ = spectral_resize_matrices(ny, my, 0)
         rz, iz = spectral_resize_matrices(nz, mz, 1)
         scale = 1.0 / (nx * ny * nz)
-
-        def padded(a, shape):
-            outp = np.zeros(shape, dtype=np.float32)
-            outp[tuple(slice(0, s) for s in a.shape)] = a.astype(np.float32)
-            return outp
-
         h = {"rxT": padded(rx.T, (nxp, mxp)), "ryT": padded(ry.T, (nyp, myp)), "rzT": padded(rz.T * scale, (nzp, mzp)),
              "izT": None, "nux": None, "vx": None, "uy2": None, "vy": None}
         fx, fy = spectral_resize_im_factors(nx, mx), spectral_resize_im_factors(ny, my)
@@ -2431,29 +2465,14 @@ class Resize3Plan:
         return h
 
     def __init__(self, nx: int, ny: int, nz: int, mx: int, my: int, mz: int, device):
-        lib = _lib.load()
-        self.sizes = (nx, ny, nz, mx, my, mz)
-        pad = lib.dpot_spectral_resize3_pad
-        want = (pad(nx, 0), pad(ny, 0), pad(nz, 0), pad(mx, 1), pad(my, 1), pad(mz, 0))
-        if want != self.pads(*self.sizes):
-            raise _lib.DpotHipError(f"Resize3Plan: the library pads {self.sizes} to {want}, this module to "
-                                    f"{self.pads(*self.sizes)}")
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.DpotHipError(f"Resize3Plan {self.sizes}: the matrices are uploaded when a size tuple is first used - "
-                                    "call ops.resize3_plan(...) (or the resize itself) once before capturing")
-        self.dev = {}
-        for name, a in self.host_matrices(*self.sizes).items():
-            if a is None:
-                self.dev[name] = None
-                continue
-            t = torch.empty(a.shape, dtype=torch.float32, device=device)
-            t.copy_(torch.from_numpy(a))
-            self.dev[name] = t
+        super().__init__((nx, ny, nz, mx, my, mz), device)
         self.terms = 1 + (self.dev["nux"] is not None) + (self.dev["uy2"] is not None) \
             + (self.dev["nux"] is not None and self.dev["uy2"] is not None)
 
+    def _check(self) -> None:
+        self._check_pads(_lib.load().dpot_spectral_resize3_pad, (0, 0, 0, 1, 1, 0))
 
-_resize3_plans = {}
+    _host = host_matrices
 
 
 def _check_resize3_sizes(sizes):
@@ -2467,15 +2486,7 @@ def _check_resize3_sizes(sizes):
 
 def resize3_plan(nx: int, ny: int, nz: int, mx: int, my: int, mz: int, device) -> Resize3Plan:
     """the cached Resize3Plan of (n_x, n_y, n_z, m_x, m_y, m_z, device)"""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    sizes = tuple(int(s) for s in (nx, ny, nz, mx, my, mz))
-    plan = _resize3_plans.get(sizes + (device,))
-    if plan is None:
-        _check_resize3_sizes(sizes)
-        plan = _resize3_plans[sizes + (device,)] = Resize3Plan(*sizes, device)
-    return plan
+    return _plan(Resize3Plan, (nx, ny, nz, mx, my, mz), device, check=_check_resize3_sizes)
 
 
 def spectral_resize3(x: Tensor, out_size, out: Optional[Tensor] = None) -> Tensor:
@@ -2486,22 +2497,16 @@ def spectral_resize3(x: Tensor, out_size, out: Optional[Tensor] = None) -> Tenso
     _req(x, "spectral_resize3: x")
     if x.dim() not in (5, 6):
         raise _lib.DpotHipError(f"spectral_resize3: x must be [B, X, Y, Z, T, C] or [B, X, Y, Z, TC], got {tuple(x.shape)}")
-    mx, my, mz = _size3(out_size)
+    m = size_tuple(out_size, 3, strict=True)
+    if m is None:
+        raise _lib.DpotHipError(f"spectral_resize3: out_size must be one int or (m_x, m_y, m_z), got {tuple(out_size)}")
+    mx, my, mz = m
     B, nx, ny, nz = x.shape[:4]
     TC = x.numel() // max(B * nx * ny * nz, 1)
     if min(B, TC) < 1:
         raise _lib.DpotHipError(f"spectral_resize3: cannot resize {tuple(x.shape)}: no dimension may be empty")
     _check_resize3_sizes((nx, ny, nz, mx, my, mz))
-    shape = (B, mx, my, mz) + tuple(x.shape[4:])
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    else:
-        _req(out, "spectral_resize3: out")
-        if tuple(out.shape) != shape or out.device != x.device:
-            raise _lib.DpotHipError(f"spectral_resize3: out must be {shape} on {x.device}, got {tuple(out.shape)} on "
-                                    f"{out.device}")
-        if out.data_ptr() == x.data_ptr():
-            raise _lib.DpotHipError("spectral_resize3: out must not alias x")
+    out = _out_buf(out, "spectral_resize3", "out", (B, mx, my, mz) + tuple(x.shape[4:]), x.device, x=x)
     lib = _lib.load()
     d = resize3_plan(nx, ny, nz, mx, my, mz, x.device).dev
     n_ws = lib.dpot_spectral_resize3_ws_elems(B, nx, ny, nz, mx, my, mz, TC)
@@ -2648,7 +2653,7 @@ def eval_finish(acc, samples: int, *dims: int, ilow: int = 4, ihigh: int = 12):
     return out
 
 
-class EvalPlan:
+class EvalPlan(_TablePlan):
     """The tables of dpot_eval_metrics_stats / dpot_eval3_stats for one plane or field size, built in float64, rounded to
     fp32, zero-padded to the kernels' tile multiples and kept in device memory.  `host_tables` is the host part alone."""
 
@@ -2673,26 +2678,23 @@ class EvalPlan:
         return out
 
     def __init__(self, *sizes_device):
-        *sizes, device = sizes_device
-        sizes = tuple(sizes)
-        lib = _lib.load()
-        self.sizes, self.rank = sizes, _eval_rank("EvalPlan", sizes)
+        super().__init__(sizes_device[:-1], sizes_device[-1])
+        self.work = {}
+
+    @property
+    def words(self):
+        return "EvalPlan", "eval_plan", "tables", f"{self.rank.noun} size", "(or one update)"
+
+    def _check(self) -> None:
+        lib, sizes = _lib.load(), self.sizes
+        self.rank = _eval_rank("EvalPlan", sizes)
         limits = [getattr(lib, self.rank.max_size)(a) for a in range(len(sizes))]
         if any(n > m for n, m in zip(sizes, limits)):
             raise _lib.DpotHipError(f"eval_metrics: a {' x '.join(map(str, sizes))} {self.rank.noun} is beyond the supported "
                                     f"size ({self.rank.limits.format(*limits)})")
-        want = tuple(getattr(lib, self.rank.pad)(n, h) for h in (0, 1) for n in sizes)
-        if want != self.pads(*sizes):
-            raise _lib.DpotHipError(f"EvalPlan: the library pads {sizes} to {want}, this module to {self.pads(*sizes)}")
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.DpotHipError(f"EvalPlan {sizes}: the tables are uploaded when a {self.rank.noun} size is first used - "
-                                    "call ops.eval_plan(...) (or one update) before capturing")
-        self.dev = {}
-        for name, a in self.host_tables(*sizes).items():
-            t = torch.empty(a.shape, dtype=torch.int32 if name == "jlo" else torch.float32, device=device)
-            t.copy_(torch.from_numpy(a))
-            self.dev[name] = t
-        self.work = {}
+        self._check_pads(getattr(lib, self.rank.pad), (0,) * len(sizes) + (1,) * len(sizes), sizes * 2)
+
+    _host = host_tables
 
     def workspace(self, B: int, TC: int, device):
         """the buffers of a batch size between the two launches - statp (doubles), then the fp32 ones, in the order the
@@ -2710,20 +2712,9 @@ class EvalPlan:
         return w
 
 
-_eval_plans = {}
-
-
 def eval_plan(*sizes_device) -> EvalPlan:
     """the cached EvalPlan of (n_x, n_y[, n_z], device)"""
-    *sizes, device = sizes_device
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = tuple(int(n) for n in sizes) + (device,)
-    plan = _eval_plans.get(key)
-    if plan is None:
-        plan = _eval_plans[key] = EvalPlan(*key)
-    return plan
+    return _plan(EvalPlan, sizes_device[:-1], sizes_device[-1])
 
 
 def eval_acc_alloc(*dims_device) -> Tensor:
@@ -2856,56 +2847,48 @@ def aa_up_tables(h: int, w: int, H: int, W: int):
     return np.concatenate(parts)
 
 
-class AAPlan:
+class AAPlan(_TablePlan):
     """The tap tables of the anti-aliased activation for one size tuple (h, w, H, W) - H = W = 0: no output size - built in
-    float64, rounded to fp32 and kept in device memory"""
+    float64, rounded to fp32 and kept in device memory: .tab, and .vtab of the output size (else None)"""
+    words = ("AAPlan", "aa_plan", "tap tables", "size tuple", "(or the operator itself) once")
 
     def __init__(self, h: int, w: int, H: int, W: int, device):
-        lib = _lib.load()
-        self.sizes = (h, w, H, W)
+        super().__init__((h, w, H, W), device)
+        self.tab, self.vtab = self.dev["tab"], self.dev["vtab"]
+
+    def _check(self) -> None:
+        lib, (h, w, H, W) = _lib.load(), self.sizes
         lat, outm = lib.dpot_aa_max_size(0), lib.dpot_aa_max_size(1)
         if not (1 <= h <= lat and 1 <= w <= lat):
             raise ValueError(f"aa_lrelu: latent size {h}x{w} is not supported (1 <= h, w <= {lat})")
         if (H or W) and not (h <= H <= outm and w <= W <= outm):
             raise ValueError(f"aa_lrelu: output size {H}x{W} is not supported for a {h}x{w} field (per axis: input size <= "
                              f"output size <= {outm})")
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.DpotHipError(f"AAPlan {self.sizes}: the tap tables are uploaded when a size tuple is first used - call "
-                                    "ops.aa_plan(...) (or the operator itself) once before capturing")
-        core = aa_core_tables(h, w)
+
+    @staticmethod
+    def _host(h: int, w: int, H: int, W: int):
+        """the word tables, each held to the length the library expects"""
+        lib = _lib.load()
+        core, up = aa_core_tables(h, w), None
         if len(core) != lib.dpot_aa_tab_words(h, w):
             raise _lib.DpotHipError(f"AAPlan: {len(core)} table words, the library expects {lib.dpot_aa_tab_words(h, w)}")
-        self.tab = torch.empty(len(core), dtype=torch.int32, device=device)
-        self.tab.copy_(torch.from_numpy(core))
-        self.vtab = None
         if H or W:
             up = aa_up_tables(h, w, H, W)
             if len(up) != lib.dpot_aa_vtab_words(h, w, H, W):
                 raise _lib.DpotHipError(f"AAPlan: {len(up)} up-sampling table words, the library expects "
                                         f"{lib.dpot_aa_vtab_words(h, w, H, W)}")
-            self.vtab = torch.empty(len(up), dtype=torch.int32, device=device)
-            self.vtab.copy_(torch.from_numpy(up))
-
-
-_aa_plans = {}
+        return {"tab": core, "vtab": up}
 
 
 def aa_plan(h: int, w: int, H: int, W: int, device) -> AAPlan:
     """the cached AAPlan of (h, w, H, W, device); H = W = 0 without an output size"""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (int(h), int(w), int(H), int(W), device)
-    plan = _aa_plans.get(key)
-    if plan is None:
-        plan = _aa_plans[key] = AAPlan(*key)
-    return plan
+    return _plan(AAPlan, (h, w, H, W), device)
 
 
 def _aa_out_size(out_size, h: int, w: int):
     if out_size is None:
         return 0, 0
-    H, W = (int(out_size), int(out_size)) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
+    H, W = size_tuple(out_size, 2)
     return (0, 0) if (H, W) == (h, w) else (H, W)      # V is the identity at the input size: skipped, as the reference does
 
 
@@ -2927,15 +2910,7 @@ def aa_lrelu(x: Tensor, bias: Tensor, out_size=None, slope: float = 0.01, out: O
     N, h, w, C = _aa_args(x, bias, "aa_lrelu")
     H, W = _aa_out_size(out_size, h, w)
     plan = aa_plan(h, w, H, W, x.device)
-    shape = (N, H or h, W or w, C)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    else:
-        _req(out, "aa_lrelu: out")
-        if tuple(out.shape) != shape or out.device != x.device:
-            raise _lib.DpotHipError(f"aa_lrelu: out must be {shape} on {x.device}, got {tuple(out.shape)} on {out.device}")
-        if out.data_ptr() == x.data_ptr():
-            raise _lib.DpotHipError("aa_lrelu: out must not alias x")
+    out = _out_buf(out, "aa_lrelu", "out", (N, H or h, W or w, C), x.device, x=x)
     lib = _lib.load()
     Cb = bias.shape[0]
     if plan.vtab is None:
@@ -3069,66 +3044,47 @@ def fno_col_weights(W: int, m2: int):
     return w
 
 
-class FNOPlan:
+class FNOPlan(_TablePlan):
     """The twiddle tables of the truncated transforms for one (H, W, m1, m2, device) or (X, Y, Z, m1, m2, m3, device): .tx, .ty
-    (and .tz), one per axis, built in float64, rounded to fp32 and kept in device memory.  FNO3Plan is the same class: the
-    number of sizes gives the rank."""
+    (and .tz), one per axis and all of them in .tables, built in float64, rounded to fp32 and kept in device memory.  FNO3Plan
+    is the same class: the number of sizes gives the rank."""
 
     def __init__(self, *sizes_device):
-        *sizes, device = sizes_device
-        rank = len(sizes) // 2
-        dims, modes = tuple(sizes[:rank]), tuple(sizes[rank:])
-        name, entry = ("FNOPlan", "fno_plan") if rank == 2 else ("FNO3Plan", "fno3_plan")
-        _fno_check_modes(dims, modes, name)
+        super().__init__(sizes_device[:-1], sizes_device[-1])
+        self.tables = list(self.dev.values())
+        for axis, t in self.dev.items():
+            setattr(self, axis, t)
+
+    @property
+    def words(self):
+        name, entry = ("FNOPlan", "fno_plan") if len(self.sizes) == 4 else ("FNO3Plan", "fno3_plan")
+        return name, entry, "tables", "size tuple", "(or the operator itself) once"
+
+    def _check(self) -> None:
+        rank = len(self.sizes) // 2
+        dims, modes = self.sizes[:rank], self.sizes[rank:]
+        _fno_check_modes(dims, modes, self.words[0])
         if not _fno_supported(dims, modes):
             n, m = _fno_limits(rank)
-            raise ValueError(f"{name}: field {'x'.join(map(str, dims))} with modes {modes} is beyond the kernels' limits "
-                             f"({', '.join(_FNO_AXES[rank])} <= {n}, modes <= {m})")
-        self.sizes = dims + modes
-        if torch.cuda.is_current_stream_capturing():
-            raise _lib.DpotHipError(f"{name} {self.sizes}: the tables are uploaded when a size tuple is first used - call "
-                                    f"ops.{entry}(...) (or the operator itself) once before capturing")
-        self.tables = []
-        for axis, t in zip(("tx", "ty", "tz"), (fno_twiddles if rank == 2 else fno3_twiddles)(*self.sizes)):
-            dev = torch.empty(t.shape, dtype=torch.float32, device=device)
-            dev.copy_(torch.from_numpy(t.astype("float32")))
-            setattr(self, axis, dev)
-            self.tables.append(dev)
+            raise ValueError(f"{self.words[0]}: field {'x'.join(map(str, dims))} with modes {modes} is beyond the kernels' "
+                             f"limits ({', '.join(_FNO_AXES[rank])} <= {n}, modes <= {m})")
+
+    @staticmethod
+    def _host(*sizes):
+        return dict(zip(("tx", "ty", "tz"), (fno_twiddles if len(sizes) == 4 else fno3_twiddles)(*sizes)))
 
 
 FNO3Plan = FNOPlan
-_fno_plans = {}
-
-
-def _fno_plan(dims, modes, device) -> FNOPlan:
-    """the cached plan of (dims, modes, device)"""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = tuple(int(n) for n in (*dims, *modes)) + (device,)
-    plan = _fno_plans.get(key)
-    if plan is None:
-        plan = _fno_plans[key] = FNOPlan(*key)
-    return plan
 
 
 def fno_plan(H: int, W: int, m1: int, m2: int, device) -> FNOPlan:
     """the cached FNOPlan of (H, W, m1, m2, device)"""
-    return _fno_plan((H, W), (m1, m2), device)
+    return _plan(FNOPlan, (H, W, m1, m2), device)
 
 
 def fno3_plan(X: int, Y: int, Z: int, m1: int, m2: int, m3: int, device) -> FNOPlan:
     """the cached FNO3Plan of (X, Y, Z, m1, m2, m3, device)"""
-    return _fno_plan((X, Y, Z), (m1, m2, m3), device)
-
-
-def _fno_buf(t: Optional[Tensor], what: str, name: str, shape, device) -> Tensor:
-    """`t`, checked to be a kernel-ready tensor of `shape` on `device`; a fresh one when it is None"""
-    if t is None:
-        return torch.empty(shape, dtype=torch.float32, device=device)
-    if tuple(_req(t, f"{what}: {name}").shape) != tuple(shape) or t.device != device:
-        raise ValueError(f"{what}: {name} must be {tuple(shape)} on {device}, got {tuple(t.shape)} on {t.device}")
-    return t
+    return _plan(FNOPlan, (X, Y, Z, m1, m2, m3), device)
 
 
 def _fno_kept(modes):
@@ -3153,7 +3109,7 @@ def _fno_transform(what: str, head, B: int, dims, Cc: int, modes, tail, device) 
     [B, X, 2 m2, m3, 2, C] between the two launches is a local here: it lives until both launches have been issued and is
     dropped when the operator returns"""
     lib = _lib.load()
-    plan = _fno_plan(dims, modes, device)
+    plan = _plan(FNOPlan, (*dims, *modes), device)
     entry = getattr(lib, "dpot_" + what)
     tables = [t.data_ptr() for t in plan.tables]
     sizes = (B, *dims, Cc, *modes, *tail, _stream())
@@ -3171,7 +3127,7 @@ def _fno_rfft(what: str, x: Tensor, modes, adjoint: bool, out: Optional[Tensor])
     B, *dims, Cc = x.shape
     _fno_check_modes(dims, modes, what)
     _req(x, f"{what}: x")
-    out = _fno_buf(out, what, "out", (B,) + _fno_kept(modes) + (2, Cc), x.device)
+    out = _out_buf(out, what, "out", (B,) + _fno_kept(modes) + (2, Cc), x.device, ValueError)
     _fno_transform(what, (x.data_ptr(), out.data_ptr()), B, dims, Cc, modes,
                    (1 if adjoint else 0, 1.0 / math.prod(dims) if adjoint else 1.0), x.device)
     return out
@@ -3186,8 +3142,8 @@ def _fno_irfft(what: str, S: Tensor, dims, add, act: int, save_pre: bool, adjoin
     _req(S, f"{what}: S")
     shape = (B, *dims, Cc)
     if add is not None:
-        _fno_buf(add, what, "add", shape, S.device)
-    out = _fno_buf(out, what, "out", shape, S.device)
+        _out_buf(add, what, "add", shape, S.device, ValueError)
+    out = _out_buf(out, what, "out", shape, S.device, ValueError)
     pre = torch.empty_like(out) if save_pre else None
     _fno_transform(what, (S.data_ptr(), _p(add), out.data_ptr(), _p(pre)), B, tuple(dims), Cc, modes,
                    (0 if adjoint else 1, 1.0 if adjoint else 1.0 / math.prod(dims), int(act)), S.device)
@@ -3262,7 +3218,7 @@ def _fno_mix_wgrad(what: str, X: Tensor, dO: Tensor, outs, accumulate: bool, pla
         raise ValueError(f"{what}: X [B, {kept}, 2, Cin] and dO [B, {kept}, 2, Cout], got {tuple(X.shape)} and {tuple(dO.shape)}")
     B, Cin, Cout = X.shape[0], X.shape[-1], dO.shape[-1]
     shape = (2, Cin, Cout, *modes) if planar else (Cin, Cout, *modes, 2)
-    outs = [_fno_buf(o, what, "out", shape, X.device) for o in outs]
+    outs = [_out_buf(o, what, "out", shape, X.device, ValueError) for o in outs]
     check(getattr(_lib.load(), "dpot_" + what)(X.data_ptr(), dO.data_ptr(), *(o.data_ptr() for o in outs), B, Cin, Cout, *modes,
                                                1 if accumulate else 0, _stream()), what)
     return tuple(outs)
