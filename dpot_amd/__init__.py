@@ -12,6 +12,7 @@
     from dpot_amd import FNO2d              # drop-in for models/fno.py::FNO2d, the baseline (truncated-DFT and per-mode mixing kernels)
     from dpot_amd import FNO3d              # drop-in for models/fno.py::FNO3d, the 3-D baseline of finetune3d.py
     from dpot_amd import Resized3D, spectral_resize3, resize3_plan   # 3-D rollouts at any data resolution
+    from dpot_amd import UNet               # drop-in for models/unet.py::UNet (n_dim = 2): 3x3 convolution, BatchNorm and pooling kernels
 
 The compute path is libdpot_hip.so (hand-written HIP kernels behind the C ABI in include/dpot_hip.h).
 """
@@ -20,6 +21,7 @@ from .model3d import DPOTNet3D  # noqa: F401
 from .model_c import CDPOTNet  # noqa: F401
 from .model_fno import FNO2d  # noqa: F401
 from .model_fno3d import FNO3d  # noqa: F401
+from .model_unet import UNet  # noqa: F401
 from . import _lib  # noqa: F401
 from .functional import ClsCEFn, cls_ce_loss  # noqa: F401
 from .train import StepMetrics  # noqa: F401
@@ -32,4 +34,4 @@ __version__ = "0.3.0"
 __all__ = ["DPOTNet", "StepMetrics", "ClsCEFn", "cls_ce_loss", "GraphedRollout", "rollout_eval", "refill_mask",
            "spectral_resize", "spectral_resize_matrices", "ResizePlan", "RolloutEvaluator", "DPOTNet3D",
            "load_3d_components_from_2d", "DeviceBatcher3D", "resize_pad_window3", "target_mask3", "CDPOTNet", "FNO2d",
-           "FNO3d", "Resized3D", "spectral_resize3", "resize3_plan", "Resize3Plan"]
+           "FNO3d", "Resized3D", "spectral_resize3", "resize3_plan", "Resize3Plan", "UNet"]

@@ -292,6 +292,17 @@ SIGNATURES = {
     "dpot_fno3_irfft3": (c_i, [c_fp] * 8 + [c_i] * 9 + [c_f, c_i, c_fp]),
     "dpot_fno3_mix": (c_i, [c_fp] * 6 + [c_i] * 7 + [c_fp]),
     "dpot_fno3_mix_wgrad": (c_i, [c_fp] * 6 + [c_i] * 7 + [c_fp]),
+    "dpot_unet_max_size": (c_i, [c_i]),
+    "dpot_conv3x3_stats_elems": (c_i64, [c_i64, c_i]),
+    "dpot_conv3x3": (c_i, [c_fp] * 4 + [c_i] * 6 + [c_fp]),
+    "dpot_bn_finalize": (c_i, [c_fp, c_i64, c_i] + [c_fp] * 5 + [c_f, c_f, c_fp]),
+    "dpot_bn_act": (c_i, [c_fp] * 7 + [c_i] * 6 + [c_f, c_fp]),
+    "dpot_bn_act_bwd_ws_elems": (c_i64, [c_i64, c_i]),
+    "dpot_bn_act_bwd_reduce": (c_i, [c_fp] * 8 + [c_i] * 5 + [c_fp]),
+    "dpot_bn_act_bwd_apply": (c_i, [c_fp] * 11 + [c_i] * 5 + [c_fp]),
+    "dpot_conv3x3_wgrad_ws_elems": (c_i64, [c_i64, c_i, c_i]),
+    "dpot_conv3x3_wgrad": (c_i, [c_fp] * 4 + [c_i] * 6 + [c_fp]),
+    "dpot_unet_upshuffle": (c_i, [c_fp] * 3 + [c_i] * 5 + [c_fp]),
 }
 
 _lib = None

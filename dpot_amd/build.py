@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdpot_hip.so")
-SOURCES = ["core.hip", "gemm.hip", "gemm_panel.hip", "gemm_tn.hip", "lane.hip", "gemm_bf16p.hip", "afno_mlp.hip", "afno_mlp6.hip", "afno_fused.hip", "dft.hip", "dft3.hip", "norm.hip", "gn_dft.hip", "misc.hip", "patch3d.hip", "loss_opt.hip", "metrics.hip", "tail.hip", "data.hip", "data3d.hip", "embed.hip", "resize.hip", "resize3.hip", "evalmetrics.hip", "evalmetrics3d.hip", "aa_act.hip", "fno.hip", "fno3.hip"]
+SOURCES = ["core.hip", "gemm.hip", "gemm_panel.hip", "gemm_tn.hip", "lane.hip", "gemm_bf16p.hip", "afno_mlp.hip", "afno_mlp6.hip", "afno_fused.hip", "dft.hip", "dft3.hip", "norm.hip", "gn_dft.hip", "misc.hip", "patch3d.hip", "loss_opt.hip", "metrics.hip", "tail.hip", "data.hip", "data3d.hip", "embed.hip", "resize.hip", "resize3.hip", "evalmetrics.hip", "evalmetrics3d.hip", "aa_act.hip", "fno.hip", "fno3.hip", "unet.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-pass-failed"]
 # per-source extras.  afno_mlp6: the operand split runs beside MFMAs, where the v_pk_add_f32 the SLP vectoriser forms out of

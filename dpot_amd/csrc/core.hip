@@ -69,6 +69,6 @@ int tune(const char* key, int dflt) {
  * per complex pair; nothing existing changed
  * 278: dpot_afno_mlp2_plan, dpot_afno_mlp2_plans (csrc/afno_mlp.hip): host-only queries of the mixer's kernel selection the
  * launcher reads; nothing existing changed */
-extern "C" int dpot_version(void) { return 279; }
+extern "C" int dpot_version(void) { return 280; }
 extern "C" int dpot_tune(const char* key, int dflt) { return dpot::tune(key, dflt); }
 extern "C" const char* dpot_last_error(void) { return dpot::g_err; }

@@ -1805,3 +1805,96 @@ class FNO3dLayerFn(torch.autograd.Function):
     @ops.with_ctx_precision
     def backward(ctx, dy):
         return _fno_backward(ctx, dy, _fno3_ops()) + (None,)
+
+
+# ======================================================================================================
+# the UNet baseline (models/unet.py): csrc/unet.hip through ops.conv3x3 / bn_stats / bn_act / conv3x3_wgrad
+# ======================================================================================================
+def _deliver(sink, make):
+    """a weight gradient delivered as _fno_wgrad delivers the spectral ones: `make(out, accumulate)` writes the flat slot where
+    this is the step's first contribution, ADDS to it in a further pass of a rollout, else makes a temporary"""
+    out, acc = sink.out(), False
+    if out is None and sink.fp is not None and sink.fp.filled[sink.i]:
+        out, acc = sink.fp.grad_views[sink.i], True
+    return sink.done(make(out, acc))
+
+
+class ConvBNActFn(torch.autograd.Function):
+    """conv3x3 (no bias) -> BatchNorm2d -> act on a channels-last field x [B, H, W, Cin], one third of a UNet block
+    (models/unet.py:534-564); pool=True returns (y, max_pool2d(y, 2, 2)), the encoder's last layer and the pooling after it.
+
+    training=True: the batch statistics come out of the convolution's epilogue, and the same launch that merges them updates
+    running_mean / running_var / num_batches_tracked in place (momentum 0.1, the unbiased variance).  Keeps x, z (the
+    convolution's output), mean and invstd - not the normalised field, not y and no pooling indices: the backward recomputes
+    them.  training=False: normalises with the running buffers and writes none of them; its backward raises."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, running_mean, running_var, num_batches_tracked, act: int, pool: bool, training: bool):
+        x, w = x.contiguous(), w.contiguous()
+        B, H, W, _ = x.shape
+        ctx.training, ctx.act, ctx.pool = training, act, pool
+        ctx.set_materialize_grads(False)
+        if training:
+            z, part = ops.conv3x3(x, w, stats=True)
+            mean, invstd = ops.bn_stats(part, B * H * W, w.shape[0], running_mean, running_var, num_batches_tracked)
+            del part
+            ctx.save_for_backward(x, z, mean, invstd, w, gamma, beta)
+            ctx.sinks = _sinks(ctx, (w, gamma, beta), 1)
+            return ops.bn_act(z, mean, invstd, gamma, beta, act, pool)
+        z = ops.conv3x3(x, w)
+        return ops.bn_act(z, running_mean, running_var, gamma, beta, act, pool, stat_is_var=True)
+
+    @staticmethod
+    def backward(ctx, dy, dpool=None):
+        if not ctx.training:
+            raise RuntimeError("ConvBNActFn.backward: the forward ran in eval mode (running statistics); a backward through it "
+                               "is not built - call model.train() before a step that differentiates")
+        x, z, mean, invstd, w, gamma, beta = ctx.saved_tensors
+        s_w, s_g, s_b = ctx.sinks
+        if dy is None and dpool is None:
+            for s in ctx.sinks:
+                s.skip()
+            return (None,) * 10
+        dy = dy.contiguous() if dy is not None else None
+        dpool = dpool.contiguous() if dpool is not None else None
+        o_g, o_b = s_g.out(), s_b.out()
+        dz, dgamma, dbeta = ops.bn_act_bwd(dy, dpool, z, mean, invstd, gamma, beta, ctx.act, out_dgamma=o_g, out_dbeta=o_b)
+        dgamma, dbeta = s_g.done(dgamma), s_b.done(dbeta)
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = _deliver(s_w, lambda out, acc: ops.conv3x3_wgrad(x, dz, out, acc))
+        else:
+            s_w.skip()
+        dx = ops.conv3x3_bwd_data(dz, w) if ctx.needs_input_grad[0] else None
+        return dx, dw, dgamma, dbeta, None, None, None, None, None, None
+
+
+class UpConv2Fn(torch.autograd.Function):
+    """ConvTranspose2d(k = s = 2) on a channels-last field x [B, h, w, Cin] -> [B, 2 h, 2 w, Cout]: one GEMM of the pixel rows
+    with the parameter W [Cin, Cout, 2, 2] read in place as a [Cin, 4 Cout] matrix, then ops.unet_upshuffle (+ bias)."""
+
+    @staticmethod
+    def forward(ctx, x, W, b):
+        ops.capture_precision(ctx)
+        x, W = x.contiguous(), W.contiguous()
+        B, h, w, Cin = x.shape
+        Cout = W.shape[1]
+        Z = ops.linear_bwd_data(x.view(-1, Cin), W.view(Cin, 4 * Cout))                  # [B h w, 4 Cout] = x @ W
+        ctx.save_for_backward(x, W)
+        ctx.sinks = _sinks(ctx, (W, b), 1)
+        return ops.unet_upshuffle(Z, B, h, w, Cout, bias=b)
+
+    @staticmethod
+    @ops.with_ctx_precision
+    def backward(ctx, dy):
+        x, W = ctx.saved_tensors
+        B, h, w, Cin = x.shape
+        Cout = W.shape[1]
+        s_w, s_b = ctx.sinks
+        dy = dy.contiguous()
+        db = s_b.done(ops.colsum(dy.view(-1, Cout), B * h * w * 4, Cout, out=s_b.out()))
+        dZ = ops.unet_upshuffle(dy, B, h, w, Cout, inverse=True)                         # [B h w, 4 Cout]
+        dW = ops.linear_bwd_weight(x.view(-1, Cin), dZ, out=s_w.out())                   # [Cin, 4 Cout] = x^T dZ
+        dW = s_w.done(dW.view(W.shape))
+        dx = ops.linear_fwd(dZ, W.view(Cin, 4 * Cout), None)[0].view(x.shape) if ctx.needs_input_grad[0] else None
+        return dx, dW, db

@@ -234,6 +234,18 @@ class RolloutEvaluator:
         return ops.eval_finish(vals, int(round(vals[0])), *self.shape, self.ilow, self.ihigh)
 
 
+@contextlib.contextmanager
+def _eval_mode(model: nn.Module):
+    """THE place the evaluation paths (rollout_eval, GraphedRollout's capture) switch the model to eval mode - a UNet's BatchNorm
+    then reads its running statistics and writes nothing - and put its mode back as they found it, also when the block raises"""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
+
+
 @torch.no_grad()
 def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
                  step=None, metrics=None, model_res=None, evaluator=None) -> Tuple[Tensor, Tensor, Tensor]:
@@ -278,7 +290,7 @@ def rollout_eval(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor]
         metrics._check_steps(n_steps)
     if model_res is not None:
         model_res, data_res = _size2(model_res), (xx.shape[1], xx.shape[2])
-    with scope:
+    with scope, _eval_mode(model):
         for k, t in enumerate(range(0, T_ar, T_bundle)):
             y = yy[..., t:t + T_bundle, :]
             if model_res is None:
@@ -341,9 +353,7 @@ class GraphedRollout:
     def __init__(self, model: nn.Module, example_xx: Tensor):
         self.model = model
         self.x = example_xx.detach().clone().contiguous()
-        was_training = model.training
-        model.eval()
-        with torch.no_grad():
+        with torch.no_grad(), _eval_mode(model):
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -355,7 +365,6 @@ class GraphedRollout:
             with torch.cuda.graph(self.graph):
                 out = model(self.x)
         self.im, self.cls = (out, None) if torch.is_tensor(out) else (out[0], out[1])
-        model.train(was_training)
 
     def step(self, xx: Tensor) -> Tensor:
         self.x.copy_(xx)

@@ -3266,3 +3266,186 @@ def act_bwd_mul(dy: Tensor, pre: Tensor, act: int) -> Tensor:
     out = torch.empty_like(dy)
     check(_lib.load().dpot_fno_dact(dy.data_ptr(), pre.data_ptr(), out.data_ptr(), dy.numel(), int(act), _stream()), "fno_dact")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------
+# the UNet baseline (csrc/unet.hip): 3x3 convolution, BatchNorm statistics, normalise + activation (+ 2x2 max pooling)
+# ------------------------------------------------------------------------------------------------------
+BN_MOMENTUM, BN_EPS = 0.1, 1e-5          # torch.nn.BatchNorm2d's defaults, which the reference leaves alone
+
+
+def unet_limits() -> Tuple[int, int]:
+    """(the longest row W, the most channels) the convolution kernels take"""
+    lib = _lib.load()
+    return lib.dpot_unet_max_size(0), lib.dpot_unet_max_size(1)
+
+
+def unet_check_sizes(W: int, channels, what: str = "unet") -> None:
+    """ValueError naming the size beyond what the kernels of csrc/unet.hip stage (checked before anything is launched)"""
+    max_w, max_c = unet_limits()
+    if W > max_w:
+        raise ValueError(f"{what}: a row of {W} pixels is beyond the staged halo of the convolution kernels (W <= {max_w})")
+    for c in channels:
+        if c > max_c:
+            raise ValueError(f"{what}: {c} channels are beyond the convolution kernels' grid (channels <= {max_c})")
+
+
+def _field(t: Tensor, what: str, name: str):
+    if t.dim() != 4 or t.numel() == 0:
+        raise ValueError(f"{what}: {name} must be a non-empty channels-last field [B, H, W, C], got {tuple(t.shape)}")
+    _req(t, f"{what}: {name}")
+    return tuple(t.shape)
+
+
+def _conv_weight(w: Tensor, what: str):
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.numel() == 0:
+        raise ValueError(f"{what}: the weight must be the parameter [Cout, Cin, 3, 3], got {tuple(w.shape)}")
+    _req(w, f"{what}: weight")
+    return w.shape[0], w.shape[1]
+
+
+def conv3x3_stats_elems(npix: int, Cout: int) -> int:
+    return int(_lib.load().dpot_conv3x3_stats_elems(npix, Cout))
+
+
+def _conv3x3(what: str, x: Tensor, w: Tensor, adjoint: bool, stats: bool, out: Optional[Tensor]):
+    Cout, Cin = _conv_weight(w, what)
+    B, H, W, Cx = _field(x, what, "x")
+    K, N = (Cout, Cin) if adjoint else (Cin, Cout)
+    if Cx != K:
+        raise ValueError(f"{what}: x has {Cx} channels, the weight {tuple(w.shape)} takes {K}")
+    unet_check_sizes(W, (Cin, Cout), what)
+    out = _out_buf(out, what, "out", (B, H, W, N), x.device, ValueError, x)
+    lib = _lib.load()
+    part = None
+    if stats:
+        part = torch.empty(lib.dpot_conv3x3_stats_elems(B * H * W, N), dtype=torch.float32, device=x.device)
+    check(lib.dpot_conv3x3(x.data_ptr(), w.data_ptr(), out.data_ptr(), _p(part), B, H, W, Cin, Cout, 1 if adjoint else 0,
+                           _stream()), what)
+    return out, part
+
+
+def conv3x3(x: Tensor, w: Tensor, stats: bool = False, out: Optional[Tensor] = None):
+    """x [B, H, W, Cin], w the parameter [Cout, Cin, 3, 3] read in place -> z [B, H, W, Cout] = Conv2d(k = 3, padding 1, no
+    bias).  stats=True: (z, the per-tile count | mean | M2 partials of z that bn_stats merges) instead of z alone"""
+    z, part = _conv3x3("conv3x3", x, w, False, stats, out)
+    return (z, part) if stats else z
+
+
+def conv3x3_bwd_data(dz: Tensor, w: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """dz [B, H, W, Cout] -> dx [B, H, W, Cin]: the same kernel with the taps mirrored and the channel roles exchanged"""
+    return _conv3x3("conv3x3_bwd_data", dz, w, True, False, out)[0]
+
+
+def conv3x3_wgrad(x: Tensor, dz: Tensor, out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
+    """dw [Cout, Cin, 3, 3] = sum over the pixels of dz[p, co] x[p + tap, ci], in the parameter's layout; accumulate: added to
+    `out` (a further step of a rollout)"""
+    what = "conv3x3_wgrad"
+    B, H, W, Cin = _field(x, what, "x")
+    if tuple(dz.shape[:3]) != (B, H, W) or dz.dim() != 4:
+        raise ValueError(f"{what}: x [B, H, W, Cin] and dz [B, H, W, Cout], got {tuple(x.shape)} and {tuple(dz.shape)}")
+    Cout = _field(dz, what, "dz")[3]
+    if accumulate and out is None:
+        raise ValueError(f"{what}: accumulate needs out")
+    unet_check_sizes(W, (Cin, Cout), what)
+    out = _out_buf(out, what, "out", (Cout, Cin, 3, 3), x.device, ValueError)
+    lib = _lib.load()
+    ws = _scratch(torch.empty(lib.dpot_conv3x3_wgrad_ws_elems(B * H * W, Cin, Cout), dtype=torch.float32, device=x.device))
+    check(lib.dpot_conv3x3_wgrad(x.data_ptr(), dz.data_ptr(), out.data_ptr(), ws.data_ptr(), B, H, W, Cin, Cout,
+                                 1 if accumulate else 0, _stream()), what)
+    return out
+
+
+def _bn_vec(t: Tensor, C: int, what: str, name: str) -> Tensor:
+    if tuple(_req(t, f"{what}: {name}").shape) != (C,):
+        raise ValueError(f"{what}: {name} must be [{C}], got {tuple(t.shape)}")
+    return t
+
+
+def bn_stats(part: Tensor, npix: int, C: int, running_mean: Optional[Tensor] = None, running_var: Optional[Tensor] = None,
+             num_batches_tracked: Optional[Tensor] = None, momentum: float = BN_MOMENTUM, eps: float = BN_EPS):
+    """the partials conv3x3(stats=True) left, merged in ascending order -> (mean [C], invstd [C]) of the batch; the running
+    buffers (momentum, the unbiased variance) and the int64 counter are updated in the same launch where they are given.  One
+    value per channel has no variance: the ValueError of torch.nn.functional.batch_norm"""
+    what = "bn_stats"
+    if npix <= 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {[npix, C]}")
+    lib = _lib.load()
+    if part.numel() != lib.dpot_conv3x3_stats_elems(npix, C):
+        raise ValueError(f"{what}: {part.numel()} partials do not belong to {npix} pixels of {C} channels")
+    _req(part, f"{what}: partials")
+    for name, t in (("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None:
+            _bn_vec(t, C, what, name)
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1
+                                            or not num_batches_tracked.is_cuda):
+        raise ValueError(f"{what}: num_batches_tracked must be one int64 on the device")
+    stat = torch.empty(2, C, dtype=torch.float32, device=part.device)
+    check(lib.dpot_bn_finalize(part.data_ptr(), npix, C, stat[0].data_ptr(), stat[1].data_ptr(), _p(running_mean),
+                               _p(running_var), _p(num_batches_tracked), float(momentum), float(eps), _stream()), what)
+    return stat[0], stat[1]
+
+
+def bn_act(z: Tensor, mean: Tensor, stat2: Tensor, gamma: Tensor, beta: Tensor, act: int, pool: bool = False,
+           stat_is_var: bool = False, eps: float = BN_EPS, out: Optional[Tensor] = None, out_pool: Optional[Tensor] = None):
+    """y = act(gamma (z - mean) invstd + beta) on z [B, H, W, C]; pool: (y, the 2x2 / stride-2 maximum of y [B, H/2, W/2, C])
+    from the same launch.  stat_is_var (eval mode): stat2 is the running variance, invstd = 1 / sqrt(stat2 + eps)"""
+    what = "bn_act"
+    B, H, W, C = _field(z, what, "z")
+    for name, t in (("mean", mean), ("stat2", stat2), ("gamma", gamma), ("beta", beta)):
+        _bn_vec(t, C, what, name)
+    if pool and (H % 2 or W % 2):
+        raise ValueError(f"{what}: 2x2 pooling needs an even field, got {H}x{W}")
+    y = _out_buf(out, what, "out", (B, H, W, C), z.device, ValueError, z)
+    yp = _out_buf(out_pool, what, "out_pool", (B, H // 2, W // 2, C), z.device, ValueError, z) if pool else None
+    check(_lib.load().dpot_bn_act(z.data_ptr(), mean.data_ptr(), stat2.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                  y.data_ptr(), _p(yp), B, H, W, C, int(act), 1 if stat_is_var else 0, float(eps), _stream()),
+          what)
+    return (y, yp) if pool else y
+
+
+def bn_act_bwd(dy: Optional[Tensor], dpool: Optional[Tensor], z: Tensor, mean: Tensor, invstd: Tensor, gamma: Tensor,
+               beta: Tensor, act: int, out: Optional[Tensor] = None, out_dgamma: Optional[Tensor] = None,
+               out_dbeta: Optional[Tensor] = None):
+    """backward of bn_act in training mode -> (dz, dgamma, dbeta).  dy: the gradient of y, dpool: of the pooled field (not
+    None exactly when the forward pooled and its pooled output took a gradient; it goes to the FIRST maximum of its window, in
+    (row, column) order, as torch.max_pool2d routes it); one of the two may be None.  Two launches: the per-chunk sums of
+    g = (dy + routed dpool) act'(pre) and g xhat, then dz = gamma invstd (g - mean(g) - xhat mean(g xhat)) with the sums finished in
+    ascending order.  xhat, pre and the maxima are recomputed from z"""
+    what = "bn_act_bwd"
+    B, H, W, C = _field(z, what, "z")
+    if dy is None and dpool is None:
+        raise ValueError(f"{what}: neither dy nor dpool")
+    if dy is not None and _field(dy, what, "dy") != (B, H, W, C):
+        raise ValueError(f"{what}: dy must be {(B, H, W, C)}, got {tuple(dy.shape)}")
+    if dpool is not None:
+        if H % 2 or W % 2 or _field(dpool, what, "dpool") != (B, H // 2, W // 2, C):
+            raise ValueError(f"{what}: dpool must be the pooled field of an even {H}x{W} field, got {tuple(dpool.shape)}")
+    for name, t in (("mean", mean), ("invstd", invstd), ("gamma", gamma), ("beta", beta)):
+        _bn_vec(t, C, what, name)
+    lib = _lib.load()
+    dz = _out_buf(out, what, "out", (B, H, W, C), z.device, ValueError, z)
+    dgamma = _out_buf(out_dgamma, what, "out_dgamma", (C,), z.device, ValueError)
+    dbeta = _out_buf(out_dbeta, what, "out_dbeta", (C,), z.device, ValueError)
+    ws = _scratch(torch.empty(lib.dpot_bn_act_bwd_ws_elems(B * H * W, C), dtype=torch.float32, device=z.device))
+    head = (_p(dy), _p(dpool), z.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ws.data_ptr())
+    check(lib.dpot_bn_act_bwd_reduce(*head, B, H, W, C, int(act), _stream()), what + " (reduce)")
+    check(lib.dpot_bn_act_bwd_apply(*head, dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), B, H, W, C, int(act), _stream()),
+          what + " (apply)")
+    return dz, dgamma, dbeta
+
+
+def unet_upshuffle(z: Tensor, B: int, h: int, w: int, C: int, bias: Optional[Tensor] = None, inverse: bool = False) -> Tensor:
+    """the shuffle of a k = s = 2 transposed convolution whose GEMM read the parameter [Cin, C, 2, 2] in place as [Cin, 4 C]:
+    z [B h w, 4 C] with columns (c, i, j) -> [B, 2 h, 2 w, C] (+ bias); inverse=True: the field's gradient gathered back into
+    that matrix.  (ops.pixel_shuffle takes columns (i, j, c), which would need a permuted copy of the weight.)"""
+    what = "unet_upshuffle"
+    _req(z, f"{what}: z")
+    if z.numel() != B * h * w * 4 * C or z.numel() == 0:
+        raise ValueError(f"{what}: {tuple(z.shape)} does not hold B h w 4 C = {B} {h} {w} 4 {C} values")
+    if bias is not None:
+        _bn_vec(bias, C, what, "bias")
+    out = torch.empty((B * h * w, 4 * C) if inverse else (B, 2 * h, 2 * w, C), dtype=torch.float32, device=z.device)
+    check(_lib.load().dpot_unet_upshuffle(z.data_ptr(), None if inverse else _p(bias), out.data_ptr(), B, h, w, C,
+                                          1 if inverse else 0, _stream()), what)
+    return out

@@ -504,6 +504,8 @@ def check_cls_args(opt, cls: Optional[Tensor], cls_weight: float) -> None:
 
 _NO_CLS = ("{} returns one tensor and no cls_pred (the 3-D fine-tuning model: finetune3d.py has no classification branch), so "
            "cls_weight = {} has nothing to weigh; pass cls_weight=0")
+_CONST_CLS = ("{} returns a constant cls_pred (zeros, as the reference's UNet does: no classification head and no gradient path), "
+              "so cls_weight = {} has nothing to weigh; pass cls_weight=0")
 
 
 def rollout(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor], T_bundle: int = 1,
@@ -528,6 +530,8 @@ def rollout_total(model: nn.Module, xx: Tensor, yy: Tensor, msk: Optional[Tensor
     check_cls_args(None, cls, cls_weight)
     if cls_weight != 0.0 and not getattr(model, "cls_output", True):
         raise ValueError(_NO_CLS.format(type(model).__name__, cls_weight))
+    if cls_weight != 0.0 and not getattr(model, "cls_trainable", True):
+        raise ValueError(_CONST_CLS.format(type(model).__name__, cls_weight))
     scope = model.weights_scope() if hasattr(model, "weights_scope") else contextlib.nullcontext()
     with scope:
         return _rollout(model, xx, yy, msk, T_bundle, noise_scale, noise, cls, cls_weight, metrics)
@@ -676,20 +680,33 @@ def _optimise(opt: FlatOptimizer, update: Callable[[float], None], grad_scale: f
 
 
 @contextlib.contextmanager
-def trial_state(opt: FlatOptimizer, metrics: Optional[StepMetrics] = None, rng_device=None):
+def trial_state(opt: FlatOptimizer, metrics: Optional[StepMetrics] = None, rng_device=None, model: Optional[nn.Module] = None):
     """The steps taken inside are NOT training steps (graph warm-up, the trial steps of ``make_dp_step``): parameters,
-    optimiser state and the metrics accumulator are put back when the block ends, and with ``rng_device`` the in-kernel noise
-    generator of that device as well.  A block that raises restores nothing: what raises here is a failed stream capture, and
+    optimiser state and the metrics accumulator are put back when the block ends, with ``rng_device`` the in-kernel noise
+    generator of that device as well, and with ``model`` the persistent buffers a training-mode forward writes (BatchNorm's
+    running_mean / running_var / num_batches_tracked of a UNet); a model without persistent buffers enqueues nothing more.
+    A block that raises restores nothing: what raises here is a failed stream capture, and
     the restoring launches must not go to streams that ``_end_stray_captures`` has yet to take out of capture mode."""
     snap = opt.snapshot()
     msnap = metrics.snapshot() if metrics is not None else None
     rng = ops.rng_state(rng_device).clone() if rng_device is not None else None
+    bufs = [(b, b.clone()) for b in _persistent_buffers(model)] if model is not None else []
     yield
     opt.restore(snap)
     if msnap is not None:
         metrics.restore(msnap)
     if rng is not None:
         ops.rng_state(rng_device).copy_(rng)
+    for b, saved in bufs:
+        b.copy_(saved)
+
+
+def _persistent_buffers(model: nn.Module) -> List[Tensor]:
+    """the buffers of ``model`` that are part of its state_dict (a non-persistent one is a constant table, never written)"""
+    out = []
+    for mod in model.modules():
+        out += [b for name, b in mod._buffers.items() if b is not None and name not in mod._non_persistent_buffers_set]
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -743,7 +760,7 @@ class _GraphStep:
         """eager warm-up on a side stream (allocator + lazy inits): ``n`` times what a replay does, stage_hyper then ``body``.
         The warm-up iterations are NOT training steps (a fine-tune of a pretrained checkpoint must not receive unscheduled
         full-lr updates before its first replay), and they are not logged either"""
-        with trial_state(self.opt, self.metrics):
+        with trial_state(self.opt, self.metrics, model=self.model):
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):

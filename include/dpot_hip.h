@@ -1099,6 +1099,58 @@ int dpot_fno3_mix(const float* X, const float* w1, const float* w2, const float*
 int dpot_fno3_mix_wgrad(const float* X, const float* dO, float* dw1, float* dw2, float* dw3, float* dw4, int B, int Cin,
                         int Cout, int m1, int m2, int m3, int accumulate, dpot_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The UNet baseline (csrc/unet.hip; the reference's models/unet.py UNet with n_dim = 2) on channels-last fields [B, H, W, C],
+ * addressed as npix = B H W flat pixels:
+ *   dpot_conv3x3        out[p, co] = sum over the taps (dy, dx) and ci of x[p + (dy, dx), ci] w[co, ci, dy + 1, dx + 1], zero
+ *                       outside the field (Conv2d k = 3, padding 1, no bias): an implicit GEMM on the fp32 matrix cores over
+ *                       tiles of 128 flat pixels staged with their halo in LDS.  w is the parameter [Cout][Cin][3][3] read in
+ *                       place.  adjoint = 1: the data gradient - x is [npix, Cout], out [npix, Cin], taps mirrored.
+ *                       stats (forward only, may be NULL): dpot_conv3x3_stats_elems(npix, Cout) floats [tiles][3][Cout] - count,
+ *                       mean and M2 of the values the workgroup of a tile produced, per channel.
+ *   dpot_bn_finalize    merges those partials tile by tile in ascending order (Chan) into mean[C] and invstd[C] =
+ *                       1 / sqrt(M2 / n + eps), and - where the pointers are not NULL - running_mean and running_var
+ *                       (r += momentum (value - r); the UNBIASED variance M2 / (n - 1)) and num_batches_tracked (int64) += 1.
+ *   dpot_bn_act         y = act(gamma (z - mean) invstd + beta); pool != NULL (H, W even): also the 2x2 / stride-2 maximum of
+ *                       y as [B, H/2, W/2, C].  stat_is_var = 1: stat2 is a variance (eval mode: the running buffers),
+ *                       invstd = 1 / sqrt(stat2 + eps); else stat2 is invstd and eps is unused.
+ *   dpot_bn_act_bwd_reduce  with g = (dy + dpool routed to the window's FIRST maximum in (row, column) order) act'(pre):
+ *                       part [chunks][2][C] = sum g | sum g xhat over the 2048 pixels of a chunk;
+ *                       dpot_bn_act_bwd_ws_elems(npix, C) floats.  xhat, pre and the maximum are recomputed from z, mean,
+ *                       invstd.  One of dy, dpool may be NULL; dpool != NULL says that the forward pooled.
+ *   dpot_bn_act_bwd_apply   dbeta = sum g, dgamma = sum g xhat (the chunks in ascending order; either may be NULL) and
+ *                       dz = gamma invstd (g - mean(g) - xhat mean(g xhat)).
+ *   dpot_conv3x3_wgrad  dw[co, ci, tap] = sum_p dy[p, co] x[p + tap, ci]: split over the pixels into ws
+ *                       (dpot_conv3x3_wgrad_ws_elems(npix, Cin, Cout) floats), finished in ascending order in the parameter's
+ *                       layout; accumulate = 1 adds to dw.  Two launches.
+ *   dpot_unet_upshuffle the shuffle of the k = s = 2 transposed convolution: src [B h w, 4 C] with columns (c, i, j) - the
+ *                       GEMM of the rows with the parameter [Cin][C][2][2] read as [Cin][4 C] - to
+ *                       dst[b, 2 hy + i, 2 wx + j, c] (+ bias[c], may be NULL); inverse = 1: the gather back, no bias.
+ * Sizes: any H, B >= 1, W <= dpot_unet_max_size(0) (= 512: the halo of 2 W + 2 pixels staged beside a tile), channel counts
+ * <= dpot_unet_max_size(1) - beyond: DPOT_EUNSUP, nothing is launched.  16-byte accesses when the channel counts are multiples
+ * of 4 and the tensors 16-byte aligned, else a scalar path.  One launch each but the weight gradient; 64-bit pixel indices;
+ * fixed summation order, no atomics, no allocation, legal under stream capture. */
+int dpot_unet_max_size(int channels);
+int64_t dpot_conv3x3_stats_elems(int64_t npix, int Cout);
+int dpot_conv3x3(const float* x, const float* w, float* out, float* stats, int B, int H, int W, int Cin, int Cout, int adjoint,
+                 dpot_stream_t stream);
+int dpot_bn_finalize(const float* stats, int64_t npix, int C, float* mean, float* invstd, float* running_mean,
+                     float* running_var, void* num_batches_tracked, float momentum, float eps, dpot_stream_t stream);
+int dpot_bn_act(const float* z, const float* mean, const float* stat2, const float* gamma, const float* beta, float* y,
+                float* pool, int B, int H, int W, int C, int act, int stat_is_var, float eps, dpot_stream_t stream);
+int64_t dpot_bn_act_bwd_ws_elems(int64_t npix, int C);
+int dpot_bn_act_bwd_reduce(const float* dy, const float* dpool, const float* z, const float* mean, const float* invstd,
+                           const float* gamma, const float* beta, float* part, int B, int H, int W, int C, int act,
+                           dpot_stream_t stream);
+int dpot_bn_act_bwd_apply(const float* dy, const float* dpool, const float* z, const float* mean, const float* invstd,
+                          const float* gamma, const float* beta, const float* part, float* dz, float* dgamma, float* dbeta,
+                          int B, int H, int W, int C, int act, dpot_stream_t stream);
+int64_t dpot_conv3x3_wgrad_ws_elems(int64_t npix, int Cin, int Cout);
+int dpot_conv3x3_wgrad(const float* x, const float* dy, float* dw, float* ws, int B, int H, int W, int Cin, int Cout,
+                       int accumulate, dpot_stream_t stream);
+int dpot_unet_upshuffle(const float* src, const float* bias, float* dst, int B, int h, int w, int C, int inverse,
+                        dpot_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
